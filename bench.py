@@ -2,23 +2,31 @@
 """bench.py - denoising steps/sec on MI355X for BASELINE.json config 2
 (sdf_chd8bar conditional generation, batch 16 per GPU, DDPM sampler).
 
-  python bench.py [--gpus N] [--steps K] [--warmup W]          (N > 1: re-executes itself under torch.distributed.run, one rank per GPU)
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
+                                                              (N > 1: re-executes itself under torch.distributed.run, one rank per GPU)
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 One "step" = one iteration of SDFSampler.paint's loop on a batch of 16 piano rolls (`SDFSampler.repaint_step`, the method paint()
 itself runs): the conditional UNet evaluation (uncond_scale = 1 -> one eval per sample) and the fused DDPM/RePaint update with its two
 noise draws - exactly what `inference_sdf` executes per reverse step.  As in paint(), what the denoiser derives from (t, cond) alone is
 prepared once before the loop (`sampler.prepare`).  Inputs (x_T, chord condition from the HIP chord encoder, weights) are resident in
-HBM before the timed region.  Rank 0 prints ONE JSON line; `value` is the whole-job aggregate (sum over GPUs, weak scaling: every GPU
-denoises its own batch of 16).
+HBM before the timed region; they are generated from fixed seeds, so the same arguments give the same inputs in every run.  Rank 0
+prints ONE JSON line; `value` is the whole-job aggregate (sum over GPUs, weak scaling: every GPU denoises its own batch of 16).
 
-Timing protocol: W warm-up steps, then `--windows` (default 5) back-to-back windows of EXACTLY K steps, each between barrier +
-synchronize pairs (host clock, max over ranks).  `value` / `ms_per_step` are the MEDIAN window; every window and the spread are in
-the line (`windows_ms_per_step`), next to the average shader clock the GPU sustained over each window (`sclk_mhz`, from two probe
-kernels that read the shader-cycle and the constant-rate counters) - the part is power-managed, and box-to-box differences of the same
-binary show up there.
+Timing protocol: W warm-up steps, then EXACTLY K timed steps between barrier + synchronize pairs (host clock, max over ranks);
+`ms_per_step` is that time / K.  `--windows M` repeats the timed window M times back to back (M x K timed steps) and reports the
+MEDIAN window, every window and the spread (`windows_ms_per_step`).
 
-Extra objects (see DESIGN.md "Measurement"):
+`--dump-outputs DIR`: after the timed steps, what the last of them returned - the batch of latents x_{t-1} that repaint_step hands its
+caller, float32 [16, 2, 128, 128] - is written as DIR/x.npy (DIR/x_rank<r>.npy per rank when N > 1), so that two builds can be compared
+output for output.
+
+A plain run does only that: set up, warm up, time, dump, print the line.  Everything else is measured with `--full` (each part can
+still be switched off by its own option): the average shader clock the GPU sustained over each window (`sclk_mhz`, from two probe
+kernels that read the shader-cycle and the constant-rate counters - the part is power-managed, and box-to-box differences of the same
+binary show up there) with rocm-smi snapshots around the windows, and the extra objects below.
+
+Extra objects with --full (see DESIGN.md "Measurement"):
   roofline     - the dominant kernel family (the 3x3 convolutions, conv_bf16x3.hip: error-compensated bf16 split on the
                  bf16 matrix pipe, peak 2500/3 TFLOP/s fp32-equivalent): algorithmic FLOPs of its launches / their summed
                  duration, measured with hipEvents around every launch on the launch stream in a separate profiled pass.
@@ -222,8 +230,7 @@ def measure_traffic(precision):
     exe = shutil.which("rocprofv3") or "/opt/rocm/bin/rocprofv3"
     if not os.path.exists(exe):
         return None, "rocprofv3 not found"
-    child = [sys.executable, os.path.abspath(__file__), "--steps", "2", "--warmup", "1", "--windows", "1", "--profile-steps", "0", "--no-cpu-baseline",
-             "--small-batch-steps", "0", "--fp32-steps", "0", "--f16x3-steps", "0", "--no-pmc", "--precision", precision]
+    child = [sys.executable, os.path.abspath(__file__), "--steps", "2", "--warmup", "1", "--precision", precision]   # a plain run: no --full
     pat = "conv_bf3_kernel<" if precision == "bf16x3" else "conv_mfma_kernel<"
     tot, launches = {}, 0
     with tempfile.TemporaryDirectory(dir="/tmp") as tmp:
@@ -442,23 +449,33 @@ def long_parity_note(model, measure: bool):
     return out
 
 
+def dump_outputs(out_dir, x, rank, world):
+    """What the timed path returned from its last step (this rank's batch of latents), as float32 .npy under `out_dir`."""
+    os.makedirs(out_dir, exist_ok=True)
+    name = "x.npy" if world == 1 else f"x_rank{rank}.npy"
+    np.save(os.path.join(out_dir, name), x.detach().float().cpu().numpy())
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=50)
+    ap.add_argument("--steps", type=int, default=50, help="timed steps (per window)")
     ap.add_argument("--warmup", type=int, default=5)
-    ap.add_argument("--windows", type=int, default=5, help="back-to-back timed windows of --steps steps each; the median window is reported")
-    ap.add_argument("--profile-steps", type=int, default=2, help="profiled steps for the roofline object (0 disables)")
-    ap.add_argument("--f16x3-steps", type=int, default=20, help="steps per window of the f16x3 leg (fp16-split build, alternating with bf16x3 windows; 0 disables)")
-    ap.add_argument("--fp32-steps", type=int, default=10, help="steps of the exact-fp32-MFMA mode measured in the same run (0 disables)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-pmc", action="store_true", help="do not spawn the two rocprofv3 counter passes that measure roofline.traffic in the run")
-    ap.add_argument("--small-batch-steps", type=int, default=40, help="reverse steps of the batch-1 / batch-8 eager-vs-hipGraph lines (0 disables)")
-    ap.add_argument("--secondary-windows", type=int, default=3, help="timed windows of every secondary line (fp32 mode, small batch, configs 3 / 4); median reported")
-    ap.add_argument("--no-long-parity", action="store_true", help="do not re-measure the 50-step DDIM f32-vs-bf16x3 comparison for precision_note")
+    ap.add_argument("--windows", type=int, default=1, help="back-to-back timed windows of --steps steps each; with more than one the median window is reported")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the last timed step returned to DIR/x.npy (float32)")
+    ap.add_argument("--full", action="store_true", help="after the headline, measure everything else: shader clock, rocm-smi, roofline, fp32 / f16x3 modes, "
+                                                        "small-batch and config 3 / 4 lines, long parity, CPU baseline (the options below switch parts off)")
+    ap.add_argument("--profile-steps", type=int, default=2, help="--full: profiled steps for the roofline object (0 disables)")
+    ap.add_argument("--f16x3-steps", type=int, default=20, help="--full: steps per window of the f16x3 leg (fp16-split build, alternating with bf16x3 windows; 0 disables)")
+    ap.add_argument("--fp32-steps", type=int, default=10, help="--full: steps of the exact-fp32-MFMA mode measured in the same run (0 disables)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--no-pmc", action="store_true", help="--full: do not spawn the two rocprofv3 counter passes that measure roofline.traffic in the run")
+    ap.add_argument("--small-batch-steps", type=int, default=40, help="--full: reverse steps of the batch-1 / batch-8 eager-vs-hipGraph lines (0 disables)")
+    ap.add_argument("--secondary-windows", type=int, default=3, help="--full: timed windows of every secondary line (fp32 mode, small batch, configs 3 / 4); median reported")
+    ap.add_argument("--no-long-parity", action="store_true", help="--full: do not re-measure the 50-step DDIM f32-vs-bf16x3 comparison for precision_note")
     ap.add_argument("--precision", default="bf16x3", choices=["f32", "bf16x3"],
                     help="arithmetic of the dense contractions: exact fp32 MFMA, or the error-compensated bf16x3 split")
-    ap.add_argument("--dump-launches", action="store_true", help="print one line per kernel launch of a profiled step (stderr)")
+    ap.add_argument("--dump-launches", action="store_true", help="--full: print one line per kernel launch of a profiled step (stderr)")
     ap.add_argument("--option", action="append", default=[], metavar="NAME=0|1",
                     help="pin a plan option of the UNet handle (pf_unet_set_option: mlp_fused, attn_wide, conv_t16, conv_pp, conv_wino) for A/B runs; "
                          "the default line runs with every option automatic")
@@ -503,8 +520,8 @@ def main():
     def step_fn(x_t, step):          # the loop body of SDFSampler.paint with a known region (orig = mask = 0, as Experiments.predict passes)
         return sampler.repaint_step(x_t, cond, step, zeros, zeros, prep=prep)
 
-    probe = ClockProbe(dev)
-    smi_before = smi_snapshot() if rank == 0 else {}
+    probe = ClockProbe(dev) if args.full else None
+    smi_before = smi_snapshot() if args.full and rank == 0 else {}
     t_step = params.n_steps - 1
     for _ in range(args.warmup):
         x = step_fn(x, t_step); t_step = max(t_step - 1, 1)
@@ -512,8 +529,10 @@ def main():
     for _ in range(max(1, args.windows)):
         x, t_step, el, ev, mhz = timed_loop(step_fn, x, t_step, args.steps, probe)
         wins.append((el, ev, mhz))
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, x, rank, world)
     assert torch.isfinite(x).all(), "non-finite sample"
-    smi_after = smi_snapshot() if rank == 0 else {}
+    smi_after = smi_snapshot() if args.full and rank == 0 else {}
     order = sorted(range(len(wins)), key=lambda i: wins[i][0])
     elapsed, ev_elapsed, med_mhz = wins[order[len(order) // 2]]
 
@@ -537,11 +556,6 @@ def main():
         "windows": len(wins), "windows_ms_per_step": [round(w[0] / args.steps * 1e3, 4) for w in wins],
         "windows_spread_pct": round((max(w[0] for w in wins) - min(w[0] for w in wins)) / elapsed * 100, 2),
         "window_rule": "value / ms_per_step = the MEDIAN of the windows (each exactly --steps steps between barrier + synchronize pairs)",
-        "sclk_mhz": {"median_window": med_mhz, "per_window": [w[2] for w in wins],
-                     "how": "average shader clock of the XCDs over each timed window = d(s_memtime) / d(s_memrealtime) per XCD between two probe "
-                            "kernels on the launch stream (median / min / max over the XCDs), reference counter calibrated against the host clock "
-                            "(%s Hz)" % (None if probe.ref_hz is None else round(probe.ref_hz)),
-                     "rocm_smi_before": smi_before, "rocm_smi_after": smi_after},
         "ranks_seen": ranks_seen, "devices_seen": devices_seen,
         "path_tflops": round(f_eval * BATCH * world * args.steps / elapsed / 1e12, 3),
         "path_frac_of_f32_mfma_peak": round(f_eval * BATCH * args.steps / elapsed / (PEAK_F32_MFMA_TFLOPS * 1e12), 4),
@@ -551,8 +565,14 @@ def main():
                            "UNet max-abs-diff vs the reference 5.2e-5 (contract 1e-3)") if args.precision == "bf16x3"
         else "dense contractions on the fp32 matrix pipe (exact fp32 FMA chains)",
     }
+    if args.full:
+        out["sclk_mhz"] = {"median_window": med_mhz, "per_window": [w[2] for w in wins],
+                           "how": "average shader clock of the XCDs over each timed window = d(s_memtime) / d(s_memrealtime) per XCD between two probe "
+                                  "kernels on the launch stream (median / min / max over the XCDs), reference counter calibrated against the host clock "
+                                  "(%s Hz)" % (None if probe.ref_hz is None else round(probe.ref_hz)),
+                           "rocm_smi_before": smi_before, "rocm_smi_after": smi_after}
 
-    if rank == 0 and args.profile_steps > 0:
+    if args.full and rank == 0 and args.profile_steps > 0:
         x, agg = profiled_pass(unet, step_fn, x, t_step, args.profile_steps, args.precision, args.dump_launches)
         k = agg.get(0)
         # an event pair around a launch measures the kernel plus the pair's own cost (the pair keeps the next kernel from starting
@@ -623,7 +643,7 @@ def main():
                                              "how": "nonconv_ms_per_step = ms_per_step x (raw event time of the launches that are not 3x3 convs / raw event time of all launches)"}
         out["nonconv_frac_of_833"] = round(nonconv_fl / max(nonconv_ms * 1e-3, 1e-12) / 1e12 / PEAK_ALGO["bf16x3"], 4) if args.precision == "bf16x3" else None
 
-    if args.fp32_steps > 0 and args.precision == "bf16x3":
+    if args.full and args.fp32_steps > 0 and args.precision == "bf16x3":
         # the exact-fp32-MFMA mode in the same run, same workload, the headline's protocol (every rank runs it so the barriers line up)
         unet.set_precision("f32")
         for _ in range(2):
@@ -644,7 +664,7 @@ def main():
                 fp32["conv3x3_frac_of_157"] = round(agg32[0][2] / (agg32[0][1] * 1e-3) / 1e12 / PEAK_F32_MFMA_TFLOPS, 4)
         unet.set_precision(args.precision)
         out["fp32_mode"] = fp32
-    if args.f16x3_steps > 0 and args.precision == "bf16x3" and _lib.X3_VARIANT == "":
+    if args.full and args.f16x3_steps > 0 and args.precision == "bf16x3" and _lib.X3_VARIANT == "":
         # the fp16 split (libpfhip_f16.so) on the same workload: a second model instance in the other build of the library, same weights,
         # same sampler state; windows alternate with bf16x3 windows so both see the same clocks (every rank runs it: barriers line up)
         model16, _ = build_model(params, rank, world, x3="f16")
@@ -696,12 +716,12 @@ def main():
                                  "f16x3 1.4e-6 on the synthetic weights, 1.7e-4 / 1.6e-3 / 1.3e-4 on the worst stressed net")
         out["f16x3_mode"] = f16
         del s16, prep16, u16, model16
-    if rank == 0 and args.small_batch_steps > 0:
+    if args.full and rank == 0 and args.small_batch_steps > 0:
         out["small_batch"] = small_batch_lines(model, params, args.small_batch_steps, args.precision, args.secondary_windows, probe)
         out["config3"] = config3_line(model, params, 10, args.secondary_windows, probe)
         if world == 1:
             out["config4_shape"] = config4_line(20, args.secondary_windows, probe)
-    if rank == 0 and args.precision == "bf16x3":
+    if args.full and rank == 0 and args.precision == "bf16x3":
         out["long_parity"] = long_parity_note(model, measure=(world == 1 and not args.no_long_parity and args.small_batch_steps > 0))
         lp = out["long_parity"]
         if "config3" in lp:
@@ -710,7 +730,7 @@ def main():
                                       f"at rms {k['image_rms']:.0f}, {k['notes']['onset_bits_differ'] + k['notes']['sustain_bits_differ']} of {2 * k['notes']['cells']} note cells differ")
         out["precision_note"] += ("; the 1000-step loops (configs 2 / 5) and all three against the REAL reference: tests/test_gpu_long_parity.py, "
                                   "tests/test_gpu_long_reference.py (source: the GPU suite, not this run)")
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(params)
     if rank == 0:
         print(json.dumps(out), flush=True)

@@ -102,11 +102,9 @@ def test_split_pickle_admits_only_name_lists(tmp_path):
         pickle.dump({"train": []}, f)
     with pytest.raises(ValueError):
         ds.load_split(str(tmp_path / "odd.pickle"))
-    # the reference's own split files load (they are lists of names): checked where the reference checkout exists
-    ref = "/root/reference/data/train_split_pnt/pop909.pickle"
-    if os.path.exists(ref):
-        tr, va = ds.load_split(ref)
-        assert len(tr) == 797 and len(va) == 89 and va[0] == "258.npz"
+    # the reference's own split files load (they are lists of names): its pop909 split, stored as tests/golden/pop909_split.pickle
+    tr, va = ds.load_split(os.path.join(os.path.dirname(__file__), "golden", "pop909_split.pickle"))
+    assert len(tr) == 797 and len(va) == 89 and va[0] == "258.npz"
 
 
 # ---------------------------------------------------------------------------------------------- dataset loaders, pinned

@@ -24,7 +24,7 @@ def torchrun(args, port, timeout=600, nproc=2):
 
 
 def test_bench_two_ranks():
-    out = torchrun(["bench.py", "--gpus", "2", "--steps", "4", "--warmup", "2", "--profile-steps", "0", "--fp32-steps", "2",
+    out = torchrun(["bench.py", "--gpus", "2", "--steps", "4", "--warmup", "2", "--full", "--profile-steps", "0", "--fp32-steps", "2",
                     "--f16x3-steps", "2", "--small-batch-steps", "0"], 29641)
     assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]

@@ -2,7 +2,7 @@
 # same-box A/B of one plan option, OFF against AUTO (the plan's own choice): bash tools/ab_auto.sh conv_wino [reps]  -> gpurun_out/ab/abauto_<option>.txt
 opt=$1; reps=${2:-3}
 mkdir -p gpurun_out/ab
-F="--steps 50 --warmup 5 --no-cpu-baseline --profile-steps 0 --small-batch-steps 0 --fp32-steps 0 --f16x3-steps 0"
+F="--steps 50 --warmup 5 --windows 5 --full --no-cpu-baseline --profile-steps 0 --small-batch-steps 0 --fp32-steps 0 --f16x3-steps 0"
 : > gpurun_out/ab/abauto_$opt.txt
 for rep in $(seq $reps); do
   for v in off auto; do

@@ -2,7 +2,7 @@
 # same-box alternating A/B/C of the Winograd plan option: direct plan (conv_wino=0), AUTO (no pin), every qualifying conv (conv_wino=1)
 reps=${1:-3}
 mkdir -p gpurun_out/ab
-F="--steps 50 --warmup 5 --no-cpu-baseline --profile-steps 0 --small-batch-steps 0 --fp32-steps 0 --f16x3-steps 0"
+F="--steps 50 --warmup 5 --windows 5 --full --no-cpu-baseline --profile-steps 0 --small-batch-steps 0 --fp32-steps 0 --f16x3-steps 0"
 : > gpurun_out/ab/ab_conv_wino.txt
 for rep in $(seq $reps); do
   for v in "--option conv_wino=0" "" "--option conv_wino=1"; do
