@@ -8,19 +8,12 @@
 // conv_bf16x3.hip (GroupNorm + Swish prologue, time bias, fused 1x1 shortcut, stride 2, the parity-folded upsampling path), the GroupNorm
 // statistics of norm_stats.hip, the stem / head convs and mat-vec of small_kernels.hip, the wide-head attention, fp32 ConvT and time
 // embedding of attention_wide.hip.  As for pf_unet, the library allocates no device memory: one packed weight blob, one workspace.
-#include <string.h>
-#include <map>
 #include <memory>
-#include <string>
 #include <vector>
-#include "pf_internal.h"
+#include "plan.h"
 
 namespace pf {
 namespace {
-
-enum { DK_RAW = 0, DK_GEMM = 1, DK_CONVT = 2, DK_CONVOUT = 3 };
-struct DDest { int kind; size_t off; int taps, K, N; };
-struct DParam { std::string key; std::vector<int64_t> shape; std::vector<DDest> dests; bool packed = false; };
 
 struct DLayer {
   int kind;               // 1 ResidualBlock, 2 AttentionBlock, 3 Downsample, 4 Upsample
@@ -31,8 +24,6 @@ struct DLayer {
   bool pop;               // up-path ResidualBlock: consumes a skip
 };
 
-size_t gemm_floats(int taps, int K, int N) { return (size_t)taps * K * ((N + 63) / 64 * 64); }
-
 }  // namespace
 }  // namespace pf
 
@@ -42,31 +33,9 @@ struct pf_ddpm {
   pf_ddpm_cfg cfg;
   int d_t = 0, sum_emb = 0, final_ch = 0;
   std::vector<DLayer> down, mid, up;   // down / up: in module order; a down entry's output is a skip
-  std::vector<DParam> params;
-  std::map<std::string, int> index;
-  size_t blob_floats = 0;
+  WeightTable wt;
   size_t in_w, in_b, te_w1, te_b1, te_w2, te_b2, emb_w, emb_b, out_g, out_b, out_w, out_bias;
-  const float* wdev = nullptr;
   int precision = PF_PREC_F32;
-
-  size_t alloc(size_t n) { size_t o = blob_floats; blob_floats += (n + 63) / 64 * 64; return o; }
-  DParam& add(const std::string& key, std::vector<int64_t> shape) {
-    index[key] = (int)params.size();
-    params.push_back(DParam{key, shape, {}, false});
-    return params.back();
-  }
-  size_t raw(const std::string& key, std::vector<int64_t> shape) {
-    size_t n = 1; for (auto s : shape) n *= (size_t)s;
-    const size_t off = alloc(n);
-    add(key, shape).dests.push_back(DDest{DK_RAW, off, 0, 0, 0});
-    return off;
-  }
-  // fp32 packing then the split packing of the same byte count, back to back (as pf_unet)
-  size_t gemm(const std::string& key, int N, int K, int taps) {
-    const size_t off = alloc(2 * gemm_floats(taps, K, N));
-    add(key, taps == 1 ? std::vector<int64_t>{N, K} : std::vector<int64_t>{N, K, 3, 3}).dests.push_back(DDest{DK_GEMM, off, taps, K, N});
-    return off;
-  }
 };
 
 namespace pf {
@@ -74,32 +43,32 @@ namespace {
 
 void build_res(pf_ddpm* u, const std::string& p, DLayer& L) {
   const int ci = L.cin + L.cskip, co = L.cout;
-  L.g1 = u->raw(p + ".norm1.weight", {ci});
-  L.be1 = u->raw(p + ".norm1.bias", {ci});
-  L.w1 = u->gemm(p + ".conv1.weight", co, ci, 9);
-  L.b1 = u->raw(p + ".conv1.bias", {co});
-  L.g2 = u->raw(p + ".norm2.weight", {co});
-  L.be2 = u->raw(p + ".norm2.bias", {co});
-  L.w2 = u->gemm(p + ".conv2.weight", co, co, 9);
-  L.b2 = u->raw(p + ".conv2.bias", {co});
+  L.g1 = u->wt.raw(p + ".norm1.weight", {ci});
+  L.be1 = u->wt.raw(p + ".norm1.bias", {ci});
+  L.w1 = u->wt.gemm(p + ".conv1.weight", co, ci, 9);
+  L.b1 = u->wt.raw(p + ".conv1.bias", {co});
+  L.g2 = u->wt.raw(p + ".norm2.weight", {co});
+  L.be2 = u->wt.raw(p + ".norm2.bias", {co});
+  L.w2 = u->wt.gemm(p + ".conv2.weight", co, co, 9);
+  L.b2 = u->wt.raw(p + ".conv2.bias", {co});
   if (ci != co) {
-    L.wsk = u->gemm(p + ".shortcut.weight", co, ci, 1);
-    u->params.back().shape = {co, ci, 1, 1};
-    L.bsk = u->raw(p + ".shortcut.bias", {co});
+    L.wsk = u->wt.gemm(p + ".shortcut.weight", co, ci, 1);
+    u->wt.params.back().shape = {co, ci, 1, 1};
+    L.bsk = u->wt.raw(p + ".shortcut.bias", {co});
   }
   // time_emb rows live in the all-ResBlock matrix (one mat-vec launch per forward)
-  u->add(p + ".time_emb.weight", {co, u->d_t}).dests.push_back(DDest{DK_RAW, u->emb_w + (size_t)L.emb_off * u->d_t, 0, 0, 0});
-  u->add(p + ".time_emb.bias", {co}).dests.push_back(DDest{DK_RAW, u->emb_b + (size_t)L.emb_off, 0, 0, 0});
+  u->wt.raw_at(p + ".time_emb.weight", {co, u->d_t}, u->emb_w + (size_t)L.emb_off * u->d_t);
+  u->wt.raw_at(p + ".time_emb.bias", {co}, u->emb_b + (size_t)L.emb_off);
 }
 
 void build_attn(pf_ddpm* u, const std::string& p, DLayer& L) {
   const int C = L.cout;
-  u->add(p + ".norm.weight", {C});   // defined and saved by the reference, never applied (unet.py:170, 185-215): accepted, dropped
-  u->add(p + ".norm.bias", {C});
-  L.w1 = u->gemm(p + ".projection.weight", 3 * C, C, 1);
-  L.b1 = u->raw(p + ".projection.bias", {3 * C});
-  L.w2 = u->gemm(p + ".output.weight", C, C, 1);
-  L.b2 = u->raw(p + ".output.bias", {C});
+  u->wt.add(p + ".norm.weight", {C});   // defined and saved by the reference, never applied (unet.py:170, 185-215): accepted, dropped
+  u->wt.add(p + ".norm.bias", {C});
+  L.w1 = u->wt.gemm(p + ".projection.weight", 3 * C, C, 1);
+  L.b1 = u->wt.raw(p + ".projection.bias", {3 * C});
+  L.w2 = u->wt.gemm(p + ".output.weight", C, C, 1);
+  L.b2 = u->wt.raw(p + ".output.bias", {C});
 }
 
 void build_layer(pf_ddpm* u, const std::string& p, DLayer& L) {
@@ -107,16 +76,17 @@ void build_layer(pf_ddpm* u, const std::string& p, DLayer& L) {
     case 1: build_res(u, p, L); break;
     case 2: build_attn(u, p, L); break;
     case 3:
-      L.w1 = u->gemm(p + ".conv.weight", L.cout, L.cin, 9);
-      L.b1 = u->raw(p + ".conv.bias", {L.cout});
+      L.w1 = u->wt.gemm(p + ".conv.weight", L.cout, L.cin, 9);
+      L.b1 = u->wt.raw(p + ".conv.bias", {L.cout});
       break;
     case 4: {
       const int C = L.cout;
-      L.w1 = u->alloc((size_t)16 * C * C);
-      L.wt_bf3 = u->alloc(gemm_floats(16, C, C));
-      u->add(p + ".conv.weight", {C, C, 4, 4}).dests.push_back(DDest{DK_CONVT, L.w1, 16, C, C});
-      u->params.back().dests.push_back(DDest{DK_CONVT, L.wt_bf3, 0, C, C});
-      L.b1 = u->raw(p + ".conv.bias", {C});
+      L.w1 = u->wt.alloc((size_t)16 * C * C);
+      L.wt_bf3 = u->wt.alloc(gemm_floats(16, C, C));
+      Param& ps = u->wt.add(p + ".conv.weight", {C, C, 4, 4});
+      ps.dests.push_back(Dest{D_CONVT_F32, L.w1, 16, C, C, C, 0});
+      ps.dests.push_back(Dest{D_CONVT_BF3, L.wt_bf3, 16, C, C, (C + 63) / 64 * 64, 0});
+      L.b1 = u->wt.raw(p + ".conv.bias", {C});
       break;
     }
   }
@@ -164,16 +134,16 @@ int build(pf_ddpm* u) {
   for (auto* v : {&u->down, &u->mid, &u->up})
     for (DLayer& L : *v)
       if (L.kind == 1) { L.emb_off = u->sum_emb; u->sum_emb += L.cout; }
-  u->emb_w = u->alloc((size_t)u->sum_emb * u->d_t);
-  u->emb_b = u->alloc((size_t)u->sum_emb);
+  u->emb_w = u->wt.alloc((size_t)u->sum_emb * u->d_t);
+  u->emb_b = u->wt.alloc((size_t)u->sum_emb);
 
   // parameter table in the reference's state_dict order
-  u->in_w = u->raw("image_proj.weight", {c.n_channels, c.image_channels, 3, 3});
-  u->in_b = u->raw("image_proj.bias", {c.n_channels});
-  u->te_w1 = u->raw("time_emb.lin1.weight", {u->d_t, u->d_t / 4});
-  u->te_b1 = u->raw("time_emb.lin1.bias", {u->d_t});
-  u->te_w2 = u->raw("time_emb.lin2.weight", {u->d_t, u->d_t});
-  u->te_b2 = u->raw("time_emb.lin2.bias", {u->d_t});
+  u->in_w = u->wt.raw("image_proj.weight", {c.n_channels, c.image_channels, 3, 3});
+  u->in_b = u->wt.raw("image_proj.bias", {c.n_channels});
+  u->te_w1 = u->wt.raw("time_emb.lin1.weight", {u->d_t, u->d_t / 4});
+  u->te_b1 = u->wt.raw("time_emb.lin1.bias", {u->d_t});
+  u->te_w2 = u->wt.raw("time_emb.lin2.weight", {u->d_t, u->d_t});
+  u->te_b2 = u->wt.raw("time_emb.lin2.bias", {u->d_t});
   static const char* sub[5] = {"", ".res", ".attn", "", ""};
   int mod = -1;
   for (DLayer& L : u->down) {
@@ -187,74 +157,20 @@ int build(pf_ddpm* u) {
     if (L.kind != 2) ++mod;
     build_layer(u, "up." + std::to_string(mod) + sub[L.kind], L);
   }
-  u->out_g = u->raw("norm.weight", {u->final_ch});
-  u->out_b = u->raw("norm.bias", {u->final_ch});
-  u->out_w = u->alloc((size_t)c.image_channels * 9 * u->final_ch);
-  u->add("final.weight", {c.image_channels, u->final_ch, 3, 3}).dests.push_back(DDest{DK_CONVOUT, u->out_w, 9, u->final_ch, c.image_channels});
-  u->out_bias = u->raw("final.bias", {c.image_channels});
+  u->out_g = u->wt.raw("norm.weight", {u->final_ch});
+  u->out_b = u->wt.raw("norm.bias", {u->final_ch});
+  u->out_w = u->wt.alloc((size_t)c.image_channels * 9 * u->final_ch);
+  u->wt.add("final.weight", {c.image_channels, u->final_ch, 3, 3}).dests.push_back(Dest{D_CONVOUT, u->out_w, 9, u->final_ch, c.image_channels, 0, 0});
+  u->out_bias = u->wt.raw("final.bias", {c.image_channels});
   return PF_OK;
-}
-
-void pack_gemm_f32(float* dst, const float* src, int N, int K, int taps) {
-  const int Npad = (N + 63) / 64 * 64;
-  for (int n = 0; n < N; ++n)
-    for (int k = 0; k < K; ++k)
-      for (int t = 0; t < taps; ++t) dst[(((size_t)t * (K / 4) + k / 4) * Npad + n) * 4 + (k & 3)] = src[((size_t)n * K + k) * taps + t];
-}
-
-int pack_one(const DParam& ps, const float* src, float* blob) {
-  size_t numel = 1; for (auto s : ps.shape) numel *= (size_t)s;
-  bool fits = true;
-  for (const DDest& d : ps.dests) {
-    float* dst = blob + d.off;
-    switch (d.kind) {
-      case DK_RAW: memcpy(dst, src, numel * sizeof(float)); break;
-      case DK_GEMM:
-        pack_gemm_f32(dst, src, d.N, d.K, d.taps);
-        if (d.K % 8 == 0) fits = pack_gemm_bf3(dst + gemm_floats(d.taps, d.K, d.N), src, d.N, d.K, d.taps, (d.N + 63) / 64 * 64, 0, nullptr) && fits;
-        break;
-      case DK_CONVT:
-        if (d.taps) {
-          pack_convT_f32(src, d.K, d.N, dst);
-        } else if (d.K % 8 == 0) {
-          std::vector<float> fold((size_t)16 * d.K * d.N);
-          convT_fold(src, d.K, d.N, fold.data());
-          fits = pack_gemm_bf3(dst, fold.data(), d.N, d.K, 16, (d.N + 63) / 64 * 64, 0, nullptr) && fits;
-        }
-        break;
-      case DK_CONVOUT:   // [Cout][Cin][3][3] -> [9][Cin][Cout]
-        for (int co = 0; co < d.N; ++co)
-          for (int ci = 0; ci < d.K; ++ci)
-            for (int t = 0; t < 9; ++t) dst[((size_t)t * d.K + ci) * d.N + co] = src[((size_t)co * d.K + ci) * 9 + t];
-        break;
-    }
-  }
-  return fits ? PF_OK : PF_EINVAL;
 }
 
 // ---- forward ----
 struct DT { const float* d = nullptr; int c = 0; };
 
-struct DCtx {
-  pf_ddpm* u; hipStream_t s; bool dry;
-  char* base; size_t persist_off, temp_base, temp_off, persist_max, temp_max;
-  int B; const float* W; int n_launch; double flops; int rc;
-  float* palloc(size_t n) {
-    const size_t o = persist_off; persist_off += align_up(n * 4, 256);
-    if (persist_off > persist_max) persist_max = persist_off;
-    return dry ? nullptr : (float*)(base + o);
-  }
-  float* talloc(size_t n) {
-    const size_t o = temp_off; temp_off += align_up(n * 4, 256);
-    if (temp_off > temp_max) temp_max = temp_off;
-    return dry ? nullptr : (float*)(base + temp_base + o);
-  }
-  void treset() { temp_off = 0; }
-  const float* w(size_t off) const { return dry ? nullptr : W + off; }
-  // a launch happens only on a live run whose earlier launches all succeeded: after an error nothing more is enqueued
-  bool go() const { return !dry && rc == PF_OK; }
-  void done(int r) { ++n_launch; if (rc == PF_OK) rc = r; }
-  void conv(pf_conv_args a, size_t woff) {
+struct DCtx : PlanCtx {
+  pf_ddpm* u = nullptr;
+  void conv(pf_conv_args a) {
     const int cin = a.c0 + a.c1;
     const bool bf3 = u->precision == PF_PREC_BF16X3 && cin % 32 == 0;
     if (bf3) a.precision = PF_PREC_BF16X3;
@@ -262,10 +178,10 @@ struct DCtx {
       float* ws = talloc(wsb / 4);
       a.splitk_ws = dry ? (void*)1 : (void*)ws; a.splitk_ws_bytes = wsb;
     }
-    flops += conv_flops(a);
-    if (!go()) { done(PF_OK); return; }   // dry run, or an earlier launch failed: nothing is enqueued
-    a.w = W + woff + (bf3 ? gemm_floats(a.ks * a.ks, cin, a.n) : 0);
-    done(launch_conv(a, s));
+    launch(a.ks == 3 ? PF_K_CONV3 : PF_K_GEMM, conv_flops(a), [&] {
+      if (bf3) a.w += split_offset(a.ks * a.ks, cin, a.n);   // the region's split packing
+      return launch_conv(a, s);
+    });
   }
   // GroupNorm scale / shift of concat(x0, x1): one statistics pass + finalize; above 1024 channels (the up path's 2048 / 1280 concats)
   // the two sources get a statistics pass each and the separate finalize launch combines them
@@ -274,26 +190,18 @@ struct DCtx {
     if (C <= 1024) {
       const size_t sb = gn_scratch_bytes(B, C, hw);
       float* scr = talloc(sb / 4);
-      ++n_launch;   // (partial + finalize)
-      done(!go() ? PF_OK : launch_gn_scale_shift(x0.d, x0.c, x1.d, x1.c, B, hw, groups, 1e-5f, w(g), w(b), sc, sh, scr, sb, s));
+      launch(PF_K_GNSTAT, 0.0, [&] { return launch_gn_scale_shift(x0.d, x0.c, x1.d, x1.c, B, hw, groups, 1e-5f, w(g), w(b), sc, sh, scr, sb, s); },
+             2);   // (partial + finalize)
       return;
     }
     const int ns = gn_nsplit(hw);
     float* s0 = talloc((size_t)B * ns * x0.c * 2);
     float* s1 = talloc((size_t)B * ns * x1.c * 2);
-    done(!go() ? PF_OK : launch_gn_partial(x0.d, x0.c, nullptr, 0, B, hw, s0, s));
-    done(!go() ? PF_OK : launch_gn_partial(x1.d, x1.c, nullptr, 0, B, hw, s1, s));
-    done(!go() ? PF_OK : launch_gn_finalize_tiles(s0, ns, x0.c, s1, ns, x1.c, B, hw, groups, 1e-5f, w(g), w(b), sc, sh, s));
+    launch(PF_K_GNSTAT, 0.0, [&] { return launch_gn_partial(x0.d, x0.c, nullptr, 0, B, hw, s0, s); });
+    launch(PF_K_GNSTAT, 0.0, [&] { return launch_gn_partial(x1.d, x1.c, nullptr, 0, B, hw, s1, s); });
+    launch(PF_K_GNSTAT, 0.0, [&] { return launch_gn_finalize_tiles(s0, ns, x0.c, s1, ns, x1.c, B, hw, groups, 1e-5f, w(g), w(b), sc, sh, s); });
   }
 };
-
-pf_conv_args conv_base(const float* x0, int c0, const float* x1, int c1, int B, int hin, int win, int ks, int n, float* out) {
-  pf_conv_args a;
-  memset(&a, 0, sizeof a);
-  a.x0 = x0; a.c0 = c0; a.x1 = x1; a.c1 = c1; a.batch = B; a.hin = hin; a.win = win; a.ks = ks; a.stride = 1;
-  a.w = nullptr; a.n = n; a.out = out; a.ld_out = n;   // (w: the layer's packing, set right before a live launch)
-  return a;
-}
 
 // ResidualBlock.forward (unet.py:128-141): conv2(Swish(GN(conv1(Swish(GN(x))) + time_emb(t)))) + shortcut(x)
 DT run_res(DCtx& c, const DLayer& L, const DT& x0, const DT& x1, int H, int W_, const float* tb) {
@@ -305,31 +213,31 @@ DT run_res(DCtx& c, const DLayer& L, const DT& x0, const DT& x1, int H, int W_, 
   float* sc2 = c.talloc((size_t)B * co); float* sh2 = c.talloc((size_t)B * co);
   c.gn(x0, x1, hw, 32, L.g1, L.be1, sc1, sh1);
   {
-    pf_conv_args a = conv_base(x0.d, x0.c, x1.d, x1.c, B, H, W_, 3, co, h);
+    pf_conv_args a = conv_base(x0.d, x0.c, x1.d, x1.c, B, H, W_, 3, c.w(L.w1), co, h);
     a.prologue = 1; a.sc = sc1; a.sh = sh1; a.bias = c.w(L.b1);
     a.sbias = c.dry ? nullptr : tb + L.emb_off; a.ld_sbias = c.u->sum_emb;
-    c.conv(a, L.w1);
+    c.conv(a);
   }
   c.gn(DT{h, co}, DT{}, hw, 32, L.g2, L.be2, sc2, sh2);
   const float* resid = x0.d;
   const bool fuse = ci != co && c.u->precision == PF_PREC_BF16X3;   // 1x1 shortcut as one more K range of conv2 (split modes)
   if (ci != co && !fuse) {
     float* sk = c.talloc((size_t)B * hw * co);
-    pf_conv_args a = conv_base(x0.d, x0.c, x1.d, x1.c, B, 1, hw, 1, co, sk);
+    pf_conv_args a = conv_base(x0.d, x0.c, x1.d, x1.c, B, 1, hw, 1, c.w(L.wsk), co, sk);
     a.bias = c.w(L.bsk);
-    c.conv(a, L.wsk);
+    c.conv(a);
     resid = sk;
   }
-  pf_conv_args a = conv_base(h, co, nullptr, 0, B, H, W_, 3, co, out);
+  pf_conv_args a = conv_base(h, co, nullptr, 0, B, H, W_, 3, c.w(L.w2), co, out);
   a.prologue = 1; a.sc = sc2; a.sh = sh2; a.bias = c.w(L.b2);
   if (fuse) {
     a.skip_x0 = x0.d; a.skip_c0 = x0.c; a.skip_x1 = x1.d; a.skip_c1 = x1.c;
-    a.skip_w = c.dry ? (const void*)16 : (const void*)(c.w(L.wsk) + gemm_floats(1, ci, co));
+    a.skip_w = c.w_split(L.wsk, 1, ci, co);
     a.skip_bias = c.w(L.bsk);
   } else {
     a.res = resid; a.ld_res = co;
   }
-  c.conv(a, L.w2);
+  c.conv(a);
   return DT{out, co};
 }
 
@@ -343,17 +251,16 @@ DT run_attn(DCtx& c, const DLayer& L, const DT& x, int H, int W_) {
   const size_t sfl = attention_wide_scratch_floats(B, l);
   float* scr = c.talloc(sfl);
   {
-    pf_conv_args a = conv_base(x.d, C, nullptr, 0, B, 1, l, 1, 3 * C, qkv);
+    pf_conv_args a = conv_base(x.d, C, nullptr, 0, B, 1, l, 1, c.w(L.w1), 3 * C, qkv);
     a.bias = c.w(L.b1);
-    c.conv(a, L.w1);
+    c.conv(a);
   }
-  c.flops += 4.0 * B * (double)l * l * C;
-  c.n_launch += 2;
-  c.done(!c.go() ? PF_OK : launch_attention_wide(qkv, qkv + C, qkv + 2 * C, 3 * C, o, C, B, l, C, scr, sfl, c.s));
+  c.launch(PF_K_ATTN, 4.0 * B * (double)l * l * C, [&] { return launch_attention_wide(qkv, qkv + C, qkv + 2 * C, 3 * C, o, C, B, l, C, scr, sfl, c.s); },
+           3);   // (scores, softmax, output)
   {
-    pf_conv_args a = conv_base(o, C, nullptr, 0, B, 1, l, 1, C, out);
+    pf_conv_args a = conv_base(o, C, nullptr, 0, B, 1, l, 1, c.w(L.w2), C, out);
     a.bias = c.w(L.b2); a.res = x.d; a.ld_res = C;
-    c.conv(a, L.w2);
+    c.conv(a);
   }
   return DT{out, C};
 }
@@ -364,12 +271,12 @@ int run(pf_ddpm* u, DCtx& c, const float* x, const int64_t* t, float* eps) {
   int H = cfg.img_h, W_ = cfg.img_w;
   float* temb = c.palloc((size_t)B * u->d_t);
   float* tb = c.palloc((size_t)B * u->sum_emb);
-  c.done(!c.go() ? PF_OK : launch_ddpm_time_embed(t, c.w(u->te_w1), c.w(u->te_b1), c.w(u->te_w2), c.w(u->te_b2), temb, B, u->d_t, c.s));
-  c.done(!c.go() ? PF_OK : launch_matvec(temb, u->d_t, c.w(u->emb_w), c.w(u->emb_b), tb, u->sum_emb, B, u->sum_emb, u->d_t, c.s));
+  c.launch(PF_K_SMALL, 0.0, [&] { return launch_ddpm_time_embed(t, c.w(u->te_w1), c.w(u->te_b1), c.w(u->te_w2), c.w(u->te_b2), temb, B, u->d_t, c.s); });
+  c.launch(PF_K_SMALL, 0.0, [&] { return launch_matvec(temb, u->d_t, c.w(u->emb_w), c.w(u->emb_b), tb, u->sum_emb, B, u->sum_emb, u->d_t, c.s); });
 
   DT cur{c.palloc((size_t)B * H * W_ * cfg.n_channels), cfg.n_channels};
-  c.flops += 2.0 * B * H * W_ * 9.0 * cfg.image_channels * cfg.n_channels;
-  c.done(!c.go() ? PF_OK : launch_conv_in(x, c.w(u->in_w), c.w(u->in_b), const_cast<float*>(cur.d), B, cfg.image_channels, cfg.n_channels, H, W_, c.s));
+  c.launch(PF_K_SMALL, 2.0 * B * H * W_ * 9.0 * cfg.image_channels * cfg.n_channels,
+           [&] { return launch_conv_in(x, c.w(u->in_w), c.w(u->in_b), const_cast<float*>(cur.d), B, cfg.image_channels, cfg.n_channels, H, W_, c.s); });
   std::vector<DT> skips{cur};
   auto step = [&](const DLayer& L, const DT* skip) {
     switch (L.kind) {
@@ -377,23 +284,21 @@ int run(pf_ddpm* u, DCtx& c, const float* x, const int64_t* t, float* eps) {
       case 2: cur = run_attn(c, L, cur, H, W_); break;
       case 3: {
         float* od = c.palloc((size_t)B * (H / 2) * (W_ / 2) * L.cout);
-        pf_conv_args a = conv_base(cur.d, cur.c, nullptr, 0, B, H, W_, 3, L.cout, od);
+        pf_conv_args a = conv_base(cur.d, cur.c, nullptr, 0, B, H, W_, 3, c.w(L.w1), L.cout, od);
         a.stride = 2; a.bias = c.w(L.b1);
-        c.conv(a, L.w1);
+        c.conv(a);
         cur = DT{od, L.cout}; H /= 2; W_ /= 2;
         break;
       }
       case 4: {
         float* od = c.palloc((size_t)B * (2 * H) * (2 * W_) * L.cout);
         if (u->precision == PF_PREC_BF16X3 && L.cin % 32 == 0) {   // the split conv's parity-folded upsampling path on the ConvT fold
-          pf_conv_args a = conv_base(cur.d, cur.c, nullptr, 0, B, H, W_, 3, L.cout, od);
+          pf_conv_args a = conv_base(cur.d, cur.c, nullptr, 0, B, H, W_, 3, c.w(L.wt_bf3), L.cout, od);
           a.ups = 1; a.ups_fold = 1; a.precision = PF_PREC_BF16X3; a.bias = c.w(L.b1);
-          c.flops += conv_flops(a);
-          if (c.go()) a.w = c.w(L.wt_bf3);
-          c.done(!c.go() ? PF_OK : launch_conv(a, c.s));
+          c.launch(PF_K_CONV3, conv_flops(a), [&] { return launch_conv(a, c.s); });
         } else {
-          c.flops += 2.0 * B * (4.0 * H * W_) * L.cout * 4.0 * L.cin;
-          c.done(!c.go() ? PF_OK : launch_convT_f32(cur.d, B, H, W_, L.cin, c.w(L.w1), L.cout, c.w(L.b1), od, c.s));
+          c.launch(PF_K_CONV3, 2.0 * B * (4.0 * H * W_) * L.cout * 4.0 * L.cin,
+                   [&] { return launch_convT_f32(cur.d, B, H, W_, L.cin, c.w(L.w1), L.cout, c.w(L.b1), od, c.s); });
         }
         cur = DT{od, L.cout}; H *= 2; W_ *= 2;
         break;
@@ -419,20 +324,17 @@ int run(pf_ddpm* u, DCtx& c, const float* x, const int64_t* t, float* eps) {
   c.treset();
   float* sc = c.talloc((size_t)B * cur.c); float* sh = c.talloc((size_t)B * cur.c);
   c.gn(cur, DT{}, H * W_, 8, u->out_g, u->out_b, sc, sh);
-  c.flops += 2.0 * B * H * W_ * 9.0 * cur.c * cfg.image_channels;
-  c.done(!c.go() ? PF_OK : launch_conv_out(cur.d, sc, sh, c.w(u->out_w), c.w(u->out_bias), eps, B, cur.c, cfg.image_channels, H, W_, c.s));
+  c.launch(PF_K_SMALL, 2.0 * B * H * W_ * 9.0 * cur.c * cfg.image_channels,
+           [&] { return launch_conv_out(cur.d, sc, sh, c.w(u->out_w), c.w(u->out_bias), eps, B, cur.c, cfg.image_channels, H, W_, c.s); });
   return c.rc;
 }
 
-void plan_sizes(pf_ddpm* u, int batch, size_t* persist, size_t* temp, int* launches, double* flops) {
-  DCtx c{};
-  c.u = u; c.dry = true; c.B = batch; c.rc = PF_OK;
-  run(u, c, nullptr, nullptr, nullptr);
-  *persist = align_up(c.persist_max, 4096);
-  *temp = align_up(c.temp_max, 4096);
-  if (launches) *launches = c.n_launch;
-  if (flops) *flops = c.flops;
+DCtx make_ctx(const pf_ddpm* u, int batch) {
+  DCtx c;
+  c.u = const_cast<pf_ddpm*>(u); c.B = batch;
+  return c;
 }
+PlanSize ddpm_plan(const DCtx& c) { return plan_sizes(c, [](DCtx& d) { run(d.u, d, nullptr, nullptr, nullptr); }); }
 
 }  // namespace
 }  // namespace pf
@@ -450,53 +352,21 @@ int pf_ddpm_create(const pf_ddpm_cfg* cfg, pf_ddpm** out) {
 }
 void pf_ddpm_destroy(pf_ddpm* u) { delete u; }
 
-size_t pf_ddpm_weight_bytes(const pf_ddpm* u) { return u ? u->blob_floats * sizeof(float) : 0; }
-int pf_ddpm_n_params(const pf_ddpm* u) { return u ? (int)u->params.size() : 0; }
+size_t pf_ddpm_weight_bytes(const pf_ddpm* u) { return u ? u->wt.blob_floats * sizeof(float) : 0; }
+int pf_ddpm_n_params(const pf_ddpm* u) { return u ? (int)u->wt.params.size() : 0; }
 
 int pf_ddpm_param_info(const pf_ddpm* u, int i, char* key_buf, size_t key_buf_len, int64_t shape[4], int* ndim) {
-  PF_REQUIRE(u && i >= 0 && i < (int)u->params.size() && key_buf && shape && ndim, "pf_ddpm_param_info: bad arguments");
-  const DParam& ps = u->params[i];
-  snprintf(key_buf, key_buf_len, "%s", ps.key.c_str());
-  *ndim = (int)ps.shape.size();
-  for (int d = 0; d < 4; ++d) shape[d] = d < *ndim ? ps.shape[d] : 1;
-  return PF_OK;
+  PF_REQUIRE(u, "pf_ddpm_param_info: bad arguments");
+  return u->wt.param_info("pf_ddpm_param_info", i, key_buf, key_buf_len, shape, ndim);
 }
-
 int pf_ddpm_pack_param(pf_ddpm* u, const char* key, const float* src, const int64_t* shape, int ndim, void* host_blob) {
-  PF_REQUIRE(u && key && src && shape && host_blob, "pf_ddpm_pack_param: null argument");
-  auto it = u->index.find(key);
-  if (it == u->index.end()) return set_error(PF_ENOTFOUND, "unexpected key '%s' (not a parameter of this DDPM UNet)", key);
-  DParam& ps = u->params[it->second];
-  bool ok = ndim == (int)ps.shape.size();
-  for (int d = 0; ok && d < ndim; ++d) ok = shape[d] == ps.shape[d];
-  if (!ok) {
-    std::string want, got;
-    for (auto s : ps.shape) want += std::to_string(s) + ",";
-    for (int d = 0; d < ndim; ++d) got += std::to_string(shape[d]) + ",";
-    return set_error(PF_EINVAL, "size mismatch for '%s': expected [%s] got [%s]", key, want.c_str(), got.c_str());
-  }
-  if (pack_one(ps, src, (float*)host_blob) != PF_OK)
-    return set_error(PF_EINVAL, "%s: a weight exceeds what this library's fp16 split packing holds (|w| <= 255.8)", key);
-  ps.packed = true;
-  return PF_OK;
+  PF_REQUIRE(u, "pf_ddpm_pack_param: null argument");
+  return u->wt.pack_param("pf_ddpm_pack_param", "DDPM UNet", key, src, shape, ndim, host_blob);
 }
-
-int pf_ddpm_pack_missing(const pf_ddpm* u, char* buf, size_t buf_len) {
-  if (!u) return set_error(PF_EINVAL, "null handle");
-  int n = 0;
-  for (const DParam& ps : u->params)
-    if (!ps.packed) {
-      if (n == 0 && buf && buf_len) snprintf(buf, buf_len, "%s", ps.key.c_str());
-      ++n;
-    }
-  return n;
-}
-
+int pf_ddpm_pack_missing(const pf_ddpm* u, char* buf, size_t buf_len) { return u ? u->wt.pack_missing(buf, buf_len) : set_error(PF_EINVAL, "null handle"); }
 int pf_ddpm_bind_weights(pf_ddpm* u, const void* dev_blob) {
-  PF_REQUIRE(u && dev_blob, "pf_ddpm_bind_weights: null argument");
-  PF_REQUIRE(((uintptr_t)dev_blob & 255) == 0, "pf_ddpm_bind_weights: blob must be 256-byte aligned");
-  u->wdev = (const float*)dev_blob;
-  return PF_OK;
+  PF_REQUIRE(u, "pf_ddpm_bind_weights: null argument");
+  return u->wt.bind("pf_ddpm_bind_weights", dev_blob, true);
 }
 
 int pf_ddpm_set_precision(pf_ddpm* u, int precision) {
@@ -506,35 +376,17 @@ int pf_ddpm_set_precision(pf_ddpm* u, int precision) {
 }
 int pf_ddpm_get_precision(const pf_ddpm* u) { return u ? u->precision : -1; }
 
-size_t pf_ddpm_workspace_bytes(const pf_ddpm* u, int batch) {
-  if (!u || batch <= 0) return 0;
-  size_t p, t;
-  plan_sizes(const_cast<pf_ddpm*>(u), batch, &p, &t, nullptr, nullptr);
-  return p + t;
-}
-int pf_ddpm_n_launches(const pf_ddpm* u, int batch) {
-  if (!u || batch <= 0) return 0;
-  size_t p, t; int n = 0;
-  plan_sizes(const_cast<pf_ddpm*>(u), batch, &p, &t, &n, nullptr);
-  return n;
-}
-double pf_ddpm_flops(const pf_ddpm* u, int batch) {
-  if (!u || batch <= 0) return 0.0;
-  size_t p, t; double f = 0.0;
-  plan_sizes(const_cast<pf_ddpm*>(u), batch, &p, &t, nullptr, &f);
-  return f;
-}
+size_t pf_ddpm_workspace_bytes(const pf_ddpm* u, int batch) { return (u && batch > 0) ? ddpm_plan(make_ctx(u, batch)).bytes() : 0; }
+int pf_ddpm_n_launches(const pf_ddpm* u, int batch) { return (u && batch > 0) ? ddpm_plan(make_ctx(u, batch)).n_launch : 0; }
+double pf_ddpm_flops(const pf_ddpm* u, int batch) { return (u && batch > 0) ? ddpm_plan(make_ctx(u, batch)).flops : 0.0; }
 
 int pf_ddpm_forward(pf_ddpm* u, const float* x, const int64_t* t, int batch, float* eps, void* workspace, size_t workspace_bytes, void* stream) {
   PF_REQUIRE(u && x && t && eps && workspace && batch > 0, "pf_ddpm_forward: bad arguments");
-  if (!u->wdev) return set_error(PF_ESTATE, "pf_ddpm_forward: weights not bound (call pf_ddpm_bind_weights)");
-  PF_REQUIRE(((uintptr_t)workspace & 255) == 0, "pf_ddpm_forward: workspace must be 256-byte aligned");
-  size_t p, tmp;
-  plan_sizes(u, batch, &p, &tmp, nullptr, nullptr);
-  if (workspace_bytes < p + tmp) return set_error(PF_EINVAL, "pf_ddpm_forward: workspace too small (%zu < %zu)", workspace_bytes, p + tmp);
-  DCtx c{};
-  c.u = u; c.s = (hipStream_t)stream; c.dry = false; c.base = (char*)workspace; c.temp_base = p;
-  c.B = batch; c.W = u->wdev; c.rc = PF_OK;
+  if (!u->wt.wdev) return set_error(PF_ESTATE, "pf_ddpm_forward: weights not bound (call pf_ddpm_bind_weights)");
+  DCtx c = make_ctx(u, batch);
+  const int rc = c.use_workspace("pf_ddpm_forward", workspace, workspace_bytes, ddpm_plan(c));
+  if (rc != PF_OK) return rc;
+  c.s = (hipStream_t)stream; c.W = u->wt.wdev;
   return run(u, c, x, t, eps);
 }
 

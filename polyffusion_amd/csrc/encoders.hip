@@ -6,31 +6,19 @@
 // accepted at pack time (checkpoint compatibility) and ignored.  Weights keep their torch
 // row-major layout; every contraction is the batched mat-vec kernel (weights stream once per
 // 8 samples), the recurrence is one mat-vec + one gate kernel per time step.
-#include <string.h>
-#include <map>
 #include <memory>
 #include <string>
 #include <vector>
-#include "pf_internal.h"
+#include "plan.h"
 
 using namespace pf;
 
 struct pf_encoder {
   int kind, input_dim, emb, hidden, z, nch;
-  struct P { std::string key; std::vector<int64_t> shape; size_t off; bool packed; bool used; };
-  std::vector<P> params;
-  std::map<std::string, int> index;
-  size_t blob_floats = 0;
-  const float* wdev = nullptr;
-  size_t add(const std::string& key, std::vector<int64_t> shape, bool used = true) {
-    size_t n = 1; for (auto s : shape) n *= (size_t)s;
-    size_t off = blob_floats;
-    if (used) blob_floats += (n + 63) / 64 * 64;
-    index[key] = (int)params.size();
-    params.push_back(P{key, shape, off, false, used});
-    return off;
-  }
-  size_t off(const std::string& key) const { return params[index.at(key)].off; }
+  WeightTable wt;
+  void add(const std::string& key, std::vector<int64_t> shape) { wt.raw(key, std::move(shape)); }
+  void add_unused(const std::string& key, std::vector<int64_t> shape) { wt.add(key, std::move(shape)).optional = true; }
+  size_t off(const std::string& key) const { return wt.params[wt.index.at(key)].dests[0].off; }
 };
 
 extern "C" {
@@ -60,8 +48,8 @@ int pf_encoder_create(int kind, int input_dim, int emb_size, int hidden_dim, int
     }
     e->add("linear_mu.weight", {z_dim, 2 * hidden_dim});
     e->add("linear_mu.bias", {z_dim});
-    e->add("linear_std.weight", {z_dim, 2 * hidden_dim}, false);
-    e->add("linear_std.bias", {z_dim}, false);
+    e->add_unused("linear_std.weight", {z_dim, 2 * hidden_dim});
+    e->add_unused("linear_std.bias", {z_dim});
     *out = e.release();
     return PF_OK;
   }
@@ -83,44 +71,24 @@ int pf_encoder_create(int kind, int input_dim, int emb_size, int hidden_dim, int
   }
   e->add("linear_mu.weight", {z_dim, 2 * hidden_dim});
   e->add("linear_mu.bias", {z_dim});
-  e->add("linear_var.weight", {z_dim, 2 * hidden_dim}, false);
-  e->add("linear_var.bias", {z_dim}, false);
+  e->add_unused("linear_var.weight", {z_dim, 2 * hidden_dim});
+  e->add_unused("linear_var.bias", {z_dim});
   *out = e.release();
   return PF_OK;
 }
 
 void pf_encoder_destroy(pf_encoder* e) { delete e; }
-size_t pf_encoder_weight_bytes(const pf_encoder* e) { return e ? e->blob_floats * sizeof(float) : 0; }
+size_t pf_encoder_weight_bytes(const pf_encoder* e) { return e ? e->wt.blob_floats * sizeof(float) : 0; }
 
 int pf_encoder_pack_param(pf_encoder* e, const char* key, const float* src, const int64_t* shape, int ndim, void* host_blob) {
-  PF_REQUIRE(e && key && src && shape && host_blob, "pf_encoder_pack_param: null argument");
-  auto it = e->index.find(key);
-  if (it == e->index.end()) return set_error(PF_ENOTFOUND, "unexpected key '%s' (not a parameter of this encoder)", key);
-  pf_encoder::P& p = e->params[it->second];
-  bool ok = ndim == (int)p.shape.size();
-  size_t n = 1;
-  for (int d = 0; ok && d < ndim; ++d) { ok = shape[d] == p.shape[d]; n *= (size_t)shape[d]; }
-  if (!ok) return set_error(PF_EINVAL, "size mismatch for '%s'", key);
-  if (p.used) memcpy((float*)host_blob + p.off, src, n * sizeof(float));
-  p.packed = true;
-  return PF_OK;
+  PF_REQUIRE(e, "pf_encoder_pack_param: null argument");
+  return e->wt.pack_param("pf_encoder_pack_param", "encoder", key, src, shape, ndim, host_blob);
 }
-
-int pf_encoder_pack_missing(const pf_encoder* e, char* buf, size_t buf_len) {
-  if (!e) return set_error(PF_EINVAL, "null handle");
-  int n = 0;
-  for (auto& p : e->params)
-    if (!p.packed && p.used) {
-      if (n == 0 && buf && buf_len) snprintf(buf, buf_len, "%s", p.key.c_str());
-      ++n;
-    }
-  return n;
-}
-
+int pf_encoder_pack_missing(const pf_encoder* e, char* buf, size_t buf_len) { return e ? e->wt.pack_missing(buf, buf_len) : set_error(PF_EINVAL, "null handle"); }
+// (no alignment requirement, unlike the UNets: an encoder blob may be a slice of a larger buffer)
 int pf_encoder_bind_weights(pf_encoder* e, const void* dev_blob) {
-  PF_REQUIRE(e && dev_blob, "pf_encoder_bind_weights: null argument");
-  e->wdev = (const float*)dev_blob;
-  return PF_OK;
+  PF_REQUIRE(e, "pf_encoder_bind_weights: null argument");
+  return e->wt.bind("pf_encoder_bind_weights", dev_blob, false);
 }
 
 static size_t enc_ws_floats(const pf_encoder* e, int B, int T) {
@@ -147,7 +115,7 @@ size_t pf_encoder_workspace_bytes(const pf_encoder* e, int batch) {
 int pf_encoder_forward(pf_encoder* e, const float* x, int batch, int n_step, float* mu, void* workspace, size_t workspace_bytes,
                        void* stream) {
   PF_REQUIRE(e && x && mu && workspace && batch > 0, "pf_encoder_forward: bad arguments");
-  if (!e->wdev) return set_error(PF_ESTATE, "pf_encoder_forward: weights not bound");
+  if (!e->wt.wdev) return set_error(PF_ESTATE, "pf_encoder_forward: weights not bound");
   hipStream_t s = (hipStream_t)stream;
   const int B = batch, H = e->hidden;
   int T = n_step, gru_in = e->input_dim;
@@ -158,7 +126,7 @@ int pf_encoder_forward(pf_encoder* e, const float* x, int batch, int n_step, flo
     const int S = T, E = e->emb, Hn = e->nch, N = B * 32;
     PF_REQUIRE(S <= 32, "pf_encoder_forward: at most 32 simultaneous notes");
     PF_REQUIRE(workspace_bytes >= enc_ws_floats(e, B, S) * sizeof(float), "pf_encoder_forward: workspace too small");
-    const float* W = e->wdev;
+    const float* W = e->wt.wdev;
     float* ws = (float*)workspace;
     auto take = [&](size_t n) { float* p = ws; ws += (n + 63) / 64 * 64; return p; };
     float* emb = take((size_t)N * S * E);
@@ -206,7 +174,7 @@ int pf_encoder_forward(pf_encoder* e, const float* x, int batch, int n_step, flo
   }
   if (e->kind == PF_ENC_TEXTURE) { T = 8; gru_in = e->emb; }
   PF_REQUIRE(workspace_bytes >= enc_ws_floats(e, B, T) * sizeof(float), "pf_encoder_forward: workspace too small");
-  const float* W = e->wdev;
+  const float* W = e->wt.wdev;
   float* ws = (float*)workspace;
   auto take = [&](size_t n) { float* p = ws; ws += (n + 63) / 64 * 64; return p; };
   const float* seq = x;  // [B][T][gru_in]

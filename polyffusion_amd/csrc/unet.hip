@@ -9,10 +9,9 @@
 #include <stdarg.h>
 #include <string.h>
 #include <algorithm>
-#include <map>
 #include <memory>
 #include <vector>
-#include "pf_internal.h"
+#include "plan.h"
 
 namespace pf {
 
@@ -26,10 +25,6 @@ int set_error(int code, const char* fmt, ...) {
   g_err = buf;
   return code;
 }
-
-enum DestKind { D_RAW = 0, D_GEMM = 1, D_GEGLU_W = 2, D_GEGLU_B = 3, D_CONVOUT = 4, D_UPFOLD = 5, D_WINO = 6 };
-struct Dest { int kind; size_t off; int taps, K, N, Npad, n_off; };
-struct ParamSpec { std::string key; std::vector<int64_t> shape; std::vector<Dest> dests; bool packed = false; };
 
 struct Layer {
   int kind;  // 0 conv_in, 1 res, 2 st, 3 down, 4 up
@@ -58,9 +53,7 @@ struct pf_unet {
   Block mid;
   std::vector<int> skip_ch;
   int final_ch = 0, n_st = 0, sum_emb = 0, d_t = 0;
-  std::vector<ParamSpec> params;
-  std::map<std::string, int> index;
-  size_t blob_floats = 0;
+  WeightTable wt;
   size_t te_w0, te_b0, te_w2, te_b2, emb_w, emb_b, out_g, out_b, out_w, out_bias, in_w, in_b;
   // n_cond == 1 cross-attention collapse: to_v / to_out / bias of ALL transformer blocks, contiguous
   size_t cross_v = 0, cross_o = 0, cross_b = 0;
@@ -69,146 +62,115 @@ struct pf_unet {
   int cross_c = 0;
   int cross_cursor = 0;
   size_t cross_o_cursor = 0;
-  const float* wdev = nullptr;
   void* amax_slot = nullptr;    // pf_unet_track_absmax: caller-owned device word, nullptr = off
   int opt[PF_OPT_COUNT] = {PF_OPT_AUTO, PF_OPT_AUTO, PF_OPT_AUTO, PF_OPT_AUTO, PF_OPT_AUTO};   // pf_unet_set_option
-  // profiling
   int precision = PF_PREC_F32;
   bool profiling = false;
-  std::vector<hipEvent_t> ev;
-  std::vector<int> pkind;
-  std::vector<double> pflops, pdirect;   // per launch: operations executed / operations of the direct form (differ for Winograd launches)
-  int n_prof = 0;
-
-  size_t alloc(size_t nfloats) { size_t o = blob_floats; blob_floats += (nfloats + 63) / 64 * 64; return o; }
-  ParamSpec& add(const std::string& key, std::vector<int64_t> shape) {
-    index[key] = (int)params.size();
-    params.push_back(ParamSpec{key, shape, {}, false});
-    return params.back();
-  }
-  size_t add_raw(const std::string& key, std::vector<int64_t> shape) {
-    size_t n = 1; for (auto s : shape) n *= (size_t)s;
-    size_t off = alloc(n);
-    add(key, shape).dests.push_back(Dest{D_RAW, off, 1, 0, 0, 0, 0});
-    return off;
-  }
-  // raw copy into a pre-allocated region at a float offset
-  void add_raw_at(const std::string& key, std::vector<int64_t> shape, size_t off) {
-    add(key, shape).dests.push_back(Dest{D_RAW, off, 1, 0, 0, 0, 0});
-  }
-  static size_t gemm_floats(int taps, int K, int N) { return (size_t)taps * K * ((N + 63) / 64 * 64); }
-  // every GEMM weight is stored twice, back to back: fp32 packing, then the bf16x3 packing (same byte count)
-  static size_t gemm_alloc(int taps, int K, int N) { return 2 * gemm_floats(taps, K, N); }
-  size_t add_gemm(const std::string& key, int N, int K, int taps) {
-    size_t off = alloc(gemm_alloc(taps, K, N));
-    std::vector<int64_t> shape = taps == 1 ? std::vector<int64_t>{N, K} : std::vector<int64_t>{N, K, 3, 3};
-    add(key, shape).dests.push_back(Dest{D_GEMM, off, taps, K, N, (N + 63) / 64 * 64, 0});
-    return off;
-  }
+  Profiler prof;   // records of the last profiled forward
 };
 
 namespace pf {
 
 static void build_res(pf_unet* u, const std::string& p, Layer& L) {
   const int ci = L.cin, co = L.cout;
-  L.gn1_g = u->add_raw(p + ".in_layers.0.weight", {ci});
-  L.gn1_b = u->add_raw(p + ".in_layers.0.bias", {ci});
-  L.w1 = u->add_gemm(p + ".in_layers.2.weight", co, ci, 9);
+  L.gn1_g = u->wt.raw(p + ".in_layers.0.weight", {ci});
+  L.gn1_b = u->wt.raw(p + ".in_layers.0.bias", {ci});
+  L.w1 = u->wt.gemm(p + ".in_layers.2.weight", co, ci, 9);
   // the Winograd F(2x2, 3x3) packing beside it where the fused form can run (conv_wino.hip: 16x16-pixel tiles, 64-channel blocks)
   const bool wino_ok = L.hw_h >= 32 && L.hw_w >= 32 && L.hw_h % 16 == 0 && L.hw_w % 16 == 0 && co % 64 == 0 && ci % 32 == 0 && ci <= 1024;
   if (wino_ok) {
-    L.wino1 = u->alloc((size_t)16 * ci * co);
-    u->params.back().dests.push_back(Dest{D_WINO, L.wino1, 9, ci, co, co, 0});
+    L.wino1 = u->wt.alloc((size_t)16 * ci * co);
+    u->wt.params.back().dests.push_back(Dest{D_WINO, L.wino1, 9, ci, co, co, 0});
   }
-  L.b1 = u->add_raw(p + ".in_layers.2.bias", {co});
+  L.b1 = u->wt.raw(p + ".in_layers.2.bias", {co});
   L.emb_off = u->sum_emb;
   u->sum_emb += co;
-  L.gn2_g = u->add_raw(p + ".out_layers.0.weight", {co});
-  L.gn2_b = u->add_raw(p + ".out_layers.0.bias", {co});
-  L.w2 = u->add_gemm(p + ".out_layers.3.weight", co, co, 9);
+  L.gn2_g = u->wt.raw(p + ".out_layers.0.weight", {co});
+  L.gn2_b = u->wt.raw(p + ".out_layers.0.bias", {co});
+  L.w2 = u->wt.gemm(p + ".out_layers.3.weight", co, co, 9);
   if (wino_ok && ci == co) {   // (a channel-changing block folds its 1x1 skip projection into this conv: direct form only)
-    L.wino2 = u->alloc((size_t)16 * co * co);
-    u->params.back().dests.push_back(Dest{D_WINO, L.wino2, 9, co, co, co, 0});
+    L.wino2 = u->wt.alloc((size_t)16 * co * co);
+    u->wt.params.back().dests.push_back(Dest{D_WINO, L.wino2, 9, co, co, co, 0});
   }
-  L.b2 = u->add_raw(p + ".out_layers.3.bias", {co});
+  L.b2 = u->wt.raw(p + ".out_layers.3.bias", {co});
   if (ci != co) {
-    L.wskip = u->add_gemm(p + ".skip_connection.weight", co, ci, 1);
-    u->params.back().shape = {co, ci, 1, 1};
-    L.bskip = u->add_raw(p + ".skip_connection.bias", {co});
+    L.wskip = u->wt.gemm(p + ".skip_connection.weight", co, ci, 1);
+    u->wt.params.back().shape = {co, ci, 1, 1};
+    L.bskip = u->wt.raw(p + ".skip_connection.bias", {co});
   }
 }
 
 static void build_st(pf_unet* u, const std::string& p, Layer& L) {
   const int C = L.cin, dc = u->cfg.d_cond;
   L.st_index = u->n_st++;
-  L.norm_g = u->add_raw(p + ".norm.weight", {C});
-  L.norm_b = u->add_raw(p + ".norm.bias", {C});
-  L.pin_w = u->add_gemm(p + ".proj_in.weight", C, C, 1);
-  u->params.back().shape = {C, C, 1, 1};
-  L.pin_b = u->add_raw(p + ".proj_in.bias", {C});
+  L.norm_g = u->wt.raw(p + ".norm.weight", {C});
+  L.norm_b = u->wt.raw(p + ".norm.bias", {C});
+  L.pin_w = u->wt.gemm(p + ".proj_in.weight", C, C, 1);
+  u->wt.params.back().shape = {C, C, 1, 1};
+  L.pin_b = u->wt.raw(p + ".proj_in.bias", {C});
   for (int i = 0; i < u->cfg.tf_layers; ++i) {
     Layer::TB t{};
     const std::string tb = p + ".transformer_blocks." + std::to_string(i);
     // attn1: q,k,v fused into one [C -> 3C] matrix
-    t.qkv = u->alloc(pf_unet::gemm_alloc(1, C, 3 * C));
+    t.qkv = u->wt.alloc_gemm(1, C, 3 * C);
     const char* nm[3] = {".attn1.to_q.weight", ".attn1.to_k.weight", ".attn1.to_v.weight"};
     for (int j = 0; j < 3; ++j)
-      u->add(tb + nm[j], {C, C}).dests.push_back(Dest{D_GEMM, t.qkv, 1, C, C, (3 * C + 63) / 64 * 64, j * C});
-    t.o1w = u->add_gemm(tb + ".attn1.to_out.0.weight", C, C, 1);
-    t.o1b = u->add_raw(tb + ".attn1.to_out.0.bias", {C});
+      u->wt.add(tb + nm[j], {C, C}).dests.push_back(Dest{D_GEMM, t.qkv, 1, C, C, (3 * C + 63) / 64 * 64, j * C});
+    t.o1w = u->wt.gemm(tb + ".attn1.to_out.0.weight", C, C, 1);
+    t.o1b = u->wt.raw(tb + ".attn1.to_out.0.bias", {C});
     // attn2: general (n_cond > 1) form + collapsed (n_cond == 1) raw form of to_v / to_out
-    t.q2 = u->add_gemm(tb + ".attn2.to_q.weight", C, C, 1);
-    t.kv2 = u->alloc(pf_unet::gemm_alloc(1, dc, 2 * C));
-    u->add(tb + ".attn2.to_k.weight", {C, dc}).dests.push_back(Dest{D_GEMM, t.kv2, 1, dc, C, (2 * C + 63) / 64 * 64, 0});
+    t.q2 = u->wt.gemm(tb + ".attn2.to_q.weight", C, C, 1);
+    t.kv2 = u->wt.alloc_gemm(1, dc, 2 * C);
+    u->wt.add(tb + ".attn2.to_k.weight", {C, dc}).dests.push_back(Dest{D_GEMM, t.kv2, 1, dc, C, (2 * C + 63) / 64 * 64, 0});
     {
-      ParamSpec& ps = u->add(tb + ".attn2.to_v.weight", {C, dc});
+      Param& ps = u->wt.add(tb + ".attn2.to_v.weight", {C, dc});
       ps.dests.push_back(Dest{D_GEMM, t.kv2, 1, dc, C, (2 * C + 63) / 64 * 64, C});
       t.cross_off = u->cross_cursor;
       u->cross_cursor += C;
       t.v2raw = u->cross_v + (size_t)t.cross_off * dc;
-      u->params[u->index[tb + ".attn2.to_v.weight"]].dests.push_back(Dest{D_RAW, t.v2raw, 1, 0, 0, 0, 0});
+      ps.dests.push_back(Dest{D_RAW, t.v2raw, 1, 0, 0, 0, 0});
     }
-    t.o2w = u->add_gemm(tb + ".attn2.to_out.0.weight", C, C, 1);
+    t.o2w = u->wt.gemm(tb + ".attn2.to_out.0.weight", C, C, 1);
     t.o2raw = u->cross_o + u->cross_o_cursor;
     u->cross_o_cursor += (size_t)C * C;
-    u->params.back().dests.push_back(Dest{D_RAW, t.o2raw, 1, 0, 0, 0, 0});
-    t.o2b = u->add_raw(tb + ".attn2.to_out.0.bias", {C});
-    u->params.back().dests.push_back(Dest{D_RAW, u->cross_b + (size_t)t.cross_off, 1, 0, 0, 0, 0});
-    t.n1g = u->add_raw(tb + ".norm1.weight", {C}); t.n1b = u->add_raw(tb + ".norm1.bias", {C});
-    t.n2g = u->add_raw(tb + ".norm2.weight", {C}); t.n2b = u->add_raw(tb + ".norm2.bias", {C});
-    t.n3g = u->add_raw(tb + ".norm3.weight", {C}); t.n3b = u->add_raw(tb + ".norm3.bias", {C});
-    t.ff1w = u->alloc(pf_unet::gemm_alloc(1, C, 8 * C));
-    u->add(tb + ".ff.net.0.proj.weight", {8 * C, C}).dests.push_back(Dest{D_GEGLU_W, t.ff1w, 1, C, 8 * C, 8 * C, 0});
-    t.ff1b = u->alloc((size_t)8 * C);
-    u->add(tb + ".ff.net.0.proj.bias", {8 * C}).dests.push_back(Dest{D_GEGLU_B, t.ff1b, 1, 0, 8 * C, 8 * C, 0});
-    t.ff2w = u->add_gemm(tb + ".ff.net.2.weight", C, 4 * C, 1);
-    t.ff2b = u->add_raw(tb + ".ff.net.2.bias", {C});
+    u->wt.params.back().dests.push_back(Dest{D_RAW, t.o2raw, 1, 0, 0, 0, 0});
+    t.o2b = u->wt.raw(tb + ".attn2.to_out.0.bias", {C});
+    u->wt.params.back().dests.push_back(Dest{D_RAW, u->cross_b + (size_t)t.cross_off, 1, 0, 0, 0, 0});
+    t.n1g = u->wt.raw(tb + ".norm1.weight", {C}); t.n1b = u->wt.raw(tb + ".norm1.bias", {C});
+    t.n2g = u->wt.raw(tb + ".norm2.weight", {C}); t.n2b = u->wt.raw(tb + ".norm2.bias", {C});
+    t.n3g = u->wt.raw(tb + ".norm3.weight", {C}); t.n3b = u->wt.raw(tb + ".norm3.bias", {C});
+    t.ff1w = u->wt.alloc_gemm(1, C, 8 * C);
+    u->wt.add(tb + ".ff.net.0.proj.weight", {8 * C, C}).dests.push_back(Dest{D_GEGLU_W, t.ff1w, 1, C, 8 * C, 8 * C, 0});
+    t.ff1b = u->wt.alloc((size_t)8 * C);
+    u->wt.add(tb + ".ff.net.0.proj.bias", {8 * C}).dests.push_back(Dest{D_GEGLU_B, t.ff1b, 1, 0, 8 * C, 8 * C, 0});
+    t.ff2w = u->wt.gemm(tb + ".ff.net.2.weight", C, 4 * C, 1);
+    t.ff2b = u->wt.raw(tb + ".ff.net.2.bias", {C});
     L.tbs.push_back(t);
   }
-  L.pout_w = u->add_gemm(p + ".proj_out.weight", C, C, 1);
-  u->params.back().shape = {C, C, 1, 1};
-  L.pout_b = u->add_raw(p + ".proj_out.bias", {C});
+  L.pout_w = u->wt.gemm(p + ".proj_out.weight", C, C, 1);
+  u->wt.params.back().shape = {C, C, 1, 1};
+  L.pout_b = u->wt.raw(p + ".proj_out.bias", {C});
 }
 
 static void build_layer(pf_unet* u, const std::string& p, Layer& L) {
   switch (L.kind) {
     case 0:
-      u->in_w = u->add_raw(p + ".weight", {L.cout, L.cin, 3, 3});
-      u->in_b = u->add_raw(p + ".bias", {L.cout});
+      u->in_w = u->wt.raw(p + ".weight", {L.cout, L.cin, 3, 3});
+      u->in_b = u->wt.raw(p + ".bias", {L.cout});
       break;
     case 1: build_res(u, p, L); break;
     case 2: build_st(u, p, L); break;
     case 3:
-      L.w1 = u->add_gemm(p + ".op.weight", L.cout, L.cin, 9);
-      L.b1 = u->add_raw(p + ".op.bias", {L.cout});
+      L.w1 = u->wt.gemm(p + ".op.weight", L.cout, L.cin, 9);
+      L.b1 = u->wt.raw(p + ".op.bias", {L.cout});
       break;
     case 4:
-      L.w1 = u->add_gemm(p + ".conv.weight", L.cout, L.cin, 9);
+      L.w1 = u->wt.gemm(p + ".conv.weight", L.cout, L.cin, 9);
       if (L.cin % 8 == 0) {   // bf16x3 mode runs the layer as four 2x2 convs on the source grid
-        L.wfold = u->alloc(pf_unet::gemm_floats(16, L.cin, L.cout));
-        u->params.back().dests.push_back(Dest{D_UPFOLD, L.wfold, 16, L.cin, L.cout, (L.cout + 63) / 64 * 64, 0});
+        L.wfold = u->wt.alloc(gemm_floats(16, L.cin, L.cout));
+        u->wt.params.back().dests.push_back(Dest{D_UPFOLD, L.wfold, 16, L.cin, L.cout, (L.cout + 63) / 64 * 64, 0});
       }
-      L.b1 = u->add_raw(p + ".conv.bias", {L.cout});
+      L.b1 = u->wt.raw(p + ".conv.bias", {L.cout});
       break;
   }
 }
@@ -226,10 +188,10 @@ static int build(pf_unet* u) {
   PF_REQUIRE(c.n_heads > 0 && c.tf_layers >= 1 && c.d_cond > 0 && c.d_cond % 4 == 0, "unet: bad attention config");
   PF_REQUIRE(c.img_h % (1 << (c.n_levels - 1)) == 0 && c.img_w % (1 << (c.n_levels - 1)) == 0, "unet: image size must be divisible by 2^(levels-1)");
   u->d_t = c.channels * 4;
-  u->te_w0 = u->add_raw("time_embed.0.weight", {u->d_t, c.channels});
-  u->te_b0 = u->add_raw("time_embed.0.bias", {u->d_t});
-  u->te_w2 = u->add_raw("time_embed.2.weight", {u->d_t, u->d_t});
-  u->te_b2 = u->add_raw("time_embed.2.bias", {u->d_t});
+  u->te_w0 = u->wt.raw("time_embed.0.weight", {u->d_t, c.channels});
+  u->te_b0 = u->wt.raw("time_embed.0.bias", {u->d_t});
+  u->te_w2 = u->wt.raw("time_embed.2.weight", {u->d_t, u->d_t});
+  u->te_b2 = u->wt.raw("time_embed.2.bias", {u->d_t});
 
   int ch = c.channels;
   std::vector<int> stack;
@@ -291,9 +253,9 @@ static int build(pf_unet* u) {
     for (auto& b : u->in_blocks) for (auto& L : b.layers) visit(L);
     for (auto& L : u->mid.layers) visit(L);
     for (auto& b : u->out_blocks) for (auto& L : b.layers) visit(L);
-    u->cross_v = u->alloc((size_t)u->cross_total * c.d_cond);
-    u->cross_o = u->alloc(o_floats);
-    u->cross_b = u->alloc((size_t)u->cross_total);
+    u->cross_v = u->wt.alloc((size_t)u->cross_total * c.d_cond);
+    u->cross_o = u->wt.alloc(o_floats);
+    u->cross_b = u->wt.alloc((size_t)u->cross_total);
   }
 
   // parameter table in the reference key order
@@ -304,19 +266,19 @@ static int build(pf_unet* u) {
   for (size_t bi = 0; bi < u->out_blocks.size(); ++bi)
     for (size_t li = 0; li < u->out_blocks[bi].layers.size(); ++li)
       build_layer(u, "output_blocks." + std::to_string(bi) + "." + std::to_string(li), u->out_blocks[bi].layers[li]);
-  u->out_g = u->add_raw("out.0.weight", {ch});
-  u->out_b = u->add_raw("out.0.bias", {ch});
-  u->out_w = u->alloc((size_t)c.out_channels * 9 * ch);
-  u->add("out.2.weight", {c.out_channels, ch, 3, 3}).dests.push_back(Dest{D_CONVOUT, u->out_w, 9, ch, c.out_channels, 0, 0});
-  u->out_bias = u->add_raw("out.2.bias", {c.out_channels});
+  u->out_g = u->wt.raw("out.0.weight", {ch});
+  u->out_b = u->wt.raw("out.0.bias", {ch});
+  u->out_w = u->wt.alloc((size_t)c.out_channels * 9 * ch);
+  u->wt.add("out.2.weight", {c.out_channels, ch, 3, 3}).dests.push_back(Dest{D_CONVOUT, u->out_w, 9, ch, c.out_channels, 0, 0});
+  u->out_bias = u->wt.raw("out.2.bias", {c.out_channels});
 
   // all ResBlock emb_layers concatenated into one [sum_emb][d_t] matrix (+ bias) for a single mat-vec launch
-  u->emb_w = u->alloc((size_t)u->sum_emb * u->d_t);
-  u->emb_b = u->alloc((size_t)u->sum_emb);
+  u->emb_w = u->wt.alloc((size_t)u->sum_emb * u->d_t);
+  u->emb_b = u->wt.alloc((size_t)u->sum_emb);
   auto add_emb = [&](const std::string& p, Layer& L) {
     if (L.kind != 1) return;
-    u->add_raw_at(p + ".emb_layers.1.weight", {L.cout, u->d_t}, u->emb_w + (size_t)L.emb_off * u->d_t);
-    u->add_raw_at(p + ".emb_layers.1.bias", {L.cout}, u->emb_b + L.emb_off);
+    u->wt.raw_at(p + ".emb_layers.1.weight", {L.cout, u->d_t}, u->emb_w + (size_t)L.emb_off * u->d_t);
+    u->wt.raw_at(p + ".emb_layers.1.bias", {L.cout}, u->emb_b + L.emb_off);
   };
   for (size_t bi = 0; bi < u->in_blocks.size(); ++bi)
     for (size_t li = 0; li < u->in_blocks[bi].layers.size(); ++li)
@@ -328,57 +290,6 @@ static int build(pf_unet* u) {
   return PF_OK;
 }
 
-// ---- weight repacking (host) ----
-static void pack_gemm(float* dst, const float* src, int n_src, int K, int taps, int Npad, int n_off) {
-  for (int n = 0; n < n_src; ++n)
-    for (int k = 0; k < K; ++k)
-      for (int t = 0; t < taps; ++t)
-        dst[(((size_t)t * (K / 4) + k / 4) * Npad + n_off + n) * 4 + (k & 3)] = src[((size_t)n * K + k) * taps + t];
-}
-static inline int geglu_col(int n, int inner) {  // torch row n of ff.net.0.proj -> packed column
-  const int j = n < inner ? n : n - inner;
-  return 64 * (j / 32) + (n < inner ? 0 : 32) + (j % 32);
-}
-
-// (fp16 build only: bf16 pieces have fp32's range)
-#define X3_RANGE_MSG "%s: a weight exceeds what this library's fp16 split packing holds (|w| <= 255.8; weights are stored times 2^8): load the checkpoint with the default library (bf16x3 / f32)"
-static int pack_one(const ParamSpec& ps, const float* src, float* blob) {
-  size_t numel = 1; for (auto s : ps.shape) numel *= (size_t)s;
-  bool fits = true;
-  for (const Dest& d : ps.dests) {
-    float* dst = blob + d.off;
-    switch (d.kind) {
-      case D_RAW: memcpy(dst, src, numel * sizeof(float)); break;
-      case D_GEMM:
-        pack_gemm(dst, src, d.N, d.K, d.taps, d.Npad, d.n_off);
-        if (d.K % 8 == 0) fits = pack_gemm_bf3(dst + (size_t)d.taps * d.K * d.Npad, src, d.N, d.K, d.taps, d.Npad, d.n_off, nullptr) && fits;
-        break;
-      case D_UPFOLD: fits = pack_upfold_bf3(dst, src, d.N, d.K, d.Npad) && fits; break;
-      case D_WINO: fits = pack_wino_bf3(dst, src, d.N, d.K) && fits; break;
-      case D_GEGLU_W: {
-        const int inner = d.N / 2;
-        for (int n = 0; n < d.N; ++n)
-          for (int k = 0; k < d.K; ++k) dst[((size_t)(k / 4) * d.Npad + geglu_col(n, inner)) * 4 + (k & 3)] = src[(size_t)n * d.K + k];
-        std::vector<int> cm(d.N);
-        for (int n = 0; n < d.N; ++n) cm[n] = geglu_col(n, inner);
-        fits = pack_gemm_bf3(dst + (size_t)d.K * d.Npad, src, d.N, d.K, 1, d.Npad, 0, cm.data()) && fits;
-        break;
-      }
-      case D_GEGLU_B: {
-        const int inner = d.N / 2;
-        for (int n = 0; n < d.N; ++n) dst[geglu_col(n, inner)] = src[n];
-        break;
-      }
-      case D_CONVOUT:  // [Cout][Cin][3][3] -> [9][Cin][Cout]
-        for (int co = 0; co < d.N; ++co)
-          for (int ci = 0; ci < d.K; ++ci)
-            for (int t = 0; t < 9; ++t) dst[((size_t)t * d.K + ci) * d.N + co] = src[((size_t)co * d.K + ci) * 9 + t];
-        break;
-    }
-  }
-  return fits ? PF_OK : PF_EINVAL;
-}
-
 // ---- forward ----
 // A tensor in the workspace: NHWC data + (optionally) the per-tile channel statistics its producer emitted.
 struct Tn {
@@ -387,13 +298,9 @@ struct Tn {
   int bmod = 0;                            // > 0: the tensor (and its statistics) holds only bmod samples, shared by samples b and b + bmod (pf_unet_forward_cfg)
 };
 
-struct Ctx {
-  pf_unet* u; hipStream_t s; bool dry;
-  char* base; size_t persist_off, temp_base, temp_off, persist_max, temp_max;
-  int B, n_cond;
-  const float* W;
-  int n_launch;
-  int rc;
+struct Ctx : PlanCtx {
+  pf_unet* u = nullptr;
+  int n_cond = 0;
   // hoisted step-invariant prefix (pf_unet_prepared): supplied parts are not recomputed; dry runs only need to know WHETHER they are
   bool has_time = false, has_cross = false;
   const float* prep_time = nullptr; int prep_time_rows = 0; const float* prep_cross = nullptr;
@@ -402,33 +309,6 @@ struct Ctx {
   bool cfg_share = false, shared = false; int Bfull = 0;
   int x1mod(const Tn& x1) const { return (x1.c > 0 && x1.bmod > 0 && x1.bmod != B) ? x1.bmod : 0; }
 
-  float* palloc(size_t nfloats) {
-    size_t o = persist_off; persist_off += align_up(nfloats * 4, 256);
-    if (persist_off > persist_max) persist_max = persist_off;
-    return dry ? nullptr : (float*)(base + o);
-  }
-  float* talloc(size_t nfloats) {
-    size_t o = temp_off; temp_off += align_up(nfloats * 4, 256);
-    if (temp_off > temp_max) temp_max = temp_off;
-    return dry ? nullptr : (float*)(base + temp_base + o);
-  }
-  void treset() { temp_off = 0; }
-  const float* w(size_t off) const { return dry ? nullptr : W + off; }
-
-  void prof_begin(int kind, double flops, double direct = -1.0) {
-    ++n_launch;
-    if (dry || !u->profiling) return;
-    u->pdirect.push_back(direct < 0.0 ? flops : direct);
-    const size_t need = (size_t)(u->n_prof + 1) * 2;
-    while (u->ev.size() < need) { hipEvent_t e; (void)hipEventCreate(&e); u->ev.push_back(e); }
-    u->pkind.push_back(kind); u->pflops.push_back(flops);
-    (void)hipEventRecord(u->ev[(size_t)u->n_prof * 2], s);
-  }
-  void prof_end() {
-    if (dry || !u->profiling) return;
-    (void)hipEventRecord(u->ev[(size_t)u->n_prof * 2 + 1], s);
-    ++u->n_prof;
-  }
   // launch a conv/linear; when `stats` is given, the producer also emits per-tile channel statistics for a later GroupNorm
   // (buffer from the persistent or the temp region, matching the lifetime of the output tensor)
   void conv(pf_conv_args a, int kind, Tn* stats = nullptr, bool persist = true, const float* w_bf3 = nullptr) {
@@ -450,13 +330,11 @@ struct Ctx {
     }
     double direct = -1.0;
     if (a.wino) { pf_conv_args d = a; d.wino = 0; direct = conv_flops(d); }
-    prof_begin(kind, conv_flops(a), direct);
-    if (!dry && rc == PF_OK) {
-      if (w_bf3) a.w = w_bf3;                                                       // a packing of its own (folded upsampling conv)
-      else if (bf3) a.w = a.w + (size_t)a.ks * a.ks * cin_ * ((a.n + 63) / 64 * 64);  // second half of the region = bf16x3 packing
-      rc = launch_conv(a, s);
-    }
-    prof_end();
+    launch(kind, conv_flops(a), [&] {
+      if (w_bf3) a.w = w_bf3;                                        // a packing of its own (folded upsampling conv)
+      else if (bf3) a.w += split_offset(a.ks * a.ks, cin_, a.n);     // the region's split packing
+      return launch_conv(a, s);
+    }, 1, direct);
   }
   // GroupNorm scale/shift of concat(x0, x1) from the producers' tile statistics (no pass over the data).
   // `fuse_ok`: the consumer is a bf16x3 conv that can do this reduction in its own prologue (pf_conv_args.gn_*): worth it when a
@@ -495,39 +373,27 @@ struct Ctx {
     a.gn_gamma = w(r.g); a.gn_beta = w(r.b); a.gn_eps = r.eps; a.gn_groups = 32;
   }
   void gn_launch(const Tn& x0, const Tn& x1, int hw, float eps, size_t g, size_t b_, float* sc, float* sh) {
-    prof_begin(PF_K_GNSTAT, 0.0);
-    if (!dry && rc == PF_OK)
-      rc = launch_gn_finalize_tiles(x0.st, x0.nt, x0.c, x1.st, x1.nt, x1.c, B, hw, 32, eps, w(g), w(b_), sc, sh, s, x1mod(x1));
-    prof_end();
+    launch(PF_K_GNSTAT, 0.0, [&] { return launch_gn_finalize_tiles(x0.st, x0.nt, x0.c, x1.st, x1.nt, x1.c, B, hw, 32, eps, w(g), w(b_), sc, sh, s, x1mod(x1)); });
   }
   // statistics for a tensor whose producer emitted none (the stem conv output)
   void gn_partial(Tn& x, int hw) {
     const int ns = gn_nsplit(hw);
     float* sb = palloc((size_t)B * ns * x.c * 2);
-    prof_begin(PF_K_GNSTAT, 0.0);
-    if (!dry && rc == PF_OK) rc = launch_gn_partial(x.d, x.c, nullptr, 0, B, hw, sb, s);
-    prof_end();
+    launch(PF_K_GNSTAT, 0.0, [&] { return launch_gn_partial(x.d, x.c, nullptr, 0, B, hw, sb, s); });
     x.st = sb; x.nt = ns;
   }
   void lnp(const float* x, int rows, int c, size_t gamma, size_t beta, float* planes) {   // LayerNorm -> hi/lo planes
-    prof_begin(PF_K_LNSTAT, 0.0);
-    if (!dry && rc == PF_OK) rc = launch_ln_planes(x, rows, c, 1e-5f, w(gamma), w(beta), planes, s);
-    prof_end();
+    launch(PF_K_LNSTAT, 0.0, [&] { return launch_ln_planes(x, rows, c, 1e-5f, w(gamma), w(beta), planes, s); });
   }
   void ln(const float* x, int rows, int c, float* mu, float* rs) {
-    prof_begin(PF_K_LNSTAT, 0.0);
-    if (!dry && rc == PF_OK) rc = launch_ln_stats(x, rows, c, 1e-5f, mu, rs, s);
-    prof_end();
+    launch(PF_K_LNSTAT, 0.0, [&] { return launch_ln_stats(x, rows, c, 1e-5f, mu, rs, s); });
   }
 };
 
-static pf_conv_args conv_base(const float* x0, int c0, const float* x1, int c1, int B, int hin, int win, int ks,
-                              const float* wgt, int n, float* out) {
-  pf_conv_args a;
-  memset(&a, 0, sizeof a);
-  a.x0 = x0; a.c0 = c0; a.x1 = x1; a.c1 = c1; a.batch = B; a.hin = hin; a.win = win; a.ks = ks; a.stride = 1;
-  a.w = wgt; a.n = n; a.out = out; a.ld_out = n;
-  return a;
+static int device_copy(float* dst, const float* src, size_t nfloats, hipStream_t s) {
+  if (hipMemcpyAsync(dst, src, nfloats * sizeof(float), hipMemcpyDeviceToDevice, s) != hipSuccess)
+    return set_error(PF_EHIP, "pf_unet_forward_cfg: device copy failed");
+  return PF_OK;
 }
 
 static Tn run_res(Ctx& c, const Layer& L, const Tn& x0, const Tn& x1, int H, int W_, const float* tb_all) {
@@ -569,7 +435,7 @@ static Tn run_res(Ctx& c, const Layer& L, const Tn& x0, const Tn& x1, int H, int
     c.gn_attach(a, g2);
     if (fuse_skip) {
       a.skip_x0 = x0.d; a.skip_c0 = x0.c; a.skip_x1 = x1.d; a.skip_c1 = x1.c;
-      a.skip_w = c.dry ? (const void*)1 : (const void*)(c.w(L.wskip) + (size_t)ci * ((co + 63) / 64 * 64));   // its bf16x3 packing
+      a.skip_w = c.w_split(L.wskip, 1, ci, co);
       a.skip_bias = c.w(L.bskip);
       a.x1_bmod = c.x1mod(x1);
     } else {
@@ -639,12 +505,11 @@ static Tn run_st(Ctx& c, const Layer& L, const Tn& xin, int H, int W_, const flo
     int att_ns = 1;
     const size_t att_sf = planes ? attention_bf3_split_floats(B, nh, hw, &att_ns) : 0;
     float* att_scratch = att_sf ? c.talloc(att_sf) : nullptr;
-    c.prof_begin(PF_K_ATTN, 4.0 * B * nh * (double)hw * hw * dh);
-    if (att_sf && c.u->opt[PF_OPT_ATTN_WIDE] != PF_OPT_ON) ++c.n_launch;   // the merge
-    if (!c.dry && c.rc == PF_OK)
-      c.rc = planes ? launch_attention_bf3(qkv, nullptr, C, att, B, nh, hw, c.u->opt[PF_OPT_ATTN_WIDE], c.s, att_scratch, att_sf)   // att as hi/lo planes for the to_out GEMM
+    const bool merge = att_sf && c.u->opt[PF_OPT_ATTN_WIDE] != PF_OPT_ON;   // (a second, merging launch)
+    c.launch(PF_K_ATTN, 4.0 * B * nh * (double)hw * hw * dh, [&] {
+      return planes ? launch_attention_bf3(qkv, nullptr, C, att, B, nh, hw, c.u->opt[PF_OPT_ATTN_WIDE], c.s, att_scratch, att_sf)   // att as hi/lo planes for the to_out GEMM
                     : launch_attention(qkv, 3 * C, qkv + C, 3 * C, qkv + 2 * C, 3 * C, att, C, B, nh, dh, hw, hw, c.s);
-    c.prof_end();
+    }, merge ? 2 : 1);
     last_planes = planes && (i + 1 == L.tbs.size());
     const bool fuse_mlp = planes && mlp_fused_wanted(C, hw, M, c.u->opt[PF_OPT_MLP_FUSED]) && !c.u->amax_slot;
     {
@@ -668,9 +533,8 @@ static Tn run_st(Ctx& c, const Layer& L, const Tn& xin, int H, int W_, const flo
         pf_conv_args a = conv_base(cond, dc, nullptr, 0, B, 1, c.n_cond, 1, c.w(t.kv2), 2 * C, kv);
         c.conv(a, PF_K_GEMM);
       }
-      c.prof_begin(PF_K_ATTN, 4.0 * B * nh * (double)hw * c.n_cond * dh);
-      if (!c.dry && c.rc == PF_OK) c.rc = launch_attention(q2, C, kv, 2 * C, kv + C, 2 * C, att, C, B, nh, dh, hw, c.n_cond, c.s);
-      c.prof_end();
+      c.launch(PF_K_ATTN, 4.0 * B * nh * (double)hw * c.n_cond * dh,
+               [&] { return launch_attention(q2, C, kv, 2 * C, kv + C, 2 * C, att, C, B, nh, dh, hw, c.n_cond, c.s); });
       {
         pf_conv_args a = conv_base(att, C, nullptr, 0, B, 1, hw, 1, c.w(t.o2w), C, t2);
         a.bias = c.w(t.o2b); a.res = t1; a.ld_res = C;
@@ -686,20 +550,18 @@ static Tn run_st(Ctx& c, const Layer& L, const Tn& xin, int H, int W_, const flo
         // together with the 64-row-tile statistics the next GroupNorm reads
         const int nt = hw / 64;
         float* sb = c.palloc((size_t)B * nt * C * 2);
-        c.prof_begin(PF_K_GEMM, 2.0 * M * ((double)C * 8 * C + 4.0 * C * C + (double)C * C));
-        if (!c.dry && c.rc == PF_OK)
-          c.rc = launch_mlp_fused(t1, B, hw, c.w(t.n3g), c.w(t.n3b), 1e-5f, c.w(t.ff1w) + (size_t)C * 8 * C, c.w(t.ff1b),
-                                  c.w(t.ff2w) + (size_t)4 * C * C, c.w(t.ff2b), out, nullptr, c.s, c.w(L.pout_w) + (size_t)C * C, c.w(L.pout_b), x, sb);
-        c.prof_end();
+        c.launch(PF_K_GEMM, 2.0 * M * ((double)C * 8 * C + 4.0 * C * C + (double)C * C), [&] {
+          return launch_mlp_fused(t1, B, hw, c.w(t.n3g), c.w(t.n3b), 1e-5f, c.w_split(t.ff1w, 1, C, 8 * C), c.w(t.ff1b), c.w_split(t.ff2w, 1, 4 * C, C),
+                                  c.w(t.ff2b), out, nullptr, c.s, c.w_split(L.pout_w, 1, C, C), c.w(L.pout_b), x, sb);
+        });
         Tn ot;
         ot.d = out; ot.c = C; ot.st = sb; ot.nt = nt;
         return ot;
       }
-      c.prof_begin(PF_K_GEMM, 2.0 * M * ((double)C * 8 * C + 4.0 * C * C));
-      if (!c.dry && c.rc == PF_OK)
-        c.rc = launch_mlp_fused(t1, B, hw, c.w(t.n3g), c.w(t.n3b), 1e-5f, c.w(t.ff1w) + (size_t)C * 8 * C, c.w(t.ff1b),
-                                c.w(t.ff2w) + (size_t)4 * C * C, c.w(t.ff2b), t2, nullptr, c.s);
-      c.prof_end();
+      c.launch(PF_K_GEMM, 2.0 * M * ((double)C * 8 * C + 4.0 * C * C), [&] {
+        return launch_mlp_fused(t1, B, hw, c.w(t.n3g), c.w(t.n3b), 1e-5f, c.w_split(t.ff1w, 1, C, 8 * C), c.w(t.ff1b), c.w_split(t.ff2w, 1, 4 * C, C),
+                                c.w(t.ff2b), t2, nullptr, c.s);
+      });
       std::swap(t0, t2);
       continue;
     }
@@ -733,27 +595,19 @@ static Tn run_st(Ctx& c, const Layer& L, const Tn& xin, int H, int W_, const flo
   return ot;
 }
 
-static void small_launch(Ctx& c, int rc_in) { if (c.rc == PF_OK) c.rc = rc_in; }
-
 // n_cond == 1: cross[b] = to_out(to_v(cond[b])) + bias of EVERY transformer block (softmax over one key == 1, unet_attention.py:186-212):
 // two grouped mat-vec launches (one per block when the blocks differ in width).  Shared by the forward plan and pf_unet_prepare_cond.
 static void cross_bias_launches(pf_unet* u, Ctx& c, const float* cond, int B, float* cross, float* vtmp) {
   const int T = u->cross_total, dc = u->cfg.d_cond;
-  c.prof_begin(PF_K_SMALL, 0);
-  if (!c.dry) small_launch(c, launch_matvec(cond, dc, c.w(u->cross_v), nullptr, vtmp, T, B, T, dc, c.s));
-  c.prof_end();
+  c.launch(PF_K_SMALL, 0, [&] { return launch_matvec(cond, dc, c.w(u->cross_v), nullptr, vtmp, T, B, T, dc, c.s); });
   if (u->cross_uniform) {
-    c.prof_begin(PF_K_SMALL, 0);
-    if (!c.dry) small_launch(c, launch_matvec(vtmp, T, c.w(u->cross_o), c.w(u->cross_b), cross, T, B, T, u->cross_c, c.s, u->cross_c, u->cross_c));
-    c.prof_end();
+    c.launch(PF_K_SMALL, 0, [&] { return launch_matvec(vtmp, T, c.w(u->cross_o), c.w(u->cross_b), cross, T, B, T, u->cross_c, c.s, u->cross_c, u->cross_c); });
     return;
   }
   auto each_tb = [&](const Layer& L) {
     if (L.kind != 2) return;
     for (const Layer::TB& tb : L.tbs) {
-      c.prof_begin(PF_K_SMALL, 0);
-      if (!c.dry) small_launch(c, launch_matvec(vtmp + tb.cross_off, T, c.w(tb.o2raw), c.w(tb.o2b), cross + tb.cross_off, T, B, L.cin, L.cin, c.s));
-      c.prof_end();
+      c.launch(PF_K_SMALL, 0, [&] { return launch_matvec(vtmp + tb.cross_off, T, c.w(tb.o2raw), c.w(tb.o2b), cross + tb.cross_off, T, B, L.cin, L.cin, c.s); });
     }
   };
   for (auto& b : u->in_blocks) for (auto& L : b.layers) each_tb(L);
@@ -773,8 +627,8 @@ static int run(pf_unet* u, Ctx& c, const float* x, const int64_t* t, const float
     tb_all = c.prep_time; c.t_rows = t;
   } else {
     float* tb = const_cast<float*>(tb_all);
-    c.prof_begin(PF_K_SMALL, 0); if (!c.dry) small_launch(c, launch_time_embed(t, c.w(u->te_w0), c.w(u->te_b0), c.w(u->te_w2), c.w(u->te_b2), tsilu, B, cfg.channels, u->d_t, c.s)); c.prof_end();
-    c.prof_begin(PF_K_SMALL, 0); if (!c.dry) small_launch(c, launch_matvec(tsilu, u->d_t, c.w(u->emb_w), c.w(u->emb_b), tb, u->sum_emb, B, u->sum_emb, u->d_t, c.s)); c.prof_end();
+    c.launch(PF_K_SMALL, 0, [&] { return launch_time_embed(t, c.w(u->te_w0), c.w(u->te_b0), c.w(u->te_w2), c.w(u->te_b2), tsilu, B, cfg.channels, u->d_t, c.s); });
+    c.launch(PF_K_SMALL, 0, [&] { return launch_matvec(tsilu, u->d_t, c.w(u->emb_w), c.w(u->emb_b), tb, u->sum_emb, B, u->sum_emb, u->d_t, c.s); });
   }
   const float* cross_all = nullptr;  // [B][cross_total]: to_out(to_v(c)) + bias of every transformer block
   if (c.n_cond == 1 && u->cross_total > 0) {
@@ -795,12 +649,8 @@ static int run(pf_unet* u, Ctx& c, const float* x, const int64_t* t, const float
   if (c.cfg_share) { c.Bfull = c.B; c.B = c.B / 2; c.shared = true; }
   auto dup_rows = [&](const float* src, size_t floats_per_half) -> const float* {
     float* dst = c.palloc(2 * floats_per_half);
-    for (int h = 0; h < 2; ++h) {
-      c.prof_begin(PF_K_SMALL, 0);
-      if (!c.dry && c.rc == PF_OK && hipMemcpyAsync(dst + h * floats_per_half, src, floats_per_half * sizeof(float), hipMemcpyDeviceToDevice, c.s) != hipSuccess)
-        c.rc = set_error(PF_EHIP, "pf_unet_forward_cfg: device copy failed");
-      c.prof_end();
-    }
+    for (int h = 0; h < 2; ++h)
+      c.launch(PF_K_SMALL, 0, [&] { return device_copy(dst + h * floats_per_half, src, floats_per_half, c.s); });
     return dst;
   };
   auto leave_shared_phase = [&](Tn& a0, int h, int w_) {
@@ -824,9 +674,7 @@ static int run(pf_unet* u, Ctx& c, const float* x, const int64_t* t, const float
           // otherwise a statistics pass over the output follows
           const int nst = launch_conv_in_stats_tiles(L.cin, L.cout, H, W_);
           float* sb = nst ? c.palloc((size_t)B * nst * L.cout * 2) : nullptr;
-          c.prof_begin(PF_K_SMALL, 2.0 * B * H * W_ * 9.0 * L.cin * L.cout);
-          if (!c.dry) small_launch(c, launch_conv_in(x, c.w(u->in_w), c.w(u->in_b), od, B, L.cin, L.cout, H, W_, c.s, sb));
-          c.prof_end();
+          c.launch(PF_K_SMALL, 2.0 * B * H * W_ * 9.0 * L.cin * L.cout, [&] { return launch_conv_in(x, c.w(u->in_w), c.w(u->in_b), od, B, L.cin, L.cout, H, W_, c.s, sb); });
           o.d = od; o.c = L.cout;
           if (nst) { o.st = sb; o.nt = nst; } else c.gn_partial(o, H * W_);
           break;
@@ -847,7 +695,7 @@ static int run(pf_unet* u, Ctx& c, const float* x, const int64_t* t, const float
           a.ups = 1; a.bias = c.w(L.b1);
           if (c.u->precision == PF_PREC_BF16X3 && L.wfold && L.cin % 32 == 0) {
             a.ups_fold = 1; a.precision = PF_PREC_BF16X3;
-            c.conv(a, PF_K_CONV3, &o, true, c.dry ? nullptr : c.w(L.wfold));
+            c.conv(a, PF_K_CONV3, &o, true, c.w(L.wfold));
           } else {
             c.conv(a, PF_K_CONV3, &o, true);
           }
@@ -877,29 +725,22 @@ static int run(pf_unet* u, Ctx& c, const float* x, const int64_t* t, const float
   const int Bo = c.B;   // (still the half batch only for a UNet without any transformer block: eps is then duplicated below)
   float* sc = c.talloc((size_t)Bo * cur.c); float* sh = c.talloc((size_t)Bo * cur.c);
   c.gn(cur, Tn{}, H * W_, 1e-5f, u->out_g, u->out_b, sc, sh);
-  c.prof_begin(PF_K_SMALL, 2.0 * Bo * H * W_ * 9.0 * cur.c * cfg.out_channels);
-  if (!c.dry) small_launch(c, launch_conv_out(cur.d, sc, sh, c.w(u->out_w), c.w(u->out_bias), eps, Bo, cur.c, cfg.out_channels, H, W_, c.s));
-  c.prof_end();
+  c.launch(PF_K_SMALL, 2.0 * Bo * H * W_ * 9.0 * cur.c * cfg.out_channels,
+           [&] { return launch_conv_out(cur.d, sc, sh, c.w(u->out_w), c.w(u->out_bias), eps, Bo, cur.c, cfg.out_channels, H, W_, c.s); });
   if (c.shared) {   // no layer ever looked at the condition: both halves of eps are the same image
     const size_t n = (size_t)Bo * cfg.out_channels * H * W_;
-    c.prof_begin(PF_K_SMALL, 0);
-    if (!c.dry && c.rc == PF_OK && hipMemcpyAsync(eps + n, eps, n * sizeof(float), hipMemcpyDeviceToDevice, c.s) != hipSuccess)
-      c.rc = set_error(PF_EHIP, "pf_unet_forward_cfg: device copy failed");
-    c.prof_end();
+    c.launch(PF_K_SMALL, 0, [&] { return device_copy(eps + n, eps, n, c.s); });
     c.B = c.Bfull; c.shared = false;
   }
   return c.rc;
 }
 
-static void plan_sizes(pf_unet* u, int batch, int n_cond, size_t* persist, size_t* temp, int* launches, bool has_time = false, bool has_cross = false,
-                       bool cfg_share = false) {
-  Ctx c{};
-  c.u = u; c.dry = true; c.B = batch; c.n_cond = n_cond; c.rc = PF_OK; c.has_time = has_time; c.has_cross = has_cross; c.cfg_share = cfg_share;
-  run(u, c, nullptr, nullptr, nullptr, nullptr);
-  *persist = align_up(c.persist_max, 4096);
-  *temp = align_up(c.temp_max, 4096);
-  if (launches) *launches = c.n_launch;
+static Ctx make_ctx(const pf_unet* u, int batch, int n_cond, bool cfg_share, bool has_time = false, bool has_cross = false) {
+  Ctx c;
+  c.u = const_cast<pf_unet*>(u); c.B = batch; c.n_cond = n_cond; c.cfg_share = cfg_share; c.has_time = has_time; c.has_cross = has_cross;
+  return c;
 }
+static PlanSize unet_plan(const Ctx& c) { return plan_sizes(c, [](Ctx& d) { run(d.u, d, nullptr, nullptr, nullptr, nullptr); }); }
 
 }  // namespace pf
 
@@ -918,72 +759,30 @@ int pf_unet_create(const pf_unet_cfg* cfg, pf_unet** out) {
   return PF_OK;
 }
 
-void pf_unet_destroy(pf_unet* u) {
-  if (!u) return;
-  for (auto e : u->ev) (void)hipEventDestroy(e);
-  delete u;
-}
+void pf_unet_destroy(pf_unet* u) { delete u; }
 
-size_t pf_unet_weight_bytes(const pf_unet* u) { return u ? u->blob_floats * sizeof(float) : 0; }
-int pf_unet_n_params(const pf_unet* u) { return u ? (int)u->params.size() : 0; }
+size_t pf_unet_weight_bytes(const pf_unet* u) { return u ? u->wt.blob_floats * sizeof(float) : 0; }
+int pf_unet_n_params(const pf_unet* u) { return u ? (int)u->wt.params.size() : 0; }
 
 int pf_unet_param_info(const pf_unet* u, int i, char* key_buf, size_t key_buf_len, int64_t shape[4], int* ndim) {
-  PF_REQUIRE(u && i >= 0 && i < (int)u->params.size() && key_buf && shape && ndim, "pf_unet_param_info: bad arguments");
-  const ParamSpec& ps = u->params[i];
-  snprintf(key_buf, key_buf_len, "%s", ps.key.c_str());
-  *ndim = (int)ps.shape.size();
-  for (int d = 0; d < 4; ++d) shape[d] = d < *ndim ? ps.shape[d] : 1;
-  return PF_OK;
+  PF_REQUIRE(u, "pf_unet_param_info: bad arguments");
+  return u->wt.param_info("pf_unet_param_info", i, key_buf, key_buf_len, shape, ndim);
 }
-
 int pf_unet_pack_param(pf_unet* u, const char* key, const float* src, const int64_t* shape, int ndim, void* host_blob) {
-  PF_REQUIRE(u && key && src && shape && host_blob, "pf_unet_pack_param: null argument");
-  auto it = u->index.find(key);
-  if (it == u->index.end()) return set_error(PF_ENOTFOUND, "unexpected key '%s' (not a parameter of this UNet)", key);
-  ParamSpec& ps = u->params[it->second];
-  bool ok = ndim == (int)ps.shape.size();
-  for (int d = 0; ok && d < ndim; ++d) ok = shape[d] == ps.shape[d];
-  if (!ok) {
-    std::string want, got;
-    for (auto s : ps.shape) want += std::to_string(s) + ",";
-    for (int d = 0; d < ndim; ++d) got += std::to_string(shape[d]) + ",";
-    return set_error(PF_EINVAL, "size mismatch for '%s': expected [%s] got [%s]", key, want.c_str(), got.c_str());
-  }
-  if (pack_one(ps, src, (float*)host_blob) != PF_OK) return set_error(PF_EINVAL, X3_RANGE_MSG, key);
-  ps.packed = true;
-  return PF_OK;
+  PF_REQUIRE(u, "pf_unet_pack_param: null argument");
+  return u->wt.pack_param("pf_unet_pack_param", "UNet", key, src, shape, ndim, host_blob);
 }
-
-int pf_unet_pack_missing(const pf_unet* u, char* buf, size_t buf_len) {
-  if (!u) return set_error(PF_EINVAL, "null handle");
-  int n = 0;
-  for (const ParamSpec& ps : u->params)
-    if (!ps.packed) {
-      if (n == 0 && buf && buf_len) snprintf(buf, buf_len, "%s", ps.key.c_str());
-      ++n;
-    }
-  return n;
-}
-
+int pf_unet_pack_missing(const pf_unet* u, char* buf, size_t buf_len) { return u ? u->wt.pack_missing(buf, buf_len) : set_error(PF_EINVAL, "null handle"); }
 int pf_unet_bind_weights(pf_unet* u, const void* dev_blob) {
-  PF_REQUIRE(u && dev_blob, "pf_unet_bind_weights: null argument");
-  PF_REQUIRE(((uintptr_t)dev_blob & 255) == 0, "pf_unet_bind_weights: blob must be 256-byte aligned");
-  u->wdev = (const float*)dev_blob;
-  return PF_OK;
+  PF_REQUIRE(u, "pf_unet_bind_weights: null argument");
+  return u->wt.bind("pf_unet_bind_weights", dev_blob, true);
 }
 
 size_t pf_unet_workspace_bytes(const pf_unet* u, int batch, int n_cond) {
-  if (!u || batch <= 0 || n_cond <= 0) return 0;
-  size_t p, t;
-  plan_sizes(const_cast<pf_unet*>(u), batch, n_cond, &p, &t, nullptr);
-  return p + t;
+  return (u && batch > 0 && n_cond > 0) ? unet_plan(make_ctx(u, batch, n_cond, false)).bytes() : 0;
 }
-
 int pf_unet_n_launches(const pf_unet* u, int batch, int n_cond) {
-  if (!u || batch <= 0 || n_cond <= 0) return 0;
-  size_t p, t; int n = 0;
-  plan_sizes(const_cast<pf_unet*>(u), batch, n_cond, &p, &t, &n);
-  return n;
+  return (u && batch > 0 && n_cond > 0) ? unet_plan(make_ctx(u, batch, n_cond, false)).n_launch : 0;
 }
 
 int pf_unet_forward(pf_unet* u, const float* x, const int64_t* t, const float* cond, int batch, int n_cond, float* eps,
@@ -998,18 +797,15 @@ static int forward_impl(pf_unet* u, const float* x, const int64_t* t, const floa
   PF_REQUIRE(!prep || !prep->cross_bias || n_cond == 1, "pf_unet_forward: the collapsed cross-attention bias exists only for n_cond == 1");
   PF_REQUIRE(batch > 0 && n_cond > 0, "pf_unet_forward: batch and n_cond must be positive");
   PF_REQUIRE(!cfg_share || batch % 2 == 0, "pf_unet_forward_cfg: the batch is the two guidance halves (got %d)", batch);
-  if (!u->wdev) return set_error(PF_ESTATE, "pf_unet_forward: weights not bound (call pf_unet_bind_weights)");
+  if (!u->wt.wdev) return set_error(PF_ESTATE, "pf_unet_forward: weights not bound (call pf_unet_bind_weights)");
   PF_REQUIRE(n_cond == 1 || u->cfg.d_cond % 32 == 0, "pf_unet_forward: n_cond > 1 needs d_cond %% 32 == 0");
-  PF_REQUIRE(((uintptr_t)workspace & 255) == 0, "pf_unet_forward: workspace must be 256-byte aligned");
-  size_t p, tmp;
-  plan_sizes(u, batch, n_cond, &p, &tmp, nullptr, false, false, cfg_share);
-  if (workspace_bytes < p + tmp) return set_error(PF_EINVAL, "pf_unet_forward: workspace too small (%zu < %zu)", workspace_bytes, p + tmp);
-  Ctx c{};
-  c.u = u; c.s = (hipStream_t)stream; c.dry = false; c.base = (char*)workspace; c.temp_base = p;
-  c.B = batch; c.n_cond = n_cond; c.W = u->wdev; c.rc = PF_OK; c.cfg_share = cfg_share;
+  Ctx c = make_ctx(u, batch, n_cond, cfg_share);
+  const int rc = c.use_workspace("pf_unet_forward", workspace, workspace_bytes, unet_plan(c));   // (the layout does not depend on `prep`)
+  if (rc != PF_OK) return rc;
+  c.s = (hipStream_t)stream; c.W = u->wt.wdev;
   if (prep && prep->time_table) { c.has_time = true; c.prep_time = prep->time_table; c.prep_time_rows = prep->n_time_rows; }
   if (prep && prep->cross_bias && u->cross_total > 0) { c.has_cross = true; c.prep_cross = prep->cross_bias; }
-  if (u->profiling) { u->n_prof = 0; u->pkind.clear(); u->pflops.clear(); }
+  if (u->profiling) { u->prof.rec.clear(); c.prof = &u->prof; }
   return run(u, c, x, t, cond, eps);
 }
 
@@ -1024,17 +820,11 @@ int pf_unet_forward_cfg(pf_unet* u, const float* x, const int64_t* t, const floa
 }
 
 size_t pf_unet_workspace_bytes_cfg(const pf_unet* u, int batch2, int n_cond) {
-  if (!u || batch2 <= 0 || batch2 % 2 || n_cond <= 0) return 0;
-  size_t p, t;
-  plan_sizes(const_cast<pf_unet*>(u), batch2, n_cond, &p, &t, nullptr, false, false, true);
-  return p + t;
+  return (u && batch2 > 0 && batch2 % 2 == 0 && n_cond > 0) ? unet_plan(make_ctx(u, batch2, n_cond, true)).bytes() : 0;
 }
-
 int pf_unet_n_launches_cfg(const pf_unet* u, int batch2, int n_cond, int has_time, int has_cross) {
   if (!u || batch2 <= 0 || batch2 % 2 || n_cond <= 0) return 0;
-  size_t p, t; int n = 0;
-  plan_sizes(const_cast<pf_unet*>(u), batch2, n_cond, &p, &t, &n, has_time != 0, has_cross != 0 && n_cond == 1, true);
-  return n;
+  return unet_plan(make_ctx(u, batch2, n_cond, true, has_time != 0, has_cross != 0 && n_cond == 1)).n_launch;
 }
 
 int pf_unet_time_bias_width(const pf_unet* u) { return u ? u->sum_emb : 0; }
@@ -1042,10 +832,10 @@ int pf_unet_cross_bias_width(const pf_unet* u) { return u ? u->cross_total : 0; 
 
 int pf_unet_prepare_time(pf_unet* u, int n_rows, float* table, void* scratch, size_t scratch_bytes, void* stream) {
   PF_REQUIRE(u && table && scratch && n_rows > 0, "pf_unet_prepare_time: bad arguments");
-  if (!u->wdev) return set_error(PF_ESTATE, "pf_unet_prepare_time: weights not bound (call pf_unet_bind_weights)");
+  if (!u->wt.wdev) return set_error(PF_ESTATE, "pf_unet_prepare_time: weights not bound (call pf_unet_bind_weights)");
   PF_REQUIRE(scratch_bytes >= (size_t)n_rows * u->d_t * sizeof(float), "pf_unet_prepare_time: scratch too small (%zu < %zu)", scratch_bytes,
              (size_t)n_rows * u->d_t * sizeof(float));
-  const float* W = u->wdev;
+  const float* W = u->wt.wdev;
   float* tsilu = static_cast<float*>(scratch);
   // the same two launches forward issues per call (row r <- time-step value r): bit-identical to the unprepared path
   int rc = launch_time_embed(nullptr, W + u->te_w0, W + u->te_b0, W + u->te_w2, W + u->te_b2, tsilu, n_rows, u->cfg.channels, u->d_t, (hipStream_t)stream);
@@ -1055,23 +845,18 @@ int pf_unet_prepare_time(pf_unet* u, int n_rows, float* table, void* scratch, si
 
 int pf_unet_prepare_cond(pf_unet* u, const float* cond, int batch, float* cross, void* scratch, size_t scratch_bytes, void* stream) {
   PF_REQUIRE(u && cond && cross && scratch && batch > 0, "pf_unet_prepare_cond: bad arguments");
-  if (!u->wdev) return set_error(PF_ESTATE, "pf_unet_prepare_cond: weights not bound (call pf_unet_bind_weights)");
+  if (!u->wt.wdev) return set_error(PF_ESTATE, "pf_unet_prepare_cond: weights not bound (call pf_unet_bind_weights)");
   PF_REQUIRE(u->cross_total > 0, "pf_unet_prepare_cond: this UNet has no transformer block");
   PF_REQUIRE(scratch_bytes >= (size_t)batch * u->cross_total * sizeof(float), "pf_unet_prepare_cond: scratch too small");
-  Ctx c{};
-  c.u = u; c.s = (hipStream_t)stream; c.dry = false; c.B = batch; c.n_cond = 1; c.W = u->wdev; c.rc = PF_OK;
-  const bool prof = u->profiling;
-  u->profiling = false;
+  Ctx c = make_ctx(u, batch, 1, false);   // a live context without a workspace (and without the profiler)
+  c.dry = false; c.s = (hipStream_t)stream; c.W = u->wt.wdev;
   cross_bias_launches(u, c, cond, batch, cross, static_cast<float*>(scratch));
-  u->profiling = prof;
   return c.rc;
 }
 
 int pf_unet_n_launches_prepared(const pf_unet* u, int batch, int n_cond, int has_time, int has_cross) {
   if (!u || batch <= 0 || n_cond <= 0) return 0;
-  size_t p, t; int n = 0;
-  plan_sizes(const_cast<pf_unet*>(u), batch, n_cond, &p, &t, &n, has_time != 0, has_cross != 0 && n_cond == 1);
-  return n;
+  return unet_plan(make_ctx(u, batch, n_cond, false, has_time != 0, has_cross != 0 && n_cond == 1)).n_launch;
 }
 
 int pf_unet_set_option(pf_unet* u, int option, int value) {
@@ -1103,40 +888,41 @@ int pf_x3_element(void) {
 int pf_unet_set_profiling(pf_unet* u, int enabled) {
   PF_REQUIRE(u, "null handle");
   u->profiling = enabled != 0;
-  u->n_prof = 0; u->pkind.clear(); u->pflops.clear(); u->pdirect.clear();
+  u->prof.rec.clear();
   return PF_OK;
 }
 
 int pf_unet_profile_read(pf_unet* u, int* kind, float* ms, double* flops, int capacity) {
   PF_REQUIRE(u && kind && ms && flops, "pf_unet_profile_read: null argument");
-  const int n = u->n_prof < capacity ? u->n_prof : capacity;
+  const Profiler& p = u->prof;
+  const int n = std::min((int)p.rec.size(), capacity);
   for (int i = 0; i < n; ++i) {
-    PF_CHECK_HIP(hipEventSynchronize(u->ev[(size_t)i * 2 + 1]));
+    PF_CHECK_HIP(hipEventSynchronize(p.ev[(size_t)i * 2 + 1]));
     float v = 0.f;
-    PF_CHECK_HIP(hipEventElapsedTime(&v, u->ev[(size_t)i * 2], u->ev[(size_t)i * 2 + 1]));
-    kind[i] = u->pkind[i]; ms[i] = v; flops[i] = u->pflops[i];
+    PF_CHECK_HIP(hipEventElapsedTime(&v, p.ev[(size_t)i * 2], p.ev[(size_t)i * 2 + 1]));
+    kind[i] = p.rec[i].kind; ms[i] = v; flops[i] = p.rec[i].flops;
   }
   return n;
 }
 
 int pf_unet_profile_read_direct(pf_unet* u, double* direct_flops, int capacity) {
   PF_REQUIRE(u && direct_flops, "pf_unet_profile_read_direct: null argument");
-  const int n = u->n_prof < capacity ? u->n_prof : capacity;
-  for (int i = 0; i < n; ++i) direct_flops[i] = u->pdirect[i];
+  const int n = std::min((int)u->prof.rec.size(), capacity);
+  for (int i = 0; i < n; ++i) direct_flops[i] = u->prof.rec[i].direct;
   return n;
 }
 
-size_t pf_packed_gemm_weight_floats(int n, int k, int taps) { return pf_unet::gemm_floats(taps, k, n); }
+size_t pf_packed_gemm_weight_floats(int n, int k, int taps) { return gemm_floats(taps, k, n); }
 int pf_pack_gemm_weight(const float* w, int n, int k, int taps, float* dst) {
   PF_REQUIRE(w && dst && n > 0 && k > 0 && k % 4 == 0 && (taps == 1 || taps == 9), "pf_pack_gemm_weight: bad arguments");
-  memset(dst, 0, pf_unet::gemm_floats(taps, k, n) * sizeof(float));
+  memset(dst, 0, gemm_floats(taps, k, n) * sizeof(float));
   pack_gemm(dst, w, n, k, taps, (n + 63) / 64 * 64, 0);
   return PF_OK;
 }
 
 int pf_pack_gemm_weight_bf16x3(const float* w, int n, int k, int taps, void* dst) {
   PF_REQUIRE(w && dst && n > 0 && k > 0 && k % 8 == 0 && (taps == 1 || taps == 9), "pf_pack_gemm_weight_bf16x3: bad arguments");
-  memset(dst, 0, pf_unet::gemm_floats(taps, k, n) * sizeof(float));
+  memset(dst, 0, gemm_floats(taps, k, n) * sizeof(float));
   PF_REQUIRE(pack_gemm_bf3(dst, w, n, k, taps, (n + 63) / 64 * 64, 0, nullptr), X3_RANGE_MSG, "pf_pack_gemm_weight_bf16x3");
   return PF_OK;
 }

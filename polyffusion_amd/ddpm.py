@@ -20,6 +20,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from ._handle import ModelHandle
 
 # params/ddpm.yaml of the reference (the keys the sampler reads)
 DDPM_PARAMS = {
@@ -109,81 +110,20 @@ def ddpm_param_shapes(cfg: DDPMConfig) -> "OrderedDict[str, Tuple[int, ...]]":
     return out
 
 
-class DDPMUNet:
+class DDPMUNet(ModelHandle):
     """``eps = UNet(x, t)`` (unet.py:398-421) on the ``pf_ddpm`` plan.  ``x3="f16"``: the model lives in libpfhip_f16.so, whose split
-    mode is "f16x3"."""
+    mode is "f16x3".  Weights (ModelHandle): state_dict keys relative to ``eps_model.``."""
+    PREFIX = "pf_ddpm"
 
     def __init__(self, cfg: DDPMConfig = DDPMConfig(), device: Optional[torch.device] = None, x3: Optional[str] = None):
         self.cfg = cfg
-        self._lib = _lib.load(x3)
         self._split_name = "f16x3" if x3 == "f16" else "bf16x3"
         c = _lib.DDPMCfg()
         c.image_channels, c.n_channels, c.n_levels = cfg.image_channels, cfg.n_channels, len(cfg.ch_mults)
         for i, (mu, at) in enumerate(zip(cfg.ch_mults, cfg.is_attn)):
             c.ch_mults[i], c.is_attn[i] = mu, int(bool(at))
         c.n_blocks, c.img_h, c.img_w = cfg.n_blocks, cfg.img_h, cfg.img_w
-        h = C.c_void_p()
-        self._check(self._lib.pf_ddpm_create(C.byref(c), C.byref(h)), "pf_ddpm_create")
-        self._h = h
-        self.device = torch.device(device) if device is not None else (
-            torch.device("cuda", torch.cuda.current_device()) if torch.cuda.is_available() else None)
-        self._blob_dev: Optional[torch.Tensor] = None
-        self._ws: Optional[torch.Tensor] = None
-
-    def _check(self, rc: int, what: str = "") -> int:
-        return _lib.check(rc, what, self._lib)
-
-    def __del__(self):
-        try:
-            if getattr(self, "_h", None):
-                self._lib.pf_ddpm_destroy(self._h)
-                self._h = None
-        except Exception:
-            pass
-
-    def param_shapes(self) -> "OrderedDict[str, Tuple[int, ...]]":
-        out: "OrderedDict[str, Tuple[int, ...]]" = OrderedDict()
-        buf = C.create_string_buffer(256)
-        shape = (C.c_int64 * 4)()
-        nd = C.c_int()
-        for i in range(self._lib.pf_ddpm_n_params(self._h)):
-            self._check(self._lib.pf_ddpm_param_info(self._h, i, buf, 256, shape, C.byref(nd)))
-            out[buf.value.decode()] = tuple(int(shape[d]) for d in range(nd.value))
-        return out
-
-    def pack_param(self, key: str, val, blob: torch.Tensor) -> int:
-        """Pack one tensor into the host blob; returns the library's code (PF_ENOTFOUND = -2 for a key this UNet does not have)."""
-        t = torch.as_tensor(np.asarray(val) if not isinstance(val, torch.Tensor) else val).detach().to("cpu", torch.float32).contiguous()
-        shape = (C.c_int64 * max(1, t.dim()))(*t.shape)
-        return self._lib.pf_ddpm_pack_param(self._h, key.encode(), t.data_ptr(), shape, t.dim(), blob.data_ptr())
-
-    def pack_missing(self) -> Tuple[int, str]:
-        buf = C.create_string_buffer(256)
-        n = self._lib.pf_ddpm_pack_missing(self._h, buf, 256)
-        return n, buf.value.decode()
-
-    def pack_state_dict(self, state: Mapping[str, object], strict: bool = True) -> torch.Tensor:
-        """Repack reference-named tensors (keys relative to ``eps_model.``) into the host blob (no GPU needed)."""
-        blob = torch.zeros(self.weight_bytes() // 4, dtype=torch.float32)
-        for key, val in state.items():
-            rc = self.pack_param(key, val, blob)
-            if rc == -2 and not strict:
-                continue
-            self._check(rc, f"load_state_dict({key})")
-        n, first = self.pack_missing()
-        if n:
-            raise RuntimeError(f"load_state_dict: {n} missing key(s), first: {first}")
-        return blob
-
-    def weight_bytes(self) -> int:
-        return int(self._lib.pf_ddpm_weight_bytes(self._h))
-
-    def load_state_dict(self, state: Mapping[str, object], strict: bool = True):
-        _lib.require_gpu()
-        blob = self.pack_state_dict(state, strict).to(self.device)
-        self._blob_dev = blob
-        self._check(self._lib.pf_ddpm_bind_weights(self._h, blob.data_ptr()), "pf_ddpm_bind_weights")
-        return self
+        super().__init__(_lib.load(x3), C.byref(c), device=device)
 
     def workspace(self, batch: int) -> torch.Tensor:
         nbytes = int(self._lib.pf_ddpm_workspace_bytes(self._h, batch))

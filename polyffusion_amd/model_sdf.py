@@ -10,64 +10,27 @@
 """
 from __future__ import annotations
 
-import ctypes as C
 from types import SimpleNamespace
 from typing import Mapping, Optional
 
-import numpy as np
 import torch
 
 from . import _lib
+from ._handle import ModelHandle
 from .unet import LatentDiffusion
 
 
-class _Encoder:
+class _Encoder(ModelHandle):
+    """A frozen encoder on the ``pf_encoder`` handle (weights: ModelHandle; no parameter table)."""
+    PREFIX = "pf_encoder"
     KIND = -1
 
     def __init__(self, input_dim, emb_size, hidden_dim, z_dim, num_channel, device=None):
-        self._lib = _lib.load()
         self.hidden_dim, self.z_dim = hidden_dim, z_dim
-        h = C.c_void_p()
-        _lib.check(self._lib.pf_encoder_create(self.KIND, input_dim, emb_size, hidden_dim, z_dim, num_channel, C.byref(h)),
-                   "pf_encoder_create")
-        self._h = h
-        self.device = torch.device(device) if device is not None else (
-            torch.device("cuda", torch.cuda.current_device()) if torch.cuda.is_available() else None)
-        self._blob = None
-        self._ws = None
-
-    def __del__(self):
-        try:
-            if getattr(self, "_h", None):
-                self._lib.pf_encoder_destroy(self._h)
-                self._h = None
-        except Exception:
-            pass
-
-    def pack_state_dict(self, state: Mapping[str, object]) -> torch.Tensor:
-        blob = torch.zeros(self._lib.pf_encoder_weight_bytes(self._h) // 4, dtype=torch.float32)
-        for key, val in state.items():
-            t = torch.as_tensor(np.asarray(val) if not isinstance(val, torch.Tensor) else val).detach().to("cpu", torch.float32).contiguous()
-            shape = (C.c_int64 * max(1, t.dim()))(*t.shape)
-            _lib.check(self._lib.pf_encoder_pack_param(self._h, key.encode(), t.data_ptr(), shape, t.dim(), blob.data_ptr()),
-                       f"load_state_dict({key})")
-        buf = C.create_string_buffer(256)
-        if self._lib.pf_encoder_pack_missing(self._h, buf, 256):
-            raise RuntimeError(f"load_state_dict: missing key {buf.value.decode()}")
-        return blob
-
-    def bind_packed(self, blob_dev: torch.Tensor):
-        self._blob = blob_dev
-        self.device = blob_dev.device
-        _lib.check(self._lib.pf_encoder_bind_weights(self._h, blob_dev.data_ptr()))
-
-    def load_state_dict(self, state: Mapping[str, object]):
-        _lib.require_gpu()
-        self.bind_packed(self.pack_state_dict(state).to(self.device))
-        return self
+        super().__init__(_lib.load(), self.KIND, input_dim, emb_size, hidden_dim, z_dim, num_channel, device=device)
 
     def _run(self, x: torch.Tensor, n_step: int) -> torch.Tensor:
-        if self._blob is None:
+        if self._blob_dev is None:
             raise RuntimeError("encoder weights not loaded")
         x = x.contiguous().float()
         B = x.shape[0]

@@ -13,16 +13,18 @@ the RCCL broadcast of the packed weight blob.
 from __future__ import annotations
 
 import ctypes as C
-from typing import Dict, Iterable, List, Mapping, Optional, Tuple
+from typing import Iterable, List, Optional, Tuple
 
-import numpy as np
 import torch
 
 from . import _lib
+from ._handle import ModelHandle
 from .arch import UNetConfig
 
 
-class UNetModel:
+class UNetModel(ModelHandle):
+    PREFIX = "pf_unet"
+
     def __init__(self, *, in_channels: int, out_channels: int, channels: int, n_res_blocks: int,
                  attention_levels: Iterable[int], channel_multipliers: Iterable[int], n_heads: int,
                  tf_layers: int = 1, d_cond: int = 768, img_h: int = 128, img_w: int = 128,
@@ -35,7 +37,6 @@ class UNetModel:
         self.img_h, self.img_w = int(img_h), int(img_w)
         self.channels = channels
         self.x3 = x3
-        self._lib = _lib.load(x3)
         # name of the split mode: "f16x3" for a model asked to live in the fp16 build; a model in the process default keeps "bf16x3"
         # (also under PF_X3=f16, which exists to run unchanged callers against the other build)
         self._split_name = "f16x3" if x3 == "f16" else "bf16x3"
@@ -48,74 +49,11 @@ class UNetModel:
         for i, v in enumerate(self.cfg.channel_multipliers):
             c.channel_multipliers[i] = v
         c.n_heads, c.tf_layers, c.d_cond, c.img_h, c.img_w = n_heads, tf_layers, d_cond, self.img_h, self.img_w
-        h = C.c_void_p()
-        self._check(self._lib.pf_unet_create(C.byref(c), C.byref(h)), "pf_unet_create")
-        self._h = h
-        self.device = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device()) \
-            if torch.cuda.is_available() else None
-        self._blob_host: Optional[torch.Tensor] = None
-        self._blob_dev: Optional[torch.Tensor] = None
-        self._ws: Optional[torch.Tensor] = None
+        super().__init__(_lib.load(x3), C.byref(c), device=device)
         self._amax: Optional[torch.Tensor] = None      # range telemetry word (track_absmax)
         self._ws_key = (0, 0, 0)
 
-    def _check(self, rc: int, what: str = "") -> int:
-        return _lib.check(rc, what, self._lib)
-
-    def __del__(self):
-        try:
-            if getattr(self, "_h", None):
-                self._lib.pf_unet_destroy(self._h)
-                self._h = None
-        except Exception:
-            pass
-
-    # ---- weights --------------------------------------------------------------------------------
-    def param_shapes(self) -> "Dict[str, Tuple[int, ...]]":
-        out = {}
-        buf = C.create_string_buffer(256)
-        shape = (C.c_int64 * 4)()
-        nd = C.c_int()
-        for i in range(self._lib.pf_unet_n_params(self._h)):
-            self._check(self._lib.pf_unet_param_info(self._h, i, buf, 256, shape, C.byref(nd)))
-            out[buf.value.decode()] = tuple(int(shape[d]) for d in range(nd.value))
-        return out
-
-    def pack_state_dict(self, state: Mapping[str, object], strict: bool = True) -> torch.Tensor:
-        """Repack reference-named tensors into the kernel-friendly host blob (no GPU needed)."""
-        nbytes = self._lib.pf_unet_weight_bytes(self._h)
-        blob = torch.zeros(nbytes // 4, dtype=torch.float32)
-        for key, val in state.items():
-            t = torch.as_tensor(np.asarray(val) if not isinstance(val, torch.Tensor) else val).detach().to("cpu", torch.float32).contiguous()
-            shape = (C.c_int64 * max(1, t.dim()))(*t.shape)
-            rc = self._lib.pf_unet_pack_param(self._h, key.encode(), t.data_ptr(), shape, t.dim(), blob.data_ptr())
-            if rc == -2 and not strict:
-                continue
-            self._check(rc, f"load_state_dict({key})")
-        buf = C.create_string_buffer(256)
-        missing = self._lib.pf_unet_pack_missing(self._h, buf, 256)
-        if missing:
-            raise RuntimeError(f"load_state_dict: {missing} missing key(s), first: {buf.value.decode()}")
-        self._blob_host = blob
-        return blob
-
-    def weight_bytes(self) -> int:
-        return int(self._lib.pf_unet_weight_bytes(self._h))
-
-    def bind_packed(self, blob_dev: torch.Tensor):
-        """Attach a packed blob that already lives on the GPU (e.g. received by RCCL broadcast)."""
-        assert blob_dev.is_cuda and blob_dev.dtype == torch.float32 and blob_dev.numel() * 4 == self.weight_bytes()
-        self._blob_dev = blob_dev
-        self.device = blob_dev.device
-        self._check(self._lib.pf_unet_bind_weights(self._h, blob_dev.data_ptr()), "pf_unet_bind_weights")
-
-    def load_state_dict(self, state: Mapping[str, object], strict: bool = True):
-        """Reference-compatible weight ingestion (keys relative to ``eps_model``)."""
-        _lib.require_gpu()
-        blob = self.pack_state_dict(state, strict)
-        self.bind_packed(blob.to(self.device))
-        return self
-
+    # (weights: ModelHandle - state_dict keys relative to ``eps_model``)
     def eval(self):
         return self
 

@@ -127,6 +127,23 @@ def test_pack_state_dict_errors_without_gpu(lib):
         _unet(lib, UNetConfig(channels=48))
 
 
+def test_encoder_pack_messages_and_optional_keys(lib):
+    """The encoders share the UNet's weight table: a shape mismatch names both shapes, an incomplete state is refused with a count,
+    and the variance head linear_var.* (never evaluated) may be left out."""
+    from polyffusion_amd.model_sdf import ChordEncoder
+    from polyffusion_amd.weights import synth_chord_encoder_state
+    st = synth_chord_encoder_state(0)
+    bad = dict(st); bad["linear_mu.bias"] = np.zeros(3, np.float32)
+    with pytest.raises(RuntimeError, match=r"size mismatch for 'linear_mu.bias': expected \[512,\] got \[3,\]"):
+        ChordEncoder(36, 512, 512).pack_state_dict(bad)
+    bad = dict(st); del bad["linear_mu.weight"]
+    with pytest.raises(RuntimeError, match=r"1 missing key\(s\), first: linear_mu.weight"):
+        ChordEncoder(36, 512, 512).pack_state_dict(bad)
+    no_var = {k: v for k, v in st.items() if not k.startswith("linear_var.")}
+    assert len(no_var) == len(st) - 2
+    assert torch.equal(ChordEncoder(36, 512, 512).pack_state_dict(no_var), ChordEncoder(36, 512, 512).pack_state_dict(st))
+
+
 def test_product_refuses_to_run_without_gpu(lib):
     if torch.cuda.is_available():
         pytest.skip("GPU present")

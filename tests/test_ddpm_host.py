@@ -62,6 +62,16 @@ def test_pack_synthetic_state_and_unknown_keys(lib):
         u.forward(torch.zeros(2, 2, 32, 32), torch.zeros(2, dtype=torch.int64))   # weights not bound: no fallback
 
 
+def test_attention_norm_keys_are_required(lib):
+    """AttentionBlock.norm is saved by the reference but never applied: its keys are accepted and dropped, yet a state without them
+    is refused like any other incomplete one."""
+    st = synth_ddpm_state(SMALL, 0)
+    norm = [k for k in st if ".attn.norm." in k]
+    assert norm
+    with pytest.raises(RuntimeError, match=rf"{len(norm)} missing key\(s\), first: {re.escape(norm[0])}"):
+        DDPMUNet(SMALL).pack_state_dict({k: v for k, v in st.items() if k not in norm})
+
+
 def _piece(lib):
     if lib.pf_x3_element() == 0:
         return (lambda u: (u.astype(np.uint32) << 16).view(np.float32)), 1.0

@@ -195,3 +195,30 @@ def test_winograd_large_batch_bit_reproducible(B, shared):
     for _ in range(4):
         assert torch.equal(m(x, t, c, shared_x=shared).view(torch.int32), ref.view(torch.int32))
     assert 0 < (ref - direct).abs().max().item() < 1e-4
+
+
+def test_profile_records_describe_the_last_forward_after_a_plan_change():
+    """Profiling stays on across a plan change (f32 -> bf16x3 with every qualifying conv in the Winograd form): read_profile() and
+    read_profile_direct() both describe the second forward, record for record, as a fresh profile of that plan does."""
+    from polyffusion_amd import synth
+    m = _unet()
+    x = torch.from_numpy(synth.gaussian((2, 2, 128, 128), 3)).cuda()
+    c = torch.from_numpy(synth.gaussian((2, 1, 512), 4)).cuda()
+    t = torch.tensor([999, 3], device="cuda")
+    m.set_profiling(True)
+    m(x, t, c)
+    m.set_precision("bf16x3")
+    m.set_option("conv_wino", True)
+    m(x, t, c)
+    torch.cuda.synchronize()
+    prof, direct = m.read_profile(), m.read_profile_direct()
+    m.set_profiling(True)
+    m(x, t, c)
+    torch.cuda.synchronize()
+    fresh, fresh_direct = m.read_profile(), m.read_profile_direct()
+    m.set_profiling(False)
+    assert len(prof) == len(direct) == len(fresh) == len(fresh_direct) > 0
+    assert [(k, f) for k, _, f in prof] == [(k, f) for k, _, f in fresh] and direct == fresh_direct
+    assert all(d >= f for (_, _, f), d in zip(prof, direct))
+    wino = [i for i, ((_, _, f), d) in enumerate(zip(prof, direct)) if d != f]
+    assert wino and all(prof[i][0] == 0 for i in wino)   # only 3x3 convs (PF_K_CONV3) run in the Winograd form
