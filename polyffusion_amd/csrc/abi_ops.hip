@@ -1,0 +1,195 @@
+// abi_ops.hip - the part of the C ABI that belongs to no model handle: the library's error state, its version and build queries, and the
+// entry points that launch a single kernel or pack a single weight (sampler steps, RNG, attention, convs, norms, packers, probes, step state).
+#include <stdarg.h>
+#include <vector>
+#include "plan.h"
+
+namespace pf {
+
+static thread_local std::string g_err;
+int set_error(int code, const char* fmt, ...) {
+  char buf[512];
+  va_list ap;
+  va_start(ap, fmt);
+  vsnprintf(buf, sizeof buf, fmt, ap);
+  va_end(ap);
+  g_err = buf;
+  return code;
+}
+
+}  // namespace pf
+
+using namespace pf;
+
+extern "C" {
+
+int pf_version(void) { return 100; }
+const char* pf_last_error(void) { return g_err.c_str(); }
+int pf_x3_element(void) {
+#ifdef PF_X3_F16
+  return 1;
+#else
+  return 0;
+#endif
+}
+
+size_t pf_packed_gemm_weight_floats(int n, int k, int taps) { return gemm_floats(taps, k, n); }
+int pf_pack_gemm_weight(const float* w, int n, int k, int taps, float* dst) {
+  PF_REQUIRE(w && dst && n > 0 && k > 0 && k % 4 == 0 && (taps == 1 || taps == 9), "pf_pack_gemm_weight: bad arguments");
+  memset(dst, 0, gemm_floats(taps, k, n) * sizeof(float));
+  pack_gemm(dst, w, n, k, taps, (n + 63) / 64 * 64, 0);
+  return PF_OK;
+}
+
+int pf_pack_gemm_weight_bf16x3(const float* w, int n, int k, int taps, void* dst) {
+  PF_REQUIRE(w && dst && n > 0 && k > 0 && k % 8 == 0 && (taps == 1 || taps == 9), "pf_pack_gemm_weight_bf16x3: bad arguments");
+  memset(dst, 0, gemm_floats(taps, k, n) * sizeof(float));
+  PF_REQUIRE(pack_gemm_bf3(dst, w, n, k, taps, (n + 63) / 64 * 64, 0, nullptr), X3_RANGE_MSG, "pf_pack_gemm_weight_bf16x3");
+  return PF_OK;
+}
+
+int pf_gn_scale_shift(const float* x0, int c0, const float* x1, int c1, int batch, int hw, int groups, float eps,
+                      const float* gamma, const float* beta, float* scale, float* shift, void* scratch, size_t scratch_bytes,
+                      void* stream) {
+  return launch_gn_scale_shift(x0, c0, x1, c1, batch, hw, groups, eps, gamma, beta, scale, shift, scratch, scratch_bytes, (hipStream_t)stream);
+}
+int pf_pack_upfold_weight_bf16x3(const float* w, int n, int k, void* dst) {
+  PF_REQUIRE(w && dst && n > 0 && k > 0 && k % 8 == 0, "pack_upfold: bad arguments");
+  PF_REQUIRE(pack_upfold_bf3(dst, w, n, k, (n + 63) / 64 * 64), X3_RANGE_MSG, "pf_pack_upfold_weight_bf16x3");
+  return PF_OK;
+}
+size_t pf_wino_weight_bytes(int n, int k) { return (n > 0 && k > 0) ? (size_t)16 * k * n * 4 : 0; }
+int pf_pack_wino_weight_bf16x3(const float* w, int n, int k, void* dst) {
+  PF_REQUIRE(w && dst && n > 0 && k > 0 && n % 64 == 0 && k % 16 == 0, "pack_wino: n must be a multiple of 64 and k of 16 (n=%d k=%d)", n, k);
+  PF_REQUIRE(pack_wino_bf3(dst, w, n, k), X3_RANGE_MSG, "pf_pack_wino_weight_bf16x3");
+  return PF_OK;
+}
+int pf_prmat2c_durations(const float* prmat2c, int n, int steps, int custom_round, int32_t* dur, void* stream) {
+  return launch_prmat2c_durations(prmat2c, n, steps, custom_round, dur, (hipStream_t)stream);
+}
+int pf_mlp_geglu_fused(const float* x, int batch, int l, const float* ln_gamma, const float* ln_beta, float ln_eps,
+                       const void* w1_bf16x3, const float* b1, const void* w2_bf16x3, const float* b2,
+                       float* out, void* out_planes, void* stream) {
+  return launch_mlp_fused(x, batch, l, ln_gamma, ln_beta, ln_eps, w1_bf16x3, b1, w2_bf16x3, b2, out, out_planes, (hipStream_t)stream);
+}
+int pf_mlp_geglu_proj_fused(const float* x, int batch, int l, const float* ln_gamma, const float* ln_beta, float ln_eps,
+                            const void* w1_bf16x3, const float* b1, const void* w2_bf16x3, const float* b2,
+                            const void* w3_bf16x3, const float* b3, const float* res3, float* out, float* stats3, void* stream) {
+  if (!w3_bf16x3) return set_error(PF_EINVAL, "pf_mlp_geglu_proj_fused: null projection weight");
+  return launch_mlp_fused(x, batch, l, ln_gamma, ln_beta, ln_eps, w1_bf16x3, b1, w2_bf16x3, b2, out, nullptr, (hipStream_t)stream, w3_bf16x3, b3,
+                          res3, stats3);
+}
+int pf_ln_planes(const float* x, int rows, int c, float eps, const float* gamma, const float* beta, void* planes, void* stream) {
+  return launch_ln_planes(x, rows, c, eps, gamma, beta, planes, (hipStream_t)stream);
+}
+int pf_ln_stats(const float* x, int rows, int c, float eps, float* mean, float* rstd, void* stream) {
+  return launch_ln_stats(x, rows, c, eps, mean, rstd, (hipStream_t)stream);
+}
+int pf_conv_stats_tiles(const pf_conv_args* a) { return a ? conv_stats_tiles(*a) : 0; }
+size_t pf_conv_splitk_ws_bytes(const pf_conv_args* a) { return a ? conv_splitk_ws_bytes(*a) : 0; }
+int pf_gn_finalize_tiles(const float* stats0, int tiles0, int c0, const float* stats1, int tiles1, int c1, int batch, int hw,
+                         int groups, float eps, const float* gamma, const float* beta, float* scale, float* shift, void* stream) {
+  return launch_gn_finalize_tiles(stats0, tiles0, c0, stats1, tiles1, c1, batch, hw, groups, eps, gamma, beta, scale, shift,
+                                  (hipStream_t)stream);
+}
+int pf_conv2d(const pf_conv_args* a, void* stream) {
+  PF_REQUIRE(a, "pf_conv2d: null argument");
+  return launch_conv(*a, (hipStream_t)stream);
+}
+size_t pf_attention_split_scratch_bytes(int batch, int n_heads, int l) {
+  return (batch > 0 && n_heads > 0 && l > 0) ? attention_bf3_split_floats(batch, n_heads, l, nullptr) * sizeof(float) : 0;
+}
+int pf_attention_bf16x3_split(const void* qkv_planes, float* o, int ldo, void* o_planes, int batch, int n_heads, int l, void* scratch, size_t scratch_bytes,
+                              void* stream) {
+  return launch_attention_bf3(qkv_planes, o, ldo, o_planes, batch, n_heads, l, 0, (hipStream_t)stream, static_cast<float*>(scratch), scratch_bytes / sizeof(float));
+}
+int pf_attention_bf16x3(const void* qkv_planes, float* o, int ldo, void* o_planes, int batch, int n_heads, int l, int form, void* stream) {
+  return launch_attention_bf3(qkv_planes, o, ldo, o_planes, batch, n_heads, l, form, (hipStream_t)stream);
+}
+int pf_attention(const float* q, int ldq, const float* k, int ldk, const float* v, int ldv, float* o, int ldo, int batch,
+                 int n_heads, int d_head, int lq, int lk, void* stream) {
+  PF_REQUIRE(q && k && v && o, "pf_attention: null argument");
+  return launch_attention(q, ldq, k, ldk, v, ldv, o, ldo, batch, n_heads, d_head, lq, lk, (hipStream_t)stream);
+}
+
+int pf_cfg_combine(const float* eps2, float scale, float* eps, size_t n, void* stream) { return launch_cfg_combine(eps2, scale, eps, n, (hipStream_t)stream); }
+int pf_ddpm_step(const float* x, const float* eps, const float* noise_p, const float* noise_q, const float* orig, const float* mask,
+                 const pf_ddpm_coef* c, float* x_out, size_t n, void* stream) {
+  PF_REQUIRE(c, "pf_ddpm_step: null coefficients");
+  return launch_ddpm_step(x, eps, noise_p, noise_q, orig, mask, *c, x_out, n, (hipStream_t)stream);
+}
+int pf_axpby(const float* x, const float* noise, float a, float b, float* out, size_t n, void* stream) { return launch_axpby(x, noise, a, b, out, n, (hipStream_t)stream); }
+int pf_ddim_step(const float* x, const float* eps, const float* noise, const float* orig, const float* orig_noise, const float* mask,
+                 const pf_ddim_coef* c, float* x_out, size_t n, void* stream) {
+  PF_REQUIRE(c, "pf_ddim_step: null coefficients");
+  return launch_ddim_step(x, eps, noise, orig, orig_noise, mask, *c, x_out, n, (hipStream_t)stream);
+}
+int pf_randn(float* out, size_t n, uint64_t seed, uint64_t stream_id, uint64_t elem_offset, void* stream) {
+  return launch_randn(out, n, seed, stream_id, elem_offset, (hipStream_t)stream);
+}
+int pf_ddpm_step_rng(const float* x, const float* eps, const float* orig, const float* mask, const pf_ddpm_coef* c, uint64_t seed,
+                     uint64_t draw_q, uint64_t draw_p, uint64_t elem_offset, float* x_out, size_t n, void* stream) {
+  PF_REQUIRE(c, "pf_ddpm_step_rng: null coefficients");
+  return launch_ddpm_step_rng(x, eps, orig, mask, c, nullptr, nullptr, seed, draw_q, draw_p, elem_offset, x_out, n, (hipStream_t)stream);
+}
+int pf_ddim_step_rng(const float* x, const float* eps, const float* orig, const float* orig_noise, const float* mask, const pf_ddim_coef* c,
+                     uint64_t seed, uint64_t draw, uint64_t elem_offset, float* x_out, size_t n, void* stream) {
+  PF_REQUIRE(c, "pf_ddim_step_rng: null coefficients");
+  return launch_ddim_step_rng(x, eps, orig, orig_noise, mask, c, nullptr, nullptr, seed, draw, elem_offset, x_out, n, (hipStream_t)stream);
+}
+int pf_ddpm_step_rng_dev(const float* x, const float* eps, const float* orig, const float* mask, const pf_ddpm_coef* table,
+                         const pf_step_state* st, uint64_t seed, uint64_t elem_offset, float* x_out, size_t n, void* stream) {
+  PF_REQUIRE(table && st, "pf_ddpm_step_rng_dev: null table / state");
+  return launch_ddpm_step_rng(x, eps, orig, mask, nullptr, table, st, seed, 0, 0, elem_offset, x_out, n, (hipStream_t)stream);
+}
+int pf_ddim_step_rng_dev(const float* x, const float* eps, const float* orig, const float* orig_noise, const float* mask,
+                         const pf_ddim_coef* table, const pf_step_state* st, uint64_t seed, uint64_t elem_offset, float* x_out, size_t n,
+                         void* stream) {
+  PF_REQUIRE(table && st, "pf_ddim_step_rng_dev: null table / state");
+  return launch_ddim_step_rng(x, eps, orig, orig_noise, mask, nullptr, table, st, seed, 0, elem_offset, x_out, n, (hipStream_t)stream);
+}
+int pf_mfma_probe(float* sink, int iters, double* flops_out, void* stream) { return launch_mfma_probe(sink, iters, flops_out, (hipStream_t)stream); }
+int pf_clock_probe(uint64_t* out2, void* stream) { return launch_clock_probe(reinterpret_cast<unsigned long long*>(out2), (hipStream_t)stream); }
+int pf_step_state_set(pf_step_state* st, int64_t index, uint64_t draws, void* stream) { return launch_step_state_set(st, index, draws, (hipStream_t)stream); }
+int pf_step_begin(const pf_step_state* st, const int32_t* time_steps, int64_t* t_out, int batch, void* stream) {
+  return launch_step_begin(st, time_steps, t_out, batch, (hipStream_t)stream);
+}
+int pf_step_end(pf_step_state* st, int draws_used, void* stream) { return launch_step_end(st, draws_used, (hipStream_t)stream); }
+int pf_randn_dev(float* out, size_t n, uint64_t seed, const pf_step_state* st, int slot, uint64_t elem_offset, void* stream) {
+  return launch_randn_dev(out, n, seed, st, slot, elem_offset, (hipStream_t)stream);
+}
+int pf_ddpm_step_dev(const float* x, const float* eps, const float* noise_p, const float* noise_q, const float* orig, const float* mask,
+                     const pf_ddpm_coef* table, const pf_step_state* st, float* x_out, size_t n, void* stream) {
+  return launch_ddpm_step_dev(x, eps, noise_p, noise_q, orig, mask, table, st, x_out, n, (hipStream_t)stream);
+}
+int pf_ddim_step_dev(const float* x, const float* eps, const float* noise, const float* orig, const float* orig_noise, const float* mask,
+                     const pf_ddim_coef* table, const pf_step_state* st, float* x_out, size_t n, void* stream) {
+  return launch_ddim_step_dev(x, eps, noise, orig, orig_noise, mask, table, st, x_out, n, (hipStream_t)stream);
+}
+
+size_t pf_attention_wide_scratch_bytes(int batch, int l) { return (batch > 0 && l > 0) ? attention_wide_scratch_floats(batch, l) * sizeof(float) : 0; }
+int pf_attention_wide(const float* q, const float* k, const float* v, int ld, float* o, int ldo, int batch, int l, int d, void* scratch,
+                      size_t scratch_bytes, void* stream) {
+  return launch_attention_wide(q, k, v, ld, o, ldo, batch, l, d, static_cast<float*>(scratch), scratch_bytes / sizeof(float), (hipStream_t)stream);
+}
+size_t pf_convt_weight_floats(int cin, int cout) { return (cin > 0 && cout > 0) ? (size_t)16 * cin * cout : 0; }
+int pf_pack_convt_weight_f32(const float* w, int cin, int cout, float* dst) {
+  PF_REQUIRE(w && dst && cin > 0 && cout > 0 && cin % 4 == 0, "pf_pack_convt_weight_f32: bad arguments");
+  pack_convT_f32(w, cin, cout, dst);
+  return PF_OK;
+}
+int pf_pack_convt_weight_bf16x3(const float* w, int cin, int cout, void* dst) {
+  PF_REQUIRE(w && dst && cin > 0 && cout > 0 && cin % 8 == 0, "pf_pack_convt_weight_bf16x3: bad arguments");
+  std::vector<float> fold((size_t)16 * cin * cout);
+  convT_fold(w, cin, cout, fold.data());
+  memset(dst, 0, gemm_floats(16, cin, cout) * sizeof(float));
+  PF_REQUIRE(pack_gemm_bf3(dst, fold.data(), cout, cin, 16, (cout + 63) / 64 * 64, 0, nullptr),
+             "pf_pack_convt_weight_bf16x3: a weight exceeds what this library's fp16 split packing holds");
+  return PF_OK;
+}
+int pf_conv_transpose_f32(const float* x, int batch, int h, int w, int cin, const float* w_packed, int cout, const float* bias, float* out,
+                          void* stream) {
+  return launch_convT_f32(x, batch, h, w, cin, w_packed, cout, bias, out, (hipStream_t)stream);
+}
+
+}  // extern "C"

@@ -136,13 +136,14 @@ struct PlanCtx {
     if (prof) prof->end(s);
   }
 
-  // live run in `ws`: checks it against the plan's dry-run sizes, then carves it
-  int use_workspace(const char* fn, void* ws, size_t ws_bytes, const PlanSize& z) {
+  // live run in `ws`, on `stream`, with the bound blob: checks the workspace against the plan's dry-run sizes, then carves it
+  int use_workspace(const char* fn, void* ws, size_t ws_bytes, const PlanSize& z, void* stream, const float* wdev) {
     PF_REQUIRE(((uintptr_t)ws & 255) == 0, "%s: workspace must be 256-byte aligned", fn);
     if (ws_bytes < z.bytes()) return set_error(PF_EINVAL, "%s: workspace too small (%zu < %zu)", fn, ws_bytes, z.bytes());
     dry = false;
     base = (char*)ws;
     temp_base = z.persist;
+    s = (hipStream_t)stream; W = wdev;
     return PF_OK;
   }
 };

@@ -235,7 +235,7 @@ def test_planes_gemm_chain(lib, B, L, k, n):
         wg, bg = rnd((2 * n, k), 95, k ** -0.5), rnd((2 * n,), 96, 0.1)
         h = F.linear(x, wg, bg)
         gref = h[..., :n] * F.gelu(h[..., n:])
-        # interleaved GeGLU packing is the plan's job (unet.hip D_GEGLU_W): value/gate rows alternate in 32-column blocks
+        # interleaved GeGLU packing is the plan's job (plan.hip D_GEGLU_W): value/gate rows alternate in 32-column blocks
         wi = torch.stack([wg[:n].view(n // 32, 32, k), wg[n:].view(n // 32, 32, k)], 1).reshape(2 * n, k)
         bi = torch.stack([bg[:n].view(n // 32, 32), bg[n:].view(n // 32, 32)], 1).reshape(2 * n)
         gp = torch.zeros(B * L * n, device="cuda")

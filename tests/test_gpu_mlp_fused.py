@@ -24,7 +24,7 @@ def _weights(seed):
     w1, b1 = rnd((2 * HID, C), seed, C ** -0.5), rnd((2 * HID,), seed + 1, 0.1)
     w2, b2 = rnd((C, HID), seed + 2, HID ** -0.5), rnd((C,), seed + 3, 0.1)
     gamma, beta = 1 + 0.1 * rnd((C,), seed + 4), 0.1 * rnd((C,), seed + 5)
-    # value/gate rows interleaved in 32-row blocks: what the plan's D_GEGLU_W packing does (unet.hip geglu_col)
+    # value/gate rows interleaved in 32-row blocks: what the plan's D_GEGLU_W packing does (plan.hip geglu_col)
     w1i = torch.stack([w1[:HID].view(HID // 32, 32, C), w1[HID:].view(HID // 32, 32, C)], 1).reshape(2 * HID, C)
     b1i = torch.stack([b1[:HID].view(HID // 32, 32), b1[HID:].view(HID // 32, 32)], 1).reshape(2 * HID)
     return w1, b1, w2, b2, gamma, beta, w1i, b1i
