@@ -252,6 +252,40 @@ size_t pf_encoder_workspace_bytes(const pf_encoder* e, int batch);
 int pf_encoder_forward(pf_encoder* e, const float* x, int batch, int n_step, float* mu,
                        void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- frozen decoders, inference mode (greedy: every arg-max is fed back as the next token; ties go to the lowest index); plain fp32.
+ *      PF_DEC_PNOTREE replaces PianoTreeDecoder.decoder(z, True, None, None, 0, 0) (dl_modules/pianotree_dec.py:155-332) at the default
+ *      sizes of PianoTreeDecoder.__init__ (:11-99); only max_simu_note (2..32) is an argument, the other create arguments are ignored.
+ *      PF_DEC_CHORD replaces ChordDecoder.forward(z_chd, True, 0.) (dl_modules/chord_dec.py:27-70) for
+ *      ChordDecoder(input_dim = 36, z_input_dim, hidden_dim, z_dim, n_step) (:8-25).
+ *      Parameter keys and shapes are the state_dict of those modules, in its order (pf_decoder_param_info). */
+typedef struct pf_decoder pf_decoder;
+enum { PF_DEC_CHORD = 0, PF_DEC_PNOTREE = 1 };
+int pf_decoder_create(int kind, int max_simu_note, int input_dim, int z_input_dim, int hidden_dim, int z_dim, int n_step,
+                      pf_decoder** out);
+void pf_decoder_destroy(pf_decoder* d);
+size_t pf_decoder_weight_bytes(const pf_decoder* d);
+int pf_decoder_n_params(const pf_decoder* d);
+int pf_decoder_param_info(const pf_decoder* d, int i, char* key_buf, size_t key_buf_len, int64_t shape[4], int* ndim);
+/* nn.Module.load_state_dict of the two decoders: one tensor into the host blob (same messages as the other handles) */
+int pf_decoder_pack_param(pf_decoder* d, const char* key, const float* src, const int64_t* shape, int ndim, void* host_blob);
+int pf_decoder_pack_missing(const pf_decoder* d, char* buf, size_t buf_len);
+/* The blob must be writable and 16-byte aligned: for PF_DEC_PNOTREE its tail is filled here, on the device, with what the decode loop
+ * reads instead of note_embedding + the token columns of the GRU input weights (pianotree_dec.py:147-153 folded into :214-216 and
+ * :320-327).  Synchronises the device; not part of a decode. */
+int pf_decoder_bind_weights(pf_decoder* d, void* dev_blob);
+size_t pf_decoder_workspace_bytes(const pf_decoder* d, int rows);
+/* Kernel launches one pf_decoder_forward enqueues (host arithmetic, no GPU needed); it does not depend on rows. */
+int pf_decoder_launches(const pf_decoder* d, int rows);
+/* pnotree: z [rows,512] -> out0 = recon_pitch [rows,32,S-1,130], out1 = recon_dur [rows,32,S-1,5,2] (the two tensors
+ *          PianoTreeDecoder.forward returns, pianotree_dec.py:334-339), out2 unused, est [rows,32,S-1,6] = their max(-1)[1]
+ *          (pitch index, 5 duration digits: output_to_numpy, :375-378), S = max_simu_note.
+ * chord:   z [rows,z_dim] -> out0 = recon_root [rows,n_step,12], out1 = recon_chroma [rows,n_step,12,2], out2 = recon_bass
+ *          [rows,n_step,12] (chord_dec.py:66-70), est unused.
+ * Everything is caller-owned device memory (workspace 16-byte aligned); launches only, on `stream`: capturable as a graph.  A row's
+ * result does not depend on the other rows of the call. */
+int pf_decoder_forward(pf_decoder* d, const float* z, int rows, float* out0, float* out1, float* out2, int32_t* est,
+                       void* workspace, size_t workspace_bytes, void* stream);
+
 /* Arithmetic of the dense contractions (convs / linears):
  *   PF_PREC_F32    - v_mfma_f32_32x32x2_f32, exact fp32 FMA chains (157 TFLOP/s pipe);
  *   PF_PREC_BF16X3 - error-compensated split on the bf16 pipe: a.w ~= a_hi.w_hi + a_hi.w_lo + a_lo.w_hi with fp32

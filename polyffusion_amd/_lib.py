@@ -162,6 +162,18 @@ SIGNATURES = {
     "pf_encoder_bind_weights": (C.c_int, [C.c_void_p, C.c_void_p]),
     "pf_encoder_workspace_bytes": (C.c_size_t, [C.c_void_p, C.c_int]),
     "pf_encoder_forward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "pf_decoder_create": (C.c_int, [C.c_int] * 7 + [C.POINTER(C.c_void_p)]),
+    "pf_decoder_destroy": (None, [C.c_void_p]),
+    "pf_decoder_weight_bytes": (C.c_size_t, [C.c_void_p]),
+    "pf_decoder_n_params": (C.c_int, [C.c_void_p]),
+    "pf_decoder_param_info": (C.c_int, [C.c_void_p, C.c_int, C.c_char_p, C.c_size_t, c_i64_p, C.POINTER(C.c_int)]),
+    "pf_decoder_pack_param": (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, c_i64_p, C.c_int, C.c_void_p]),
+    "pf_decoder_pack_missing": (C.c_int, [C.c_void_p, C.c_char_p, C.c_size_t]),
+    "pf_decoder_bind_weights": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "pf_decoder_workspace_bytes": (C.c_size_t, [C.c_void_p, C.c_int]),
+    "pf_decoder_launches": (C.c_int, [C.c_void_p, C.c_int]),
+    "pf_decoder_forward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                     C.c_size_t, C.c_void_p]),
     "pf_packed_gemm_weight_floats": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
     "pf_pack_gemm_weight": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "pf_pack_gemm_weight_bf16x3": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]),

@@ -237,3 +237,57 @@ def pianotree_encoder_param_shapes(note_size=135, note_emb_size=128, enc_notes_h
     out["linear_std.weight"] = (z_size, 2 * enc_time_hid_size)
     out["linear_std.bias"] = (z_size,)
     return out
+
+
+def _gru_shapes(out, name, inp, hid, bidirectional=False):
+    for sfx in ("", "_reverse") if bidirectional else ("",):
+        out[f"{name}.weight_ih_l0{sfx}"] = (3 * hid, inp)
+        out[f"{name}.weight_hh_l0{sfx}"] = (3 * hid, hid)
+        out[f"{name}.bias_ih_l0{sfx}"] = (3 * hid,)
+        out[f"{name}.bias_hh_l0{sfx}"] = (3 * hid,)
+
+
+def pianotree_decoder_param_shapes(note_size=135, note_emb_size=128, z_size=512, dec_emb_hid_size=128, dec_time_hid_size=1024,
+                                   dec_notes_hid_size=512, dec_z_in_size=256, dec_dur_hid_size=16, dur_width=5):
+    """reference: dl_modules/pianotree_dec.py:53-99, in state_dict order (the two bare parameters first)."""
+    pitch_range = note_size - dur_width
+    out = OrderedDict()
+    out["dec_init_input"] = (2 * dec_emb_hid_size,)
+    out["dur_sos_token"] = (dur_width,)
+    out["note_embedding.weight"] = (note_emb_size, note_size)
+    out["note_embedding.bias"] = (note_emb_size,)
+    out["z2dec_hid_linear.weight"] = (dec_time_hid_size, z_size)
+    out["z2dec_hid_linear.bias"] = (dec_time_hid_size,)
+    out["z2dec_in_linear.weight"] = (dec_z_in_size, z_size)
+    out["z2dec_in_linear.bias"] = (dec_z_in_size,)
+    _gru_shapes(out, "dec_notes_emb_gru", note_emb_size, dec_emb_hid_size, bidirectional=True)
+    _gru_shapes(out, "dec_time_gru", dec_z_in_size + 2 * dec_emb_hid_size, dec_time_hid_size)
+    out["dec_time_to_notes_hid.weight"] = (dec_notes_hid_size, dec_time_hid_size)
+    out["dec_time_to_notes_hid.bias"] = (dec_notes_hid_size,)
+    _gru_shapes(out, "dec_notes_gru", dec_time_hid_size + note_emb_size, dec_notes_hid_size)
+    out["pitch_out_linear.weight"] = (pitch_range, dec_notes_hid_size)
+    out["pitch_out_linear.bias"] = (pitch_range,)
+    _gru_shapes(out, "dec_dur_gru", dur_width, dec_dur_hid_size)
+    out["dur_hid_linear.weight"] = (dec_dur_hid_size, pitch_range + dec_notes_hid_size)
+    out["dur_hid_linear.bias"] = (dec_dur_hid_size,)
+    out["dur_out_linear.weight"] = (2, dec_dur_hid_size)
+    out["dur_out_linear.bias"] = (2,)
+    return out
+
+
+def chord_decoder_param_shapes(input_dim=36, z_input_dim=256, hidden_dim=512, z_dim=256):
+    """reference: dl_modules/chord_dec.py:8-25, in state_dict order (``init_input`` is a bare parameter: first)."""
+    out = OrderedDict()
+    out["init_input"] = (36,)
+    out["z2dec_hid.weight"] = (hidden_dim, z_dim)
+    out["z2dec_hid.bias"] = (hidden_dim,)
+    out["z2dec_in.weight"] = (z_input_dim, z_dim)
+    out["z2dec_in.bias"] = (z_input_dim,)
+    _gru_shapes(out, "gru", input_dim + z_input_dim, hidden_dim)
+    out["root_out.weight"] = (12, hidden_dim)
+    out["root_out.bias"] = (12,)
+    out["chroma_out.weight"] = (24, hidden_dim)
+    out["chroma_out.bias"] = (24,)
+    out["bass_out.weight"] = (12, hidden_dim)
+    out["bass_out.bias"] = (12,)
+    return out

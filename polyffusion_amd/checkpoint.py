@@ -176,6 +176,16 @@ def split_state_full(state: Mapping[str, torch.Tensor]) -> Dict[str, State]:
     return out
 
 
+def split_state_decoders(state: Mapping[str, torch.Tensor]) -> Dict[str, State]:
+    """The decode-only parts ``split_state_full`` drops: sub-dicts ``chord_dec`` / ``pnotree_dec`` with their prefixes removed."""
+    out: Dict[str, State] = {"chord_dec": {}, "pnotree_dec": {}}
+    for k, v in state.items():
+        part = k.split(".")[0]
+        if part in out:
+            out[part][k[len(part) + 1:]] = v
+    return out
+
+
 def split_state(state: Mapping[str, torch.Tensor]):
     """(unet, chord_enc, txt_enc) of ``split_state_full`` (the PianoTree encoder of the sdf_pnotree variant: use the full form)."""
     f = split_state_full(state)

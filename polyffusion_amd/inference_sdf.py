@@ -393,15 +393,43 @@ def make_parser() -> ArgumentParser:
                    "ordinarily-conditioned weights); f16x3 = the same split in fp16 pieces (libpfhip_f16.so: fp32-class error at ~0.97 of bf16x3's "
                    "speed, activations must stay below 65504); auto (default) = evaluate f32 and bf16x3 once on this checkpoint and keep bf16x3 "
                    "only if they agree to 3e-4 of the output scale; auto-f16x3 = the same probe for f16x3 (it catches a range overflow)")
+    p.add_argument("--no_pnotree_recon", action="store_true", help="cond_type pnotree: do not decode the encoded condition into "
+                   "pnotree_recon.mid (the generated songs are the same either way)")
     p.add_argument("--hip_graph", action="store_true", help="capture one reverse step as a hipGraph and replay it (same results; "
                    "removes the host-side launch cost that bounds small batches, e.g. the batch-1 runs of --autoreg)")
     return p
 
 
+def write_pnotree_recon(model: Polyffusion_SDF, args, cond, say=print):
+    """ref:inference_sdf.py:761-762 - decode the encoded condition back to notes and write ``pnotree_recon.mid`` into the output
+    directory: what the condition the denoiser sees actually encodes.  Needs PianoTree decoder weights (synthetic, or
+    ``pnotree_dec.*`` keys of the checkpoint); without them one line is printed and the run goes on.  Draws no random numbers."""
+    from .model_sdf import PianoTreeDecoder
+    if args.synthetic_weights:
+        from .weights import synth_pianotree_decoder_state
+        state = synth_pianotree_decoder_state(0)
+    else:
+        state = getattr(model, "pnotree_dec_state", None)      # left by load_model (rank 0) from the checkpoint it read
+    model.pnotree_dec_state = None                             # the tensors are needed once
+    if not state:
+        say("pnotree_recon.mid not written: the checkpoint has no pnotree_dec.* weights")
+        return None
+    # the decoder lives for this call only: its blob and workspace do not stay on the GPU through sampling
+    dec = PianoTreeDecoder(max_simu_note=20).load_state_dict(state)
+    grid = Polyffusion_SDF(None, "pnotree", pnotree_dec=dec)._decode_pnotree(cond)
+    del dec
+    os.makedirs(args.output_dir, exist_ok=True)
+    path = os.path.join(args.output_dir, "pnotree_recon.mid")
+    midi.estx_to_midi_file(grid, path)
+    say(f"condition reconstruction: grid {tuple(grid.shape)} -> {path}")
+    return path
+
+
 def _packed_blobs(params, args, parts, chord_enc, txt_enc):
-    """Rank 0's half of ``load_model``: checkpoint (or synthetic) state_dicts -> packed host blobs, one per sub-model."""
-    from .checkpoint import load_checkpoint, split_state_full
-    states = {}
+    """Rank 0's half of ``load_model``: checkpoint (or synthetic) state_dicts -> packed host blobs, one per sub-model; the second
+    result is the checkpoint's ``pnotree_dec.*`` part (empty without one), which ``write_pnotree_recon`` uses."""
+    from .checkpoint import load_checkpoint, split_state_decoders, split_state_full
+    states, pnotree_dec_state = {}, {}
     if args.synthetic_weights:
         from .arch import UNetConfig
         from .weights import synth_chord_encoder_state, synth_pianotree_encoder_state, synth_texture_encoder_state, synth_unet_state
@@ -419,13 +447,15 @@ def _packed_blobs(params, args, parts, chord_enc, txt_enc):
             path = f"{path}/chkpts/{args.chkpt_name}"
         if not path or not (path.endswith(".pt") or path.endswith(".ckpt")):
             raise SystemExit("--chkpt_path must name a legacy .pt or a Lightning .ckpt checkpoint (or a run directory holding chkpts/)")
-        states = split_state_full(load_checkpoint(path)[0])
+        full = load_checkpoint(path)[0]
+        states = split_state_full(full)
+        pnotree_dec_state = split_state_decoders(full)["pnotree_dec"] if params.cond_type == "pnotree" else {}
     blobs = {}
     for name, mod, _ in parts:
         if not states.get(name):
             raise SystemExit(f"checkpoint has no {name} weights")
         blobs[name] = mod.pack_state_dict(states[name])
-    return blobs
+    return blobs, pnotree_dec_state
 
 
 def load_model(params, args, rank: int = 0, world: int = 1) -> Polyffusion_SDF:
@@ -444,12 +474,13 @@ def load_model(params, args, rank: int = 0, world: int = 1) -> Polyffusion_SDF:
     if pnotree_enc is not None:
         parts.append(("pnotree_enc", pnotree_enc, int(_lib.load().pf_encoder_weight_bytes(pnotree_enc._h))))
     dev = _dev()
-    blobs, failure = {}, None
+    blobs, failure, pnotree_dec_state = {}, None, None
     if rank == 0:
         # every failure of the load (bad path, missing sub-model, unexpected / mis-shaped key) happens on rank 0 only while the
         # other ranks already wait for the blobs: catch it, tell them, and let every rank leave with the same message
         try:
-            blobs = {name: blob.to(dev) for name, blob in _packed_blobs(params, args, parts, chord_enc, txt_enc).items()}
+            host_blobs, pnotree_dec_state = _packed_blobs(params, args, parts, chord_enc, txt_enc)
+            blobs = {name: blob.to(dev) for name, blob in host_blobs.items()}
         except (SystemExit, Exception) as e:   # noqa: BLE001 - re-raised below on every rank
             failure = e
     if pfdist.broadcast_int(0 if failure is None else 1) != 0:
@@ -463,8 +494,10 @@ def load_model(params, args, rank: int = 0, world: int = 1) -> Polyffusion_SDF:
         blob = blobs[name] if rank == 0 else torch.empty(nbytes // 4, dtype=torch.float32, device=dev)
         pfdist.broadcast_blob(blob, 0)
         mod.bind_packed(blob)
-    return Polyffusion_SDF(build_ldm(params, unet), params.cond_type, params.cond_mode, chord_enc=chord_enc, txt_enc=txt_enc,
-                           pnotree_enc=pnotree_enc)
+    model = Polyffusion_SDF(build_ldm(params, unet), params.cond_type, params.cond_mode, chord_enc=chord_enc, txt_enc=txt_enc,
+                            pnotree_enc=pnotree_enc)
+    model.pnotree_dec_state = pnotree_dec_state or None
+    return model
 
 
 def make_sampler(model, args, seed: int, sample_offset: int = 0):
@@ -644,6 +677,8 @@ def main(argv=None):
     if params.cond_type == "pnotree" and pnotree is None:
         raise SystemExit("cond_type pnotree needs the piano-tree grid: --from_midi, --from_song_npz, pnotree in --cond_npz or --synthetic")
     cond, cond_mid = encode_conditions(model, params, chd, prmat, args.autoreg, pnotree=pnotree)
+    if params.cond_type == "pnotree" and rank == 0 and not args.no_pnotree_recon:
+        write_pnotree_recon(model, args, cond, say)
     if params.cond_mode == "uncond":
         cond = -torch.ones_like(cond)
     if length > 0:

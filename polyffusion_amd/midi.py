@@ -76,6 +76,32 @@ def prmat2c_to_midi_file(prmat2c, fpath: str, labels: Optional[Sequence[str]] = 
     write_smf(fpath, [origin, inpainted] if inp_mask is not None else [origin], lyrics)
 
 
+def estx_note_list(est_x) -> List[Note]:
+    """The notes ref:utils.py:324-349 appends for an index grid ``[N, steps, slots, 6]`` (pitch index, five binary duration digits,
+    most significant first), in its order (segment, step, slot).  EVERY slot whose pitch is 0..127 is a note - also one after an end
+    token: the reference does not stop there.  A step is 1/8 s, a note is clipped to the end of its segment."""
+    x = est_x.detach().cpu().numpy() if isinstance(est_x, torch.Tensor) else np.asarray(est_x)
+    if x.ndim != 4 or x.shape[3] != 6:
+        raise RuntimeError(f"est_x must be [N, steps, slots, 6], got {tuple(x.shape)}")
+    x = x.astype(np.int64)
+    n_step = x.shape[1]
+    seg, step, slot = np.nonzero((x[..., 0] >= 0) & (x[..., 0] <= 127))
+    key = x[seg, step, slot]
+    dur = key[:, 5] + (key[:, 4] << 1) + (key[:, 3] << 2) + (key[:, 2] << 3) + (key[:, 1] << 4) + 1
+    t0 = seg * (n_step / 8)
+    start = t0 + step * 1 / 8
+    end = np.minimum(t0 + (step + dur) * 1 / 8, t0 + n_step / 8)
+    return list(zip(key[:, 0].tolist(), start.tolist(), end.tolist()))
+
+
+def estx_to_midi_file(est_x, fpath: str, labels: Optional[Sequence[str]] = None) -> None:
+    """ref:utils.py:311-359 - an index grid (``Polyffusion_SDF._decode_pnotree``) as a MIDI file: one piano track, velocity 80, plus
+    one lyric per segment when ``labels`` is given.  Host code: the grid is a few thousand integers."""
+    n_step = est_x.shape[1]
+    lyrics = [(str(lab), float(i * (n_step / 8))) for i, lab in enumerate(labels)] if labels is not None else None
+    write_smf(fpath, [estx_note_list(est_x)], lyrics)
+
+
 # ---------------------------------------------------------------------------------------------- standard MIDI file
 def _vlq(v: int) -> bytes:
     out = [v & 0x7F]

@@ -7,6 +7,8 @@
   (:153-164) and ``load_trained`` (:59-84; legacy ``.pt`` with ``{"model": state_dict}``).
 * ``load_pretrained_chd_enc`` / ``load_pretrained_txt_enc``: the key-prefix remaps of
   ``utils.py:48-86`` (``chord_enc.`` / ``rhy_encoder.``).
+* ``PianoTreeDecoder`` / ``ChordDecoder`` (``decoders.py``), ``_decode_pnotree`` (:166-183), ``_decode_chord`` (:108-136) and
+  ``load_pretrained_pnotree_enc_dec`` / ``load_pretrained_chd_enc_dec`` (``utils.py:19-69``).
 """
 from __future__ import annotations
 
@@ -17,6 +19,7 @@ import torch
 
 from . import _lib
 from ._handle import ModelHandle
+from .decoders import ChordDecoder, PianoTreeDecoder  # noqa: F401  (part of this module's surface, like the reference's dl_modules)
 from .unet import LatentDiffusion
 
 
@@ -115,14 +118,46 @@ def load_pretrained_txt_enc(state: Mapping[str, object], emb_size, hidden_dim, z
     return TextureEncoder(emb_size, hidden_dim, z_dim, num_channel, device).load_state_dict(_strip(state, "rhy_encoder"))
 
 
+def split_pnotree_vae_state(state: Mapping[str, object]):
+    """The key routing of utils.py:23-42: encoder parts to the encoder, everything else to the decoder, ``note_embedding.*`` to both."""
+    enc_parts = ("note_embedding", "enc_notes_gru", "enc_time_gru", "linear_mu", "linear_std")
+    enc_state, dec_state = {}, {}
+    for k, v in state.items():
+        part = k.split(".")[0]
+        if part in enc_parts:
+            enc_state[k] = v
+            if part == "note_embedding":
+                dec_state[k] = v
+        else:
+            dec_state[k] = v
+    return enc_state, dec_state
+
+
+def load_pretrained_pnotree_enc_dec(state, max_simu_note, device=None):
+    """utils.py:19-45: a PianoTree VAE checkpoint (bare keys) -> (encoder, decoder); ``note_embedding.*`` goes to both."""
+    if isinstance(state, (str, bytes)) or hasattr(state, "__fspath__"):
+        from .checkpoint import load_legacy_pt
+        state = load_legacy_pt(str(state))
+    enc_state, dec_state = split_pnotree_vae_state(state)
+    enc = PianoTreeEncoder(max_simu_note=max_simu_note, device=device)
+    dec = PianoTreeDecoder(max_simu_note=max_simu_note, device=device)
+    return enc.load_state_dict(enc_state), dec.load_state_dict(dec_state)
+
+
+def load_pretrained_chd_enc_dec(state, input_dim, z_input_dim, hidden_dim, z_dim, n_step, device=None):
+    """utils.py:48-69: the ``chord_enc.`` / ``chord_dec.`` keys of a chd_8bar checkpoint -> (encoder, decoder)."""
+    enc = ChordEncoder(input_dim, hidden_dim, z_dim, device).load_state_dict(_strip(state, "chord_enc"))
+    dec = ChordDecoder(input_dim, z_input_dim, hidden_dim, z_dim, n_step, device).load_state_dict(_strip(state, "chord_dec"))
+    return enc, dec
+
+
 class Polyffusion_SDF:
     def __init__(self, ldm: LatentDiffusion, cond_type, cond_mode="cond", chord_enc: Optional[ChordEncoder] = None,
                  chord_dec=None, pnotree_enc=None, pnotree_dec=None, txt_enc: Optional[TextureEncoder] = None,
                  concat_blurry=False, concat_ratio=1 / 8):
-        if pnotree_dec is not None or chord_dec is not None:
-            raise NotImplementedError("decoder modules (reconstruction / debugging output) are outside the denoising path (SURVEY.md 2 #12)")
         self.ldm, self.cond_type, self.cond_mode = ldm, cond_type, cond_mode
         self.chord_enc, self.txt_enc, self.pnotree_enc = chord_enc, txt_enc, pnotree_enc
+        self.chord_dec, self.pnotree_dec = chord_dec, pnotree_dec
         self.concat_blurry, self.concat_ratio = concat_blurry, concat_ratio
 
     @classmethod
@@ -137,9 +172,14 @@ class Polyffusion_SDF:
         return model
 
     def load_state_dict(self, state: Mapping[str, object]):
-        from .checkpoint import split_state, split_state_full
+        from .checkpoint import split_state, split_state_decoders, split_state_full
         unet, ce, te = split_state(state)
         self.ldm.eps_model.load_state_dict(unet)
+        dec = split_state_decoders(state)     # decoder keys go to an attached decoder; without one they are dropped
+        if self.pnotree_dec is not None and dec["pnotree_dec"]:
+            self.pnotree_dec.load_state_dict(dec["pnotree_dec"])
+        if self.chord_dec is not None and dec["chord_dec"]:
+            self.chord_dec.load_state_dict(dec["chord_dec"])
         pe = split_state_full(state)["pnotree_enc"]
         if self.pnotree_enc is not None and pe:
             self.pnotree_enc.load_state_dict(pe)
@@ -156,6 +196,26 @@ class Polyffusion_SDF:
         if self.chord_enc is not None:
             return self.chord_enc(chord).mean.unsqueeze(1)  # [B,1,512]
         return torch.reshape(chord, (-1, 1, chord.shape[1] * chord.shape[2]))
+
+    def _decode_chord(self, z: torch.Tensor) -> torch.Tensor:
+        """models/model_sdf.py:108-136: ``z`` [B, z_dim] -> [B, n_step, 36] int64 (one-hot root | chroma bits | one-hot bass); ``z``
+        itself without a decoder."""
+        if self.chord_dec is None:
+            return z
+        root, chroma, bass = self.chord_dec(z, inference=True, tfr=0.0)
+        one_hot = torch.nn.functional.one_hot
+        return torch.cat([one_hot(root.max(-1)[1], 12), chroma.max(-1)[1], one_hot(bass.max(-1)[1], 12)], dim=-1)
+
+    def _decode_pnotree(self, z: torch.Tensor) -> torch.Tensor:
+        """models/model_sdf.py:166-183: ``z`` [B, 1, 4*z_dim] (or [B, 4*z_dim]) -> the index grid [B, 128, S-1, 6] int64, the four
+        two-bar segments of a sample along dim 1.  The four slices of every sample are decoded as ONE batch of 4B rows.
+        Not kept from the reference: its ``z_seg.squeeze()`` also removes the batch dimension at B = 1 (and then fails inside the
+        decoder); here B = 1 is one sample."""
+        assert self.pnotree_dec is not None
+        B = z.shape[0]
+        rows = z.reshape(B * 4, -1)                            # rows (b, segment): [B, 4*z_dim] -> [4B, z_dim] is a pure view
+        est = self.pnotree_dec.decode(rows)[2]                 # [4B, 32, S-1, 6]
+        return est.view(B, 4 * 32, est.shape[2], 6)
 
     def _encode_pnotree(self, pnotree: torch.Tensor) -> torch.Tensor:
         """models/model_sdf.py:138-151: the four 2-bar segments of every sample through the encoder, means concatenated: [B,1,4z]."""

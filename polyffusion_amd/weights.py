@@ -84,3 +84,38 @@ def synth_ddpm_state(cfg, seed: int = 0) -> "OrderedDict[str, np.ndarray]":
     """Vanilla DDPM UNet tensors (ddpm.DDPMConfig) keyed relative to ``eps_model`` (e.g. ``down.0.res.conv1.weight``)."""
     from .ddpm import ddpm_param_shapes
     return synth_tensors(ddpm_param_shapes(cfg), seed)
+
+
+def _synth_decoder(shapes, seed, prefix, gru_hidden, rand_keys):
+    out = OrderedDict()
+    for k, s in shapes.items():
+        rng = np.random.Generator(np.random.PCG64([seed, zlib.crc32((prefix + k).encode())]))
+        if ".weight_" in k or ".bias_ih_" in k or ".bias_hh_" in k:      # GRU tensors: torch's U(-1/sqrt(H), 1/sqrt(H))
+            b = 1.0 / gru_hidden(k) ** 0.5
+            out[k] = rng.uniform(-b, b, size=s).astype(np.float32)
+        elif k in rand_keys:                                             # nn.Parameter(torch.rand(...)): U(0, 1)
+            out[k] = rng.uniform(0.0, 1.0, size=s).astype(np.float32)
+        else:
+            out[k] = _draw(prefix + k, s, seed)
+    return out
+
+
+def synth_pianotree_decoder_state(seed: int = 0):
+    """PianoTreeDecoder tensors at its default sizes (dl_modules/pianotree_dec.py).  ``note_embedding.*`` is the encoder's (the trained
+    model shares it); the end-token bias is raised so that end tokens occur and the predicted lengths vary."""
+    from .arch import pianotree_decoder_param_shapes
+    hid = {"dec_notes_emb_gru": 128, "dec_time_gru": 1024, "dec_notes_gru": 512, "dec_dur_gru": 16}
+    out = _synth_decoder(pianotree_decoder_param_shapes(), seed, "pnotree_dec.", lambda k: hid[k.split(".")[0]],
+                         ("dec_init_input", "dur_sos_token"))
+    enc = synth_pianotree_encoder_state(seed)
+    out["note_embedding.weight"], out["note_embedding.bias"] = enc["note_embedding.weight"], enc["note_embedding.bias"]
+    out["pitch_out_linear.bias"] = out["pitch_out_linear.bias"].copy()
+    out["pitch_out_linear.bias"][129] += np.float32(0.3)
+    return out
+
+
+def synth_chord_decoder_state(seed: int = 0, input_dim=36, z_input_dim=256, hidden_dim=512, z_dim=256):
+    """ChordDecoder tensors (dl_modules/chord_dec.py)."""
+    from .arch import chord_decoder_param_shapes
+    return _synth_decoder(chord_decoder_param_shapes(input_dim, z_input_dim, hidden_dim, z_dim), seed, "chord_dec.", lambda k: hidden_dim,
+                          ("init_input",))
