@@ -251,10 +251,23 @@ size_t pf_encoder_workspace_bytes(const pf_encoder* e, int batch);
  *          entries per time step, stored as floats - -> mu [B,z_dim] */
 int pf_encoder_forward(pf_encoder* e, const float* x, int batch, int n_step, float* mu,
                        void* workspace, size_t workspace_bytes, void* stream);
+/* The whole Normal of the Polydis encoders (polydis/ptvae.py RnnEncoder.forward :21-28 and TextureEncoder.forward :106-118):
+ * mu = linear_mu(h) as above and scale = exp(linear_var(h)), which DisentangleVAE's samplers need (polydis/model.py:188-239).
+ * pf_encoder_create_dist is pf_encoder_create with one more flag: with_scale != 0 (PF_ENC_CHORD and PF_ENC_TEXTURE only) gives
+ * linear_var.* a place in the blob and makes both keys required; pf_encoder_create is its with_scale = 0 case, whose blob size,
+ * layout and mu are unchanged (linear_var.* accepted and ignored).  pf_encoder_forward_dist runs the pipeline of pf_encoder_forward
+ * and writes mu [B,z_dim] and scale [B,z_dim]; on an encoder created without scale, or on PF_ENC_PNOTREE, it is an error. */
+int pf_encoder_create_dist(int kind, int input_dim, int emb_size, int hidden_dim, int z_dim, int num_channel, int with_scale,
+                           pf_encoder** out);
+int pf_encoder_forward_dist(pf_encoder* e, const float* x, int batch, int n_step, float* mu, float* scale,
+                            void* workspace, size_t workspace_bytes, void* stream);
 
 /* ---- frozen decoders, inference mode (greedy: every arg-max is fed back as the next token; ties go to the lowest index); plain fp32.
  *      PF_DEC_PNOTREE replaces PianoTreeDecoder.decoder(z, True, None, None, 0, 0) (dl_modules/pianotree_dec.py:155-332) at the default
- *      sizes of PianoTreeDecoder.__init__ (:11-99); only max_simu_note (2..32) is an argument, the other create arguments are ignored.
+ *      sizes of PianoTreeDecoder.__init__ (:11-99); max_simu_note (2..32) is an argument, and hidden_dim is dec_dur_hid_size, the width
+ *      of the duration GRU: 0 or 16 (the default of PianoTreeDecoder) or 64 (polydis/ptvae.py PtvaeDecoder as DisentangleVAE.init_model
+ *      builds it, polydis/model.py:314-316; the class is PianoTreeDecoder statement for statement); any other value is an error.  The
+ *      other create arguments are ignored.
  *      PF_DEC_CHORD replaces ChordDecoder.forward(z_chd, True, 0.) (dl_modules/chord_dec.py:27-70) for
  *      ChordDecoder(input_dim = 36, z_input_dim, hidden_dim, z_dim, n_step) (:8-25).
  *      Parameter keys and shapes are the state_dict of those modules, in its order (pf_decoder_param_info). */

@@ -155,6 +155,7 @@ SIGNATURES = {
     "pf_comm_destroy": (C.c_int, [C.c_void_p]),
     "pf_prmat2c_durations": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "pf_encoder_create": (C.c_int, [C.c_int] * 6 + [C.POINTER(C.c_void_p)]),
+    "pf_encoder_create_dist": (C.c_int, [C.c_int] * 7 + [C.POINTER(C.c_void_p)]),
     "pf_encoder_destroy": (None, [C.c_void_p]),
     "pf_encoder_weight_bytes": (C.c_size_t, [C.c_void_p]),
     "pf_encoder_pack_param": (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, c_i64_p, C.c_int, C.c_void_p]),
@@ -162,6 +163,8 @@ SIGNATURES = {
     "pf_encoder_bind_weights": (C.c_int, [C.c_void_p, C.c_void_p]),
     "pf_encoder_workspace_bytes": (C.c_size_t, [C.c_void_p, C.c_int]),
     "pf_encoder_forward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "pf_encoder_forward_dist": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
+                                          C.c_void_p]),
     "pf_decoder_create": (C.c_int, [C.c_int] * 7 + [C.POINTER(C.c_void_p)]),
     "pf_decoder_destroy": (None, [C.c_void_p]),
     "pf_decoder_weight_bytes": (C.c_size_t, [C.c_void_p]),

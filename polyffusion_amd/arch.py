@@ -291,3 +291,18 @@ def chord_decoder_param_shapes(input_dim=36, z_input_dim=256, hidden_dim=512, z_
     out["bass_out.weight"] = (12, hidden_dim)
     out["bass_out.bias"] = (12,)
     return out
+
+
+def polydis_param_shapes(chd_size=256, txt_size=256, num_channel=10):
+    """reference: polydis/model.py:303-319 ``DisentangleVAE.init_model`` in state_dict order - ``chd_encoder.*`` RnnEncoder(36, 1024,
+    chd_size), ``rhy_encoder.*`` TextureEncoder(256, 1024, txt_size, num_channel), ``decoder.*`` PtvaeDecoder(dec_dur_hid_size=64,
+    z_size=chd_size + txt_size) and ``chd_decoder.*`` RnnDecoder(z_dim=chd_size) (polydis/ptvae.py; the same tensors as the chord
+    encoder, the texture encoder, the PianoTree decoder and the chord decoder)."""
+    out = OrderedDict()
+    for prefix, shapes in (("chd_encoder.", chord_encoder_param_shapes(36, 1024, chd_size)),
+                           ("rhy_encoder.", texture_encoder_param_shapes(256, 1024, txt_size, num_channel)),
+                           ("decoder.", pianotree_decoder_param_shapes(z_size=chd_size + txt_size, dec_dur_hid_size=64)),
+                           ("chd_decoder.", chord_decoder_param_shapes(36, 256, 512, chd_size))):
+        for k, s in shapes.items():
+            out[prefix + k] = s
+    return out

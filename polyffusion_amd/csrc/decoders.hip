@@ -23,7 +23,8 @@ constexpr int PN_P = 130;      // pitch classes (128 pitches, sos, eos)
 constexpr int PN_DW = 5;       // duration digits
 constexpr int PN_TOK = PN_P + PN_DW;   // note token width (135)
 constexpr int PN_E = 128;      // note embedding
-constexpr int PN_Z = 512, PN_ZIN = 256, PN_HT = 1024, PN_HN = 512, PN_HE = 128, PN_HD = 16;
+constexpr int PN_Z = 512, PN_ZIN = 256, PN_HT = 1024, PN_HN = 512, PN_HE = 128;
+// (the duration GRU's width, dec_dur_hid_size, is the template parameter HD of the heads kernel: 16 or 64)
 constexpr int PN_TROWS = PN_TOK + 1;   // table rows: 135 token columns + the embedding-bias row
 
 __device__ __forceinline__ float wave_sum(float v) {
@@ -150,21 +151,31 @@ __global__ __launch_bounds__(256) void gru_step_kernel(GruStepArgs a) {
 }
 
 // ---- PianoTree heads: one workgroup per row, one note slot (decode_note + the bookkeeping of decode_notes, pianotree_dec.py:155-244)
+// HD = dec_dur_hid_size.  At 16 a thread per hidden unit walks its three rows of the duration GRU's W_hh (48 x 16 floats, in cache).  At 64
+// that walk would be 64 threads striding 64 floats apart, five times per slot, so the 192 gate rows get a thread each instead: W_hh is
+// read in a transposed copy made at bind time (consecutive threads, consecutive addresses: the form of pnotree_emb_gru_kernel), a
+// thread keeps its column in registers over the five digits, and the two output logits are one wave-wide product each.  k runs 0..63 in
+// a thread (gates) or over the fixed butterfly of wave_sum (logits): the same order for every row of every batch.
 struct PnHeadsArgs {
   const float* h;                                    // [R][512] the notes-GRU output of this slot
   const float *wp, *bp;                              // pitch_out_linear [130][512]
-  const float *wdh, *bdh;                            // dur_hid_linear [16][512 + 130]
-  const float *wdi, *wdhh, *bdi, *bdhh;              // dec_dur_gru [48][5] [48][16] [48] [48]
-  const float *wdo, *bdo;                            // dur_out_linear [2][16]
+  const float *wdh, *bdh;                            // dur_hid_linear [HD][512 + 130]
+  const float *wdi, *wdhh, *bdi, *bdhh;              // dec_dur_gru [3 HD][5] [3 HD][HD] [3 HD] [3 HD]
+  const float *wdo, *bdo;                            // dur_out_linear [2][HD]
   const float* dur_sos;                              // [5]
   const float *tn, *te;                              // token tables [136][1536] (notes GRU) and [136][768] (embedding GRU, both directions)
   float *recon_pitch, *recon_dur; int32_t* est;      // [R][32][S-1][130], [R][32][S-1][5][2], [R][32][S-1][6]
   float *gi_tok, *gie; int* lens;                    // [R][1536], [R][S][768], [R]
   int t, s, S;
+  const float* wdhh_t;                               // HD = 64: dec_dur_gru.weight_hh_l0 transposed, [64][192]
 };
+template <int HD>
 __global__ __launch_bounds__(256) void pnotree_heads_kernel(PnHeadsArgs a) {
+  static_assert(HD == 16 || HD == 64, "the duration GRU is 16 or 64 wide");
+  constexpr int PN_HD = HD;
   __shared__ __attribute__((aligned(16))) float hs[PN_HN + PN_P];   // [note_summary | est_pitch]: the input of dur_hid_linear
   __shared__ float dh[PN_HD], dl[2];
+  __shared__ float gs[HD == 64 ? 3 * HD : 1], is[HD == 64 ? 3 * HD : 1];   // HD = 64: the gate rows' hidden / input parts
   __shared__ int pidx;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, row = blockIdx.x;
   const size_t slot = ((size_t)row * 32 + a.t) * (a.S - 1) + (a.s - 1);
@@ -209,6 +220,49 @@ __global__ __launch_bounds__(256) void pnotree_heads_kernel(PnHeadsArgs a) {
   const int pitch = pidx;
   int digit[PN_DW];
   int prev = 0;
+  if constexpr (HD == 64) {
+    float wcol[HD];                    // this gate row of W_hh, kept over the five digits
+    float bh = 0.f, bi = 0.f;
+    if (tid < 3 * HD) {
+#pragma unroll
+      for (int k = 0; k < HD; ++k) wcol[k] = a.wdhh_t[k * (3 * HD) + tid];
+      bh = a.bdhh[tid];
+      bi = a.bdi[tid];
+    }
+#pragma unroll
+    for (int d = 0; d < PN_DW; ++d) {
+      if (tid < 3 * HD) {
+        float g = bh;
+#pragma unroll
+        for (int k = 0; k < HD; ++k) g = fmaf(wcol[k], dh[k], g);
+        float i = bi;
+        if (d == 0) {
+          for (int k = 0; k < PN_DW; ++k) i = fmaf(a.wdi[tid * PN_DW + k], a.dur_sos[k], i);
+        } else {
+          i += a.wdi[tid * PN_DW + prev];
+        }
+        gs[tid] = g;
+        is[tid] = i;
+      }
+      __syncthreads();
+      if (tid < HD) {
+        const float rg = sigmoid_f(is[tid] + gs[tid]), zg = sigmoid_f(is[HD + tid] + gs[HD + tid]);
+        const float ng = tanhf(is[2 * HD + tid] + rg * gs[2 * HD + tid]);
+        dh[tid] = (1.0f - zg) * ng + zg * dh[tid];
+      }
+      __syncthreads();
+      if (wave < 2) {                  // HD == 64 == a wave: one product per lane
+        const float l = wave_sum(a.wdo[wave * HD + lane] * dh[lane]) + a.bdo[wave];
+        if (lane == 0) {
+          dl[wave] = l;
+          a.recon_dur[(slot * PN_DW + d) * 2 + wave] = l;
+        }
+      }
+      __syncthreads();
+      prev = dl[1] > dl[0] ? 1 : 0;
+      digit[d] = prev;
+    }
+  } else {
 #pragma unroll
   for (int d = 0; d < PN_DW; ++d) {   // dec_dur_gru + dur_out_linear, the arg-max fed back as a one-hot of width 5
     float hn = 0.f;
@@ -249,6 +303,7 @@ __global__ __launch_bounds__(256) void pnotree_heads_kernel(PnHeadsArgs a) {
     __syncthreads();
     prev = dl[1] > dl[0] ? 1 : 0;
     digit[d] = prev;
+  }
   }
   if (tid == 0) {
     int32_t* e = a.est + slot * 6;
@@ -406,10 +461,11 @@ int launch_gru_step(const GruStepArgs& a, hipStream_t s) {
 
 struct pf_decoder {
   int kind = 0;
-  int S = 0;                                                   // pnotree: max_simu_note
+  int S = 0, HD = 16;                                          // pnotree: max_simu_note, dec_dur_hid_size
   int input_dim = 0, z_input_dim = 0, hidden = 0, z_dim = 0, n_step = 0;   // chord
   WeightTable wt;
   size_t tn = 0, te = 0, tn_sos = 0, te_sos = 0, whh_t = 0;   // pnotree: bind-time tables (float offsets into the blob)
+  size_t wdhh_t = 0;                                           // pnotree, HD = 64: transposed dec_dur_gru.weight_hh_l0
   void add(const std::string& key, std::vector<int64_t> shape) { wt.raw(key, std::move(shape)); }
   void add_gru(const std::string& name, int in, int hid, bool bidir) {
     for (const char* sfx : {"", "_reverse"}) {
@@ -444,9 +500,12 @@ int pf_decoder_create(int kind, int max_simu_note, int input_dim, int z_input_di
   PF_REQUIRE(out && (kind == PF_DEC_CHORD || kind == PF_DEC_PNOTREE), "pf_decoder_create: bad kind");
   std::unique_ptr<pf_decoder> d(new pf_decoder());
   d->kind = kind;
-  if (kind == PF_DEC_PNOTREE) {   // dl_modules/pianotree_dec.py:11-99, default sizes
+  if (kind == PF_DEC_PNOTREE) {   // dl_modules/pianotree_dec.py:11-99, default sizes; hidden_dim = dec_dur_hid_size (0: the default 16)
     PF_REQUIRE(max_simu_note >= 2 && max_simu_note <= 32, "pf_decoder_create: max_simu_note must be in 2..32");
+    PF_REQUIRE(hidden_dim == 0 || hidden_dim == 16 || hidden_dim == 64, "pf_decoder_create: dec_dur_hid_size (hidden_dim) must be 16 or 64, got %d", hidden_dim);
     d->S = max_simu_note;
+    d->HD = hidden_dim ? hidden_dim : 16;
+    const int PN_HD = d->HD;
     d->add("dec_init_input", {2 * PN_HE});
     d->add("dur_sos_token", {PN_DW});
     d->add("note_embedding.weight", {PN_E, PN_TOK});
@@ -472,6 +531,7 @@ int pf_decoder_create(int kind, int max_simu_note, int input_dim, int z_input_di
     d->tn_sos = d->wt.alloc(3 * PN_HN);
     d->te_sos = d->wt.alloc(6 * PN_HE);
     d->whh_t = d->wt.alloc((size_t)2 * PN_HE * 3 * PN_HE);
+    if (d->HD == 64) d->wdhh_t = d->wt.alloc((size_t)64 * 3 * 64);
   } else {                        // dl_modules/chord_dec.py:8-25
     PF_REQUIRE(input_dim == 36, "pf_decoder_create: the chord token is root 12 | chroma 12 | bass 12 (input_dim 36)");
     PF_REQUIRE(z_input_dim > 0 && z_dim > 0 && n_step > 0, "pf_decoder_create: bad dims");
@@ -530,6 +590,9 @@ int pf_decoder_bind_weights(pf_decoder* d, void* dev_blob) {
     hipLaunchKernelGGL(transpose_kernel, dim3(cdiv(3 * PN_HE * PN_HE, 256)), dim3(256), 0, s,
                        W + d->off("dec_notes_emb_gru.weight_hh_l0" + sx), 3 * PN_HE, PN_HE, W + d->whh_t + (size_t)dir * PN_HE * 3 * PN_HE);
   }
+  if (d->HD == 64)
+    hipLaunchKernelGGL(transpose_kernel, dim3(cdiv(3 * 64 * 64, 256)), dim3(256), 0, s, W + d->off("dec_dur_gru.weight_hh_l0"), 3 * 64, 64,
+                       W + d->wdhh_t);
   hipLaunchKernelGGL(sos_row_kernel, dim3(cdiv(3 * PN_HN, 128)), dim3(128), 0, s, W + d->tn, 3 * PN_HN, W + d->tn_sos);
   hipLaunchKernelGGL(sos_row_kernel, dim3(cdiv(6 * PN_HE, 128)), dim3(128), 0, s, W + d->te, 6 * PN_HE, W + d->te_sos);
   PF_CHECK_HIP(hipGetLastError());
@@ -601,6 +664,7 @@ int pf_decoder_forward(pf_decoder* d, const float* z, int rows, float* out0, flo
   ha.wdh = W + d->off("dur_hid_linear.weight"); ha.bdh = W + d->off("dur_hid_linear.bias");
   ha.wdi = W + d->off("dec_dur_gru.weight_ih_l0"); ha.wdhh = W + d->off("dec_dur_gru.weight_hh_l0");
   ha.bdi = W + d->off("dec_dur_gru.bias_ih_l0"); ha.bdhh = W + d->off("dec_dur_gru.bias_hh_l0");
+  ha.wdhh_t = d->HD == 64 ? W + d->wdhh_t : nullptr;
   ha.wdo = W + d->off("dur_out_linear.weight"); ha.bdo = W + d->off("dur_out_linear.bias");
   ha.dur_sos = W + d->off("dur_sos_token");
   ha.tn = W + d->tn; ha.te = W + d->te;
@@ -630,7 +694,8 @@ int pf_decoder_forward(pf_decoder* d, const float* z, int rows, float* out0, flo
       n.h_out = hn_out; n.R = R; n.H = PN_HN;
       if ((rc = launch_gru_step(n, s))) return rc;
       ha.h = hn_out; ha.t = t; ha.s = sl;
-      hipLaunchKernelGGL(pnotree_heads_kernel, dim3(R), dim3(256), 0, s, ha);
+      if (d->HD == 64) hipLaunchKernelGGL(pnotree_heads_kernel<64>, dim3(R), dim3(256), 0, s, ha);
+      else hipLaunchKernelGGL(pnotree_heads_kernel<16>, dim3(R), dim3(256), 0, s, ha);
       PF_CHECK_HIP(hipGetLastError());
     }
     if (t == 31) break;

@@ -3,7 +3,10 @@
 //   texture: TextureEncoder(conv 4x12 -> ReLU -> pool -> fc1 -> fc2 -> bi-GRU 1024 -> mu 256)
 //                                                                   (dl_modules/txt_enc.py:5-35)
 // Only Normal(mu, .).mean is consumed downstream (models/model_sdf.py:99,157), so linear_var is
-// accepted at pack time (checkpoint compatibility) and ignored.  Weights keep their torch
+// accepted at pack time (checkpoint compatibility) and ignored - unless the encoder was created
+// with_scale (pf_encoder_create_dist): Polydis samples from the Normal (polydis/model.py:188-239), so
+// linear_var.* then has a place at the end of the blob and pf_encoder_forward_dist also writes
+// scale = exp(linear_var(h)) (polydis/ptvae.py:25-27, :115-117).  Weights keep their torch
 // row-major layout; every contraction is the batched mat-vec kernel (weights stream once per
 // 8 samples), the recurrence is one mat-vec + one gate kernel per time step.
 #include <memory>
@@ -15,6 +18,7 @@ using namespace pf;
 
 struct pf_encoder {
   int kind, input_dim, emb, hidden, z, nch;
+  bool with_scale = false;
   WeightTable wt;
   void add(const std::string& key, std::vector<int64_t> shape) { wt.raw(key, std::move(shape)); }
   void add_unused(const std::string& key, std::vector<int64_t> shape) { wt.add(key, std::move(shape)).optional = true; }
@@ -23,10 +27,13 @@ struct pf_encoder {
 
 extern "C" {
 
-int pf_encoder_create(int kind, int input_dim, int emb_size, int hidden_dim, int z_dim, int num_channel, pf_encoder** out) {
+int pf_encoder_create_dist(int kind, int input_dim, int emb_size, int hidden_dim, int z_dim, int num_channel, int with_scale,
+                           pf_encoder** out) {
   PF_REQUIRE(out && (kind == PF_ENC_CHORD || kind == PF_ENC_TEXTURE || kind == PF_ENC_PNOTREE), "pf_encoder_create: bad kind");
   PF_REQUIRE(hidden_dim > 0 && z_dim > 0, "pf_encoder_create: bad dims");
+  PF_REQUIRE(!with_scale || kind != PF_ENC_PNOTREE, "pf_encoder_create_dist: the scale head exists for the chord and texture encoders only");
   std::unique_ptr<pf_encoder> e(new pf_encoder());
+  e->with_scale = with_scale != 0;
   e->kind = kind; e->input_dim = input_dim; e->emb = emb_size; e->hidden = hidden_dim; e->z = z_dim; e->nch = num_channel;
   int gru_in = input_dim;
   if (kind == PF_ENC_PNOTREE) {   // dl_modules/pianotree_enc.py:43-59
@@ -71,10 +78,18 @@ int pf_encoder_create(int kind, int input_dim, int emb_size, int hidden_dim, int
   }
   e->add("linear_mu.weight", {z_dim, 2 * hidden_dim});
   e->add("linear_mu.bias", {z_dim});
-  e->add_unused("linear_var.weight", {z_dim, 2 * hidden_dim});
-  e->add_unused("linear_var.bias", {z_dim});
+  if (e->with_scale) {   // last in the table: everything before it sits where it does without the scale head
+    e->add("linear_var.weight", {z_dim, 2 * hidden_dim});
+    e->add("linear_var.bias", {z_dim});
+  } else {
+    e->add_unused("linear_var.weight", {z_dim, 2 * hidden_dim});
+    e->add_unused("linear_var.bias", {z_dim});
+  }
   *out = e.release();
   return PF_OK;
+}
+int pf_encoder_create(int kind, int input_dim, int emb_size, int hidden_dim, int z_dim, int num_channel, pf_encoder** out) {
+  return pf_encoder_create_dist(kind, input_dim, emb_size, hidden_dim, z_dim, num_channel, 0, out);
 }
 
 void pf_encoder_destroy(pf_encoder* e) { delete e; }
@@ -112,8 +127,8 @@ size_t pf_encoder_workspace_bytes(const pf_encoder* e, int batch) {
   return enc_ws_floats(e, batch, e->kind == PF_ENC_TEXTURE ? 8 : (e->kind == PF_ENC_PNOTREE ? 32 : 64)) * sizeof(float);
 }
 
-int pf_encoder_forward(pf_encoder* e, const float* x, int batch, int n_step, float* mu, void* workspace, size_t workspace_bytes,
-                       void* stream) {
+static int enc_forward(pf_encoder* e, const float* x, int batch, int n_step, float* mu, float* scale, void* workspace,
+                       size_t workspace_bytes, void* stream) {
   PF_REQUIRE(e && x && mu && workspace && batch > 0, "pf_encoder_forward: bad arguments");
   if (!e->wt.wdev) return set_error(PF_ESTATE, "pf_encoder_forward: weights not bound");
   hipStream_t s = (hipStream_t)stream;
@@ -211,7 +226,22 @@ int pf_encoder_forward(pf_encoder* e, const float* x, int batch, int n_step, flo
       if (rc) return rc;
     }
   }
-  return launch_matvec(hcat, 2 * H, W + e->off("linear_mu.weight"), W + e->off("linear_mu.bias"), mu, e->z, B, e->z, 2 * H, s);
+  rc = launch_matvec(hcat, 2 * H, W + e->off("linear_mu.weight"), W + e->off("linear_mu.bias"), mu, e->z, B, e->z, 2 * H, s);
+  if (rc || !scale) return rc;
+  return launch_matvec_exp(hcat, 2 * H, W + e->off("linear_var.weight"), W + e->off("linear_var.bias"), scale, e->z, B, e->z, 2 * H, s);
+}
+
+int pf_encoder_forward(pf_encoder* e, const float* x, int batch, int n_step, float* mu, void* workspace, size_t workspace_bytes,
+                       void* stream) {
+  return enc_forward(e, x, batch, n_step, mu, nullptr, workspace, workspace_bytes, stream);
+}
+
+int pf_encoder_forward_dist(pf_encoder* e, const float* x, int batch, int n_step, float* mu, float* scale, void* workspace,
+                            size_t workspace_bytes, void* stream) {
+  PF_REQUIRE(e && scale, "pf_encoder_forward_dist: bad arguments");
+  PF_REQUIRE(e->kind != PF_ENC_PNOTREE, "pf_encoder_forward_dist: the PianoTree encoder has no scale head on this path (chord and texture encoders only)");
+  PF_REQUIRE(e->with_scale, "pf_encoder_forward_dist: this encoder was created without the scale head (use pf_encoder_create_dist with with_scale = 1)");
+  return enc_forward(e, x, batch, n_step, mu, scale, workspace, workspace_bytes, stream);
 }
 
 }  // extern "C"

@@ -103,6 +103,9 @@ int launch_time_embed(const int64_t* t, const float* w0, const float* b0, const 
 int launch_prmat2c_durations(const float* x, int n, int steps, int custom_round, int32_t* dur, hipStream_t stream);
 int launch_matvec(const float* x, int ldx, const float* w, const float* bias, float* y, int ldy, int batch, int n, int k,
                   hipStream_t stream, int n_per_group = 0, int x_group_stride = 0);
+// y[b][n] = expf(sum_k W[n][k] * x[b][k] + bias[n]): the same kernel with the exponential in its epilogue
+int launch_matvec_exp(const float* x, int ldx, const float* w, const float* bias, float* y, int ldy, int batch, int n, int k,
+                      hipStream_t stream);
 
 // sampler elementwise kernels
 int launch_cfg_combine(const float* eps2, float scale, float* eps, size_t n, hipStream_t s);

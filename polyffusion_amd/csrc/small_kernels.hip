@@ -348,6 +348,8 @@ int launch_time_embed(const int64_t* t, const float* w0, const float* b0, const 
 // (the only data every output needs), so the global loads of the main loop are the weight pieces alone - independent,
 // unrolled 8 deep, all in flight together - instead of nine dependent-latency loads per K step.
 // Each row's accumulation is an explicit fmaf chain in a fixed order (identical for every row: batch-position invariant).
+// EXP: the stored value is expf(y) (the scale head of the Polydis encoders, exp(linear_var(h))); the sums are the same.
+template <bool EXP>
 __global__ __launch_bounds__(256) void matvec_kernel(const float* __restrict__ x0, int ldx, const float* __restrict__ w,
                                                      const float* __restrict__ bias, float* __restrict__ y, int ldy, int B, int N,
                                                      int K, int n_per_group, int x_group_stride) {
@@ -404,19 +406,31 @@ __global__ __launch_bounds__(256) void matvec_kernel(const float* __restrict__ x
   for (int r = 0; r < RB; ++r) {
     float v = acc[r];
     v += __shfl_xor(v, 1); v += __shfl_xor(v, 2); v += __shfl_xor(v, 4);
-    if (j == 0 && n < N && r < nb) y[(size_t)(b0 + r) * ldy + n] = v + (bias ? bias[n] : 0.f);
+    if (j == 0 && n < N && r < nb) {
+      const float o = v + (bias ? bias[n] : 0.f);
+      y[(size_t)(b0 + r) * ldy + n] = EXP ? expf(o) : o;
+    }
   }
 }
 
-int launch_matvec(const float* x, int ldx, const float* w, const float* bias, float* y, int ldy, int batch, int n, int k,
-                  hipStream_t stream, int n_per_group, int x_group_stride) {
+template <bool EXP>
+static int launch_matvec_t(const float* x, int ldx, const float* w, const float* bias, float* y, int ldy, int batch, int n, int k,
+                           hipStream_t stream, int n_per_group, int x_group_stride) {
   PF_REQUIRE(x && w && y && batch > 0 && n > 0 && k > 0, "matvec: bad arguments");
   if (n_per_group <= 0) { n_per_group = n; x_group_stride = 0; }
   PF_REQUIRE((size_t)8 * k * sizeof(float) <= 64 * 1024, "matvec: K=%d too large for the staged input rows", k);
-  hipLaunchKernelGGL(matvec_kernel, dim3(cdiv(n, 32), cdiv(batch, 8)), dim3(256), (size_t)8 * k * sizeof(float), stream, x, ldx, w, bias, y, ldy, batch, n, k,
-                     n_per_group, x_group_stride);
+  hipLaunchKernelGGL(matvec_kernel<EXP>, dim3(cdiv(n, 32), cdiv(batch, 8)), dim3(256), (size_t)8 * k * sizeof(float), stream, x, ldx, w, bias, y, ldy,
+                     batch, n, k, n_per_group, x_group_stride);
   PF_CHECK_HIP(hipGetLastError());
   return PF_OK;
+}
+int launch_matvec(const float* x, int ldx, const float* w, const float* bias, float* y, int ldy, int batch, int n, int k,
+                  hipStream_t stream, int n_per_group, int x_group_stride) {
+  return launch_matvec_t<false>(x, ldx, w, bias, y, ldy, batch, n, k, stream, n_per_group, x_group_stride);
+}
+int launch_matvec_exp(const float* x, int ldx, const float* w, const float* bias, float* y, int ldy, int batch, int n, int k,
+                      hipStream_t stream) {
+  return launch_matvec_t<true>(x, ldx, w, bias, y, ldy, batch, n, k, stream, 0, 0);
 }
 
 // ------------------------------------------------------------------ sampler elementwise kernels

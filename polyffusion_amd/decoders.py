@@ -41,7 +41,8 @@ class _Decoder(ModelHandle):
 
 
 class PianoTreeDecoder(_Decoder):
-    """``PianoTreeDecoder(...)`` of the reference at its default sizes; ``max_simu_note`` (at most 32) is free."""
+    """``PianoTreeDecoder(...)`` of the reference at its default sizes; ``max_simu_note`` (at most 32) is free, and ``dec_dur_hid_size``
+    is 16 (the default) or 64 (what Polydis builds, ``polydis/model.py:314-316``)."""
     KIND = 1
 
     def __init__(self, note_embedding=None, max_simu_note=20, max_pitch=127, min_pitch=0, pitch_sos=128, pitch_eos=129, pitch_pad=130,
@@ -50,14 +51,16 @@ class PianoTreeDecoder(_Decoder):
         if note_embedding is not None:
             raise ValueError("PianoTreeDecoder: a shared note_embedding module is not supported; its tensors arrive as note_embedding.* keys")
         got = (max_pitch, min_pitch, pitch_sos, pitch_eos, pitch_pad, dur_pad, dur_width, num_step, note_emb_size, z_size, dec_emb_hid_size,
-               dec_time_hid_size, dec_notes_hid_size, dec_z_in_size, dec_dur_hid_size)
-        if got != (127, 0, 128, 129, 130, 2, 5, 32, 128, 512, 128, 1024, 512, 256, 16):
+               dec_time_hid_size, dec_notes_hid_size, dec_z_in_size)
+        if got != (127, 0, 128, 129, 130, 2, 5, 32, 128, 512, 128, 1024, 512, 256):
             raise ValueError("PianoTreeDecoder: only the reference's default sizes are built (max_simu_note is free)")
+        if dec_dur_hid_size not in (16, 64):
+            raise ValueError(f"PianoTreeDecoder: dec_dur_hid_size must be 16 or 64, got {dec_dur_hid_size}")
         if not 2 <= max_simu_note <= 32:
             raise ValueError("PianoTreeDecoder: max_simu_note must be in 2..32")
         self.max_simu_note, self.num_step, self.z_size = max_simu_note, num_step, z_size
-        self.pitch_range, self.dur_width = 130, dur_width
-        super().__init__(_lib.load(), self.KIND, max_simu_note, 0, 0, 0, 0, 0, device=device)
+        self.pitch_range, self.dur_width, self.dec_dur_hid_size = 130, dur_width, dec_dur_hid_size
+        super().__init__(_lib.load(), self.KIND, max_simu_note, 0, 0, dec_dur_hid_size, 0, 0, device=device)   # hidden_dim = the duration width
 
     def decode(self, z: torch.Tensor):
         """``z`` [R, 512] -> ``(recon_pitch [R,32,S-1,130], recon_dur [R,32,S-1,5,2], est [R,32,S-1,6] int64)``; ``est`` is the

@@ -33,6 +33,9 @@ from .sampler import DDIMSampler, DiffusionSampler, SDFSampler
 from .unet import LatentDiffusion, UNetModel
 
 
+POLYDIS_MODEL_PATH = "pretrained/polydis/model_master_final.pt"   # ref:polydis_aftertouch.py:6
+
+
 def _dev():
     return torch.device("cuda", torch.cuda.current_device())
 
@@ -395,9 +398,60 @@ def make_parser() -> ArgumentParser:
                    "only if they agree to 3e-4 of the output scale; auto-f16x3 = the same probe for f16x3 (it catches a range overflow)")
     p.add_argument("--no_pnotree_recon", action="store_true", help="cond_type pnotree: do not decode the encoded condition into "
                    "pnotree_recon.mid (the generated songs are the same either way)")
+    p.add_argument("--polydis_recon", action="store_true", help="whether to use polydis to reconstruct the generated midi from diffusion model")
+    p.add_argument("--polydis", action="store_true", help="use polydis to generate MIDI. For comparison.")
+    p.add_argument("--polydis_chd_resample", action="store_true", help="Whether to resample chord with polydis generation")
+    p.add_argument("--polydis_path", default=POLYDIS_MODEL_PATH, help="extension: the Polydis checkpoint (the reference hard-codes this path); "
+                   "--synthetic_weights selects the synthetic Polydis state instead")
     p.add_argument("--hip_graph", action="store_true", help="capture one reverse step as a hipGraph and replay it (same results; "
                    "removes the host-side launch cost that bounds small batches, e.g. the batch-1 runs of --autoreg)")
     return p
+
+
+def polydis_aftertouch(args, say=print):
+    """``PolydisAftertouch()`` of ref:inference_sdf.py:340,661 - from ``--polydis_path``, or the synthetic state with
+    ``--synthetic_weights``.  Built for one call and dropped by the caller: its blobs and workspaces do not stay on the GPU."""
+    from .polydis import PolydisAftertouch
+    if args.synthetic_weights:
+        from .weights import synth_polydis_state
+        return PolydisAftertouch(state=synth_polydis_state(0), say=say)
+    return PolydisAftertouch(model_path=args.polydis_path, say=say)
+
+
+def write_polydis(args, chd, prmat, seed: int, say=print):
+    """ref:inference_sdf.py:653-671 (``--polydis``) - the condition song's own texture and chords through Polydis, for comparison:
+    ``polydis_prmat.mid`` (the texture as given) and ``polydis_gen.mid`` (its reconstruction) in the output directory (the reference
+    writes into ``exp/`` whatever ``--output_dir`` says).  The chord resampling draws from a generator of its own, keyed by the seed."""
+    if chd is None or prmat is None:
+        raise SystemExit("--polydis needs both the chords and the texture of a condition song (chd and prmat)")
+    n = min(chd.shape[0], prmat.shape[0])
+    polydis_prmat, polydis_chd = prmat[:n].reshape(-1, 32, 128), chd[:n].reshape(-1, 8, 36)    # 2-bar rows
+    os.makedirs(args.output_dir, exist_ok=True)
+    p_in, p_gen = os.path.join(args.output_dir, "polydis_prmat.mid"), os.path.join(args.output_dir, "polydis_gen.mid")
+    midi.prmat_to_midi_file(polydis_prmat, p_in)
+    aftertouch = polydis_aftertouch(args, say)
+    aftertouch.reconstruct(polydis_prmat, polydis_chd, p_gen, chd_sample=args.polydis_chd_resample,
+                           generator=torch.Generator().manual_seed(seed))
+    del aftertouch
+    say(f"polydis: {tuple(polydis_prmat.shape)} -> {p_in}, {p_gen}")
+    return p_in, p_gen
+
+
+def write_polydis_recon(args, gen_songs, stamps, chd, say=print):
+    """ref:inference_sdf.py:339-348 (``--polydis_recon``) - every generated song's texture with the condition chords through Polydis,
+    as ``<stamp>_recon.mid``.  The reference also overwrites ``<stamp>.mid`` with a ``prmat_to_midi_file`` rendering; here the song
+    files stay what they are without the flag.  Deterministic (means only): no random numbers."""
+    aftertouch = polydis_aftertouch(args, say)
+    paths = []
+    for song, stamp in zip(gen_songs, stamps):
+        prmat = torch.from_numpy(midi.prmat2c_to_prmat(song))                    # [rows, 32, 128]
+        polydis_chd = chd.reshape(-1, 8, 36)
+        n = min(prmat.shape[0], polydis_chd.shape[0])
+        paths.append(stamp + "_recon.mid")
+        aftertouch.reconstruct(prmat[:n], polydis_chd[:n], paths[-1])
+        say(f"polydis reconstruction: {n} two-bar rows -> {paths[-1]}")
+    del aftertouch
+    return paths
 
 
 def write_pnotree_recon(model: Polyffusion_SDF, args, cond, say=print):
@@ -676,6 +730,8 @@ def main(argv=None):
 
     if params.cond_type == "pnotree" and pnotree is None:
         raise SystemExit("cond_type pnotree needs the piano-tree grid: --from_midi, --from_song_npz, pnotree in --cond_npz or --synthetic")
+    if args.polydis and rank == 0:
+        write_polydis(args, chd, prmat, seed, say)
     cond, cond_mid = encode_conditions(model, params, chd, prmat, args.autoreg, pnotree=pnotree)
     if params.cond_type == "pnotree" and rank == 0 and not args.no_pnotree_recon:
         write_pnotree_recon(model, args, cond, say)
@@ -747,13 +803,21 @@ def main(argv=None):
                          + ("; f16x3 overflows beyond 65504: rerun with --precision bf16x3 or f32" if mode == "f16x3" else ""))
     if rank == 0:
         os.makedirs(args.output_dir, exist_ok=True)
+        stamps = []
         for i in range(S):
             extra = "" if args.inpaint_type is None else f"_inp{args.repaint_n}_{args.inpaint_type}"
             stamp = os.path.join(args.output_dir, expmt._stamp(args.uncond_scale, args.autoreg, extra) + (f"_{i}" if S > 1 else ""))
+            stamps.append(stamp)
             np.save(stamp + ".npy", gen[i].cpu().numpy())
             # generated cells on their own track when inpainting (ref:inference_sdf.py:385-389)
             midi.prmat2c_to_midi_file(gen[i], stamp + ".mid", inp_mask=None if args.autoreg else mask)
             say(f"song {i}: piano_roll {tuple(gen[i].shape)}  onsets>0.5: {int((gen[i][:, 0] > 0.5).sum())}  -> {stamp}.mid")
+        if args.polydis_recon:
+            if params.cond_type in ("chord", "chord+txt") and args.inpaint_type is None and chd is not None:
+                n_seg = min(chd.shape[0], prmat.shape[0]) if params.cond_type == "chord+txt" and prmat is not None else chd.shape[0]
+                write_polydis_recon(args, [gen[i] for i in range(S)], stamps, chd[:min(n_seg, B)], say)
+            else:
+                say("--polydis_recon does nothing here: it applies to generation (not inpainting) with cond_type chord or chord+txt")
     pfdist.barrier()
     return 0
 

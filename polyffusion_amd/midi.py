@@ -1,7 +1,8 @@
 """Output step of the generation path: generated onset/sustain images -> notes -> standard MIDI file.
 
-Mirror of the reference's ``utils.prmat2c_to_prmat`` (ref:utils.py:240-269) and ``utils.prmat2c_to_midi_file``
-(ref:utils.py:433-485), same names, arguments and note semantics.  The reference walks B x steps x 128 cells in Python
+Mirror of the reference's ``utils.prmat2c_to_prmat`` (ref:utils.py:240-269), ``utils.prmat2c_to_midi_file``
+(ref:utils.py:433-485), ``utils.estx_to_midi_file`` (:311-359) and ``utils.prmat_to_midi_file`` (:362-392), same names, arguments
+and note semantics.  The reference walks B x steps x 128 cells in Python
 and delegates the file to pretty_midi; here the note extraction is one HIP kernel (``pf_prmat2c_durations``) on the image
 where the sampler left it, and the file is written by a small SMF writer with pretty_midi's defaults (format 1,
 220 ticks per beat, 120 bpm, 4/4, program 0 "Acoustic Grand Piano", note-off as note-on with velocity 0), so one 1/8 s
@@ -100,6 +101,28 @@ def estx_to_midi_file(est_x, fpath: str, labels: Optional[Sequence[str]] = None)
     n_step = est_x.shape[1]
     lyrics = [(str(lab), float(i * (n_step / 8))) for i, lab in enumerate(labels)] if labels is not None else None
     write_smf(fpath, [estx_note_list(est_x)], lyrics)
+
+
+def prmat_note_list(prmat) -> List[Note]:
+    """The notes ref:utils.py:372-384 appends for a duration matrix ``[N, steps, 128]`` (length in steps at each onset cell, 0 elsewhere;
+    what ``prmat2c_to_prmat`` returns), in its order (bar, step, key).  A step is 1/8 s, a note is clipped to the end of its bar."""
+    x = prmat.detach().cpu().numpy() if isinstance(prmat, torch.Tensor) else np.asarray(prmat)
+    if x.ndim != 3:
+        raise RuntimeError(f"prmat must be [N, steps, keys], got {tuple(x.shape)}")
+    x = x.astype(np.int64)                         # the reference's int(dur): truncation
+    t_bar = int(x.shape[1] / 8)
+    b, step, key = np.nonzero(x > 0)
+    start = b * t_bar + step * 1 / 8
+    end = np.minimum(b * t_bar + (step + x[b, step, key]) * 1 / 8, b * t_bar + t_bar)
+    return list(zip(key.tolist(), start.tolist(), end.tolist()))
+
+
+def prmat_to_midi_file(prmat, fpath: str, labels: Optional[Sequence[str]] = None) -> None:
+    """ref:utils.py:362-392 - a duration matrix ``[N, 32, 128]`` as a MIDI file: one piano track, velocity 80, plus one lyric per bar
+    group when ``labels`` is given.  Host code, like the reference's."""
+    t_bar = int(prmat.shape[1] / 8)
+    lyrics = [(str(lab), float(i * t_bar)) for i, lab in enumerate(labels)] if labels is not None else None
+    write_smf(fpath, [prmat_note_list(prmat)], lyrics)
 
 
 # ---------------------------------------------------------------------------------------------- standard MIDI file

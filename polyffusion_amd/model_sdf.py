@@ -28,11 +28,15 @@ class _Encoder(ModelHandle):
     PREFIX = "pf_encoder"
     KIND = -1
 
-    def __init__(self, input_dim, emb_size, hidden_dim, z_dim, num_channel, device=None):
-        self.hidden_dim, self.z_dim = hidden_dim, z_dim
-        super().__init__(_lib.load(), self.KIND, input_dim, emb_size, hidden_dim, z_dim, num_channel, device=device)
+    def __init__(self, input_dim, emb_size, hidden_dim, z_dim, num_channel, device=None, with_scale=False):
+        """``with_scale``: keep ``linear_var.*`` and produce the Normal's scale too (``encode_dist``; the Polydis encoders)."""
+        self.hidden_dim, self.z_dim, self.with_scale = hidden_dim, z_dim, bool(with_scale)
+        super().__init__(_lib.load(), self.KIND, input_dim, emb_size, hidden_dim, z_dim, num_channel, int(self.with_scale), device=device)
 
-    def _run(self, x: torch.Tensor, n_step: int) -> torch.Tensor:
+    def _fn(self, name: str):
+        return super()._fn("create_dist" if name == "create" else name)   # pf_encoder_create is its with_scale = 0 case
+
+    def _run(self, x: torch.Tensor, n_step: int, dist: bool = False):
         if self._blob_dev is None:
             raise RuntimeError("encoder weights not loaded")
         x = x.contiguous().float()
@@ -41,6 +45,11 @@ class _Encoder(ModelHandle):
         if self._ws is None or self._ws.numel() < nbytes:
             self._ws = torch.empty(nbytes, dtype=torch.uint8, device=x.device)
         mu = torch.empty(B, self.z_dim, dtype=torch.float32, device=x.device)
+        if dist:
+            scale = torch.empty(B, self.z_dim, dtype=torch.float32, device=x.device)
+            _lib.check(self._lib.pf_encoder_forward_dist(self._h, x.data_ptr(), B, n_step, mu.data_ptr(), scale.data_ptr(), self._ws.data_ptr(),
+                                                         self._ws.numel(), _lib.current_stream()), "pf_encoder_forward_dist", self._lib)
+            return mu, scale
         _lib.check(self._lib.pf_encoder_forward(self._h, x.data_ptr(), B, n_step, mu.data_ptr(), self._ws.data_ptr(),
                                                 self._ws.numel(), _lib.current_stream()), "pf_encoder_forward")
         return mu
@@ -55,22 +64,29 @@ class _Encoder(ModelHandle):
 class ChordEncoder(_Encoder):
     KIND = 0
 
-    def __init__(self, input_dim, hidden_dim, z_dim, device=None):
-        super().__init__(input_dim, 0, hidden_dim, z_dim, 0, device)
+    def __init__(self, input_dim, hidden_dim, z_dim, device=None, with_scale=False):
+        super().__init__(input_dim, 0, hidden_dim, z_dim, 0, device, with_scale)
 
     def encode_mean(self, chord: torch.Tensor) -> torch.Tensor:  # [B,T,input_dim] -> [B,z]
         return self._run(chord, chord.shape[1])
+
+    def encode_dist(self, chord: torch.Tensor):                  # -> (mean [B,z], scale [B,z]); needs with_scale
+        return self._run(chord, chord.shape[1], dist=True)
 
 
 class TextureEncoder(_Encoder):
     KIND = 1
 
-    def __init__(self, emb_size, hidden_dim, z_dim, num_channel=10, device=None):
-        super().__init__(0, emb_size, hidden_dim, z_dim, num_channel, device)
+    def __init__(self, emb_size, hidden_dim, z_dim, num_channel=10, device=None, with_scale=False):
+        super().__init__(0, emb_size, hidden_dim, z_dim, num_channel, device, with_scale)
 
     def encode_mean(self, pr: torch.Tensor) -> torch.Tensor:  # [B,32,128] -> [B,z]
         assert tuple(pr.shape[1:]) == (32, 128), "texture encoder input must be [B,32,128]"
         return self._run(pr, 8)
+
+    def encode_dist(self, pr: torch.Tensor):                   # -> (mean [B,z], scale [B,z]); needs with_scale
+        assert tuple(pr.shape[1:]) == (32, 128), "texture encoder input must be [B,32,128]"
+        return self._run(pr, 8, dist=True)
 
 
 class PianoTreeEncoder(_Encoder):

@@ -100,13 +100,14 @@ def _synth_decoder(shapes, seed, prefix, gru_hidden, rand_keys):
     return out
 
 
-def synth_pianotree_decoder_state(seed: int = 0):
-    """PianoTreeDecoder tensors at its default sizes (dl_modules/pianotree_dec.py).  ``note_embedding.*`` is the encoder's (the trained
-    model shares it); the end-token bias is raised so that end tokens occur and the predicted lengths vary."""
+def synth_pianotree_decoder_state(seed: int = 0, dec_dur_hid_size: int = 16):
+    """PianoTreeDecoder tensors at its default sizes (dl_modules/pianotree_dec.py); ``dec_dur_hid_size`` is the width of the duration
+    GRU (16, or 64 as Polydis builds it).  ``note_embedding.*`` is the encoder's (the trained model shares it); the end-token bias is
+    raised so that end tokens occur and the predicted lengths vary."""
     from .arch import pianotree_decoder_param_shapes
-    hid = {"dec_notes_emb_gru": 128, "dec_time_gru": 1024, "dec_notes_gru": 512, "dec_dur_gru": 16}
-    out = _synth_decoder(pianotree_decoder_param_shapes(), seed, "pnotree_dec.", lambda k: hid[k.split(".")[0]],
-                         ("dec_init_input", "dur_sos_token"))
+    hid = {"dec_notes_emb_gru": 128, "dec_time_gru": 1024, "dec_notes_gru": 512, "dec_dur_gru": dec_dur_hid_size}
+    out = _synth_decoder(pianotree_decoder_param_shapes(dec_dur_hid_size=dec_dur_hid_size), seed, "pnotree_dec.",
+                         lambda k: hid[k.split(".")[0]], ("dec_init_input", "dur_sos_token"))
     enc = synth_pianotree_encoder_state(seed)
     out["note_embedding.weight"], out["note_embedding.bias"] = enc["note_embedding.weight"], enc["note_embedding.bias"]
     out["pitch_out_linear.bias"] = out["pitch_out_linear.bias"].copy()
@@ -119,3 +120,26 @@ def synth_chord_decoder_state(seed: int = 0, input_dim=36, z_input_dim=256, hidd
     from .arch import chord_decoder_param_shapes
     return _synth_decoder(chord_decoder_param_shapes(input_dim, z_input_dim, hidden_dim, z_dim), seed, "chord_dec.", lambda k: hidden_dim,
                           ("init_input",))
+
+
+# The synthetic linear_mu (rows of std 1/sqrt(2048) on the final GRU state) gives encoded means of rms 0.044 (chord encoder) and 0.32
+# (texture encoder) on synth.chords / synth.prmat rows: below about 0.5 every row decodes to the same notes.  A constant gain on
+# linear_mu.weight brings the rms of the means into [0.5, 2] (measured: about 0.9 and 1.0).  The two encoders' rms differ by a factor of
+# 7.4, more than the band is wide, so there is one constant per encoder - chosen once, never per row or per input.
+POLYDIS_MU_GAIN = {"chd_encoder.": 24.0, "rhy_encoder.": 3.0}
+
+
+def synth_polydis_state(seed: int = 0):
+    """A ``DisentangleVAE.init_model()`` state_dict (polydis/model.py:303-319) in its key order: ``chd_encoder.*`` RnnEncoder(36, 1024,
+    256), ``rhy_encoder.*`` TextureEncoder(256, 1024, 256, 10), ``decoder.*`` PtvaeDecoder(dec_dur_hid_size=64), ``chd_decoder.*``
+    RnnDecoder(z_dim=256) - the existing encoder / decoder generators under the four prefixes, the encoders' ``linear_mu.weight`` times
+    ``POLYDIS_MU_GAIN``."""
+    parts = (("chd_encoder.", synth_chord_encoder_state(seed, 36, 1024, 256)),
+             ("rhy_encoder.", synth_texture_encoder_state(seed, 256, 1024, 256, 10)),
+             ("decoder.", synth_pianotree_decoder_state(seed, 64)),
+             ("chd_decoder.", synth_chord_decoder_state(seed, 36, 256, 512, 256)))
+    out = OrderedDict()
+    for prefix, st in parts:
+        for k, v in st.items():
+            out[prefix + k] = v * np.float32(POLYDIS_MU_GAIN[prefix]) if prefix in POLYDIS_MU_GAIN and k == "linear_mu.weight" else v
+    return out
