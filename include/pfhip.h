@@ -287,7 +287,8 @@ int pf_decoder_pack_missing(const pf_decoder* d, char* buf, size_t buf_len);
  * :320-327).  Synchronises the device; not part of a decode. */
 int pf_decoder_bind_weights(pf_decoder* d, void* dev_blob);
 size_t pf_decoder_workspace_bytes(const pf_decoder* d, int rows);
-/* Kernel launches one pf_decoder_forward enqueues (host arithmetic, no GPU needed); it does not depend on rows. */
+/* Kernel launches one pf_decoder_forward enqueues, counted by a dry run of the very walk that forward enqueues (no GPU needed); it
+ * does not depend on rows. */
 int pf_decoder_launches(const pf_decoder* d, int rows);
 /* pnotree: z [rows,512] -> out0 = recon_pitch [rows,32,S-1,130], out1 = recon_dur [rows,32,S-1,5,2] (the two tensors
  *          PianoTreeDecoder.forward returns, pianotree_dec.py:334-339), out2 unused, est [rows,32,S-1,6] = their max(-1)[1]

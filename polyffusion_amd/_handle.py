@@ -13,7 +13,7 @@ from . import _lib
 
 
 class ModelHandle:
-    PREFIX = ""   # "pf_unet", "pf_ddpm", "pf_encoder"
+    PREFIX = ""   # "pf_unet", "pf_ddpm", "pf_encoder", "pf_decoder"
 
     def __init__(self, lib: C.CDLL, *create_args, device=None):
         self._lib = lib
@@ -38,6 +38,17 @@ class ModelHandle:
                 self._h = None
         except Exception:
             pass
+
+    def workspace_for(self, nbytes: int, device) -> torch.Tensor:
+        """The cached workspace, at least ``nbytes`` long and on ``device``: grown, or moved to another device, by dropping the old
+        buffer before the new one is allocated."""
+        device = torch.device(device)
+        if device.type == "cuda" and device.index is None:
+            device = torch.device("cuda", torch.cuda.current_device())
+        if self._ws is None or self._ws.numel() < nbytes or self._ws.device != device:
+            self._ws = None
+            self._ws = torch.empty(int(nbytes), dtype=torch.uint8, device=device)
+        return self._ws
 
     def param_shapes(self) -> "OrderedDict[str, Tuple[int, ...]]":
         """The parameter table in state_dict order (models with a ``<prefix>_param_info``)."""

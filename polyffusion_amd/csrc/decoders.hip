@@ -10,8 +10,6 @@
 // only dependency between workgroups.  Every reduction runs over k in an order that depends on neither the row's position in the batch
 // nor the batch size.
 #include <memory>
-#include <string>
-#include <vector>
 #include "plan.h"
 
 using namespace pf;
@@ -442,19 +440,21 @@ __global__ void transpose_kernel(const float* __restrict__ w, int rows, int cols
   out[(size_t)c * rows + r] = w[i];
 }
 
+int launched() {   // after a hipLaunchKernelGGL
+  PF_CHECK_HIP(hipGetLastError());
+  return PF_OK;
+}
 int launch_linear(const float* x, int ldx, const float* w, int ldw, const float* bias, float* y, int ldy, int R, int N, int K,
                   hipStream_t s) {
   PF_REQUIRE(K <= 2048, "decoder linear: K=%d too large", K);
   const int vec = (K % 4 == 0) && (ldw % 4 == 0) && (((uintptr_t)w & 15) == 0);
   hipLaunchKernelGGL(dec_linear_kernel, dim3(cdiv(N, 4), cdiv(R, RT)), dim3(256), (size_t)RT * K * sizeof(float), s, x, ldx, w, ldw, bias,
                      y, ldy, R, N, K, vec);
-  PF_CHECK_HIP(hipGetLastError());
-  return PF_OK;
+  return launched();
 }
 int launch_gru_step(const GruStepArgs& a, hipStream_t s) {
   hipLaunchKernelGGL(gru_step_kernel, dim3(cdiv(a.H, 4), cdiv(a.R, RT)), dim3(256), (size_t)RT * (a.H + a.Kx) * sizeof(float), s, a);
-  PF_CHECK_HIP(hipGetLastError());
-  return PF_OK;
+  return launched();
 }
 
 }  // namespace
@@ -464,34 +464,117 @@ struct pf_decoder {
   int S = 0, HD = 16;                                          // pnotree: max_simu_note, dec_dur_hid_size
   int input_dim = 0, z_input_dim = 0, hidden = 0, z_dim = 0, n_step = 0;   // chord
   WeightTable wt;
-  size_t tn = 0, te = 0, tn_sos = 0, te_sos = 0, whh_t = 0;   // pnotree: bind-time tables (float offsets into the blob)
-  size_t wdhh_t = 0;                                           // pnotree, HD = 64: transposed dec_dur_gru.weight_hh_l0
-  void add(const std::string& key, std::vector<int64_t> shape) { wt.raw(key, std::move(shape)); }
-  void add_gru(const std::string& name, int in, int hid, bool bidir) {
-    for (const char* sfx : {"", "_reverse"}) {
-      add(name + ".weight_ih_l0" + sfx, {3 * hid, in});
-      add(name + ".weight_hh_l0" + sfx, {3 * hid, hid});
-      add(name + ".bias_ih_l0" + sfx, {3 * hid});
-      add(name + ".bias_hh_l0" + sfx, {3 * hid});
-      if (!bidir) break;
-    }
-  }
-  size_t off(const std::string& key) const { return wt.params[wt.index.at(key)].dests[0].off; }
+  // blob offsets of everything forward and bind read, resolved at create
+  size_t init_input = 0;                                       // dec_init_input / init_input
+  LinOff z2hid{}, z2in{};                                      // z2dec_hid(_linear), z2dec_in(_linear)
+  GruOff gru{};                                                // dec_time_gru / the chord decoder's gru
+  LinOff root{}, chroma{}, bass{};                             // chord heads
+  size_t dur_sos = 0;                                          // pnotree from here on
+  LinOff note_emb{}, t2n{}, pitch{}, dur_hid{}, dur_out{};
+  GruOff emb_gru[2] = {}, notes_gru{}, dur_gru{};
+  size_t tn = 0, te = 0, tn_sos = 0, te_sos = 0, whh_t = 0;   // bind-time tables
+  size_t wdhh_t = 0;                                           // HD = 64: transposed dec_dur_gru.weight_hh_l0
 };
 
-static int dec_launches(const pf_decoder* d) {
-  if (d->kind == PF_DEC_CHORD) return 3 + 2 * d->n_step;                       // z2dec_hid, z2dec_in, hoisted input part; GRU step + heads
-  return 3 + 32 * (3 + 2 * (d->S - 1)) + 31;                                   // + per time step: time GRU, two linears, embedding GRU
+namespace {
+
+// The decode of either kind, dry or live (c.B = rows).  The two halves of a ping-pong buffer are told apart inside the closures: a
+// dry run carries null pointers and does no arithmetic on them.
+int dec_run(const pf_decoder* d, PlanCtx& c, const float* z, float* out0, float* out1, float* out2, int32_t* est) {
+  const int R = c.B;
+  // one fused GRU step h[cur] -> h[cur ^ 1] of the ping-pong pair h [2][R][H]
+  auto gru_step = [&](const GruOff& g, const float* x, int ldx, int Kx, int ldwx, float* h, int cur, int H, const float* add1, const float* add2, int ld2) {
+    c.launch(PF_K_SMALL, 0.0, [&] {
+      GruStepArgs a;
+      a.x = x; a.ldx = ldx; a.Kx = Kx; a.wx = Kx ? c.w(g.w_ih) : nullptr; a.ldwx = ldwx;
+      a.h_in = h + (size_t)cur * R * H; a.wh = c.w(g.w_hh); a.b_hh = c.w(g.b_hh);
+      a.add1 = add1; a.ld1 = 3 * H; a.add2 = add2; a.ld2 = ld2;
+      a.h_out = h + (size_t)(cur ^ 1) * R * H; a.R = R; a.H = H;
+      return launch_gru_step(a, c.s);
+    });
+  };
+  auto linear = [&](const float* x, int ldx, size_t w, int ldw, size_t bias, float* y, int N, int K) {
+    c.launch(PF_K_SMALL, 0.0, [&] { return launch_linear(x, ldx, c.w(w), ldw, c.w(bias), y, N, R, N, K, c.s); });
+  };
+  if (d->kind == PF_DEC_CHORD) {
+    const int H = d->hidden, ZI = d->z_input_dim, IN = d->input_dim, ldw = IN + ZI;
+    float* h = c.palloc((size_t)2 * R * H);
+    float* z_in = c.palloc((size_t)R * ZI);
+    float* gi_z = c.palloc((size_t)R * 3 * H);
+    float* token = c.palloc((size_t)R * 36);
+    linear(z, d->z_dim, d->z2hid.w, d->z_dim, d->z2hid.b, h, H, d->z_dim);
+    linear(z, d->z_dim, d->z2in.w, d->z_dim, d->z2in.b, z_in, ZI, d->z_dim);
+    // the z_in part of the GRU input is the same at every step: applied once (bias_ih included)
+    linear(z_in, ZI, d->gru.w_ih + IN, ldw, d->gru.b_ih, gi_z, 3 * H, ZI);
+    for (int t = 0; t < d->n_step; ++t) {
+      gru_step(d->gru, t == 0 ? c.w(d->init_input) : token, t == 0 ? 0 : 36, IN, ldw, h, t & 1, H, gi_z, nullptr, 0);
+      c.launch(PF_K_SMALL, 0.0, [&] {
+        hipLaunchKernelGGL(chord_heads_kernel, dim3(R), dim3(256), 0, c.s, (const float*)(h + (size_t)((t + 1) & 1) * R * H), H, c.w(d->root.w),
+                           c.w(d->root.b), c.w(d->chroma.w), c.w(d->chroma.b), c.w(d->bass.w), c.w(d->bass.b), out0, out1, out2, token, t,
+                           d->n_step);
+        return launched();
+      });
+    }
+    return c.rc;
+  }
+  const int S = d->S;
+  float* ht = c.palloc((size_t)2 * R * PN_HT);
+  float* z_in = c.palloc((size_t)R * PN_ZIN);
+  float* gi_z = c.palloc((size_t)R * 3 * PN_HT);
+  float* tok_t = c.palloc((size_t)R * 2 * PN_HE);
+  float* hn = c.palloc((size_t)2 * R * PN_HN);
+  float* gi_ns = c.palloc((size_t)R * 3 * PN_HN);
+  float* gi_tok = c.palloc((size_t)R * 3 * PN_HN);
+  float* gie = c.palloc((size_t)R * S * 6 * PN_HE);
+  int* lens = reinterpret_cast<int*>(c.palloc(R));
+  const int ldt = PN_ZIN + 2 * PN_HE, ldn = PN_HT + PN_E;
+  linear(z, PN_Z, d->z2hid.w, PN_Z, d->z2hid.b, ht, PN_HT, PN_Z);
+  linear(z, PN_Z, d->z2in.w, PN_Z, d->z2in.b, z_in, PN_ZIN, PN_Z);
+  // dec_time_gru input = [token | z_in] (pianotree_dec.py:286-288): the z_in half is constant over the 32 steps
+  linear(z_in, PN_ZIN, d->gru.w_ih + 2 * PN_HE, ldt, d->gru.b_ih, gi_z, 3 * PN_HT, PN_ZIN);
+  PnHeadsArgs ha;
+  ha.wp = c.w(d->pitch.w); ha.bp = c.w(d->pitch.b);
+  ha.wdh = c.w(d->dur_hid.w); ha.bdh = c.w(d->dur_hid.b);
+  ha.wdi = c.w(d->dur_gru.w_ih); ha.wdhh = c.w(d->dur_gru.w_hh);
+  ha.bdi = c.w(d->dur_gru.b_ih); ha.bdhh = c.w(d->dur_gru.b_hh);
+  ha.wdhh_t = d->HD == 64 ? c.w(d->wdhh_t) : nullptr;
+  ha.wdo = c.w(d->dur_out.w); ha.bdo = c.w(d->dur_out.b);
+  ha.dur_sos = c.w(d->dur_sos);
+  ha.tn = c.w(d->tn); ha.te = c.w(d->te);
+  ha.recon_pitch = out0; ha.recon_dur = out1; ha.est = est;
+  ha.gi_tok = gi_tok; ha.gie = gie; ha.lens = lens; ha.S = S;
+  for (int t = 0; t < 32; ++t) {
+    gru_step(d->gru, t == 0 ? c.w(d->init_input) : tok_t, t == 0 ? 0 : 2 * PN_HE, 2 * PN_HE, ldt, ht, t & 1, PN_HT, gi_z, nullptr, 0);
+    // decode_notes: initial hidden of the notes GRU, and the notes_summary part of its input (constant over the slots)
+    const size_t ht_out = (size_t)((t + 1) & 1) * R * PN_HT;
+    c.launch(PF_K_SMALL, 0.0, [&] { return launch_linear(ht + ht_out, PN_HT, c.w(d->t2n.w), PN_HT, c.w(d->t2n.b), hn, PN_HN, R, PN_HN, PN_HT, c.s); });
+    c.launch(PF_K_SMALL, 0.0, [&] { return launch_linear(ht + ht_out, PN_HT, c.w(d->notes_gru.w_ih), ldn, c.w(d->notes_gru.b_ih), gi_ns, 3 * PN_HN, R, 3 * PN_HN, PN_HT, c.s); });
+    for (int sl = 1; sl < S; ++sl) {
+      gru_step(d->notes_gru, nullptr, 0, 0, 0, hn, (sl - 1) & 1, PN_HN, gi_ns, sl == 1 ? c.w(d->tn_sos) : gi_tok, sl == 1 ? 0 : 3 * PN_HN);
+      c.launch(PF_K_SMALL, 0.0, [&] {
+        ha.h = hn + (size_t)(sl & 1) * R * PN_HN; ha.t = t; ha.s = sl;
+        if (d->HD == 64) hipLaunchKernelGGL(pnotree_heads_kernel<64>, dim3(R), dim3(256), 0, c.s, ha);
+        else hipLaunchKernelGGL(pnotree_heads_kernel<16>, dim3(R), dim3(256), 0, c.s, ha);
+        return launched();
+      });
+    }
+    if (t == 31) break;
+    c.launch(PF_K_SMALL, 0.0, [&] {
+      hipLaunchKernelGGL(pnotree_emb_gru_kernel, dim3(R, 2), dim3(3 * PN_HE), 0, c.s, (const float*)gie, c.w(d->te_sos), c.w(d->whh_t),
+                         c.w(d->emb_gru[0].b_hh), c.w(d->emb_gru[1].b_hh), (const int*)lens, tok_t, S);
+      return launched();
+    });
+  }
+  return c.rc;
 }
 
-static size_t r64(size_t n) { return (n + 63) / 64 * 64; }
-static size_t dec_ws_floats(const pf_decoder* d, int R) {
-  const size_t r = (size_t)R;
-  if (d->kind == PF_DEC_CHORD)
-    return r64(2 * r * d->hidden) + r64(r * d->z_input_dim) + r64(r * 3 * d->hidden) + r64(r * 36);
-  return r64(2 * r * PN_HT) + r64(r * PN_ZIN) + r64(r * 3 * PN_HT) + r64(r * 2 * PN_HE) + r64(2 * r * PN_HN) + 2 * r64(r * 3 * PN_HN) +
-         r64(r * d->S * 6 * PN_HE) + r64(r);
+PlanSize dec_plan(const pf_decoder* d, int rows) {
+  PlanCtx c;
+  c.B = rows;
+  return plan_sizes(c, [d](PlanCtx& dry) { dec_run(d, dry, nullptr, nullptr, nullptr, nullptr, nullptr); });
 }
+
+}  // namespace
 
 extern "C" {
 
@@ -500,56 +583,45 @@ int pf_decoder_create(int kind, int max_simu_note, int input_dim, int z_input_di
   PF_REQUIRE(out && (kind == PF_DEC_CHORD || kind == PF_DEC_PNOTREE), "pf_decoder_create: bad kind");
   std::unique_ptr<pf_decoder> d(new pf_decoder());
   d->kind = kind;
+  WeightTable& wt = d->wt;
   if (kind == PF_DEC_PNOTREE) {   // dl_modules/pianotree_dec.py:11-99, default sizes; hidden_dim = dec_dur_hid_size (0: the default 16)
     PF_REQUIRE(max_simu_note >= 2 && max_simu_note <= 32, "pf_decoder_create: max_simu_note must be in 2..32");
     PF_REQUIRE(hidden_dim == 0 || hidden_dim == 16 || hidden_dim == 64, "pf_decoder_create: dec_dur_hid_size (hidden_dim) must be 16 or 64, got %d", hidden_dim);
     d->S = max_simu_note;
     d->HD = hidden_dim ? hidden_dim : 16;
     const int PN_HD = d->HD;
-    d->add("dec_init_input", {2 * PN_HE});
-    d->add("dur_sos_token", {PN_DW});
-    d->add("note_embedding.weight", {PN_E, PN_TOK});
-    d->add("note_embedding.bias", {PN_E});
-    d->add("z2dec_hid_linear.weight", {PN_HT, PN_Z});
-    d->add("z2dec_hid_linear.bias", {PN_HT});
-    d->add("z2dec_in_linear.weight", {PN_ZIN, PN_Z});
-    d->add("z2dec_in_linear.bias", {PN_ZIN});
-    d->add_gru("dec_notes_emb_gru", PN_E, PN_HE, true);
-    d->add_gru("dec_time_gru", PN_ZIN + 2 * PN_HE, PN_HT, false);
-    d->add("dec_time_to_notes_hid.weight", {PN_HN, PN_HT});
-    d->add("dec_time_to_notes_hid.bias", {PN_HN});
-    d->add_gru("dec_notes_gru", PN_HT + PN_E, PN_HN, false);
-    d->add("pitch_out_linear.weight", {PN_P, PN_HN});
-    d->add("pitch_out_linear.bias", {PN_P});
-    d->add_gru("dec_dur_gru", PN_DW, PN_HD, false);
-    d->add("dur_hid_linear.weight", {PN_HD, PN_P + PN_HN});
-    d->add("dur_hid_linear.bias", {PN_HD});
-    d->add("dur_out_linear.weight", {2, PN_HD});
-    d->add("dur_out_linear.bias", {2});
-    d->tn = d->wt.alloc((size_t)PN_TROWS * 3 * PN_HN);
-    d->te = d->wt.alloc((size_t)PN_TROWS * 6 * PN_HE);
-    d->tn_sos = d->wt.alloc(3 * PN_HN);
-    d->te_sos = d->wt.alloc(6 * PN_HE);
-    d->whh_t = d->wt.alloc((size_t)2 * PN_HE * 3 * PN_HE);
-    if (d->HD == 64) d->wdhh_t = d->wt.alloc((size_t)64 * 3 * 64);
+    d->init_input = wt.raw("dec_init_input", {2 * PN_HE});
+    d->dur_sos = wt.raw("dur_sos_token", {PN_DW});
+    d->note_emb = wt.linear("note_embedding", PN_E, PN_TOK);
+    d->z2hid = wt.linear("z2dec_hid_linear", PN_HT, PN_Z);
+    d->z2in = wt.linear("z2dec_in_linear", PN_ZIN, PN_Z);
+    wt.gru("dec_notes_emb_gru", PN_E, PN_HE, 2, d->emb_gru);
+    wt.gru("dec_time_gru", PN_ZIN + 2 * PN_HE, PN_HT, 1, &d->gru);
+    d->t2n = wt.linear("dec_time_to_notes_hid", PN_HN, PN_HT);
+    wt.gru("dec_notes_gru", PN_HT + PN_E, PN_HN, 1, &d->notes_gru);
+    d->pitch = wt.linear("pitch_out_linear", PN_P, PN_HN);
+    wt.gru("dec_dur_gru", PN_DW, PN_HD, 1, &d->dur_gru);
+    d->dur_hid = wt.linear("dur_hid_linear", PN_HD, PN_P + PN_HN);
+    d->dur_out = wt.linear("dur_out_linear", 2, PN_HD);
+    d->tn = wt.alloc((size_t)PN_TROWS * 3 * PN_HN);
+    d->te = wt.alloc((size_t)PN_TROWS * 6 * PN_HE);
+    d->tn_sos = wt.alloc(3 * PN_HN);
+    d->te_sos = wt.alloc(6 * PN_HE);
+    d->whh_t = wt.alloc((size_t)2 * PN_HE * 3 * PN_HE);
+    if (d->HD == 64) d->wdhh_t = wt.alloc((size_t)64 * 3 * 64);
   } else {                        // dl_modules/chord_dec.py:8-25
     PF_REQUIRE(input_dim == 36, "pf_decoder_create: the chord token is root 12 | chroma 12 | bass 12 (input_dim 36)");
     PF_REQUIRE(z_input_dim > 0 && z_dim > 0 && n_step > 0, "pf_decoder_create: bad dims");
     PF_REQUIRE(hidden_dim > 0 && hidden_dim % 4 == 0 && hidden_dim <= 1024, "pf_decoder_create: hidden_dim must be a multiple of 4, at most 1024");
     PF_REQUIRE(z_dim <= 2048 && z_input_dim <= 2048, "pf_decoder_create: z_dim / z_input_dim at most 2048");
     d->input_dim = input_dim; d->z_input_dim = z_input_dim; d->hidden = hidden_dim; d->z_dim = z_dim; d->n_step = n_step;
-    d->add("init_input", {36});
-    d->add("z2dec_hid.weight", {hidden_dim, z_dim});
-    d->add("z2dec_hid.bias", {hidden_dim});
-    d->add("z2dec_in.weight", {z_input_dim, z_dim});
-    d->add("z2dec_in.bias", {z_input_dim});
-    d->add_gru("gru", input_dim + z_input_dim, hidden_dim, false);
-    d->add("root_out.weight", {12, hidden_dim});
-    d->add("root_out.bias", {12});
-    d->add("chroma_out.weight", {24, hidden_dim});
-    d->add("chroma_out.bias", {24});
-    d->add("bass_out.weight", {12, hidden_dim});
-    d->add("bass_out.bias", {12});
+    d->init_input = wt.raw("init_input", {36});
+    d->z2hid = wt.linear("z2dec_hid", hidden_dim, z_dim);
+    d->z2in = wt.linear("z2dec_in", z_input_dim, z_dim);
+    wt.gru("gru", input_dim + z_input_dim, hidden_dim, 1, &d->gru);
+    d->root = wt.linear("root_out", 12, hidden_dim);
+    d->chroma = wt.linear("chroma_out", 24, hidden_dim);
+    d->bass = wt.linear("bass_out", 12, hidden_dim);
   }
   *out = d.release();
   return PF_OK;
@@ -577,22 +649,19 @@ int pf_decoder_bind_weights(pf_decoder* d, void* dev_blob) {
   if (rc || d->kind != PF_DEC_PNOTREE) return rc;
   float* W = (float*)dev_blob;
   PF_CHECK_HIP(hipDeviceSynchronize());   // the copy that brought the blob may be on any stream
-  const float *ew = W + d->off("note_embedding.weight"), *eb = W + d->off("note_embedding.bias");
+  const float *ew = W + d->note_emb.w, *eb = W + d->note_emb.b;
   hipStream_t s = nullptr;
-  hipLaunchKernelGGL(token_table_kernel, dim3(cdiv(3 * PN_HN, 128), PN_TROWS), dim3(128), 0, s, W + d->off("dec_notes_gru.weight_ih_l0"),
-                     PN_HT + PN_E, PN_HT, 3 * PN_HN, ew, eb, (const float*)nullptr, W + d->tn, 3 * PN_HN, 0);
-  const char* sfx[2] = {"", "_reverse"};
+  hipLaunchKernelGGL(token_table_kernel, dim3(cdiv(3 * PN_HN, 128), PN_TROWS), dim3(128), 0, s, W + d->notes_gru.w_ih, PN_HT + PN_E, PN_HT,
+                     3 * PN_HN, ew, eb, (const float*)nullptr, W + d->tn, 3 * PN_HN, 0);
   for (int dir = 0; dir < 2; ++dir) {
-    const std::string sx = sfx[dir];
-    hipLaunchKernelGGL(token_table_kernel, dim3(cdiv(3 * PN_HE, 128), PN_TROWS), dim3(128), 0, s,
-                       W + d->off("dec_notes_emb_gru.weight_ih_l0" + sx), PN_E, 0, 3 * PN_HE, ew, eb,
-                       W + d->off("dec_notes_emb_gru.bias_ih_l0" + sx), W + d->te, 6 * PN_HE, dir * 3 * PN_HE);
-    hipLaunchKernelGGL(transpose_kernel, dim3(cdiv(3 * PN_HE * PN_HE, 256)), dim3(256), 0, s,
-                       W + d->off("dec_notes_emb_gru.weight_hh_l0" + sx), 3 * PN_HE, PN_HE, W + d->whh_t + (size_t)dir * PN_HE * 3 * PN_HE);
+    const GruOff& g = d->emb_gru[dir];
+    hipLaunchKernelGGL(token_table_kernel, dim3(cdiv(3 * PN_HE, 128), PN_TROWS), dim3(128), 0, s, W + g.w_ih, PN_E, 0, 3 * PN_HE, ew, eb,
+                       W + g.b_ih, W + d->te, 6 * PN_HE, dir * 3 * PN_HE);
+    hipLaunchKernelGGL(transpose_kernel, dim3(cdiv(3 * PN_HE * PN_HE, 256)), dim3(256), 0, s, W + g.w_hh, 3 * PN_HE, PN_HE,
+                       W + d->whh_t + (size_t)dir * PN_HE * 3 * PN_HE);
   }
   if (d->HD == 64)
-    hipLaunchKernelGGL(transpose_kernel, dim3(cdiv(3 * 64 * 64, 256)), dim3(256), 0, s, W + d->off("dec_dur_gru.weight_hh_l0"), 3 * 64, 64,
-                       W + d->wdhh_t);
+    hipLaunchKernelGGL(transpose_kernel, dim3(cdiv(3 * 64 * 64, 256)), dim3(256), 0, s, W + d->dur_gru.w_hh, 3 * 64, 64, W + d->wdhh_t);
   hipLaunchKernelGGL(sos_row_kernel, dim3(cdiv(3 * PN_HN, 128)), dim3(128), 0, s, W + d->tn, 3 * PN_HN, W + d->tn_sos);
   hipLaunchKernelGGL(sos_row_kernel, dim3(cdiv(6 * PN_HE, 128)), dim3(128), 0, s, W + d->te, 6 * PN_HE, W + d->te_sos);
   PF_CHECK_HIP(hipGetLastError());
@@ -600,110 +669,20 @@ int pf_decoder_bind_weights(pf_decoder* d, void* dev_blob) {
   return PF_OK;
 }
 
-size_t pf_decoder_workspace_bytes(const pf_decoder* d, int rows) { return (d && rows > 0) ? dec_ws_floats(d, rows) * sizeof(float) : 0; }
-int pf_decoder_launches(const pf_decoder* d, int rows) { return (d && rows > 0) ? dec_launches(d) : 0; }
+size_t pf_decoder_workspace_bytes(const pf_decoder* d, int rows) { return (d && rows > 0) ? dec_plan(d, rows).bytes() : 0; }
+int pf_decoder_launches(const pf_decoder* d, int rows) { return (d && rows > 0) ? dec_plan(d, rows).n_launch : 0; }
 
 int pf_decoder_forward(pf_decoder* d, const float* z, int rows, float* out0, float* out1, float* out2, int32_t* est, void* workspace,
                        size_t workspace_bytes, void* stream) {
   PF_REQUIRE(d && z && out0 && out1 && workspace && rows > 0, "pf_decoder_forward: bad arguments");
   if (!d->wt.wdev) return set_error(PF_ESTATE, "pf_decoder_forward: weights not bound");
-  PF_REQUIRE(((uintptr_t)workspace & 15) == 0, "pf_decoder_forward: workspace must be 16-byte aligned");
-  PF_REQUIRE(workspace_bytes >= dec_ws_floats(d, rows) * sizeof(float), "pf_decoder_forward: workspace too small");
-  hipStream_t s = (hipStream_t)stream;
-  const int R = rows;
-  const float* W = d->wt.wdev;
-  float* ws = (float*)workspace;
-  auto take = [&](size_t n) { float* p = ws; ws += r64(n); return p; };
-  int rc = PF_OK;
-  if (d->kind == PF_DEC_CHORD) {
-    PF_REQUIRE(out2, "pf_decoder_forward: the chord decoder writes three outputs");
-    const int H = d->hidden, ZI = d->z_input_dim, IN = d->input_dim, ldw = IN + ZI;
-    float* h = take((size_t)2 * R * H);
-    float* z_in = take((size_t)R * ZI);
-    float* gi_z = take((size_t)R * 3 * H);
-    float* token = take((size_t)R * 36);
-    if ((rc = launch_linear(z, d->z_dim, W + d->off("z2dec_hid.weight"), d->z_dim, W + d->off("z2dec_hid.bias"), h, H, R, H, d->z_dim, s))) return rc;
-    if ((rc = launch_linear(z, d->z_dim, W + d->off("z2dec_in.weight"), d->z_dim, W + d->off("z2dec_in.bias"), z_in, ZI, R, ZI, d->z_dim, s))) return rc;
-    // the z_in part of the GRU input is the same at every step: applied once (bias_ih included)
-    if ((rc = launch_linear(z_in, ZI, W + d->off("gru.weight_ih_l0") + IN, ldw, W + d->off("gru.bias_ih_l0"), gi_z, 3 * H, R, 3 * H, ZI, s))) return rc;
-    for (int t = 0; t < d->n_step; ++t) {
-      float *h_in = h + (size_t)(t & 1) * R * H, *h_out = h + (size_t)((t + 1) & 1) * R * H;
-      GruStepArgs a;
-      a.x = t == 0 ? W + d->off("init_input") : token; a.ldx = t == 0 ? 0 : 36; a.Kx = IN;
-      a.wx = W + d->off("gru.weight_ih_l0"); a.ldwx = ldw;
-      a.h_in = h_in; a.wh = W + d->off("gru.weight_hh_l0"); a.b_hh = W + d->off("gru.bias_hh_l0");
-      a.add1 = gi_z; a.ld1 = 3 * H; a.add2 = nullptr; a.ld2 = 0;
-      a.h_out = h_out; a.R = R; a.H = H;
-      if ((rc = launch_gru_step(a, s))) return rc;
-      hipLaunchKernelGGL(chord_heads_kernel, dim3(R), dim3(256), 0, s, (const float*)h_out, H, W + d->off("root_out.weight"),
-                         W + d->off("root_out.bias"), W + d->off("chroma_out.weight"), W + d->off("chroma_out.bias"),
-                         W + d->off("bass_out.weight"), W + d->off("bass_out.bias"), out0, out1, out2, token, t, d->n_step);
-      PF_CHECK_HIP(hipGetLastError());
-    }
-    return PF_OK;
-  }
-  PF_REQUIRE(est, "pf_decoder_forward: the PianoTree decoder writes the integer grid");
-  const int S = d->S;
-  float* ht = take((size_t)2 * R * PN_HT);
-  float* z_in = take((size_t)R * PN_ZIN);
-  float* gi_z = take((size_t)R * 3 * PN_HT);
-  float* tok_t = take((size_t)R * 2 * PN_HE);
-  float* hn = take((size_t)2 * R * PN_HN);
-  float* gi_ns = take((size_t)R * 3 * PN_HN);
-  float* gi_tok = take((size_t)R * 3 * PN_HN);
-  float* gie = take((size_t)R * S * 6 * PN_HE);
-  int* lens = reinterpret_cast<int*>(take(R));
-  const int ldt = PN_ZIN + 2 * PN_HE, ldn = PN_HT + PN_E;
-  if ((rc = launch_linear(z, PN_Z, W + d->off("z2dec_hid_linear.weight"), PN_Z, W + d->off("z2dec_hid_linear.bias"), ht, PN_HT, R, PN_HT, PN_Z, s))) return rc;
-  if ((rc = launch_linear(z, PN_Z, W + d->off("z2dec_in_linear.weight"), PN_Z, W + d->off("z2dec_in_linear.bias"), z_in, PN_ZIN, R, PN_ZIN, PN_Z, s))) return rc;
-  // dec_time_gru input = [token | z_in] (pianotree_dec.py:286-288): the z_in half is constant over the 32 steps
-  if ((rc = launch_linear(z_in, PN_ZIN, W + d->off("dec_time_gru.weight_ih_l0") + 2 * PN_HE, ldt, W + d->off("dec_time_gru.bias_ih_l0"), gi_z,
-                          3 * PN_HT, R, 3 * PN_HT, PN_ZIN, s))) return rc;
-  PnHeadsArgs ha;
-  ha.wp = W + d->off("pitch_out_linear.weight"); ha.bp = W + d->off("pitch_out_linear.bias");
-  ha.wdh = W + d->off("dur_hid_linear.weight"); ha.bdh = W + d->off("dur_hid_linear.bias");
-  ha.wdi = W + d->off("dec_dur_gru.weight_ih_l0"); ha.wdhh = W + d->off("dec_dur_gru.weight_hh_l0");
-  ha.bdi = W + d->off("dec_dur_gru.bias_ih_l0"); ha.bdhh = W + d->off("dec_dur_gru.bias_hh_l0");
-  ha.wdhh_t = d->HD == 64 ? W + d->wdhh_t : nullptr;
-  ha.wdo = W + d->off("dur_out_linear.weight"); ha.bdo = W + d->off("dur_out_linear.bias");
-  ha.dur_sos = W + d->off("dur_sos_token");
-  ha.tn = W + d->tn; ha.te = W + d->te;
-  ha.recon_pitch = out0; ha.recon_dur = out1; ha.est = est;
-  ha.gi_tok = gi_tok; ha.gie = gie; ha.lens = lens; ha.S = S;
-  for (int t = 0; t < 32; ++t) {
-    float *ht_in = ht + (size_t)(t & 1) * R * PN_HT, *ht_out = ht + (size_t)((t + 1) & 1) * R * PN_HT;
-    GruStepArgs a;
-    a.x = t == 0 ? W + d->off("dec_init_input") : tok_t; a.ldx = t == 0 ? 0 : 2 * PN_HE; a.Kx = 2 * PN_HE;
-    a.wx = W + d->off("dec_time_gru.weight_ih_l0"); a.ldwx = ldt;
-    a.h_in = ht_in; a.wh = W + d->off("dec_time_gru.weight_hh_l0"); a.b_hh = W + d->off("dec_time_gru.bias_hh_l0");
-    a.add1 = gi_z; a.ld1 = 3 * PN_HT; a.add2 = nullptr; a.ld2 = 0;
-    a.h_out = ht_out; a.R = R; a.H = PN_HT;
-    if ((rc = launch_gru_step(a, s))) return rc;
-    // decode_notes: initial hidden of the notes GRU, and the notes_summary part of its input (constant over the slots)
-    if ((rc = launch_linear(ht_out, PN_HT, W + d->off("dec_time_to_notes_hid.weight"), PN_HT, W + d->off("dec_time_to_notes_hid.bias"), hn, PN_HN,
-                            R, PN_HN, PN_HT, s))) return rc;
-    if ((rc = launch_linear(ht_out, PN_HT, W + d->off("dec_notes_gru.weight_ih_l0"), ldn, W + d->off("dec_notes_gru.bias_ih_l0"), gi_ns, 3 * PN_HN,
-                            R, 3 * PN_HN, PN_HT, s))) return rc;
-    for (int sl = 1; sl < S; ++sl) {
-      float *hn_in = hn + (size_t)((sl - 1) & 1) * R * PN_HN, *hn_out = hn + (size_t)(sl & 1) * R * PN_HN;
-      GruStepArgs n;
-      n.x = nullptr; n.ldx = 0; n.Kx = 0; n.wx = nullptr; n.ldwx = 0;
-      n.h_in = hn_in; n.wh = W + d->off("dec_notes_gru.weight_hh_l0"); n.b_hh = W + d->off("dec_notes_gru.bias_hh_l0");
-      n.add1 = gi_ns; n.ld1 = 3 * PN_HN;
-      n.add2 = sl == 1 ? W + d->tn_sos : gi_tok; n.ld2 = sl == 1 ? 0 : 3 * PN_HN;
-      n.h_out = hn_out; n.R = R; n.H = PN_HN;
-      if ((rc = launch_gru_step(n, s))) return rc;
-      ha.h = hn_out; ha.t = t; ha.s = sl;
-      if (d->HD == 64) hipLaunchKernelGGL(pnotree_heads_kernel<64>, dim3(R), dim3(256), 0, s, ha);
-      else hipLaunchKernelGGL(pnotree_heads_kernel<16>, dim3(R), dim3(256), 0, s, ha);
-      PF_CHECK_HIP(hipGetLastError());
-    }
-    if (t == 31) break;
-    hipLaunchKernelGGL(pnotree_emb_gru_kernel, dim3(R, 2), dim3(3 * PN_HE), 0, s, (const float*)gie, W + d->te_sos, W + d->whh_t,
-                       W + d->off("dec_notes_emb_gru.bias_hh_l0"), W + d->off("dec_notes_emb_gru.bias_hh_l0_reverse"), (const int*)lens, tok_t, S);
-    PF_CHECK_HIP(hipGetLastError());
-  }
-  return PF_OK;
+  PF_REQUIRE(d->kind != PF_DEC_CHORD || out2, "pf_decoder_forward: the chord decoder writes three outputs");
+  PF_REQUIRE(d->kind != PF_DEC_PNOTREE || est, "pf_decoder_forward: the PianoTree decoder writes the integer grid");
+  PlanCtx c;
+  c.B = rows;
+  const int rc = c.use_workspace("pf_decoder_forward", workspace, workspace_bytes, dec_plan(d, rows), stream, d->wt.wdev, 16);
+  if (rc != PF_OK) return rc;
+  return dec_run(d, c, z, out0, out1, out2, est);
 }
 
 }  // extern "C"

@@ -20,9 +20,10 @@ struct pf_encoder {
   int kind, input_dim, emb, hidden, z, nch;
   bool with_scale = false;
   WeightTable wt;
-  void add(const std::string& key, std::vector<int64_t> shape) { wt.raw(key, std::move(shape)); }
+  // blob offsets of everything the forward reads, resolved at create
+  LinOff note_emb{}, cnn{}, fc1{}, fc2{}, mu{}, var{};
+  GruOff notes_gru[2] = {}, gru[2] = {};   // pnotree: the GRU over the notes of a step; the GRU over time (pnotree: the 32 steps)
   void add_unused(const std::string& key, std::vector<int64_t> shape) { wt.add(key, std::move(shape)).optional = true; }
-  size_t off(const std::string& key) const { return wt.params[wt.index.at(key)].dests[0].off; }
 };
 
 extern "C" {
@@ -35,55 +36,30 @@ int pf_encoder_create_dist(int kind, int input_dim, int emb_size, int hidden_dim
   std::unique_ptr<pf_encoder> e(new pf_encoder());
   e->with_scale = with_scale != 0;
   e->kind = kind; e->input_dim = input_dim; e->emb = emb_size; e->hidden = hidden_dim; e->z = z_dim; e->nch = num_channel;
+  WeightTable& wt = e->wt;
   int gru_in = input_dim;
+  const char* unused = "linear_var";   // accepted and ignored
   if (kind == PF_ENC_PNOTREE) {   // dl_modules/pianotree_enc.py:43-59
     PF_REQUIRE(input_dim > 5 && emb_size > 0 && num_channel > 0, "pf_encoder_create: pianotree encoder needs input_dim, emb_size and the note-GRU size");
-    const int Hn = num_channel;
-    e->add("note_embedding.weight", {emb_size, input_dim});
-    e->add("note_embedding.bias", {emb_size});
-    for (const char* sfx : {"", "_reverse"}) {
-      e->add(std::string("enc_notes_gru.weight_ih_l0") + sfx, {3 * Hn, emb_size});
-      e->add(std::string("enc_notes_gru.weight_hh_l0") + sfx, {3 * Hn, Hn});
-      e->add(std::string("enc_notes_gru.bias_ih_l0") + sfx, {3 * Hn});
-      e->add(std::string("enc_notes_gru.bias_hh_l0") + sfx, {3 * Hn});
-    }
-    for (const char* sfx : {"", "_reverse"}) {
-      e->add(std::string("enc_time_gru.weight_ih_l0") + sfx, {3 * hidden_dim, 2 * Hn});
-      e->add(std::string("enc_time_gru.weight_hh_l0") + sfx, {3 * hidden_dim, hidden_dim});
-      e->add(std::string("enc_time_gru.bias_ih_l0") + sfx, {3 * hidden_dim});
-      e->add(std::string("enc_time_gru.bias_hh_l0") + sfx, {3 * hidden_dim});
-    }
-    e->add("linear_mu.weight", {z_dim, 2 * hidden_dim});
-    e->add("linear_mu.bias", {z_dim});
-    e->add_unused("linear_std.weight", {z_dim, 2 * hidden_dim});
-    e->add_unused("linear_std.bias", {z_dim});
-    *out = e.release();
-    return PF_OK;
-  }
-  if (kind == PF_ENC_TEXTURE) {
+    e->note_emb = wt.linear("note_embedding", emb_size, input_dim);
+    wt.gru("enc_notes_gru", emb_size, num_channel, 2, e->notes_gru);
+    gru_in = 2 * num_channel;
+    unused = "linear_std";
+  } else if (kind == PF_ENC_TEXTURE) {
     PF_REQUIRE(num_channel > 0 && emb_size > 0, "pf_encoder_create: texture encoder needs num_channel and emb_size");
-    e->add("cnn.0.weight", {num_channel, 1, 4, 12});
-    e->add("cnn.0.bias", {num_channel});
-    e->add("fc1.weight", {1000, num_channel * 29});
-    e->add("fc1.bias", {1000});
-    e->add("fc2.weight", {emb_size, 1000});
-    e->add("fc2.bias", {emb_size});
+    e->cnn.w = wt.raw("cnn.0.weight", {num_channel, 1, 4, 12});
+    e->cnn.b = wt.raw("cnn.0.bias", {num_channel});
+    e->fc1 = wt.linear("fc1", 1000, num_channel * 29);
+    e->fc2 = wt.linear("fc2", emb_size, 1000);
     gru_in = emb_size;
   }
-  for (const char* sfx : {"", "_reverse"}) {
-    e->add(std::string("gru.weight_ih_l0") + sfx, {3 * hidden_dim, gru_in});
-    e->add(std::string("gru.weight_hh_l0") + sfx, {3 * hidden_dim, hidden_dim});
-    e->add(std::string("gru.bias_ih_l0") + sfx, {3 * hidden_dim});
-    e->add(std::string("gru.bias_hh_l0") + sfx, {3 * hidden_dim});
-  }
-  e->add("linear_mu.weight", {z_dim, 2 * hidden_dim});
-  e->add("linear_mu.bias", {z_dim});
+  wt.gru(kind == PF_ENC_PNOTREE ? "enc_time_gru" : "gru", gru_in, hidden_dim, 2, e->gru);
+  e->mu = wt.linear("linear_mu", z_dim, 2 * hidden_dim);
   if (e->with_scale) {   // last in the table: everything before it sits where it does without the scale head
-    e->add("linear_var.weight", {z_dim, 2 * hidden_dim});
-    e->add("linear_var.bias", {z_dim});
+    e->var = wt.linear("linear_var", z_dim, 2 * hidden_dim);
   } else {
-    e->add_unused("linear_var.weight", {z_dim, 2 * hidden_dim});
-    e->add_unused("linear_var.bias", {z_dim});
+    e->add_unused(std::string(unused) + ".weight", {z_dim, 2 * hidden_dim});
+    e->add_unused(std::string(unused) + ".bias", {z_dim});
   }
   *out = e.release();
   return PF_OK;
@@ -106,130 +82,93 @@ int pf_encoder_bind_weights(pf_encoder* e, const void* dev_blob) {
   return e->wt.bind("pf_encoder_bind_weights", dev_blob, false);
 }
 
-static size_t enc_ws_floats(const pf_encoder* e, int B, int T) {
-  const size_t H = e->hidden;
-  size_t f = 0;
-  if (e->kind == PF_ENC_PNOTREE) {   // T = max_simu_note; B two-bar segments of 32 steps
-    const size_t N = (size_t)B * 32, Hn = e->nch;
-    f += N * T * e->emb + N + N * T * 3 * Hn + N * 3 * Hn + N * 2 * Hn;          // embedding, lengths, note-GRU gi / gh / [h_f | h_b]
-    f += 2 * N * 3 * H + (size_t)B * 3 * H + (size_t)B * 2 * H;                  // time-GRU gi (both directions), gh, [h_f | h_b]
-    return f + 16 * 64 + 1024;
+}  // extern "C"
+
+namespace {
+
+// One bidirectional GRU layer over x [R * T][in] (row r, step t at r * T + t): per direction the input projection of every step, then
+// T x (W_hh mat-vec + gate launch).  Returns [R][2H] = [h_forward | h_backward] at the end of each direction.  `masked`: rows end at
+// their own length lens[r] (the masked gate kernel, which finds step t of its direction itself).
+const float* bigru(PlanCtx& c, const GruOff (&g)[2], const float* x, int in, int R, int T, int H, bool masked, const int* lens) {
+  const size_t gi_floats = (size_t)R * T * 3 * H;
+  float* gi0 = c.palloc(gi_floats);
+  float* gi1 = masked ? gi0 : c.palloc(gi_floats);   // the masked (note) GRU's two projections take turns in one buffer
+  float* gh = c.palloc((size_t)R * 3 * H);
+  float* hcat = c.palloc((size_t)R * 2 * H);
+  c.launch(PF_K_SMALL, 0.0, [&] { PF_CHECK_HIP(hipMemsetAsync(hcat, 0, (size_t)R * 2 * H * sizeof(float), c.s)); return PF_OK; }, 0);
+  for (int d = 0; d < 2; ++d) {
+    float* gi = d ? gi1 : gi0;
+    c.launch(PF_K_SMALL, 0.0, [&] { return launch_matvec(x, in, c.w(g[d].w_ih), c.w(g[d].b_ih), gi, 3 * H, R * T, 3 * H, in, c.s); });
+    for (int step = 0; step < T; ++step) {
+      c.launch(PF_K_SMALL, 0.0, [&] { return launch_matvec(hcat + d * H, 2 * H, c.w(g[d].w_hh), c.w(g[d].b_hh), gh, 3 * H, R, 3 * H, H, c.s); });
+      c.launch(PF_K_SMALL, 0.0, [&] {
+        float* h = hcat + d * H;   // row stride 2H
+        if (masked) return launch_gru_gates_masked(gi, gh, h, 2 * H, R, H, T, lens, step, d, c.s);
+        return launch_gru_gates(gi + (size_t)(d ? T - 1 - step : step) * 3 * H, T * 3 * H, gh, h, 2 * H, R, H, c.s);
+      });
+    }
   }
-  if (e->kind == PF_ENC_TEXTURE) f += (size_t)B * e->nch * 8 * 29 + (size_t)B * 8 * 1000 + (size_t)B * 8 * e->emb;
-  f += 2 * (size_t)B * T * 3 * H;  // gi forward / backward
-  f += (size_t)B * 3 * H;          // gh
-  f += (size_t)B * 2 * H;          // [h_f | h_b]
-  return f + 1024;
+  return hcat;
 }
 
-size_t pf_encoder_workspace_bytes(const pf_encoder* e, int batch) {
-  if (!e || batch <= 0) return 0;
-  return enc_ws_floats(e, batch, e->kind == PF_ENC_TEXTURE ? 8 : (e->kind == PF_ENC_PNOTREE ? 32 : 64)) * sizeof(float);
-}
-
-static int enc_forward(pf_encoder* e, const float* x, int batch, int n_step, float* mu, float* scale, void* workspace,
-                       size_t workspace_bytes, void* stream) {
-  PF_REQUIRE(e && x && mu && workspace && batch > 0, "pf_encoder_forward: bad arguments");
-  if (!e->wt.wdev) return set_error(PF_ESTATE, "pf_encoder_forward: weights not bound");
-  hipStream_t s = (hipStream_t)stream;
-  const int B = batch, H = e->hidden;
-  int T = n_step, gru_in = e->input_dim;
-  PF_REQUIRE(e->kind == PF_ENC_TEXTURE || (T > 0 && T <= 64), "pf_encoder_forward: n_step must be in 1..64");
+// The forward of every encoder kind, dry or live.  n_step: T of the chord encoder, max_simu_note of the PianoTree encoder (the texture
+// encoder always has 8 steps).  c.B = batch.
+int enc_run(const pf_encoder* e, PlanCtx& c, const float* x, int n_step, float* mu, float* scale) {
+  const int B = c.B, H = e->hidden;
+  const float* h;
   if (e->kind == PF_ENC_PNOTREE) {
     // PianoTreeEncoder.forward (dl_modules/pianotree_enc.py:97-121): embed every grid row, run the bidirectional note GRU over the
     // (variable number of) notes of each of the B*32 time steps, then the bidirectional time GRU over the 32 steps, then linear_mu
-    const int S = T, E = e->emb, Hn = e->nch, N = B * 32;
-    PF_REQUIRE(S <= 32, "pf_encoder_forward: at most 32 simultaneous notes");
-    PF_REQUIRE(workspace_bytes >= enc_ws_floats(e, B, S) * sizeof(float), "pf_encoder_forward: workspace too small");
-    const float* W = e->wt.wdev;
-    float* ws = (float*)workspace;
-    auto take = [&](size_t n) { float* p = ws; ws += (n + 63) / 64 * 64; return p; };
-    float* emb = take((size_t)N * S * E);
-    int* lens = reinterpret_cast<int*>(take(N));
-    float* gin = take((size_t)N * S * 3 * Hn);
-    float* ghn = take((size_t)N * 3 * Hn);
-    float* hn = take((size_t)N * 2 * Hn);
-    int rc = launch_pnotree_embed(x, W + e->off("note_embedding.weight"), W + e->off("note_embedding.bias"), emb, N * S, E, e->input_dim - 5, s);
-    if (rc) return rc;
-    rc = launch_pnotree_lengths(x, lens, N, S, e->input_dim - 5, s);
-    if (rc) return rc;
-    PF_CHECK_HIP(hipMemsetAsync(hn, 0, (size_t)N * 2 * Hn * sizeof(float), s));
-    const char* sfx2[2] = {"", "_reverse"};
-    for (int d = 0; d < 2; ++d) {
-      const std::string sx = sfx2[d];
-      rc = launch_matvec(emb, E, W + e->off("enc_notes_gru.weight_ih_l0" + sx), W + e->off("enc_notes_gru.bias_ih_l0" + sx), gin, 3 * Hn, N * S, 3 * Hn, E, s);
-      if (rc) return rc;
-      float* h = hn + d * Hn;
-      for (int step = 0; step < S; ++step) {
-        rc = launch_matvec(h, 2 * Hn, W + e->off("enc_notes_gru.weight_hh_l0" + sx), W + e->off("enc_notes_gru.bias_hh_l0" + sx), ghn, 3 * Hn, N, 3 * Hn, Hn, s);
-        if (rc) return rc;
-        rc = launch_gru_gates_masked(gin, ghn, h, 2 * Hn, N, Hn, S, lens, step, d, s);
-        if (rc) return rc;
-      }
-    }
-    float* git[2] = {take((size_t)N * 3 * H), nullptr};
-    git[1] = take((size_t)N * 3 * H);
-    float* ght = take((size_t)B * 3 * H);
-    float* ht = take((size_t)B * 2 * H);
-    PF_CHECK_HIP(hipMemsetAsync(ht, 0, (size_t)B * 2 * H * sizeof(float), s));
-    for (int d = 0; d < 2; ++d) {
-      const std::string sx = sfx2[d];
-      rc = launch_matvec(hn, 2 * Hn, W + e->off("enc_time_gru.weight_ih_l0" + sx), W + e->off("enc_time_gru.bias_ih_l0" + sx), git[d], 3 * H, N, 3 * H, 2 * Hn, s);
-      if (rc) return rc;
-      float* h = ht + d * H;
-      for (int step = 0; step < 32; ++step) {
-        const int t = d == 0 ? step : 31 - step;
-        rc = launch_matvec(h, 2 * H, W + e->off("enc_time_gru.weight_hh_l0" + sx), W + e->off("enc_time_gru.bias_hh_l0" + sx), ght, 3 * H, B, 3 * H, H, s);
-        if (rc) return rc;
-        rc = launch_gru_gates(git[d] + (size_t)t * 3 * H, 32 * 3 * H, ght, h, 2 * H, B, H, s);
-        if (rc) return rc;
-      }
-    }
-    return launch_matvec(ht, 2 * H, W + e->off("linear_mu.weight"), W + e->off("linear_mu.bias"), mu, e->z, B, e->z, 2 * H, s);
-  }
-  if (e->kind == PF_ENC_TEXTURE) { T = 8; gru_in = e->emb; }
-  PF_REQUIRE(workspace_bytes >= enc_ws_floats(e, B, T) * sizeof(float), "pf_encoder_forward: workspace too small");
-  const float* W = e->wt.wdev;
-  float* ws = (float*)workspace;
-  auto take = [&](size_t n) { float* p = ws; ws += (n + 63) / 64 * 64; return p; };
-  const float* seq = x;  // [B][T][gru_in]
-  int rc = PF_OK;
-  if (e->kind == PF_ENC_TEXTURE) {
-    float* feat = take((size_t)B * e->nch * 8 * 29);
-    float* a1 = take((size_t)B * 8 * 1000);
-    float* em = take((size_t)B * 8 * e->emb);
-    rc = launch_txt_frontend(x, W + e->off("cnn.0.weight"), W + e->off("cnn.0.bias"), feat, B, e->nch, s);
-    if (rc) return rc;
+    const int S = n_step, E = e->emb, Hn = e->nch, N = B * 32, P = e->input_dim - 5;
+    float* emb = c.palloc((size_t)N * S * E);
+    int* lens = reinterpret_cast<int*>(c.palloc(N));
+    c.launch(PF_K_SMALL, 0.0, [&] { return launch_pnotree_embed(x, c.w(e->note_emb.w), c.w(e->note_emb.b), emb, N * S, E, P, c.s); });
+    c.launch(PF_K_SMALL, 0.0, [&] { return launch_pnotree_lengths(x, lens, N, S, P, c.s); });
+    const float* hn = bigru(c, e->notes_gru, emb, E, N, S, Hn, true, lens);
+    h = bigru(c, e->gru, hn, 2 * Hn, B, 32, H, false, nullptr);
+  } else if (e->kind == PF_ENC_TEXTURE) {
     const int K1 = e->nch * 29;  // rows of the un-permuted [B,8,-1] view (txt_enc.py:27)
-    rc = launch_matvec(feat, K1, W + e->off("fc1.weight"), W + e->off("fc1.bias"), a1, 1000, B * 8, 1000, K1, s);
-    if (rc) return rc;
-    rc = launch_matvec(a1, 1000, W + e->off("fc2.weight"), W + e->off("fc2.bias"), em, e->emb, B * 8, e->emb, 1000, s);
-    if (rc) return rc;
-    seq = em;
+    float* feat = c.palloc((size_t)B * 8 * K1);
+    float* a1 = c.palloc((size_t)B * 8 * 1000);
+    float* em = c.palloc((size_t)B * 8 * e->emb);
+    c.launch(PF_K_SMALL, 0.0, [&] { return launch_txt_frontend(x, c.w(e->cnn.w), c.w(e->cnn.b), feat, B, e->nch, c.s); });
+    c.launch(PF_K_SMALL, 0.0, [&] { return launch_matvec(feat, K1, c.w(e->fc1.w), c.w(e->fc1.b), a1, 1000, B * 8, 1000, K1, c.s); });
+    c.launch(PF_K_SMALL, 0.0, [&] { return launch_matvec(a1, 1000, c.w(e->fc2.w), c.w(e->fc2.b), em, e->emb, B * 8, e->emb, 1000, c.s); });
+    h = bigru(c, e->gru, em, e->emb, B, 8, H, false, nullptr);
+  } else {
+    h = bigru(c, e->gru, x, e->input_dim, B, n_step, H, false, nullptr);   // x [B][T][input_dim]
   }
-  float* gi[2] = {take((size_t)B * T * 3 * H), nullptr};
-  gi[1] = take((size_t)B * T * 3 * H);
-  float* gh = take((size_t)B * 3 * H);
-  float* hcat = take((size_t)B * 2 * H);
-  PF_CHECK_HIP(hipMemsetAsync(hcat, 0, (size_t)B * 2 * H * sizeof(float), s));
-  const char* sfx[2] = {"", "_reverse"};
-  for (int d = 0; d < 2; ++d) {
-    const std::string sx = sfx[d];
-    rc = launch_matvec(seq, gru_in, W + e->off("gru.weight_ih_l0" + sx), W + e->off("gru.bias_ih_l0" + sx), gi[d], 3 * H, B * T, 3 * H, gru_in, s);
-    if (rc) return rc;
-    float* h = hcat + d * H;  // row stride 2H
-    for (int step = 0; step < T; ++step) {
-      const int t = d == 0 ? step : T - 1 - step;
-      rc = launch_matvec(h, 2 * H, W + e->off("gru.weight_hh_l0" + sx), W + e->off("gru.bias_hh_l0" + sx), gh, 3 * H, B, 3 * H, H, s);
-      if (rc) return rc;
-      rc = launch_gru_gates(gi[d] + (size_t)t * 3 * H, T * 3 * H, gh, h, 2 * H, B, H, s);
-      if (rc) return rc;
-    }
-  }
-  rc = launch_matvec(hcat, 2 * H, W + e->off("linear_mu.weight"), W + e->off("linear_mu.bias"), mu, e->z, B, e->z, 2 * H, s);
-  if (rc || !scale) return rc;
-  return launch_matvec_exp(hcat, 2 * H, W + e->off("linear_var.weight"), W + e->off("linear_var.bias"), scale, e->z, B, e->z, 2 * H, s);
+  c.launch(PF_K_SMALL, 0.0, [&] { return launch_matvec(h, 2 * H, c.w(e->mu.w), c.w(e->mu.b), mu, e->z, B, e->z, 2 * H, c.s); });
+  if (scale) c.launch(PF_K_SMALL, 0.0, [&] { return launch_matvec_exp(h, 2 * H, c.w(e->var.w), c.w(e->var.b), scale, e->z, B, e->z, 2 * H, c.s); });
+  return c.rc;
 }
+
+// The workspace is sized by batch alone, for the longest sequence a forward accepts (64 chord steps, 32 simultaneous notes): the walk
+// of a shorter one carves the same buffers, each no larger, in the same order.
+PlanSize enc_plan(const pf_encoder* e, int batch) {
+  PlanCtx c;
+  c.B = batch;
+  return plan_sizes(c, [e](PlanCtx& d) { enc_run(e, d, nullptr, e->kind == PF_ENC_PNOTREE ? 32 : 64, nullptr, nullptr); });
+}
+
+int enc_forward(pf_encoder* e, const float* x, int batch, int n_step, float* mu, float* scale, void* workspace, size_t workspace_bytes,
+                void* stream) {
+  PF_REQUIRE(e && x && mu && workspace && batch > 0, "pf_encoder_forward: bad arguments");
+  if (!e->wt.wdev) return set_error(PF_ESTATE, "pf_encoder_forward: weights not bound");
+  PF_REQUIRE(e->kind == PF_ENC_TEXTURE || (n_step > 0 && n_step <= 64), "pf_encoder_forward: n_step must be in 1..64");
+  PF_REQUIRE(e->kind != PF_ENC_PNOTREE || n_step <= 32, "pf_encoder_forward: at most 32 simultaneous notes");
+  PlanCtx c;
+  c.B = batch;
+  const int rc = c.use_workspace("pf_encoder_forward", workspace, workspace_bytes, enc_plan(e, batch), stream, e->wt.wdev, 1);
+  if (rc != PF_OK) return rc;
+  return enc_run(e, c, x, n_step, mu, scale);
+}
+
+}  // namespace
+
+extern "C" {
+
+size_t pf_encoder_workspace_bytes(const pf_encoder* e, int batch) { return (e && batch > 0) ? enc_plan(e, batch).bytes() : 0; }
 
 int pf_encoder_forward(pf_encoder* e, const float* x, int batch, int n_step, float* mu, void* workspace, size_t workspace_bytes,
                        void* stream) {

@@ -1,6 +1,7 @@
-// plan.h - host machinery shared by the model handles (pf_unet, pf_ddpm, pf_encoder): the weight table that maps a reference
-// state_dict key to its place in the ONE packed blob, and the plan context that carves the workspace and accounts for the launches
-// of a forward (a dry run sizes the workspace, a live run enqueues).
+// plan.h - host machinery shared by the model handles (pf_unet, pf_ddpm, pf_encoder, pf_decoder): the weight table that maps a
+// reference state_dict key to its place in the ONE packed blob (every handle resolves its keys to blob offsets when it is created),
+// and the plan context that carves the workspace and accounts for the launches of a forward.  Each handle writes its forward once, as
+// a walk over a PlanCtx: a dry run of it sizes the workspace and counts the launches, a live run of it enqueues.
 #pragma once
 #include <map>
 #include <string>
@@ -34,6 +35,10 @@ struct Dest { int kind; size_t off; int taps, K, N, Npad, n_off; };
 // A key with no dests is accepted and dropped.  `optional`: it need not be supplied either (pack_missing does not count it).
 struct Param { std::string key; std::vector<int64_t> shape; std::vector<Dest> dests; bool optional = false; bool packed = false; };
 
+// blob offsets (in floats) of a linear layer / of one direction of a torch.nn.GRU layer
+struct LinOff { size_t w, b; };
+struct GruOff { size_t w_ih, w_hh, b_ih, b_hh; };
+
 struct WeightTable {
   std::vector<Param> params;   // state_dict order
   std::map<std::string, int> index;
@@ -56,6 +61,21 @@ struct WeightTable {
     return off;
   }
   void raw_at(const std::string& key, std::vector<int64_t> shape, size_t off) { add(key, std::move(shape)).dests.push_back(Dest{D_RAW, off, 1, 0, 0, 0, 0}); }
+  // `name`.weight [N][K] and `name`.bias [N], raw
+  LinOff linear(const std::string& name, int N, int K) {
+    const size_t w = raw(name + ".weight", {N, K});
+    return LinOff{w, raw(name + ".bias", {N})};
+  }
+  // the four raw tensors of each of the `ndir` directions of the one-layer GRU `name` (in -> hid), in state_dict order
+  void gru(const std::string& name, int in, int hid, int ndir, GruOff* out) {
+    for (int d = 0; d < ndir; ++d) {
+      const std::string sfx = d ? "_l0_reverse" : "_l0";
+      out[d].w_ih = raw(name + ".weight_ih" + sfx, {3 * hid, in});
+      out[d].w_hh = raw(name + ".weight_hh" + sfx, {3 * hid, hid});
+      out[d].b_ih = raw(name + ".bias_ih" + sfx, {3 * hid});
+      out[d].b_hh = raw(name + ".bias_hh" + sfx, {3 * hid});
+    }
+  }
   // a GEMM weight [N][K] (taps == 1) or [N][K][3][3] (taps == 9) in a region of its own
   size_t gemm(const std::string& key, int N, int K, int taps) {
     const size_t off = alloc_gemm(taps, K, N);
@@ -136,9 +156,10 @@ struct PlanCtx {
     if (prof) prof->end(s);
   }
 
-  // live run in `ws`, on `stream`, with the bound blob: checks the workspace against the plan's dry-run sizes, then carves it
-  int use_workspace(const char* fn, void* ws, size_t ws_bytes, const PlanSize& z, void* stream, const float* wdev) {
-    PF_REQUIRE(((uintptr_t)ws & 255) == 0, "%s: workspace must be 256-byte aligned", fn);
+  // live run in `ws` (aligned to `align` bytes, a power of two), on `stream`, with the bound blob: checks the workspace against the
+  // plan's dry-run sizes, then carves it
+  int use_workspace(const char* fn, void* ws, size_t ws_bytes, const PlanSize& z, void* stream, const float* wdev, size_t align = 256) {
+    PF_REQUIRE(((uintptr_t)ws & (align - 1)) == 0, "%s: workspace must be %zu-byte aligned", fn, align);
     if (ws_bytes < z.bytes()) return set_error(PF_EINVAL, "%s: workspace too small (%zu < %zu)", fn, ws_bytes, z.bytes());
     dry = false;
     base = (char*)ws;

@@ -126,11 +126,7 @@ class DDPMUNet(ModelHandle):
         super().__init__(_lib.load(x3), C.byref(c), device=device)
 
     def workspace(self, batch: int) -> torch.Tensor:
-        nbytes = int(self._lib.pf_ddpm_workspace_bytes(self._h, batch))
-        if self._ws is None or self._ws.numel() < nbytes:
-            self._ws = None
-            self._ws = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
-        return self._ws
+        return self.workspace_for(self._lib.pf_ddpm_workspace_bytes(self._h, batch), self.device)
 
     def forward(self, x: torch.Tensor, t: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
         if self._blob_dev is None:

@@ -17,14 +17,8 @@ from ._handle import ModelHandle
 class _Decoder(ModelHandle):
     PREFIX = "pf_decoder"
 
-    def _workspace(self, rows: int, device) -> torch.Tensor:
-        nbytes = self._lib.pf_decoder_workspace_bytes(self._h, rows)
-        if self._ws is None or self._ws.numel() < nbytes or self._ws.device != device:
-            self._ws = torch.empty(nbytes, dtype=torch.uint8, device=device)
-        return self._ws
-
     def n_launches(self, rows: int = 1) -> int:
-        """Kernel launches of one decode (host arithmetic)."""
+        """Kernel launches of one decode (a dry run of the plan: no GPU needed)."""
         return int(self._lib.pf_decoder_launches(self._h, rows))
 
     def _z(self, z: torch.Tensor, width: int) -> torch.Tensor:
@@ -35,7 +29,7 @@ class _Decoder(ModelHandle):
         return z.detach().to(device=self.device, dtype=torch.float32).contiguous()
 
     def _forward(self, z, out0, out1, out2, est):
-        ws = self._workspace(z.shape[0], z.device)
+        ws = self.workspace_for(self._lib.pf_decoder_workspace_bytes(self._h, z.shape[0]), z.device)
         self._check(self._lib.pf_decoder_forward(self._h, z.data_ptr(), z.shape[0], out0.data_ptr(), out1.data_ptr(), _lib.ptr(out2),
                                                  _lib.ptr(est), ws.data_ptr(), ws.numel(), _lib.current_stream()), "pf_decoder_forward")
 

@@ -41,17 +41,15 @@ class _Encoder(ModelHandle):
             raise RuntimeError("encoder weights not loaded")
         x = x.contiguous().float()
         B = x.shape[0]
-        nbytes = self._lib.pf_encoder_workspace_bytes(self._h, B)
-        if self._ws is None or self._ws.numel() < nbytes:
-            self._ws = torch.empty(nbytes, dtype=torch.uint8, device=x.device)
+        ws = self.workspace_for(self._lib.pf_encoder_workspace_bytes(self._h, B), x.device)
         mu = torch.empty(B, self.z_dim, dtype=torch.float32, device=x.device)
         if dist:
             scale = torch.empty(B, self.z_dim, dtype=torch.float32, device=x.device)
-            _lib.check(self._lib.pf_encoder_forward_dist(self._h, x.data_ptr(), B, n_step, mu.data_ptr(), scale.data_ptr(), self._ws.data_ptr(),
-                                                         self._ws.numel(), _lib.current_stream()), "pf_encoder_forward_dist", self._lib)
+            self._check(self._lib.pf_encoder_forward_dist(self._h, x.data_ptr(), B, n_step, mu.data_ptr(), scale.data_ptr(), ws.data_ptr(),
+                                                          ws.numel(), _lib.current_stream()), "pf_encoder_forward_dist")
             return mu, scale
-        _lib.check(self._lib.pf_encoder_forward(self._h, x.data_ptr(), B, n_step, mu.data_ptr(), self._ws.data_ptr(),
-                                                self._ws.numel(), _lib.current_stream()), "pf_encoder_forward")
+        self._check(self._lib.pf_encoder_forward(self._h, x.data_ptr(), B, n_step, mu.data_ptr(), ws.data_ptr(), ws.numel(),
+                                                 _lib.current_stream()), "pf_encoder_forward")
         return mu
 
     def forward(self, x):

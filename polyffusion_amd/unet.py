@@ -63,10 +63,7 @@ class UNetModel(ModelHandle):
         key = (batch, n_cond, shared_x, self._lib.pf_unet_get_precision(self._h)) + self.options_key()
         if self._ws is None or self._ws_key != key:
             size = self._lib.pf_unet_workspace_bytes_cfg if shared_x else self._lib.pf_unet_workspace_bytes
-            nbytes = size(self._h, batch, n_cond)
-            if self._ws is None or self._ws.numel() < nbytes:
-                self._ws = None
-                self._ws = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+            self.workspace_for(size(self._h, batch, n_cond), self.device)
             self._ws_key = key
         return self._ws
 

@@ -217,11 +217,13 @@ def test_decoder_pack_messages():
 
 def test_launch_counts_respect_the_structural_bound():
     """At most 3 launches per note slot and 2100 per PianoTree decode (32 x (19 x 3 + 7) + setup), at most 3 per step + 4 for the
-    chord decoder; computed on the host, the same for every batch size."""
+    chord decoder; computed on the host, the same for every batch size.  Exactly 3 + 32 (3 + 2 (S - 1)) + 31 and 3 + 2 n_step (DESIGN.md
+    section 3)."""
     from polyffusion_amd.model_sdf import ChordDecoder, PianoTreeDecoder
     for S in (20, 4, 2):
         pn = PianoTreeDecoder(max_simu_note=S)
         n = pn.n_launches(1)
+        assert n == {20: 1346, 4: 322, 2: 194}[S]
         assert [pn.n_launches(r) for r in (1, 8, 64)] == [n] * 3
         assert 32 * (S - 1) <= n <= 32 * ((S - 1) * 3 + 7) + 8
         if S == 20:
@@ -229,6 +231,7 @@ def test_launch_counts_respect_the_structural_bound():
     for n_step in (8, 32):
         chd = ChordDecoder(36, 256, 512, 256, n_step)
         n = chd.n_launches(1)
+        assert n == {8: 19, 32: 67}[n_step]
         assert [chd.n_launches(r) for r in (1, 8, 64)] == [n] * 3 and n_step <= n <= 3 * n_step + 4
 
 

@@ -1,4 +1,4 @@
-"""The host-side plans of pf_unet and pf_ddpm are the recorded ones (-m "not gpu"): parameter table in order, packed blob, workspace sizes
+"""The host-side plans of pf_unet, pf_ddpm, pf_encoder and pf_decoder are the recorded ones (-m "not gpu"): parameter table in order, packed blob, workspace sizes
 and launch counts per batch / precision / n_cond / plan option / telemetry binding, recomputed from the C ABI (tools/plan_fingerprint.py)
 and compared with tests/golden/plan_fingerprint.json.  A change that alters a plan on purpose regenerates the file with
 `python tools/plan_fingerprint.py --write` and says so."""
@@ -20,7 +20,7 @@ def recorded():
 def test_recorded_document_covers_both_builds_and_every_model(recorded):
     assert set(recorded) == {"default", "f16"}
     for doc in recorded.values():
-        assert set(doc) == {n for n, *_ in pfp.UNETS} | {n for n, *_ in pfp.DDPMS}
+        assert set(doc) == {n for group in (pfp.UNETS, pfp.DDPMS, pfp.ENCODERS, pfp.DECODERS) for n, *_ in group}
     # the figures the file was recorded with: B = 16, split mode, n_cond 1: launches, all prepared, with telemetry bound
     chd = recorded["default"]["sdf_chd8bar"]
     assert (chd["plan"]["split B16 nc1"][2], chd["plan"]["split B16 nc1"][6], chd["plan absmax"]["split B16 nc1"][2]) == (158, 154, 173)

@@ -248,8 +248,9 @@ def test_launch_counts_at_32_slots():
     for hd in (16, 64):
         dec = PtvaeDecoder(dec_dur_hid_size=hd)
         n = dec.n_launches(1)
+        assert n == 2114                                      # 3 + 32 (3 + 2 * 31) + 31
         assert [dec.n_launches(r) for r in (1, 8, 64)] == [n] * 3 and 32 * 31 <= n <= 32 * (31 * 3 + 7) + 8
-    assert PtvaeDecoder(dec_dur_hid_size=64).n_launches(1) == PtvaeDecoder().n_launches(1)       # the formula does not know the width
+    assert PtvaeDecoder(dec_dur_hid_size=64).n_launches(1) == PtvaeDecoder().n_launches(1)       # the count does not depend on the width
 
 
 def test_midi_writers_reproduce_the_reference_note_lists(tmp_path):

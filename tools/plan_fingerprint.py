@@ -1,9 +1,11 @@
-"""Fingerprint of the host-side plans of pf_unet and pf_ddpm, from the C ABI alone; needs no GPU.
+"""Fingerprint of the host-side plans of pf_unet, pf_ddpm, pf_encoder and pf_decoder, from the C ABI alone; needs no GPU.
 
 A dry-run plan touches no device (the CU count falls back to the MI355X's 256), so the document computed on a CPU-only machine describes
 what the GPU runs: per model the parameter table (count, a sha256 over its `key:shape` rows IN ORDER, blob size), the sha256 of the blob
 packed from the synthetic state (seed 0) for the models whose blob is small enough, and per batch / precision / n_cond / plan option /
-telemetry binding the workspace sizes and launch counts (pf_ddpm: workspace, launches, operations).  Both builds of the library.
+telemetry binding the workspace sizes and launch counts (pf_ddpm: workspace, launches, operations).  The encoders and decoders keep
+what a refactor of their host code must not move under "table" (blob size, the decoders' parameter table, the packed blob, the decoders'
+launch counts) and their workspace sizes, which may move by rounding, under "workspace".  Both builds of the library.
 
     python tools/plan_fingerprint.py            # print the document
     python tools/plan_fingerprint.py --check    # compare with tests/golden/plan_fingerprint.json (exit 1 and the differing keys on a mismatch)
@@ -25,8 +27,10 @@ if REPO not in sys.path:
 from polyffusion_amd import _lib  # noqa: E402
 from polyffusion_amd.arch import UNetConfig  # noqa: E402
 from polyffusion_amd.ddpm import DDPMConfig, DDPMUNet  # noqa: E402
+from polyffusion_amd._handle import ModelHandle  # noqa: E402
 from polyffusion_amd.params import preset  # noqa: E402
 from polyffusion_amd.unet import UNetModel  # noqa: E402
+from polyffusion_amd import weights as W  # noqa: E402
 from polyffusion_amd.weights import synth_ddpm_state, synth_unet_state  # noqa: E402
 
 GOLDEN = os.path.join(REPO, "tests", "golden", "plan_fingerprint.json")
@@ -37,6 +41,18 @@ DDPM_SMALL = DDPMConfig(image_channels=2, n_channels=32, ch_mults=(1, 2), is_att
 # (name, config, image side, hash the packed blob)
 UNETS = (("sdf_chd8bar", None, 128, True), ("sdf_txt", None, 128, False), ("sdf_concat", None, 128, False), ("unet_small", UNET_SMALL, 32, True))
 DDPMS = (("ddpm", DDPMConfig(), False), ("ddpm_small", DDPM_SMALL, True))   # the default config's blob is over a gigabyte
+# (name, create arguments of the C ABI, synthetic state): the encoders at the sizes tests/test_gpu_encoders.py builds, the two Polydis
+# encoders (with the scale head), the chord decoder, and the PianoTree decoder at three (max_simu_note, dec_dur_hid_size)
+# pf_encoder_create_dist(kind, input_dim, emb_size, hidden_dim, z_dim, num_channel, with_scale)
+ENCODERS = (("enc_chord", (0, 36, 0, 512, 512, 0, 0), lambda: W.synth_chord_encoder_state(0)),
+            ("enc_texture", (1, 0, 256, 1024, 256, 10, 0), lambda: W.synth_texture_encoder_state(0)),
+            ("enc_pnotree", (2, 135, 128, 512, 512, 256, 0), lambda: W.synth_pianotree_encoder_state(0)),
+            ("enc_polydis_chord", (0, 36, 0, 1024, 256, 0, 1), lambda: W.synth_chord_encoder_state(0, 36, 1024, 256)),
+            ("enc_polydis_texture", (1, 0, 256, 1024, 256, 10, 1), lambda: W.synth_texture_encoder_state(0, 256, 1024, 256, 10)))
+# pf_decoder_create(kind, max_simu_note, input_dim, z_input_dim, hidden_dim, z_dim, n_step)
+DECODERS = (("dec_chord", (0, 0, 36, 256, 512, 256, 8), lambda: W.synth_chord_decoder_state(0)),) + tuple(
+    (f"dec_pnotree_s{s}_hd{hd}", (1, s, 0, 0, hd, 0, 0), lambda hd=hd: W.synth_pianotree_decoder_state(0, hd)) for s, hd in ((20, 16), (32, 64), (4, 16)))
+ROWS = (1, 8, 9, 64)   # workspace sizes; the decoders' launch counts at 1, 8 and 64
 
 
 def _table(model) -> dict:
@@ -99,11 +115,33 @@ def _ddpm(lib, variant, cfg, blob) -> dict:
     return r
 
 
+class _Coder(ModelHandle):
+    """A pf_encoder / pf_decoder handle in the library of one build (the model classes live in the process's default library)."""
+
+    def __init__(self, lib, prefix, create, args):
+        self.PREFIX, self._create = prefix, create
+        super().__init__(lib, *args)
+
+    def _fn(self, name: str):
+        return super()._fn(self._create if name == "create" else name)
+
+
+def _coder(lib, args, state, decoder: bool) -> dict:
+    m = _Coder(lib, "pf_decoder", "create", args) if decoder else _Coder(lib, "pf_encoder", "create_dist", args)
+    t = _table(m) if decoder else {"weight_bytes": m.weight_bytes()}
+    t["blob_sha256"] = _blob_sha(m, state())
+    if decoder:
+        t["launches"] = {f"R{r}": int(lib.pf_decoder_launches(m._h, r)) for r in ROWS if r != 9}
+    return {"table": t, "workspace": {f"R{r}": int(m._fn("workspace_bytes")(m._h, r)) for r in ROWS}}
+
+
 def fingerprint(variant: str = "") -> dict:
     """The document of one build of the library ("" or "f16")."""
     lib = _lib.load(variant)
     doc = {name: _unet(lib, variant, name, cfg, side, blob) for name, cfg, side, blob in UNETS}
     doc.update({name: _ddpm(lib, variant, cfg, blob) for name, cfg, blob in DDPMS})
+    doc.update({name: _coder(lib, args, state, False) for name, args, state in ENCODERS})
+    doc.update({name: _coder(lib, args, state, True) for name, args, state in DECODERS})
     return doc
 
 
