@@ -414,7 +414,12 @@ typedef struct pf_conv_args {
   /* optional range telemetry: a device word (fp32 bit pattern, start at 0) that receives max(word, largest |value| this launch stores)
    * by atomic max - see pf_unet_track_absmax */
   void* absmax_slot;
+  /* ks = 3, stride = 2 only.  0: one zero row / column on every side (Conv2d(3, 2, padding = 1)).  PF_PAD_BOTTOM_RIGHT: none above / left,
+   * one below / right - F.pad(x, (0, 1, 0, 1)) followed by Conv2d(3, 2, padding = 0), the DownSample of the first-stage autoencoder
+   * (autoencoder.py:406-426); output pixel (y, x) then reads input rows 2y .. 2y+2 instead of 2y-1 .. 2y+1.  hin and win must be even. */
+  int32_t pad_mode;
 } pf_conv_args;
+enum { PF_PAD_SAME = 0, PF_PAD_BOTTOM_RIGHT = 1 };
 /* scratch bytes a launch with these arguments would like for split-K (0 = the launch does not split) */
 size_t pf_conv_splitk_ws_bytes(const pf_conv_args* a);
 /* number of per-sample tiles a pf_conv2d launch with these arguments emits into stats_out (0 on error) */
@@ -490,6 +495,54 @@ int pf_pack_convt_weight_bf16x3(const float* w, int cin, int cout, void* dst);
 int pf_pack_convt_weight_f32(const float* w, int cin, int cout, float* dst);
 int pf_conv_transpose_f32(const float* x, int batch, int h, int w, int cin, const float* w_packed, int cout, const float* bias, float* out,
                           void* stream);
+
+/* ---- first-stage autoencoder (replaces Autoencoder.encode / decode / forward with Encoder, Decoder, ResnetBlock, AttnBlock, UpSample,
+ *      DownSample and GaussianDistribution, stable_diffusion/model/autoencoder.py:27-490; the `autoencoder` model of params/autoencoder.yaml;
+ *      LatentDiffusion.autoencoder_encode / autoencoder_decode, latent_diffusion.py:112-136) -------
+ * Same life cycle as pf_ddpm: create, pack every key of the state_dict (encoder.*, decoder.*, quant_conv.*, post_quant_conv.*; the
+ * training-only loss.* keys are accepted and dropped), bind the device copy of the blob, then encode / decode.  The image size is an
+ * argument of the calls, not of the handle: H and W must be multiples of 2^(n_levels-1) (even at every DownSample), and the tokens of the
+ * attention, (H / 2^(n_levels-1)) * (W / 2^(n_levels-1)), a multiple of 64 and at most 1024 (pf_attention_wide).  GroupNorm is
+ * GroupNorm(32, eps 1e-6); attention is one head of width C with scale C^-0.5, exact fp32 in every mode.  channels * multiplier must be
+ * a multiple of 32 at every level, in / out channels and z / emb channels 1..4. */
+typedef struct pf_autoenc pf_autoenc;
+typedef struct pf_autoenc_cfg {
+  int32_t in_channels, out_channels, channels, n_levels;
+  int32_t channel_multipliers[8];
+  int32_t n_resnet_blocks, z_channels, emb_channels;
+} pf_autoenc_cfg;
+int pf_autoenc_create(const pf_autoenc_cfg* cfg, pf_autoenc** out);
+void pf_autoenc_destroy(pf_autoenc* u);
+size_t pf_autoenc_weight_bytes(const pf_autoenc* u);
+int pf_autoenc_n_params(const pf_autoenc* u);
+int pf_autoenc_param_info(const pf_autoenc* u, int i, char* key_buf, size_t key_buf_len, int64_t shape[4], int* ndim);
+int pf_autoenc_pack_param(pf_autoenc* u, const char* key, const float* src, const int64_t* shape, int ndim, void* host_blob);
+int pf_autoenc_pack_missing(const pf_autoenc* u, char* buf, size_t buf_len);
+int pf_autoenc_bind_weights(pf_autoenc* u, const void* dev_blob);
+int pf_autoenc_set_precision(pf_autoenc* u, int precision);
+int pf_autoenc_get_precision(const pf_autoenc* u);
+/* workspace, kernel launches and algorithmic operations of one encode of [batch, in_channels, h, w] / one decode of a latent
+ * [batch, emb_channels, zh, zw], from a dry run of the walk that the call enqueues (no GPU needed; 0 for a shape the model cannot run) */
+size_t pf_autoenc_encode_workspace_bytes(const pf_autoenc* u, int batch, int h, int w);
+size_t pf_autoenc_decode_workspace_bytes(const pf_autoenc* u, int batch, int zh, int zw);
+int pf_autoenc_encode_launches(const pf_autoenc* u, int batch, int h, int w);
+int pf_autoenc_decode_launches(const pf_autoenc* u, int batch, int zh, int zw);
+double pf_autoenc_encode_flops(const pf_autoenc* u, int batch, int h, int w);
+double pf_autoenc_decode_flops(const pf_autoenc* u, int batch, int zh, int zw);
+/* Autoencoder.encode + GaussianDistribution (+ .sample()): img NCHW [B, in_channels, h, w] -> mean, log_var (clamped to [-30, 20]) and
+ * z = scale * (mean + exp(0.5 log_var) * noise), each NCHW [B, emb_channels, h / 2^(L-1), w / 2^(L-1)]; any of the three outputs may be
+ * NULL.  noise: a tensor shaped like z, or NULL - then element i of z uses what pf_randn(seed, stream_id, elem_offset) writes at i.
+ * `scale` is the latent scaling factor (1 for the plain posterior sample). */
+int pf_autoenc_encode(pf_autoenc* u, const float* img, int batch, int h, int w, float scale, const float* noise, uint64_t seed,
+                      uint64_t stream_id, uint64_t elem_offset, float* z, float* mean, float* log_var, void* workspace,
+                      size_t workspace_bytes, void* stream);
+/* Autoencoder.decode: img = decoder(post_quant_conv(z / scale)); z NCHW [B, emb_channels, zh, zw] -> img NCHW [B, out_channels, zh 2^(L-1), zw 2^(L-1)] */
+int pf_autoenc_decode(pf_autoenc* u, const float* z, int batch, int zh, int zw, float scale, float* img, void* workspace,
+                      size_t workspace_bytes, void* stream);
+/* GaussianDistribution.sample on moments already computed: z[i] = scale * (mean[i] + exp(0.5 log_var[i]) * noise[i]), n elements; noise as
+ * for pf_autoenc_encode.  The same arithmetic as the encode launch: bit-identical to the z it writes from the same moments and noise. */
+int pf_gaussian_sample(const float* mean, const float* log_var, const float* noise, uint64_t seed, uint64_t stream_id,
+                       uint64_t elem_offset, float scale, float* z, size_t n, void* stream);
 
 /* Multi-GPU: one process per GPU.  The path shards over the batch with no exchange in the step loop; the single collective
  * (weight broadcast at start-up) goes either through the host's torch.distributed (backend "nccl" = RCCL over xGMI) on the packed

@@ -96,6 +96,17 @@ class ConvArgs(C.Structure):
         ("sbias_rows", C.c_void_p), ("sbias_nrows", C.c_int32), ("no_t16", C.c_int32), ("no_pp", C.c_int32),
         ("force_tile", C.c_int32), ("force_ksplit", C.c_int32), ("x1_bmod", C.c_int32),
         ("w_wino", C.c_void_p), ("wino", C.c_int32), ("absmax_slot", C.c_void_p),
+        ("pad_mode", C.c_int32),
+    ]
+
+
+PAD_SAME, PAD_BOTTOM_RIGHT = 0, 1   # pf_conv_args.pad_mode
+
+
+class AutoencCfg(C.Structure):
+    _fields_ = [
+        ("in_channels", C.c_int32), ("out_channels", C.c_int32), ("channels", C.c_int32), ("n_levels", C.c_int32),
+        ("channel_multipliers", C.c_int32 * 8), ("n_resnet_blocks", C.c_int32), ("z_channels", C.c_int32), ("emb_channels", C.c_int32),
     ]
 
 
@@ -217,6 +228,27 @@ SIGNATURES = {
     "pf_ddpm_n_launches": (C.c_int, [C.c_void_p, C.c_int]),
     "pf_ddpm_flops": (C.c_double, [C.c_void_p, C.c_int]),
     "pf_ddpm_forward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "pf_autoenc_create": (C.c_int, [C.POINTER(AutoencCfg), C.POINTER(C.c_void_p)]),
+    "pf_autoenc_destroy": (None, [C.c_void_p]),
+    "pf_autoenc_weight_bytes": (C.c_size_t, [C.c_void_p]),
+    "pf_autoenc_n_params": (C.c_int, [C.c_void_p]),
+    "pf_autoenc_param_info": (C.c_int, [C.c_void_p, C.c_int, C.c_char_p, C.c_size_t, c_i64_p, C.POINTER(C.c_int)]),
+    "pf_autoenc_pack_param": (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, c_i64_p, C.c_int, C.c_void_p]),
+    "pf_autoenc_pack_missing": (C.c_int, [C.c_void_p, C.c_char_p, C.c_size_t]),
+    "pf_autoenc_bind_weights": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "pf_autoenc_set_precision": (C.c_int, [C.c_void_p, C.c_int]),
+    "pf_autoenc_get_precision": (C.c_int, [C.c_void_p]),
+    "pf_autoenc_encode_workspace_bytes": (C.c_size_t, [C.c_void_p, C.c_int, C.c_int, C.c_int]),
+    "pf_autoenc_decode_workspace_bytes": (C.c_size_t, [C.c_void_p, C.c_int, C.c_int, C.c_int]),
+    "pf_autoenc_encode_launches": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int]),
+    "pf_autoenc_decode_launches": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int]),
+    "pf_autoenc_encode_flops": (C.c_double, [C.c_void_p, C.c_int, C.c_int, C.c_int]),
+    "pf_autoenc_decode_flops": (C.c_double, [C.c_void_p, C.c_int, C.c_int, C.c_int]),
+    "pf_autoenc_encode": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_float, C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64,
+                                    C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "pf_autoenc_decode": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_float, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "pf_gaussian_sample": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_float, C.c_void_p, C.c_size_t,
+                                     C.c_void_p]),
     "pf_attention_wide_scratch_bytes": (C.c_size_t, [C.c_int, C.c_int]),
     "pf_attention_wide": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,
                                     C.c_void_p, C.c_size_t, C.c_void_p]),

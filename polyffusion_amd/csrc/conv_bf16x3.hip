@@ -148,7 +148,8 @@ __global__ __launch_bounds__(KG * NWM * 128, 2) void conv_bf3_kernel(ConvP p) {
   // sample - or, with a rebased second source, of the sample the rebase points back to, so that the address stays inside both tensors
   const int ppad = p.x1_bmod > 0 ? (b - b % p.x1_bmod) * p.Hin * p.Win : 0;
   // KS == 2: output row 2y+py reads source rows {y-1, y} (py = 0) or {y, y+1} (py = 1); same for columns
-  const int iy0 = KS == 2 ? oy0 - 1 + (q >> 1) : oy0 * STRIDE - PAD, ix0 = KS == 2 ? ox0 - 1 + (q & 1) : ox0 * STRIDE - PAD;
+  const int pad = (STRIDE == 2 && p.pad_br) ? 0 : PAD;   // bottom / right-only padding: the halo starts on the first tap's pixel
+  const int iy0 = KS == 2 ? oy0 - 1 + (q >> 1) : oy0 * STRIDE - pad, ix0 = KS == 2 ? ox0 - 1 + (q & 1) : ox0 * STRIDE - pad;
   const int Hlog = UPS ? 2 * p.Hin : p.Hin, Wlog = UPS ? 2 * p.Win : p.Win;
   const int cin = p.c0 + p.c1;
   const int K8 = cin / 8;
@@ -970,6 +971,7 @@ int launch_conv_bf3(const pf_conv_args& a, hipStream_t stream) {
   p.sx0 = a.skip_x0; p.sc0 = a.skip_c0; p.sx1 = a.skip_x1; p.sc1 = a.skip_c1; p.sw = a.skip_w; p.bias2 = a.skip_w ? a.skip_bias : nullptr;
   p.x1_bmod = a.x1_bmod;
   p.amax = static_cast<unsigned*>(a.absmax_slot);
+  p.pad_br = a.pad_mode == PF_PAD_BOTTOM_RIGHT;
   const int tile = conv_pick_tile(a);
   if (a.ks == 1) {
     switch (a.prologue) {

@@ -83,6 +83,7 @@ struct ConvP {
   int x1_bmod;
   // optional range telemetry (pf_unet_track_absmax): the largest |value| this launch stores, as fp32 bits, max-combined into one device word
   unsigned* amax;
+  int pad_br;                   // stride-2 3x3 only: no padding above / left, one row / column below / right (pf_conv_args.pad_mode)
 };
 
 // rebase the second-source pointers of this workgroup's sample (see ConvP::x1_bmod); hw_in / hw_out: pixels per sample of x1 / sx1

@@ -70,7 +70,8 @@ __global__ __launch_bounds__(256, 2) void conv_mfma_kernel(ConvP p) {
   conv_shared_x1(p, b);
   const int n0 = nti * BN;
   const int oy0 = ty * TH, ox0 = tx * TW;
-  const int iy0 = oy0 * STRIDE - PAD, ix0 = ox0 * STRIDE - PAD;
+  const int pad = (STRIDE == 2 && p.pad_br) ? 0 : PAD;   // bottom / right-only padding: the halo starts on the first tap's pixel
+  const int iy0 = oy0 * STRIDE - pad, ix0 = ox0 * STRIDE - pad;
   const int Hlog = UPS ? 2 * p.Hin : p.Hin, Wlog = UPS ? 2 * p.Win : p.Win;
   const int cin = p.c0 + p.c1;
 
@@ -339,6 +340,8 @@ int launch_conv(const pf_conv_args& a, hipStream_t stream) {
   PF_REQUIRE(a.stride == 1 || a.stride == 2, "conv: stride must be 1 or 2");
   PF_REQUIRE(!(a.ks == 1 && (a.stride != 1 || a.ups)), "conv: 1x1 supports stride 1 without upsampling only");
   PF_REQUIRE(!(a.ups && a.stride != 1), "conv: upsample fold needs stride 1");
+  PF_REQUIRE(a.pad_mode == PF_PAD_SAME || (a.pad_mode == PF_PAD_BOTTOM_RIGHT && a.ks == 3 && a.stride == 2 && a.hin % 2 == 0 && a.win % 2 == 0),
+             "conv: pad_mode %d needs ks=3, stride 2 and an even input size", a.pad_mode);
   PF_REQUIRE(a.c0 > 0 && a.c0 % 32 == 0 && a.c1 >= 0 && a.c1 % 32 == 0, "conv: channel counts must be multiples of 32 (c0=%d c1=%d)", a.c0, a.c1);
   PF_REQUIRE(a.x0 && (a.c1 == 0 || a.x1), "conv: null input");
   PF_REQUIRE(a.n > 0 && a.w && a.out, "conv: null weight/output");
@@ -385,6 +388,7 @@ int launch_conv(const pf_conv_args& a, hipStream_t stream) {
   p.geglu = a.geglu; p.out = a.out; p.ld_out = a.ld_out; p.stats = a.stats_out;
   p.ksplit = 1; p.partial = nullptr; p.qkv = a.qkv_planes; p.out_planes = a.out_planes;
   p.amax = static_cast<unsigned*>(a.absmax_slot);
+  p.pad_br = a.pad_mode == PF_PAD_BOTTOM_RIGHT;
 
   const int tile = conv_pick_tile(a);
 

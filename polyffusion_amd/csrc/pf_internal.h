@@ -146,6 +146,18 @@ int launch_convT_f32(const float* x, int batch, int h, int w, int cin, const flo
 int launch_ddpm_time_embed(const int64_t* t, const float* w1, const float* b1, const float* w2, const float* b2, float* out, int batch,
                            int d_t, hipStream_t stream);
 
+// first-stage autoencoder (small_kernels.hip): GaussianDistribution.sample on computed moments; the encoder tail - GroupNorm + SiLU +
+// conv_out (3x3, cin -> z2) + quant_conv (1x1, z2 -> e2) + clamp + sample, x NHWC -> z / mean / log_var NCHW [B][e2 / 2][h][w], each
+// optional; the decoder front - z / scale + post_quant_conv (1x1, emb -> zc) + conv_in (3x3, zc -> cout), z NCHW -> out NHWC.
+// noise == nullptr: element i draws what launch_randn(seed, sid, off) writes at i
+int launch_gaussian_sample(const float* mean, const float* log_var, const float* noise, uint64_t seed, uint64_t sid, uint64_t off, float scale,
+                           float* z, size_t n, hipStream_t s);
+int launch_ae_tail(const float* x, const float* sc, const float* sh, const float* w /*[9][cin][z2]*/, const float* bias, const float* qw /*[e2][z2]*/,
+                   const float* qb, int z2, int e2, const float* noise, uint64_t seed, uint64_t sid, uint64_t off, float scale, float* z, float* mean,
+                   float* log_var, int batch, int cin, int h, int w_, hipStream_t stream);
+int launch_ae_front(const float* z, float scale, const float* pw /*[zc][emb]*/, const float* pb, const float* w /*[cout][zc][3][3]*/, const float* bias,
+                    float* out, int batch, int emb, int zc, int cout, int h, int w_, hipStream_t stream);
+
 // encoder kernels
 int launch_gru_gates(const float* gi, int ld_gi, const float* gh, float* h, int ld_h, int batch, int hidden, hipStream_t s);
 int launch_pnotree_embed(const float* grid, const float* w, const float* bias, float* out, int rows, int emb, int pitch_range, hipStream_t s);

@@ -713,6 +713,188 @@ int launch_ddim_step_rng(const float* x, const float* eps, const float* orig, co
   return PF_OK;
 }
 
+// ------------------------------------------------------------------ first-stage autoencoder: posterior sample, encoder tail, decoder front
+// GaussianDistribution.sample times the latent scaling factor (autoencoder.py:316-324, latent_diffusion.py:112-120).
+// NOT inlined, contraction off: the encoder tail and gaussian_sample_kernel must give the same bits for the same moments and noise
+// (see philox_normal4v).
+__device__ __noinline__ float gaussian_sample1(float mean, float log_var, float nz, float scale) {
+#pragma clang fp contract(off)
+  const float sd = expf(0.5f * log_var);
+  return scale * (mean + sd * nz);
+}
+// element i of a noise tensor, or - noise == nullptr - what randn_kernel(seed, sid, off) writes at i
+__device__ __forceinline__ float noise_at(const float* __restrict__ noise, size_t i, uint64_t seed, uint64_t sid, uint64_t off) {
+  if (noise) return noise[i];
+  const uint64_t e = off + i;
+  const f32x4 v = philox_normal4v(e >> 2, sid, seed);
+  const int j = (int)(e & 3);
+  return j == 0 ? v[0] : j == 1 ? v[1] : j == 2 ? v[2] : v[3];
+}
+__global__ void gaussian_sample_kernel(const float* __restrict__ mean, const float* __restrict__ log_var, const float* __restrict__ noise,
+                                       uint64_t seed, uint64_t sid, uint64_t off, float scale, float* __restrict__ z, size_t n) {
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x)
+    z[i] = gaussian_sample1(mean[i], log_var[i], noise_at(noise, i, seed, sid, off), scale);
+}
+int launch_gaussian_sample(const float* mean, const float* log_var, const float* noise, uint64_t seed, uint64_t sid, uint64_t off, float scale,
+                           float* z, size_t n, hipStream_t s) {
+  PF_REQUIRE(mean && log_var && z && n > 0, "gaussian_sample: bad arguments");
+  hipLaunchKernelGGL(gaussian_sample_kernel, ew_grid(n), dim3(256), 0, s, mean, log_var, noise, seed, sid, off, scale, z, n);
+  PF_CHECK_HIP(hipGetLastError());
+  return PF_OK;
+}
+
+// Encoder tail (autoencoder.py:198-201, 64-68, 316-324): moments = quant_conv(conv_out(swish(norm_out(x)))), mean | log_var = its halves,
+// log_var clamped to [-30, 20], z = scale * (mean + exp(0.5 log_var) * noise); x NHWC, outputs NCHW.  The layout of conv_out_kernel: a
+// workgroup owns 16x16 output pixels and stages the normalised + activated 18x18 halo in LDS 16 channels at a time; a thread owns one
+// pixel and all Z2 = 2 z_channels outputs of the 3x3 conv, so the 1x1 quant_conv and everything behind it stay in its registers.
+// Weights [9][Cin][Z2] at wave-uniform addresses (scalar loads).
+template <int Z2>
+__global__ __launch_bounds__(256) void ae_tail_kernel(const float* __restrict__ x, const float* __restrict__ sc, const float* __restrict__ sh,
+                                                      const float* __restrict__ w, const float* __restrict__ bias, const float* __restrict__ qw,
+                                                      const float* __restrict__ qb, int E2, const float* __restrict__ noise, uint64_t seed,
+                                                      uint64_t sid, uint64_t off, float scale, float* __restrict__ z, float* __restrict__ mean,
+                                                      float* __restrict__ log_var, int B, int Cin, int H, int W) {
+  constexpr int T = 16, TI = T + 2, CK = 16, CP = CK + 4, NPIECE = TI * TI * (CK / 4);
+  __shared__ __attribute__((aligned(16))) float sx[TI * TI * CP];
+  const int tid = threadIdx.x;
+  const int tilesx = (W + T - 1) / T, tilesy = (H + T - 1) / T;
+  int bid = blockIdx.x;
+  const int tx = bid % tilesx; bid /= tilesx;
+  const int ty = bid % tilesy;
+  const int b = bid / tilesy;
+  const int py = tid / T, px = tid % T;
+  float acc[Z2];
+#pragma unroll
+  for (int j = 0; j < Z2; ++j) acc[j] = 0.f;
+  for (int c0 = 0; c0 < Cin; c0 += CK) {
+    if (c0) __syncthreads();   // every thread has finished reading the previous chunk's image
+    for (int u = tid; u < NPIECE; u += 256) {
+      const int pix = u >> 2, c4 = u & 3;
+      const int iy = ty * T + pix / TI - 1, ix = tx * T + pix % TI - 1;
+      f32x4 v = {0.f, 0.f, 0.f, 0.f};   // conv padding: zeros of the ACTIVATED tensor
+      if (iy >= 0 && iy < H && ix >= 0 && ix < W) {
+        const f32x4 r = *reinterpret_cast<const f32x4*>(x + (((size_t)b * H + iy) * W + ix) * Cin + c0 + c4 * 4);
+        const f32x4 a4 = *reinterpret_cast<const f32x4*>(sc + (size_t)b * Cin + c0 + c4 * 4);
+        const f32x4 d4 = *reinterpret_cast<const f32x4*>(sh + (size_t)b * Cin + c0 + c4 * 4);
+        v = r * a4 + d4;
+        v[0] = silu_s(v[0]); v[1] = silu_s(v[1]); v[2] = silu_s(v[2]); v[3] = silu_s(v[3]);
+      }
+      *reinterpret_cast<f32x4*>(sx + pix * CP + c4 * 4) = v;
+    }
+    __syncthreads();
+#pragma unroll
+    for (int t = 0; t < 9; ++t) {
+      const float* xp = sx + ((py + t / 3) * TI + px + t % 3) * CP;
+      const float* wt = w + (size_t)__builtin_amdgcn_readfirstlane((t * Cin + c0) * Z2);
+#pragma unroll
+      for (int k4 = 0; k4 < CK / 4; ++k4) {
+        const f32x4 v = *reinterpret_cast<const f32x4*>(xp + k4 * 4);
+#pragma unroll
+        for (int e = 0; e < 4; ++e)
+#pragma unroll
+          for (int j = 0; j < Z2; ++j) acc[j] = fmaf(v[e], wt[(k4 * 4 + e) * Z2 + j], acc[j]);
+      }
+    }
+  }
+  const int oy = ty * T + py, ox = tx * T + px;
+  if (oy >= H || ox >= W) return;
+#pragma unroll
+  for (int j = 0; j < Z2; ++j) acc[j] += bias[j];
+  const int E = E2 / 2;
+#pragma unroll
+  for (int e = 0; e < 4; ++e) {   // emb_channels <= 4
+    if (e >= E) break;
+    float mu = qb[e], lv = qb[E + e];
+#pragma unroll
+    for (int j = 0; j < Z2; ++j) { mu = fmaf(qw[e * Z2 + j], acc[j], mu); lv = fmaf(qw[(E + e) * Z2 + j], acc[j], lv); }
+    lv = fminf(fmaxf(lv, -30.0f), 20.0f);
+    const size_t i = (((size_t)b * E + e) * H + oy) * W + ox;
+    if (mean) mean[i] = mu;
+    if (log_var) log_var[i] = lv;
+    if (z) z[i] = gaussian_sample1(mu, lv, noise_at(noise, i, seed, sid, off), scale);
+  }
+}
+
+int launch_ae_tail(const float* x, const float* sc, const float* sh, const float* w, const float* bias, const float* qw, const float* qb, int z2,
+                   int e2, const float* noise, uint64_t seed, uint64_t sid, uint64_t off, float scale, float* z, float* mean, float* log_var,
+                   int batch, int cin, int h, int w_, hipStream_t stream) {
+  PF_REQUIRE(z2 >= 2 && z2 <= 8 && z2 % 2 == 0 && e2 >= 2 && e2 <= 8 && e2 % 2 == 0 && cin % 16 == 0, "ae_tail: unsupported channel counts %d->%d->%d", cin, z2, e2);
+  PF_REQUIRE(x && sc && sh && w && bias && qw && qb && (z || mean || log_var), "ae_tail: null argument");
+  const int grid = batch * cdiv(h, 16) * cdiv(w_, 16);
+#define PF_AE_TAIL(Z2) hipLaunchKernelGGL(ae_tail_kernel<Z2>, dim3(grid), dim3(256), 0, stream, x, sc, sh, w, bias, qw, qb, e2, noise, seed, sid, off, \
+                                          scale, z, mean, log_var, batch, cin, h, w_)
+  switch (z2) {
+    case 2: PF_AE_TAIL(2); break;
+    case 4: PF_AE_TAIL(4); break;
+    case 6: PF_AE_TAIL(6); break;
+    default: PF_AE_TAIL(8); break;
+  }
+#undef PF_AE_TAIL
+  PF_CHECK_HIP(hipGetLastError());
+  return PF_OK;
+}
+
+// Decoder front (latent_diffusion.py:122-129, autoencoder.py:76-79, 281): h = conv_in(post_quant_conv(z / scale)); z NCHW [B][E][H][W], h NHWC
+// [B][H][W][C].  thread = (pixel, 4 output channels), as conv_in_kernel; the 1x1 conv (E -> ZC, with its bias) is evaluated for each of the
+// pixel's nine taps INSIDE the image only: the reference pads the 1x1's output, so a tap outside contributes zero, not the 1x1's bias.
+// conv_in weights [C][ZC][3][3] through LDS, the 1x1's through wave-uniform (scalar) loads.
+__global__ __launch_bounds__(256) void ae_front_kernel(const float* __restrict__ z, float scale, const float* __restrict__ pw,
+                                                       const float* __restrict__ pb, const float* __restrict__ w, const float* __restrict__ bias,
+                                                       float* __restrict__ out, int B, int E, int ZC, int C, int H, int W) {
+  extern __shared__ float sw[];  // [C][ZC*9]
+  const int K = ZC * 9;
+  for (int i = threadIdx.x; i < C * K; i += 256) sw[i] = w[i];
+  __syncthreads();
+  const int CQ = C / 4;
+  const size_t total = (size_t)B * H * W * CQ;
+  for (size_t idx = (size_t)blockIdx.x * 256 + threadIdx.x; idx < total; idx += (size_t)gridDim.x * 256) {
+    const int cq = (int)(idx % CQ);
+    const size_t pix = idx / CQ;
+    const int xw = (int)(pix % W), yh = (int)((pix / W) % H), b = (int)(pix / ((size_t)W * H));
+    float acc[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) acc[j] = bias[cq * 4 + j];
+#pragma unroll
+    for (int r = 0; r < 3; ++r) {
+      const int iy = yh + r - 1;
+      if (iy < 0 || iy >= H) continue;
+#pragma unroll
+      for (int s = 0; s < 3; ++s) {
+        const int ix = xw + s - 1;
+        if (ix < 0 || ix >= W) continue;
+        float zin[4] = {0.f, 0.f, 0.f, 0.f};   // emb_channels <= 4
+#pragma unroll
+        for (int e = 0; e < 4; ++e)
+          if (e < E) zin[e] = z[(((size_t)b * E + e) * H + iy) * W + ix] / scale;
+#pragma unroll
+        for (int ci = 0; ci < 4; ++ci) {        // z_channels <= 4
+          if (ci >= ZC) break;
+          float v = pb[ci];
+#pragma unroll
+          for (int e = 0; e < 4; ++e)
+            if (e < E) v = fmaf(pw[ci * E + e], zin[e], v);
+#pragma unroll
+          for (int j = 0; j < 4; ++j) acc[j] = fmaf(v, sw[(cq * 4 + j) * K + ci * 9 + r * 3 + s], acc[j]);
+        }
+      }
+    }
+    *reinterpret_cast<float4*>(out + pix * C + cq * 4) = make_float4(acc[0], acc[1], acc[2], acc[3]);
+  }
+}
+
+int launch_ae_front(const float* z, float scale, const float* pw, const float* pb, const float* w, const float* bias, float* out, int batch, int emb,
+                    int zc, int cout, int h, int w_, hipStream_t stream) {
+  PF_REQUIRE(z && pw && pb && w && bias && out && scale != 0.f, "ae_front: bad arguments");
+  PF_REQUIRE(emb >= 1 && emb <= 4 && zc >= 1 && zc <= 4 && cout % 4 == 0 && (size_t)cout * zc * 9 * 4 <= 64 * 1024, "ae_front: unsupported channel counts %d->%d->%d",
+             emb, zc, cout);
+  const size_t total = (size_t)batch * h * w_ * (cout / 4);
+  const int grid = (int)min((size_t)4096, (total + 255) / 256);
+  hipLaunchKernelGGL(ae_front_kernel, dim3(grid), dim3(256), (size_t)cout * zc * 9 * sizeof(float), stream, z, scale, pw, pb, w, bias, out, batch, emb, zc,
+                     cout, h, w_);
+  PF_CHECK_HIP(hipGetLastError());
+  return PF_OK;
+}
+
 // ------------------------------------------------------------------ clock probe
 // {shader-clock counter, constant-rate reference counter} per XCD at the moment the probe runs: two probes bracketing a stretch of
 // stream work give the AVERAGE shader clock of every XCD over it (the part is power-managed: the same binary clocks differently from

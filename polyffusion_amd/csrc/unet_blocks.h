@@ -1,5 +1,6 @@
 // unet_blocks.h - the block emitters both UNet plans (pf_unet, pf_ddpm) are built from: conv / linear emission, GroupNorm, ResBlock,
 // downsample, the parity-folded split upsample, stem and head convs, and the table rows of a ResBlock and of the time-bias matrix.
+// The first-stage autoencoder (pf_autoenc) walks the same emitters with GroupNorm eps 1e-6, no time bias and its DownSample's padding.
 // What the models differ in (SpatialTransformer vs wide attention, nearest-upsample + conv vs ConvTranspose, the time embeddings) stays
 // in unet.hip / ddpm_unet.hip.
 #pragma once
@@ -65,12 +66,14 @@ struct BlockCtx : PlanCtx {
   // statistics for a tensor whose producer emitted none
   void stats_pass(Tn& x, int hw, bool persist);
 
-  // conv2(SiLU(GN(conv1(SiLU(GN(x))) + time bias))) + shortcut(x), x = concat(x0, x1)
-  Tn res_block(const ResW& L, const Tn& x0, const Tn& x1, int H, int W_, int co);
-  Tn downsample(const Tn& x, int H, int W_, size_t wgt, size_t bias, int co);                 // 3x3, stride 2
+  // conv2(SiLU(GN(conv1(SiLU(GN(x))) + time bias))) + shortcut(x), x = concat(x0, x1); `time_bias` false: a block without a time
+  // projection (L.emb_off unused)
+  Tn res_block(const ResW& L, const Tn& x0, const Tn& x1, int H, int W_, int co, float eps = 1e-5f, bool time_bias = true);
+  Tn downsample(const Tn& x, int H, int W_, size_t wgt, size_t bias, int co, int pad_mode = PF_PAD_SAME);   // 3x3, stride 2
   Tn upsample_fold(const Tn& x, int H, int W_, size_t w_fold, size_t bias, int co);           // split modes: four 2x2 convs on the source grid
   Tn stem(const float* x_nchw, size_t wgt, size_t bias, int cin, int co, int H, int W_);
-  void head(const Tn& x, int H, int W_, int groups, size_t g, size_t b_, size_t wgt, size_t bias, int co, float* out_nchw);   // GN + SiLU + conv3x3 -> NCHW
+  void head(const Tn& x, int H, int W_, int groups, size_t g, size_t b_, size_t wgt, size_t bias, int co, float* out_nchw,
+            float eps = 1e-5f);   // GN + SiLU + conv3x3 -> NCHW
 };
 
 }  // namespace pf

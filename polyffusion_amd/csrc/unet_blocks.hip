@@ -111,26 +111,28 @@ void BlockCtx::wino_attach(pf_conv_args& a, size_t wino_off) {
   a.wino = 1;
 }
 
-Tn BlockCtx::res_block(const ResW& L, const Tn& x0, const Tn& x1, int H, int W_, int co) {
+Tn BlockCtx::res_block(const ResW& L, const Tn& x0, const Tn& x1, int H, int W_, int co, float eps, bool time_bias) {
   const int hw = H * W_, ci = x0.c + x1.c;
   float* out = palloc((size_t)B * hw * co);
   treset();
   float* sc1 = talloc((size_t)B * ci); float* sh1 = talloc((size_t)B * ci);
   float* h = talloc((size_t)B * hw * co);
   float* sc2 = talloc((size_t)B * co); float* sh2 = talloc((size_t)B * co);
-  const GnRef g1 = gn(x0, x1, hw, 32, 1e-5f, L.gn1_g, L.gn1_b, sc1, sh1, true);
+  const GnRef g1 = gn(x0, x1, hw, 32, eps, L.gn1_g, L.gn1_b, sc1, sh1, true);
   Tn ht;
   {
     pf_conv_args a = conv_base(x0.d, x0.c, x1.d, x1.c, B, H, W_, 3, w(L.w1), co, h);
     a.prologue = 1; a.sc = sc1; a.sh = sh1; a.bias = w(L.b1);
     gn_attach(a, g1);
-    a.sbias = dry ? nullptr : tb + L.emb_off; a.ld_sbias = tb_ld;
-    a.sbias_rows = tb_rows; a.sbias_nrows = tb_nrows;
+    if (time_bias) {
+      a.sbias = dry ? nullptr : tb + L.emb_off; a.ld_sbias = tb_ld;
+      a.sbias_rows = tb_rows; a.sbias_nrows = tb_nrows;
+    }
     a.x1_bmod = x1mod(x1);
     wino_attach(a, L.wino1);
     conv(a, &ht, false);
   }
-  const GnRef g2 = gn(ht, Tn{}, hw, 32, 1e-5f, L.gn2_g, L.gn2_b, sc2, sh2, true);
+  const GnRef g2 = gn(ht, Tn{}, hw, 32, eps, L.gn2_g, L.gn2_b, sc2, sh2, true);
   // split modes: the 1x1 shortcut conv is folded into the second 3x3 conv as one more K range (no round trip of the projected tensor
   // through HBM, one launch less)
   const bool fuse_skip = ci != co && o.precision == PF_PREC_BF16X3 && x0.c % 32 == 0 && x1.c % 32 == 0 && co % 32 == 0;
@@ -159,10 +161,10 @@ Tn BlockCtx::res_block(const ResW& L, const Tn& x0, const Tn& x1, int H, int W_,
   return ot;
 }
 
-Tn BlockCtx::downsample(const Tn& x, int H, int W_, size_t wgt, size_t bias, int co) {
+Tn BlockCtx::downsample(const Tn& x, int H, int W_, size_t wgt, size_t bias, int co, int pad_mode) {
   float* od = palloc((size_t)B * (H / 2) * (W_ / 2) * co);
   pf_conv_args a = conv_base(x.d, x.c, nullptr, 0, B, H, W_, 3, w(wgt), co, od);
-  a.stride = 2; a.bias = w(bias);
+  a.stride = 2; a.bias = w(bias); a.pad_mode = pad_mode;
   Tn ot;
   conv(a, &ot, true);
   return ot;
@@ -189,10 +191,10 @@ Tn BlockCtx::stem(const float* x_nchw, size_t wgt, size_t bias, int cin, int co,
   return ot;
 }
 
-void BlockCtx::head(const Tn& x, int H, int W_, int groups, size_t g, size_t b_, size_t wgt, size_t bias, int co, float* out_nchw) {
+void BlockCtx::head(const Tn& x, int H, int W_, int groups, size_t g, size_t b_, size_t wgt, size_t bias, int co, float* out_nchw, float eps) {
   treset();
   float* sc = talloc((size_t)B * x.c); float* sh = talloc((size_t)B * x.c);
-  gn(x, Tn{}, H * W_, groups, 1e-5f, g, b_, sc, sh);
+  gn(x, Tn{}, H * W_, groups, eps, g, b_, sc, sh);
   launch(PF_K_SMALL, 2.0 * B * H * W_ * 9.0 * x.c * co, [&] { return launch_conv_out(x.d, sc, sh, w(wgt), w(bias), out_nchw, B, x.c, co, H, W_, s); });
 }
 

@@ -46,6 +46,11 @@ PRESETS: Dict[str, Dict[str, Any]] = {
 }
 
 
+# params/autoencoder.yaml of the reference: the first-stage autoencoder's own file (no UNet keys), read by load_autoencoder_params
+AUTOENCODER_PARAMS: Dict[str, Any] = dict(model_name="autoencoder", in_channels=3, out_channels=3, z_channels=4, channels=64, n_res_blocks=2,
+                                          channel_multipliers=[1, 2, 4, 4], emb_channels=4)
+
+
 def preset(name: str) -> Params:
     if name not in PRESETS:
         raise KeyError(f"unknown params preset {name!r}; known: {sorted(PRESETS)}")
@@ -70,6 +75,24 @@ def load_params(path: str) -> Params:
     p.setdefault("cond_mode", "cond")
     p.setdefault("use_enc", True)
     p.setdefault("latent_scaling_factor", 0.18215)
+    return p
+
+
+def load_autoencoder_params(path: str) -> Params:
+    """``params/autoencoder.yaml`` (or a run's copy of it): the model-defining keys must be there, training keys are kept and ignored."""
+    if not os.path.exists(path):
+        raise FileNotFoundError(path)
+    with open(path) as f:
+        if path.endswith(".json"):
+            data = json.load(f)
+        else:
+            import yaml
+            data = yaml.safe_load(f)
+    p = Params(data)
+    for k in AUTOENCODER_PARAMS:
+        if k != "model_name" and k not in p:
+            raise KeyError(f"{path}: missing params key {k!r}")
+    p.setdefault("model_name", "autoencoder")
     return p
 
 

@@ -239,15 +239,16 @@ class UNetModel(ModelHandle):
 
 
 class LatentDiffusion:
-    """Mirror of ``stable_diffusion/latent_diffusion.py:LatentDiffusion`` without an autoencoder
-    (``inference_sdf.py:537`` passes ``autoencoder=None``)."""
+    """Mirror of ``stable_diffusion/latent_diffusion.py:LatentDiffusion``.  ``autoencoder``: None (``inference_sdf.py:537``, the
+    Polyffusion path: latents are the images) or an ``autoencoder.Autoencoder``, which ``autoencoder_encode`` / ``autoencoder_decode``
+    then call with ``latent_scaling_factor``."""
 
     def __init__(self, unet_model: UNetModel, autoencoder=None, latent_scaling_factor: float = 0.18215,
                  n_steps: int = 1000, linear_start: float = 0.00085, linear_end: float = 0.012):
-        if autoencoder is not None:
-            raise NotImplementedError("the Polyffusion path runs without a latent autoencoder")
+        if autoencoder is not None and not (hasattr(autoencoder, "encode_sample") and hasattr(autoencoder, "decode")):
+            raise TypeError("LatentDiffusion: autoencoder must be a polyffusion_amd.autoencoder.Autoencoder (or None)")
         self.eps_model = unet_model
-        self.first_stage_model = None
+        self.first_stage_model = autoencoder
         self.latent_scaling_factor = latent_scaling_factor
         self.n_steps = n_steps
         # sqrt-linear schedule computed in float64 then cast (latent_diffusion.py:90-103)
@@ -265,6 +266,20 @@ class LatentDiffusion:
 
     def eval(self):
         return self
+
+    def autoencoder_encode(self, image: torch.Tensor, noise: Optional[torch.Tensor] = None, seed: int = 0, stream_id: int = 0,
+                           offset: int = 0) -> torch.Tensor:
+        """``latent_scaling_factor * first_stage_model.encode(image).sample()`` (latent_diffusion.py:112-125); the image itself without
+        an autoencoder.  The sample's noise: as ``GaussianDistribution.sample``."""
+        if self.first_stage_model is None:
+            return image
+        return self.first_stage_model.encode_sample(image, self.latent_scaling_factor, noise, seed, stream_id, offset)[0]
+
+    def autoencoder_decode(self, z: torch.Tensor) -> torch.Tensor:
+        """``first_stage_model.decode(z / latent_scaling_factor)`` (latent_diffusion.py:127-136); ``z`` itself without an autoencoder."""
+        if self.first_stage_model is None:
+            return z
+        return self.first_stage_model.decode(z, self.latent_scaling_factor)
 
     supports_shared_x = True     # forward(..., shared_x=True): the guidance evaluation with its condition-independent prefix computed once
 

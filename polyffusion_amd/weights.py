@@ -143,3 +143,20 @@ def synth_polydis_state(seed: int = 0):
         for k, v in st.items():
             out[prefix + k] = v * np.float32(POLYDIS_MU_GAIN[prefix]) if prefix in POLYDIS_MU_GAIN and k == "linear_mu.weight" else v
     return out
+
+
+AUTOENCODER_BRANCH_GAIN = 0.5
+
+
+def synth_autoencoder_state(cfg, seed: int = 0) -> "OrderedDict[str, np.ndarray]":
+    """First-stage autoencoder tensors (autoencoder.AutoencoderConfig) keyed as the reference ``Autoencoder`` state_dict
+    (``encoder.conv_in.weight`` ...).  Every conv is drawn at 1 / sqrt(fan_in), which keeps a layer's output at its input's scale;
+    the convs that close a residual branch (``conv2`` of a ResnetBlock, ``proj_out`` of the AttnBlock) get AUTOENCODER_BRANCH_GAIN on
+    top, so each of the up to 15 blocks in a row adds a quarter of a unit of variance to the stream instead of a whole one and the
+    activations stay O(1) through the depth - which is what keeps an absolute tolerance on the outputs meaningful."""
+    from .autoencoder import autoencoder_param_shapes
+    out = synth_tensors(autoencoder_param_shapes(cfg), seed, "")
+    for k in out:
+        if k.endswith((".conv2.weight", ".proj_out.weight")):
+            out[k] = (out[k] * np.float32(AUTOENCODER_BRANCH_GAIN)).astype(np.float32)
+    return out
