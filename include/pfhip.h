@@ -150,40 +150,60 @@ int pf_unet_n_launches(const pf_unet* u, int batch, int n_cond);
  *   eps = e_uncond + scale * (e_cond - e_uncond), where eps2 = [e_uncond ; e_cond] (2n elements). */
 int pf_cfg_combine(const float* eps2, float scale, float* eps, size_t n, void* stream);
 
-/* One DDPM RePaint iteration (SDFSampler.paint body + p_sample, sampler_sdf.py:80-171,307-336):
- *   x0    = c_recip*x - c_recipm1*eps ; mean = c_x0*x0 + c_xt*x ; x_unkn = mean + sigma*noise_p
- *   x_kn  = sqrt_ab*orig + sqrt_1mab*noise_q          (skipped when orig == NULL)
- *   x_out = x_kn*mask + x_unkn*(1-mask)
- * noise_p / noise_q may be NULL (treated as zero: step 0).  x_out may alias x. */
+/* One reverse step of either sampler family as ONE elementwise kernel.  The caller zero-fills the struct and sets what it needs.
+ *   DDPM / RePaint (SDFSampler.paint body + p_sample, sampler_sdf.py:80-171,307-336):
+ *     x0    = c_recip*x - c_recipm1*eps ; mean = c_x0*x0 + c_xt*x ; x_unkn = mean + sigma*noise_p
+ *     x_kn  = sqrt_ab*orig + sqrt_1mab*noise_q          (skipped when orig == NULL)
+ *     x_out = x_kn*mask + x_unkn*(1-mask)
+ *   DDIM (DDIMSampler.get_x_prev_and_pred_x0 + paint blend, sampler_ddim.py:220-272,355-359):
+ *     pred_x0 = (x - s1m*eps)/sqrt_a ; x_prev = sqrt_aprev*pred_x0 + dir_coef*eps + sigma*noise
+ *     if orig: x_prev = (q_sqrt_a*orig + q_s1m*orig_noise)*mask + x_prev*(1-mask)
+ * Two independent choices:
+ *   coefficients - `coef` (host memory, copied at the call) or `table` + `state` (device memory: row state->index of a table with one
+ *     coefficient struct per step, what a captured step reads - see pf_step_state below).  Exactly one of the two.
+ *   noise - tensors (rng == 0; a NULL tensor means the term is absent: step 0, eta = 0), or drawn INSIDE the kernel (rng == 1): element i
+ *     of draw d is exactly what pf_randn(seed, d, elem_offset) writes at i, so the result is bit-identical to pf_randn + the tensor form,
+ *     without the noise tensors' round trip through HBM.  rng always adds the sigma term.  DDPM draws noise_q (draw_q) only with a known
+ *     region and noise_p (draw_p) always - the reference's order is q then p (sampler_sdf.py:317-321, 153-160); DDIM draws `draw`
+ *     (orig_noise stays a tensor: the reference's DDIM paint re-uses one fixed tensor).  With `state` the draw indices come from the
+ *     device: DDPM (q, p) = (state->draws, state->draws + 1), p = state->draws without a known region; DDIM draw = state->draws.
+ *     rng needs n and elem_offset to be multiples of 4 (one Philox call = 4 normals) and 16-byte aligned tensors. */
 typedef struct pf_ddpm_coef { float c_recip, c_recipm1, c_x0, c_xt, sigma, sqrt_ab, sqrt_1mab; } pf_ddpm_coef;
-int pf_ddpm_step(const float* x, const float* eps, const float* noise_p, const float* noise_q,
-                 const float* orig, const float* mask, const pf_ddpm_coef* c, float* x_out, size_t n, void* stream);
+typedef struct pf_ddim_coef { float s1m, sqrt_a, sqrt_aprev, dir_coef, sigma, q_sqrt_a, q_s1m; } pf_ddim_coef;
+typedef struct pf_step_state { int64_t index; uint64_t draws; } pf_step_state;
+typedef struct pf_ddpm_step_args {
+  const float *x, *eps;               /* [n] */
+  const float *orig, *mask;           /* known region: both or neither */
+  const float *noise_p, *noise_q;     /* noise tensors, NULL = no such term (rng == 0 only) */
+  int rng;                            /* 1: both draws made in the kernel; noise_p / noise_q must be NULL */
+  const pf_ddpm_coef* coef;           /* host coefficients, copied at the call ...            */
+  const pf_ddpm_coef* table;          /* ... or a device table, row state->index              */
+  const pf_step_state* state;         /* device step state: required with table; with rng it also supplies the draw indices */
+  uint64_t seed, draw_q, draw_p, elem_offset;   /* rng only; draw_* ignored when state is set */
+  float* x_out; size_t n;             /* x_out may alias x */
+} pf_ddpm_step_args;
+int pf_ddpm_step(const pf_ddpm_step_args* a, void* stream);
+typedef struct pf_ddim_step_args {
+  const float *x, *eps;               /* [n] */
+  const float *orig, *orig_noise, *mask;   /* known region: all three or none */
+  const float *noise;                 /* noise tensor, NULL = no sigma term (rng == 0 only) */
+  int rng;                            /* 1: the draw is made in the kernel; noise must be NULL */
+  const pf_ddim_coef* coef;           /* host coefficients, copied at the call ...            */
+  const pf_ddim_coef* table;          /* ... or a device table, row state->index              */
+  const pf_step_state* state;         /* device step state: required with table; with rng it also supplies the draw index */
+  uint64_t seed, draw, elem_offset;   /* rng only; draw ignored when state is set */
+  float* x_out; size_t n;             /* x_out may alias x */
+} pf_ddim_step_args;
+int pf_ddim_step(const pf_ddim_step_args* a, void* stream);
 
 /* RePaint re-noise between inner repeats (sampler_sdf.py:337-341; keeps the reference's beta-not-sqrt quirk):
  *   x_t = a*x + b*noise */
 int pf_axpby(const float* x, const float* noise, float a, float b, float* out, size_t n, void* stream);
 
-/* One DDIM iteration (DDIMSampler.get_x_prev_and_pred_x0 + paint blend, sampler_ddim.py:220-272,355-359):
- *   pred_x0 = (x - s1m*eps)/sqrt_a ; x_prev = sqrt_aprev*pred_x0 + dir_coef*eps + sigma*noise
- *   if orig: x_prev = (q_sqrt_a*orig + q_s1m*orig_noise)*mask + x_prev*(1-mask) */
-typedef struct pf_ddim_coef { float s1m, sqrt_a, sqrt_aprev, dir_coef, sigma, q_sqrt_a, q_s1m; } pf_ddim_coef;
-int pf_ddim_step(const float* x, const float* eps, const float* noise, const float* orig, const float* orig_noise,
-                 const float* mask, const pf_ddim_coef* c, float* x_out, size_t n, void* stream);
-
 /* Standard-normal noise, counter-based (Philox4x32-10 + Box-Muller), keyed by (seed, stream_id,
  * global element index) so results do not depend on how a batch is sharded over GPUs.
  * elem_offset = index of out[0] in the global (unsharded) tensor. */
 int pf_randn(float* out, size_t n, uint64_t seed, uint64_t stream_id, uint64_t elem_offset, void* stream);
-
-/* The same updates with the noise drawn INSIDE the kernel (no noise tensor in HBM, two launches per step less): element i of draw d is
- * exactly what pf_randn(seed, d, elem_offset) writes at i, so results are bit-identical to pf_randn + pf_ddpm_step / pf_ddim_step.
- * DDPM: noise_q = draw `draw_q` (only when orig != NULL), noise_p = draw `draw_p` - the reference's order is q then p
- * (sampler_sdf.py:317-321, 153-160).  DDIM: noise = draw `draw` (sigma != 0 steps only; orig_noise stays a tensor: the reference's DDIM
- * paint re-uses one fixed tensor, sampler_ddim.py:355-359).  n and elem_offset must be multiples of 4 (one Philox call = 4 normals). */
-int pf_ddpm_step_rng(const float* x, const float* eps, const float* orig, const float* mask, const pf_ddpm_coef* c,
-                     uint64_t seed, uint64_t draw_q, uint64_t draw_p, uint64_t elem_offset, float* x_out, size_t n, void* stream);
-int pf_ddim_step_rng(const float* x, const float* eps, const float* orig, const float* orig_noise, const float* mask, const pf_ddim_coef* c,
-                     uint64_t seed, uint64_t draw, uint64_t elem_offset, float* x_out, size_t n, void* stream);
 
 /* Measurement aid (bench.py): writes {shader-cycle counter, constant-rate reference counter} of the moment the probe kernel runs into
  * row x of out[8][2] for every XCD x (XCDs have counters and clocks of their own; rows of XCDs the part does not have stay
@@ -196,25 +216,13 @@ int pf_clock_probe(uint64_t* out8x2, void* stream);
 int pf_mfma_probe(float* sink, int iters, double* flops_out, void* stream);
 
 /* ---- replayable reverse step: everything that changes from one step to the next - the table row, the
- * time-step value fed to the denoiser, the noise draw counter - lives in a small device-resident state, so ONE captured
- * hipGraph of {begin, randn, pf_unet_forward, randn, step, end} is replayed for every step of the loop.  `table` is the
- * per-step coefficient table on the device (one pf_ddpm_coef / pf_ddim_coef per row), `time_steps` the DDIM tau table
- * (int32 per row; NULL: the row index itself is the time step, as in the DDPM sampler). */
-typedef struct pf_step_state { int64_t index; uint64_t draws; } pf_step_state;
+ * time-step value fed to the denoiser, the noise draw counter - lives in a small device-resident pf_step_state, so ONE captured
+ * hipGraph of {begin, pf_unet_forward, step, end} is replayed for every step of the loop (pf_ddpm_step / pf_ddim_step with `table` and
+ * `state`).  `time_steps` is the DDIM tau table (int32 per row; NULL: the row index itself is the time step, as in the DDPM sampler). */
 int pf_step_state_set(pf_step_state* dev_state, int64_t index, uint64_t draws, void* stream);
 int pf_step_begin(const pf_step_state* dev_state, const int32_t* time_steps, int64_t* t_out, int batch, void* stream);
 int pf_step_end(pf_step_state* dev_state, int draws_used, void* stream);          /* index -= 1; draws += draws_used */
 int pf_randn_dev(float* out, size_t n, uint64_t seed, const pf_step_state* dev_state, int slot, uint64_t elem_offset, void* stream);
-int pf_ddpm_step_dev(const float* x, const float* eps, const float* noise_p, const float* noise_q, const float* orig,
-                     const float* mask, const pf_ddpm_coef* table, const pf_step_state* dev_state, float* x_out, size_t n, void* stream);
-int pf_ddim_step_dev(const float* x, const float* eps, const float* noise, const float* orig, const float* orig_noise,
-                     const float* mask, const pf_ddim_coef* table, const pf_step_state* dev_state, float* x_out, size_t n, void* stream);
-/* in-kernel noise, draw indices from the device state: DDPM q = state.draws (orig != NULL only), p = the next one; DDIM = state.draws */
-int pf_ddpm_step_rng_dev(const float* x, const float* eps, const float* orig, const float* mask, const pf_ddpm_coef* table,
-                         const pf_step_state* dev_state, uint64_t seed, uint64_t elem_offset, float* x_out, size_t n, void* stream);
-int pf_ddim_step_rng_dev(const float* x, const float* eps, const float* orig, const float* orig_noise, const float* mask,
-                         const pf_ddim_coef* table, const pf_step_state* dev_state, uint64_t seed, uint64_t elem_offset, float* x_out,
-                         size_t n, void* stream);
 
 /* ---- weight broadcast over RCCL / xGMI.  The path has ONE exchange: rank 0 ships the packed weight
  * blob at start-up; the step loop has no collective.  librccl.so is opened on first use (dlopen), so a single-GPU process

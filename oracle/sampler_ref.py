@@ -141,6 +141,40 @@ class DDIMSamplerRef:
         return x
 
 
+def ddpm_update_f32(x, eps, coef, noise_p=None, noise_q=None, orig=None, mask=None):
+    """The library's DDPM / RePaint update (``ddpm_update_v`` of csrc/small_kernels.hip) in numpy float32: one rounded operation per
+    kernel operation, in the kernel's order.  The kernel issues one opaque VALU instruction per operation (no contraction), so for
+    inputs without subnormal intermediates this gives the same BITS.  ``coef``: the seven floats of ``pf_ddpm_coef`` in field order
+    (c_recip, c_recipm1, c_x0, c_xt, sigma, sqrt_ab, sqrt_1mab); arrays float32; ``None`` = the term is absent."""
+    c_recip, c_recipm1, c_x0, c_xt, sigma, sqrt_ab, sqrt_1mab = (np.float32(v) for v in coef)
+    x0 = c_recip * x - c_recipm1 * eps
+    xu = c_x0 * x0 + c_xt * x
+    if noise_p is not None:
+        xu = xu + sigma * noise_p
+    if orig is not None:
+        xk = sqrt_ab * orig
+        if noise_q is not None:
+            xk = xk + sqrt_1mab * noise_q
+        xu = xk * mask + xu * (np.float32(1.0) - mask)
+    assert xu.dtype == np.float32
+    return xu
+
+
+def ddim_update_f32(x, eps, coef, noise=None, orig=None, orig_noise=None, mask=None):
+    """The library's DDIM update (``ddim_update_v``) in numpy float32, as ``ddpm_update_f32``; the division is a float32 division.
+    ``coef``: ``pf_ddim_coef`` in field order (s1m, sqrt_a, sqrt_aprev, dir_coef, sigma, q_sqrt_a, q_s1m)."""
+    s1m, sqrt_a, sqrt_aprev, dir_coef, sigma, q_sqrt_a, q_s1m = (np.float32(v) for v in coef)
+    p0 = (x - s1m * eps) / sqrt_a
+    xp = sqrt_aprev * p0 + dir_coef * eps
+    if noise is not None:
+        xp = xp + sigma * noise
+    if orig is not None:
+        ot = q_sqrt_a * orig + q_s1m * orig_noise
+        xp = ot * mask + xp * (np.float32(1.0) - mask)
+    assert xp.dtype == np.float32
+    return xp
+
+
 def get_autoreg_data(data: torch.Tensor, split_dim: int = 1) -> torch.Tensor:
     """inference_sdf.py:121-129 - (second half, next item's first half)."""
     steps = data.shape[split_dim]

@@ -56,6 +56,21 @@ class DdimCoef(C.Structure):
     _fields_ = [(n, C.c_float) for n in ("s1m", "sqrt_a", "sqrt_aprev", "dir_coef", "sigma", "q_sqrt_a", "q_s1m")]
 
 
+_STEP_COMMON = [("rng", C.c_int), ("coef", C.c_void_p), ("table", C.c_void_p), ("state", C.c_void_p)]
+
+
+class DdpmStepArgs(C.Structure):
+    """pf_ddpm_step_args (include/pfhip.h); filled by ``_steps.ddpm_step`` only."""
+    _fields_ = ([(n, C.c_void_p) for n in ("x", "eps", "orig", "mask", "noise_p", "noise_q")] + _STEP_COMMON
+                + [(n, C.c_uint64) for n in ("seed", "draw_q", "draw_p", "elem_offset")] + [("x_out", C.c_void_p), ("n", C.c_size_t)])
+
+
+class DdimStepArgs(C.Structure):
+    """pf_ddim_step_args (include/pfhip.h); filled by ``_steps.ddim_step`` only."""
+    _fields_ = ([(n, C.c_void_p) for n in ("x", "eps", "orig", "orig_noise", "mask", "noise")] + _STEP_COMMON
+                + [(n, C.c_uint64) for n in ("seed", "draw", "elem_offset")] + [("x_out", C.c_void_p), ("n", C.c_size_t)])
+
+
 class UNetPrepared(C.Structure):
     """pf_unet_prepared (include/pfhip.h): the step-invariant prefix a sampler computes once per loop."""
     _fields_ = [("time_table", C.c_void_p), ("n_time_rows", C.c_int32), ("cross_bias", C.c_void_p)]
@@ -144,22 +159,16 @@ SIGNATURES = {
     "pf_unet_profile_read": (C.c_int, [C.c_void_p, C.POINTER(C.c_int), c_float_p, C.POINTER(C.c_double), C.c_int]),
     "pf_unet_n_launches": (C.c_int, [C.c_void_p, C.c_int, C.c_int]),
     "pf_cfg_combine": (C.c_int, [C.c_void_p, C.c_float, C.c_void_p, C.c_size_t, C.c_void_p]),
-    "pf_ddpm_step": (C.c_int, [C.c_void_p] * 6 + [C.POINTER(DdpmCoef), C.c_void_p, C.c_size_t, C.c_void_p]),
+    "pf_ddpm_step": (C.c_int, [C.POINTER(DdpmStepArgs), C.c_void_p]),
     "pf_axpby": (C.c_int, [C.c_void_p, C.c_void_p, C.c_float, C.c_float, C.c_void_p, C.c_size_t, C.c_void_p]),
-    "pf_ddim_step": (C.c_int, [C.c_void_p] * 6 + [C.POINTER(DdimCoef), C.c_void_p, C.c_size_t, C.c_void_p]),
+    "pf_ddim_step": (C.c_int, [C.POINTER(DdimStepArgs), C.c_void_p]),
     "pf_randn": (C.c_int, [C.c_void_p, C.c_size_t, C.c_uint64, C.c_uint64, C.c_uint64, C.c_void_p]),
-    "pf_ddpm_step_rng": (C.c_int, [C.c_void_p] * 4 + [C.POINTER(DdpmCoef), C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint64, C.c_void_p, C.c_size_t, C.c_void_p]),
-    "pf_ddim_step_rng": (C.c_int, [C.c_void_p] * 5 + [C.POINTER(DdimCoef), C.c_uint64, C.c_uint64, C.c_uint64, C.c_void_p, C.c_size_t, C.c_void_p]),
-    "pf_ddpm_step_rng_dev": (C.c_int, [C.c_void_p] * 6 + [C.c_uint64, C.c_uint64, C.c_void_p, C.c_size_t, C.c_void_p]),
-    "pf_ddim_step_rng_dev": (C.c_int, [C.c_void_p] * 7 + [C.c_uint64, C.c_uint64, C.c_void_p, C.c_size_t, C.c_void_p]),
     "pf_clock_probe": (C.c_int, [C.c_void_p, C.c_void_p]),
     "pf_mfma_probe": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_double), C.c_void_p]),
     "pf_step_state_set": (C.c_int, [C.c_void_p, C.c_int64, C.c_uint64, C.c_void_p]),
     "pf_step_begin": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
     "pf_step_end": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p]),
     "pf_randn_dev": (C.c_int, [C.c_void_p, C.c_size_t, C.c_uint64, C.c_void_p, C.c_int, C.c_uint64, C.c_void_p]),
-    "pf_ddpm_step_dev": (C.c_int, [C.c_void_p] * 6 + [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
-    "pf_ddim_step_dev": (C.c_int, [C.c_void_p] * 6 + [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "pf_comm_unique_id": (C.c_int, [C.c_void_p]),
     "pf_comm_init": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_void_p)]),
     "pf_comm_bcast": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p]),

@@ -23,7 +23,7 @@ using namespace pf;
 
 extern "C" {
 
-int pf_version(void) { return 100; }
+int pf_version(void) { return 101; }
 const char* pf_last_error(void) { return g_err.c_str(); }
 int pf_x3_element(void) {
 #ifdef PF_X3_F16
@@ -113,40 +113,17 @@ int pf_attention(const float* q, int ldq, const float* k, int ldk, const float* 
 }
 
 int pf_cfg_combine(const float* eps2, float scale, float* eps, size_t n, void* stream) { return launch_cfg_combine(eps2, scale, eps, n, (hipStream_t)stream); }
-int pf_ddpm_step(const float* x, const float* eps, const float* noise_p, const float* noise_q, const float* orig, const float* mask,
-                 const pf_ddpm_coef* c, float* x_out, size_t n, void* stream) {
-  PF_REQUIRE(c, "pf_ddpm_step: null coefficients");
-  return launch_ddpm_step(x, eps, noise_p, noise_q, orig, mask, *c, x_out, n, (hipStream_t)stream);
+int pf_ddpm_step(const pf_ddpm_step_args* a, void* stream) {
+  PF_REQUIRE(a, "pf_ddpm_step: null arguments");
+  return launch_ddpm_step(*a, (hipStream_t)stream);
+}
+int pf_ddim_step(const pf_ddim_step_args* a, void* stream) {
+  PF_REQUIRE(a, "pf_ddim_step: null arguments");
+  return launch_ddim_step(*a, (hipStream_t)stream);
 }
 int pf_axpby(const float* x, const float* noise, float a, float b, float* out, size_t n, void* stream) { return launch_axpby(x, noise, a, b, out, n, (hipStream_t)stream); }
-int pf_ddim_step(const float* x, const float* eps, const float* noise, const float* orig, const float* orig_noise, const float* mask,
-                 const pf_ddim_coef* c, float* x_out, size_t n, void* stream) {
-  PF_REQUIRE(c, "pf_ddim_step: null coefficients");
-  return launch_ddim_step(x, eps, noise, orig, orig_noise, mask, *c, x_out, n, (hipStream_t)stream);
-}
 int pf_randn(float* out, size_t n, uint64_t seed, uint64_t stream_id, uint64_t elem_offset, void* stream) {
   return launch_randn(out, n, seed, stream_id, elem_offset, (hipStream_t)stream);
-}
-int pf_ddpm_step_rng(const float* x, const float* eps, const float* orig, const float* mask, const pf_ddpm_coef* c, uint64_t seed,
-                     uint64_t draw_q, uint64_t draw_p, uint64_t elem_offset, float* x_out, size_t n, void* stream) {
-  PF_REQUIRE(c, "pf_ddpm_step_rng: null coefficients");
-  return launch_ddpm_step_rng(x, eps, orig, mask, c, nullptr, nullptr, seed, draw_q, draw_p, elem_offset, x_out, n, (hipStream_t)stream);
-}
-int pf_ddim_step_rng(const float* x, const float* eps, const float* orig, const float* orig_noise, const float* mask, const pf_ddim_coef* c,
-                     uint64_t seed, uint64_t draw, uint64_t elem_offset, float* x_out, size_t n, void* stream) {
-  PF_REQUIRE(c, "pf_ddim_step_rng: null coefficients");
-  return launch_ddim_step_rng(x, eps, orig, orig_noise, mask, c, nullptr, nullptr, seed, draw, elem_offset, x_out, n, (hipStream_t)stream);
-}
-int pf_ddpm_step_rng_dev(const float* x, const float* eps, const float* orig, const float* mask, const pf_ddpm_coef* table,
-                         const pf_step_state* st, uint64_t seed, uint64_t elem_offset, float* x_out, size_t n, void* stream) {
-  PF_REQUIRE(table && st, "pf_ddpm_step_rng_dev: null table / state");
-  return launch_ddpm_step_rng(x, eps, orig, mask, nullptr, table, st, seed, 0, 0, elem_offset, x_out, n, (hipStream_t)stream);
-}
-int pf_ddim_step_rng_dev(const float* x, const float* eps, const float* orig, const float* orig_noise, const float* mask,
-                         const pf_ddim_coef* table, const pf_step_state* st, uint64_t seed, uint64_t elem_offset, float* x_out, size_t n,
-                         void* stream) {
-  PF_REQUIRE(table && st, "pf_ddim_step_rng_dev: null table / state");
-  return launch_ddim_step_rng(x, eps, orig, orig_noise, mask, nullptr, table, st, seed, 0, elem_offset, x_out, n, (hipStream_t)stream);
 }
 int pf_mfma_probe(float* sink, int iters, double* flops_out, void* stream) { return launch_mfma_probe(sink, iters, flops_out, (hipStream_t)stream); }
 int pf_clock_probe(uint64_t* out2, void* stream) { return launch_clock_probe(reinterpret_cast<unsigned long long*>(out2), (hipStream_t)stream); }
@@ -157,14 +134,6 @@ int pf_step_begin(const pf_step_state* st, const int32_t* time_steps, int64_t* t
 int pf_step_end(pf_step_state* st, int draws_used, void* stream) { return launch_step_end(st, draws_used, (hipStream_t)stream); }
 int pf_randn_dev(float* out, size_t n, uint64_t seed, const pf_step_state* st, int slot, uint64_t elem_offset, void* stream) {
   return launch_randn_dev(out, n, seed, st, slot, elem_offset, (hipStream_t)stream);
-}
-int pf_ddpm_step_dev(const float* x, const float* eps, const float* noise_p, const float* noise_q, const float* orig, const float* mask,
-                     const pf_ddpm_coef* table, const pf_step_state* st, float* x_out, size_t n, void* stream) {
-  return launch_ddpm_step_dev(x, eps, noise_p, noise_q, orig, mask, table, st, x_out, n, (hipStream_t)stream);
-}
-int pf_ddim_step_dev(const float* x, const float* eps, const float* noise, const float* orig, const float* orig_noise, const float* mask,
-                     const pf_ddim_coef* table, const pf_step_state* st, float* x_out, size_t n, void* stream) {
-  return launch_ddim_step_dev(x, eps, noise, orig, orig_noise, mask, table, st, x_out, n, (hipStream_t)stream);
 }
 
 size_t pf_attention_wide_scratch_bytes(int batch, int l) { return (batch > 0 && l > 0) ? attention_wide_scratch_floats(batch, l) * sizeof(float) : 0; }

@@ -109,24 +109,12 @@ int launch_matvec_exp(const float* x, int ldx, const float* w, const float* bias
 
 // sampler elementwise kernels
 int launch_cfg_combine(const float* eps2, float scale, float* eps, size_t n, hipStream_t s);
-int launch_ddpm_step(const float* x, const float* eps, const float* noise_p, const float* noise_q, const float* orig,
-                     const float* mask, const pf_ddpm_coef& c, float* out, size_t n, hipStream_t s);
+// one reverse step per family: validates the arguments, then the tensor-noise or the in-kernel Philox kernel (include/pfhip.h)
+int launch_ddpm_step(const pf_ddpm_step_args& a, hipStream_t s);
+int launch_ddim_step(const pf_ddim_step_args& a, hipStream_t s);
 int launch_axpby(const float* x, const float* y, float a, float b, float* out, size_t n, hipStream_t s);
-int launch_ddim_step(const float* x, const float* eps, const float* noise, const float* orig, const float* orig_noise,
-                     const float* mask, const pf_ddim_coef& c, float* out, size_t n, hipStream_t s);
 int launch_randn(float* out, size_t n, uint64_t seed, uint64_t stream_id, uint64_t elem_offset, hipStream_t s);
 int launch_randn_dev(float* out, size_t n, uint64_t seed, const pf_step_state* st, int slot, uint64_t elem_offset, hipStream_t s);
-int launch_ddpm_step_dev(const float* x, const float* eps, const float* noise_p, const float* noise_q, const float* orig,
-                         const float* mask, const pf_ddpm_coef* table, const pf_step_state* st, float* out, size_t n, hipStream_t s);
-int launch_ddim_step_dev(const float* x, const float* eps, const float* noise, const float* orig, const float* orig_noise,
-                         const float* mask, const pf_ddim_coef* table, const pf_step_state* st, float* out, size_t n, hipStream_t s);
-// in-kernel Philox noise (draw indices by value, or - st != nullptr - from the device step state)
-int launch_ddpm_step_rng(const float* x, const float* eps, const float* orig, const float* mask, const pf_ddpm_coef* c_host,
-                         const pf_ddpm_coef* table, const pf_step_state* st, uint64_t seed, uint64_t draw_q, uint64_t draw_p, uint64_t off,
-                         float* out, size_t n, hipStream_t s);
-int launch_ddim_step_rng(const float* x, const float* eps, const float* orig, const float* orig_noise, const float* mask,
-                         const pf_ddim_coef* c_host, const pf_ddim_coef* table, const pf_step_state* st, uint64_t seed, uint64_t draw,
-                         uint64_t off, float* out, size_t n, hipStream_t s);
 int launch_clock_probe(unsigned long long* out2, hipStream_t s);
 int launch_mfma_probe(float* sink, int iters, double* flops, hipStream_t s);
 int launch_step_state_set(pf_step_state* st, int64_t index, uint64_t draws, hipStream_t s);

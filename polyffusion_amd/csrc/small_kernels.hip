@@ -478,33 +478,16 @@ __device__ __forceinline__ float ddpm_update(float xv, float ev, const float* np
   return ddpm_update_v(xv, ev, np != nullptr, np ? np[i] : 0.f, orig != nullptr, nq != nullptr, nq ? nq[i] : 0.f, orig ? orig[i] : 0.f,
                        orig ? mask[i] : 0.f, c);
 }
-__global__ void ddpm_step_kernel(const float* __restrict__ x, const float* __restrict__ eps, const float* __restrict__ np,
-                                 const float* __restrict__ nq, const float* __restrict__ orig, const float* __restrict__ mask,
-                                 pf_ddpm_coef c, float* __restrict__ out, size_t n) {
+// coefficients passed by value, or - table != nullptr - the row of a device table named by the device-resident step state (graph replay)
+template <class Coef>
+__device__ __forceinline__ Coef coef_of(const Coef& by_value, const Coef* table, const pf_step_state* st) { return table ? table[st->index] : by_value; }
+// noise from tensors.  x and out carry no __restrict__: x_out may alias x (the captured step updates x where it stands)
+__global__ void ddpm_step_kernel(const float* x, const float* __restrict__ eps, const float* __restrict__ np, const float* __restrict__ nq,
+                                 const float* __restrict__ orig, const float* __restrict__ mask, pf_ddpm_coef cv,
+                                 const pf_ddpm_coef* __restrict__ table, const pf_step_state* __restrict__ st, float* out, size_t n) {
+  const pf_ddpm_coef c = coef_of(cv, table, st);
   for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x)
     out[i] = ddpm_update(x[i], eps[i], np, nq, orig, mask, c, i);
-}
-// the same update with the coefficients read from a device table row named by the device-resident step state (graph replay)
-__global__ void ddpm_step_dev_kernel(const float* x, const float* __restrict__ eps, const float* __restrict__ np,
-                                     const float* __restrict__ nq, const float* __restrict__ orig, const float* __restrict__ mask,
-                                     const pf_ddpm_coef* __restrict__ table, const pf_step_state* __restrict__ st, float* out, size_t n) {
-  const pf_ddpm_coef c = table[st->index];
-  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x)
-    out[i] = ddpm_update(x[i], eps[i], np, nq, orig, mask, c, i);
-}
-int launch_ddpm_step_dev(const float* x, const float* eps, const float* noise_p, const float* noise_q, const float* orig,
-                         const float* mask, const pf_ddpm_coef* table, const pf_step_state* st, float* out, size_t n, hipStream_t s) {
-  PF_REQUIRE(x && eps && out && table && st && n > 0 && (!orig || mask), "ddpm_step_dev: bad arguments");
-  hipLaunchKernelGGL(ddpm_step_dev_kernel, ew_grid(n), dim3(256), 0, s, x, eps, noise_p, noise_q, orig, mask, table, st, out, n);
-  PF_CHECK_HIP(hipGetLastError());
-  return PF_OK;
-}
-int launch_ddpm_step(const float* x, const float* eps, const float* noise_p, const float* noise_q, const float* orig,
-                     const float* mask, const pf_ddpm_coef& c, float* out, size_t n, hipStream_t s) {
-  PF_REQUIRE(x && eps && out && n > 0 && (!orig || mask), "ddpm_step: bad arguments");
-  hipLaunchKernelGGL(ddpm_step_kernel, ew_grid(n), dim3(256), 0, s, x, eps, noise_p, noise_q, orig, mask, c, out, n);
-  PF_CHECK_HIP(hipGetLastError());
-  return PF_OK;
 }
 
 __global__ void axpby_kernel(const float* __restrict__ x, const float* __restrict__ y, float a, float b, float* __restrict__ out,
@@ -535,25 +518,12 @@ __device__ __forceinline__ float ddim_update(float xv, float e, const float* noi
   return ddim_update_v(xv, e, noise != nullptr, noise ? noise[i] : 0.f, orig != nullptr, orig ? orig[i] : 0.f, orig ? on[i] : 0.f,
                        orig ? mask[i] : 0.f, c);
 }
-__global__ void ddim_step_kernel(const float* __restrict__ x, const float* __restrict__ eps, const float* __restrict__ noise,
-                                 const float* __restrict__ orig, const float* __restrict__ on, const float* __restrict__ mask,
-                                 pf_ddim_coef c, float* __restrict__ out, size_t n) {
+__global__ void ddim_step_kernel(const float* x, const float* __restrict__ eps, const float* __restrict__ noise, const float* __restrict__ orig,
+                                 const float* __restrict__ on, const float* __restrict__ mask, pf_ddim_coef cv,
+                                 const pf_ddim_coef* __restrict__ table, const pf_step_state* __restrict__ st, float* out, size_t n) {
+  const pf_ddim_coef c = coef_of(cv, table, st);
   for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x)
     out[i] = ddim_update(x[i], eps[i], noise, orig, on, mask, c, i);
-}
-__global__ void ddim_step_dev_kernel(const float* x, const float* __restrict__ eps, const float* __restrict__ noise,
-                                     const float* __restrict__ orig, const float* __restrict__ on, const float* __restrict__ mask,
-                                     const pf_ddim_coef* __restrict__ table, const pf_step_state* __restrict__ st, float* out, size_t n) {
-  const pf_ddim_coef c = table[st->index];
-  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x)
-    out[i] = ddim_update(x[i], eps[i], noise, orig, on, mask, c, i);
-}
-int launch_ddim_step_dev(const float* x, const float* eps, const float* noise, const float* orig, const float* orig_noise,
-                         const float* mask, const pf_ddim_coef* table, const pf_step_state* st, float* out, size_t n, hipStream_t s) {
-  PF_REQUIRE(x && eps && out && table && st && n > 0 && (!orig || (mask && orig_noise)), "ddim_step_dev: bad arguments");
-  hipLaunchKernelGGL(ddim_step_dev_kernel, ew_grid(n), dim3(256), 0, s, x, eps, noise, orig, orig_noise, mask, table, st, out, n);
-  PF_CHECK_HIP(hipGetLastError());
-  return PF_OK;
 }
 // ---- device-resident step state: what changes from one reverse step to the next lives in device memory, so a captured
 // step (hipGraph) can be replayed unchanged
@@ -578,13 +548,6 @@ int launch_step_begin(const pf_step_state* st, const int* time_steps, int64_t* t
 int launch_step_end(pf_step_state* st, int draws_used, hipStream_t s) {
   PF_REQUIRE(st && draws_used >= 0, "step_end: bad arguments");
   hipLaunchKernelGGL(step_end_kernel, dim3(1), dim3(1), 0, s, st, draws_used);
-  PF_CHECK_HIP(hipGetLastError());
-  return PF_OK;
-}
-int launch_ddim_step(const float* x, const float* eps, const float* noise, const float* orig, const float* orig_noise,
-                     const float* mask, const pf_ddim_coef& c, float* out, size_t n, hipStream_t s) {
-  PF_REQUIRE(x && eps && out && n > 0 && (!orig || (mask && orig_noise)), "ddim_step: bad arguments");
-  hipLaunchKernelGGL(ddim_step_kernel, ew_grid(n), dim3(256), 0, s, x, eps, noise, orig, orig_noise, mask, c, out, n);
   PF_CHECK_HIP(hipGetLastError());
   return PF_OK;
 }
@@ -653,8 +616,6 @@ int launch_randn(float* out, size_t n, uint64_t seed, uint64_t stream_id, uint64
 // ---- the sampler updates with the noise drawn in the kernel: a thread owns the four elements of one Philox group, the draws are
 // philox_normal4 of (group, draw index, seed) - exactly what randn_kernel stores for that draw - and the update is ddpm_update /
 // ddim_update on those values: bit-identical to randn + step, without the noise tensors' round trip through HBM
-template <class Coef>
-__device__ __forceinline__ Coef coef_of(const Coef& by_value, const Coef* table, const pf_step_state* st) { return table ? table[st->index] : by_value; }
 __global__ void ddpm_step_rng_kernel(const float* x, const float* __restrict__ eps, const float* __restrict__ orig, const float* __restrict__ mask,
                                      pf_ddpm_coef cv, const pf_ddpm_coef* __restrict__ table, const pf_step_state* __restrict__ st, uint64_t seed,
                                      uint64_t draw_q, uint64_t draw_p, uint64_t off, float* out, size_t n) {
@@ -690,25 +651,41 @@ __global__ void ddim_step_rng_kernel(const float* x, const float* __restrict__ e
     *reinterpret_cast<f32x4*>(out + 4 * g) = o;
   }
 }
-int launch_ddpm_step_rng(const float* x, const float* eps, const float* orig, const float* mask, const pf_ddpm_coef* c_host,
-                         const pf_ddpm_coef* table, const pf_step_state* st, uint64_t seed, uint64_t draw_q, uint64_t draw_p, uint64_t off,
-                         float* out, size_t n, hipStream_t s) {
-  PF_REQUIRE(x && eps && out && n > 0 && (!orig || mask) && (c_host || (table && st)), "ddpm_step_rng: bad arguments");
-  PF_REQUIRE(n % 4 == 0 && off % 4 == 0, "ddpm_step_rng: n and elem_offset must be multiples of 4 (one Philox call yields four normals)");
-  PF_REQUIRE((((uintptr_t)x | (uintptr_t)eps | (uintptr_t)out | (uintptr_t)orig | (uintptr_t)mask) & 15) == 0, "ddpm_step_rng: tensors must be 16-byte aligned");
-  hipLaunchKernelGGL(ddpm_step_rng_kernel, ew_grid(n / 4), dim3(256), 0, s, x, eps, orig, mask, c_host ? *c_host : pf_ddpm_coef{}, c_host ? nullptr : table,
-                     c_host ? nullptr : st, seed, draw_q, draw_p, off, out, n);
+// one launcher per family: validate, then the tensor-noise or the in-kernel-noise kernel
+template <class Args>
+static int check_step_args(const Args& a, bool known_ok, bool any_noise, const char* name) {
+  PF_REQUIRE(a.x && a.eps && a.x_out && a.n > 0 && known_ok, "%s: bad arguments", name);
+  PF_REQUIRE(!(a.coef && (a.table || a.state)), "%s: coefficients both by value (coef) and from the device (table / state)", name);
+  PF_REQUIRE(a.coef || (a.table && a.state), "%s: null coefficients (set coef, or table and state)", name);
+  if (!a.rng) return PF_OK;
+  PF_REQUIRE(!any_noise, "%s_rng: the noise is drawn in the kernel, noise tensors must be NULL", name);
+  PF_REQUIRE(a.n % 4 == 0 && a.elem_offset % 4 == 0, "%s_rng: n and elem_offset must be multiples of 4 (one Philox call yields four normals)", name);
+  return PF_OK;
+}
+int launch_ddpm_step(const pf_ddpm_step_args& a, hipStream_t s) {
+  if (int rc = check_step_args(a, !a.orig || a.mask, a.noise_p || a.noise_q, "ddpm_step")) return rc;
+  const pf_ddpm_coef cv = a.coef ? *a.coef : pf_ddpm_coef{};
+  if (a.rng) {
+    PF_REQUIRE((((uintptr_t)a.x | (uintptr_t)a.eps | (uintptr_t)a.x_out | (uintptr_t)a.orig | (uintptr_t)a.mask) & 15) == 0, "ddpm_step_rng: tensors must be 16-byte aligned");
+    hipLaunchKernelGGL(ddpm_step_rng_kernel, ew_grid(a.n / 4), dim3(256), 0, s, a.x, a.eps, a.orig, a.mask, cv, a.table, a.state, a.seed, a.draw_q,
+                       a.draw_p, a.elem_offset, a.x_out, a.n);
+  } else {
+    hipLaunchKernelGGL(ddpm_step_kernel, ew_grid(a.n), dim3(256), 0, s, a.x, a.eps, a.noise_p, a.noise_q, a.orig, a.mask, cv, a.table, a.state, a.x_out, a.n);
+  }
   PF_CHECK_HIP(hipGetLastError());
   return PF_OK;
 }
-int launch_ddim_step_rng(const float* x, const float* eps, const float* orig, const float* orig_noise, const float* mask,
-                         const pf_ddim_coef* c_host, const pf_ddim_coef* table, const pf_step_state* st, uint64_t seed, uint64_t draw,
-                         uint64_t off, float* out, size_t n, hipStream_t s) {
-  PF_REQUIRE(x && eps && out && n > 0 && (!orig || (mask && orig_noise)) && (c_host || (table && st)), "ddim_step_rng: bad arguments");
-  PF_REQUIRE(n % 4 == 0 && off % 4 == 0, "ddim_step_rng: n and elem_offset must be multiples of 4 (one Philox call yields four normals)");
-  PF_REQUIRE((((uintptr_t)x | (uintptr_t)eps | (uintptr_t)out | (uintptr_t)orig | (uintptr_t)orig_noise | (uintptr_t)mask) & 15) == 0, "ddim_step_rng: tensors must be 16-byte aligned");
-  hipLaunchKernelGGL(ddim_step_rng_kernel, ew_grid(n / 4), dim3(256), 0, s, x, eps, orig, orig_noise, mask, c_host ? *c_host : pf_ddim_coef{},
-                     c_host ? nullptr : table, c_host ? nullptr : st, seed, draw, off, out, n);
+int launch_ddim_step(const pf_ddim_step_args& a, hipStream_t s) {
+  if (int rc = check_step_args(a, !a.orig || (a.mask && a.orig_noise), a.noise != nullptr, "ddim_step")) return rc;
+  const pf_ddim_coef cv = a.coef ? *a.coef : pf_ddim_coef{};
+  if (a.rng) {
+    PF_REQUIRE((((uintptr_t)a.x | (uintptr_t)a.eps | (uintptr_t)a.x_out | (uintptr_t)a.orig | (uintptr_t)a.orig_noise | (uintptr_t)a.mask) & 15) == 0,
+             "ddim_step_rng: tensors must be 16-byte aligned");
+    hipLaunchKernelGGL(ddim_step_rng_kernel, ew_grid(a.n / 4), dim3(256), 0, s, a.x, a.eps, a.orig, a.orig_noise, a.mask, cv, a.table, a.state, a.seed,
+                       a.draw, a.elem_offset, a.x_out, a.n);
+  } else {
+    hipLaunchKernelGGL(ddim_step_kernel, ew_grid(a.n), dim3(256), 0, s, a.x, a.eps, a.noise, a.orig, a.orig_noise, a.mask, cv, a.table, a.state, a.x_out, a.n);
+  }
   PF_CHECK_HIP(hipGetLastError());
   return PF_OK;
 }

@@ -2,9 +2,9 @@
 
 Mirrors ``ddpm/unet.py`` (``UNet``), ``ddpm/__init__.py`` (``DenoiseDiffusion``), ``models/model_ddpm.py`` (``load_trained``) and the
 ``Configs`` sampler of ``inference.py``.  The noise predictor is the ``pf_ddpm`` plan of ``libpfhip.so`` (``csrc/ddpm_unet.hip``);
-the reverse step is the library's ``pf_ddpm_step`` / ``pf_ddpm_step_rng`` kernel with ``c_x0 = 1, c_xt = 0, sigma = sqrt(beta)``,
-``q_sample`` its ``pf_axpby``.  PyTorch holds the buffers and builds the schedule tables on the host, in float32, as the reference
-does on the CPU.
+the reverse step is the library's ``pf_ddpm_step`` kernel with ``c_x0 = 1, c_xt = 0, sigma = sqrt(beta)``, ``q_sample`` its ``pf_axpby``
+(both launched through ``_steps``, which the SDF samplers share).  PyTorch holds the buffers and builds the schedule tables on the host,
+in float32, as the reference does on the CPU.
 
 The model's parameters (``params/ddpm.yaml``) live here as ``DDPM_PARAMS``, not in ``params.PRESETS``: that table feeds the SDF CLI.
 """
@@ -19,7 +19,7 @@ from typing import Callable, Mapping, Optional, Tuple
 import numpy as np
 import torch
 
-from . import _lib
+from . import _lib, _steps
 from ._handle import ModelHandle
 
 # params/ddpm.yaml of the reference (the keys the sampler reads)
@@ -191,24 +191,12 @@ class DenoiseDiffusion:
         self._lib = eps_model._lib
 
     def _randn(self, shape, device) -> torch.Tensor:
-        if self.noise_fn is not None:
-            return self.noise_fn(tuple(shape)).to(device=device, dtype=torch.float32).contiguous()
-        out = torch.empty(tuple(shape), dtype=torch.float32, device=device)
-        _lib.check(self._lib.pf_randn(out.data_ptr(), out.numel(), self.seed, self._draws, 0, _lib.current_stream()), "pf_randn", self._lib)
-        self._draws += 1
-        return out
+        return _steps.draw(self, shape, device)
 
     def q_sample(self, x0: torch.Tensor, t: int, eps: Optional[torch.Tensor] = None) -> torch.Tensor:
         """x_t = sqrt(alpha_bar_t) x0 + sqrt(1 - alpha_bar_t) eps (``q_xt_x0`` + ``q_sample``), one ``t`` for the whole batch."""
-        x0 = x0.contiguous().float()
-        if eps is None:
-            eps = self._randn(x0.shape, x0.device)
         ab = self.alpha_bar[t]
-        a, b = float(ab ** 0.5), float((1 - ab) ** 0.5)
-        out = torch.empty_like(x0)
-        _lib.check(self._lib.pf_axpby(x0.data_ptr(), eps.data_ptr(), a, b, out.data_ptr(), x0.numel(), _lib.current_stream()), "pf_axpby",
-                   self._lib)
-        return out
+        return _steps.q_sample(self, x0.contiguous().float(), eps, ab ** 0.5, (1 - ab) ** 0.5)
 
     def coef(self, t: int) -> "_lib.DdpmCoef":
         """``p_sample``'s mean = 1/sqrt(a) (x - (1-a)/sqrt(1-ab) eps), sigma = sqrt(beta) as the library's step coefficients."""
@@ -226,17 +214,11 @@ class DenoiseDiffusion:
         tt = torch.full((xt.shape[0],), int(t), dtype=torch.int64, device=xt.device)
         eps = self.eps_model(xt, tt)
         out = torch.empty_like(xt)
-        coef = self.coef(t)
-        stream = _lib.current_stream()
         if self.noise_fn is None:
-            _lib.check(self._lib.pf_ddpm_step_rng(xt.data_ptr(), eps.data_ptr(), None, None, C.byref(coef), self.seed, 0, self._draws, 0,
-                                                  out.data_ptr(), xt.numel(), stream), "pf_ddpm_step_rng", self._lib)
+            _steps.ddpm_step(self._lib, xt, eps, out, coef=self.coef(t), rng=(self.seed, 0, self._draws, 0))
             self._draws += 1
-        else:
-            z = self._randn(xt.shape, xt.device)
-            _lib.check(self._lib.pf_ddpm_step(xt.data_ptr(), eps.data_ptr(), z.data_ptr(), None, None, None, C.byref(coef), out.data_ptr(),
-                                              xt.numel(), stream), "pf_ddpm_step", self._lib)
-        return out
+            return out
+        return _steps.ddpm_step(self._lib, xt, eps, out, coef=self.coef(t), noise_p=self._randn(xt.shape, xt.device))
 
     def sample(self, n: int, init: Optional[torch.Tensor] = None, init_step: Optional[int] = None,
                callback: Optional[Callable[[int, int, torch.Tensor], None]] = None) -> torch.Tensor:

@@ -9,14 +9,14 @@
 Same method names and argument meaning as the reference, so ``Experiments.predict`` drives
 them unchanged.  Differences, all host-side plumbing:
   - per-step scalars are read from host tables and passed by value into ONE fused HIP kernel
-    per step (``pf_ddpm_step`` / ``pf_ddim_step``) instead of ~20 elementwise launches and five
-    device->host syncs per step;
+    per step (``pf_ddpm_step`` / ``pf_ddim_step``, launched through ``_steps`` - this module decides the route, ``_steps`` fills
+    the argument struct) instead of ~20 elementwise launches and five device->host syncs per step;
   - noise comes from ``noise_fn(shape)`` when given (parity tests inject the reference's noise
     tape) and otherwise from the counter-based on-device generator keyed by (seed, draw counter,
     global sample index), so a batch sharded over N GPUs draws the same noise per sample as the
     unsharded batch.  Inside the loops the draws happen IN the update kernel
-    (``pf_ddpm_step_rng`` / ``pf_ddim_step_rng``: bit-identical to ``pf_randn`` + step, two
-    launches and the noise tensors' HBM round trips less per step);
+    (the ``rng`` form of the step: bit-identical to ``pf_randn`` + step, two launches and the noise
+    tensors' HBM round trips less per step);
   - what the eps model computes from ``t`` and ``cond`` alone - the time MLP with every
     ResBlock's ``emb_layers`` and, for one context token, the whole cross-attention - is hoisted
     out of the loops: ``prepare()`` builds it once per ``paint()`` / ``sample()`` call and every
@@ -25,13 +25,12 @@ them unchanged.  Differences, all host-side plumbing:
 """
 from __future__ import annotations
 
-import ctypes as C
 from typing import Callable, List, Optional
 
 import numpy as np
 import torch
 
-from . import _lib
+from . import _lib, _steps
 from .unet import LatentDiffusion
 
 NoiseFn = Callable[[tuple], torch.Tensor]
@@ -140,16 +139,44 @@ class DiffusionSampler:
         restore()
         return g
 
+    def _replay_loop(self, family, inputs, table, taus, ndraw, n_noise, replays, t_start, uncond_scale, update):
+        """`replays` reverse steps from table row `t_start` down as replays of ONE captured step; returns the resulting x.  `inputs`: name ->
+        tensor or None (x, cond, uncond_cond, cond_concat and what `update` reads), `taus`: the device tau table (None: the row index is
+        the time step), `ndraw`: noise draws per step, `n_noise`: how many of them need a tensor (bufs["_noise"]; none when they are made in
+        the update kernel), `update(bufs, e_t, table, state)`: the family's in-place update of bufs["x"]."""
+        x = inputs["x"]
+        dev, B, st = x.device, x.shape[0], self._step_state(x.device)
+
+        def make_body(bf):
+            tb = bf["_t"] = torch.empty(B, dtype=torch.long, device=dev)
+            bf["_noise"] = [torch.empty_like(bf["x"]) for _ in range(n_noise)]
+
+            def body():
+                _lib.check(self._lib.pf_step_begin(st.data_ptr(), _lib.ptr(taus), tb.data_ptr(), B, _lib.current_stream()), "pf_step_begin")
+                xin = bf["x"] if bf["cond_concat"] is None else torch.cat([bf["x"], bf["cond_concat"]], dim=1)
+                e_t = self.get_eps(xin, tb, bf["cond"], uncond_scale=uncond_scale, uncond_cond=bf["uncond_cond"], prep=bf["_prep"])
+                update(bf, e_t, table, st)
+                _lib.check(self._lib.pf_step_end(st.data_ptr(), ndraw, _lib.current_stream()), "pf_step_end")
+            return body
+
+        key = (family, str(dev), float(uncond_scale), self.seed, self._elem_offset(x.shape), ndraw) + self._shape_key(**inputs)
+        ent = self._graph_for(key, inputs, make_body, lambda: self._set_state(st, t_start), uncond_scale)
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(replays):
+            ent["g"].replay()
+        e1.record()
+        self.last_replay = (e0, e1, replays)     # bench.py reads the per-step replay time from these events
+        self._draws += ndraw * replays
+        return ent["bufs"]["x"].clone()   # the static buffer is overwritten by the next paint() with these shapes
+
     # ---- noise ------------------------------------------------------------------------------------
+    def _elem_offset(self, shape) -> int:
+        """Index of this rank's first element of a [B, ...] tensor in the unsharded one."""
+        return self.sample_offset * int(np.prod(shape[1:]))
+
     def randn(self, shape, device) -> torch.Tensor:
-        if self.noise_fn is not None:
-            return self.noise_fn(tuple(shape)).to(device=device, dtype=torch.float32).contiguous()
-        out = torch.empty(tuple(shape), dtype=torch.float32, device=device)
-        per_sample = int(np.prod(shape[1:]))
-        _lib.check(self._lib.pf_randn(out.data_ptr(), out.numel(), self.seed, self._draws,
-                                      self.sample_offset * per_sample, _lib.current_stream()), "pf_randn")
-        self._draws += 1
-        return out
+        return _steps.draw(self, shape, device, self._elem_offset(shape))
 
     # ---- the step-invariant prefix of the eps model, hoisted out of the loops ------------------------------
     def prepare(self, cond: torch.Tensor, *, uncond_scale: float = 1.0, uncond_cond: Optional[torch.Tensor] = None,
@@ -215,8 +242,7 @@ class DiffusionSampler:
         update kernel reads as 16-byte vectors (x and, when present, orig / orig_noise / mask) 16-byte aligned - anything else takes
         the randn() + step path, which reads 4-byte elements.  BOTH paths read their tensors as dense buffers through raw pointers: the
         callers (``_step``, ``repaint_step``, ``p_sample``) make every tensor contiguous before they get here."""
-        per_sample = x.numel() // x.shape[0]
-        if self.noise_fn is not None or x.numel() % 4 != 0 or (self.sample_offset * per_sample) % 4 != 0:
+        if self.noise_fn is not None or x.numel() % 4 != 0 or self._elem_offset(x.shape) % 4 != 0:
             return False
         return all(v is None or (v.is_contiguous() and v.data_ptr() % 16 == 0) for v in (x,) + others)
 
@@ -249,49 +275,20 @@ class SDFSampler(DiffusionSampler):
 
     def _paint_graph(self, x, cond, t_start, orig, mask, uncond_scale, uncond_cond, cond_concat):
         """Steps t_start .. 1 as replays of one captured step; returns x_1 (the caller runs step 0, which draws no noise)."""
-        lib, dev, B, n = self._lib, x.device, x.shape[0], x.numel()
-        table, st = self._coef_table(dev), self._step_state(dev)
-        off = self.sample_offset * (n // B)
+        lib, off, rng = self._lib, self._elem_offset(x.shape), self._rng_ok(x)
         ndraw = 2 if orig is not None else 1
+
+        def update(bf, e_t, table, st):
+            xb, known = bf["x"], dict(orig=bf["orig"], mask=bf["mask"])
+            if rng:   # both draws inside the update kernel (draw order of the reference: known-region noise, then the p_sample noise)
+                _steps.ddpm_step(lib, xb, e_t, xb, table=table, state=st, rng=(self.seed, 0, 0, off), **known)
+                return
+            nq = None if orig is None else _steps.randn_dev(lib, bf["_noise"][0], self.seed, st, 0, off)
+            npz = _steps.randn_dev(lib, bf["_noise"][-1], self.seed, st, ndraw - 1, off)
+            _steps.ddpm_step(lib, xb, e_t, xb, table=table, state=st, noise_p=npz, noise_q=nq, **known)
+
         inputs = dict(x=x, cond=cond, orig=orig, mask=mask, uncond_cond=uncond_cond, cond_concat=cond_concat)
-
-        rng = self._rng_ok(x)
-
-        def make_body(bf):
-            xb, tb = bf["x"], torch.empty(B, dtype=torch.long, device=dev)
-            npz = None if rng else torch.empty_like(xb)
-            nq = torch.empty_like(xb) if (bf["orig"] is not None and not rng) else None
-            bf["_keep"] = (tb, npz, nq)
-
-            def body():
-                stream = _lib.current_stream()
-                _lib.check(lib.pf_step_begin(st.data_ptr(), None, tb.data_ptr(), B, stream), "pf_step_begin")
-                xin = xb if bf["cond_concat"] is None else torch.cat([xb, bf["cond_concat"]], dim=1)
-                e_t = self.get_eps(xin, tb, bf["cond"], uncond_scale=uncond_scale, uncond_cond=bf["uncond_cond"], prep=bf["_prep"])
-                if rng:   # both draws inside the update kernel (draw order of the reference: known-region noise, then the p_sample noise)
-                    _lib.check(lib.pf_ddpm_step_rng_dev(xb.data_ptr(), e_t.data_ptr(), _lib.ptr(bf["orig"]), _lib.ptr(bf["mask"]), table.data_ptr(),
-                                                        st.data_ptr(), self.seed, off, xb.data_ptr(), n, stream), "pf_ddpm_step_rng_dev")
-                else:
-                    if nq is not None:
-                        _lib.check(lib.pf_randn_dev(nq.data_ptr(), n, self.seed, st.data_ptr(), 0, off, stream), "pf_randn_dev")
-                    _lib.check(lib.pf_randn_dev(npz.data_ptr(), n, self.seed, st.data_ptr(), ndraw - 1, off, stream), "pf_randn_dev")
-                    _lib.check(lib.pf_ddpm_step_dev(xb.data_ptr(), e_t.data_ptr(), npz.data_ptr(), _lib.ptr(nq), _lib.ptr(bf["orig"]),
-                                                    _lib.ptr(bf["mask"]), table.data_ptr(), st.data_ptr(), xb.data_ptr(), n, stream),
-                               "pf_ddpm_step_dev")
-                _lib.check(lib.pf_step_end(st.data_ptr(), ndraw, stream), "pf_step_end")
-            return body
-
-        key = ("ddpm", str(dev), float(uncond_scale), self.seed, off) + self._shape_key(**inputs)
-        ent = self._graph_for(key, inputs, make_body, lambda: self._set_state(st, t_start), uncond_scale)
-        g = ent["g"]
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        for _ in range(t_start):
-            g.replay()
-        e1.record()
-        self.last_replay = (e0, e1, t_start)     # bench.py reads the per-step replay time from these events
-        self._draws += ndraw * t_start
-        return ent["bufs"]["x"].clone()   # the static buffer is overwritten by the next paint() with these shapes
+        return self._replay_loop("ddpm", inputs, self._coef_table(x.device), None, ndraw, 0 if rng else ndraw, t_start, t_start, uncond_scale, update)
 
     def _coef(self, step: int) -> _lib.DdpmCoef:
         return _lib.DdpmCoef(float(self.sqrt_recip_alpha_bar[step]), float(self.sqrt_recip_m1_alpha_bar[step]),
@@ -310,11 +307,8 @@ class SDFSampler(DiffusionSampler):
         coef = self._coef(step)
         x_prev = torch.empty_like(x)
         if step != 0 and not repeat_noise and temperature == 1.0 and self._rng_ok(x):
-            # the draw happens inside the update kernel: same values as randn() + pf_ddpm_step, one launch
-            per_sample = x.numel() // x.shape[0]
-            _lib.check(self._lib.pf_ddpm_step_rng(x.data_ptr(), e_t.data_ptr(), None, None, C.byref(coef), self.seed, 0, self._draws,
-                                                  self.sample_offset * per_sample, x_prev.data_ptr(), x.numel(), _lib.current_stream()),
-                       "pf_ddpm_step_rng")
+            # the draw happens inside the update kernel: same values as randn() + the tensor form, one launch
+            _steps.ddpm_step(self._lib, x, e_t, x_prev, coef=coef, rng=(self.seed, 0, self._draws, self._elem_offset(x.shape)))
             self._draws += 1
             x0 = (coef.c_recip * x - coef.c_recipm1 * e_t) if return_x0 else None
             return x_prev, x0, e_t
@@ -325,20 +319,13 @@ class SDFSampler(DiffusionSampler):
                 noise = noise.expand_as(x).contiguous()
             if temperature != 1.0:
                 noise = noise * temperature
-        _lib.check(self._lib.pf_ddpm_step(x.data_ptr(), e_t.data_ptr(), _lib.ptr(noise), None, None, None, C.byref(coef),
-                                          x_prev.data_ptr(), x.numel(), _lib.current_stream()), "pf_ddpm_step")
+        _steps.ddpm_step(self._lib, x, e_t, x_prev, coef=coef, noise_p=noise)
         x0 = (coef.c_recip * x - coef.c_recipm1 * e_t) if return_x0 else None
         return x_prev, x0, e_t
 
     @torch.no_grad()
     def q_sample(self, x0: torch.Tensor, index: int, noise: Optional[torch.Tensor] = None):
-        if noise is None:
-            noise = self.randn(x0.shape, x0.device)
-        out = torch.empty_like(x0)
-        _lib.check(self._lib.pf_axpby(x0.contiguous().data_ptr(), noise.contiguous().data_ptr(),
-                                      float(self.sqrt_alpha_bar[index]), float(self.sqrt_1m_alpha_bar[index]),
-                                      out.data_ptr(), out.numel(), _lib.current_stream()), "pf_axpby")
-        return out
+        return _steps.q_sample(self, x0, noise, self.sqrt_alpha_bar[index], self.sqrt_1m_alpha_bar[index], self._elem_offset(x0.shape))
 
     @torch.no_grad()
     def sample(self, shape: List[int], cond, repeat_noise=False, temperature=1.0, x_last=None, uncond_scale=1.0,
@@ -356,35 +343,30 @@ class SDFSampler(DiffusionSampler):
         region, the forward-noised known region, the blend.  Two noise draws for step > 0 - known-region noise first, then the
         ``p_sample`` noise, the reference's order - made inside the update kernel when the on-device generator is in use.
         ``bench.py`` times exactly this method."""
-        lib, step, n = self._lib, int(step), x_t.numel()
+        lib, step = self._lib, int(step)
         coef = self._coef(step)
         x_t, orig, mask = x_t.contiguous(), orig.contiguous(), mask.contiguous()     # the update kernels read dense buffers
         e_t = self._eps(x_t, cond, step, uncond_scale, uncond_cond, cond_concat, prep)
         x = torch.empty_like(x_t)
         if step > 0 and self._rng_ok(x_t, orig, mask):
-            _lib.check(lib.pf_ddpm_step_rng(x_t.data_ptr(), e_t.data_ptr(), orig.data_ptr(), mask.data_ptr(), C.byref(coef), self.seed,
-                                            self._draws, self._draws + 1, self.sample_offset * (n // x_t.shape[0]), x.data_ptr(), n,
-                                            _lib.current_stream()), "pf_ddpm_step_rng")
+            _steps.ddpm_step(lib, x_t, e_t, x, coef=coef, orig=orig, mask=mask,
+                             rng=(self.seed, self._draws, self._draws + 1, self._elem_offset(x_t.shape)))
             self._draws += 2
             return x
         # injected noise tape (parity tests) / step 0: the draws are tensors.  The tape's order is the reference's: q before the eps
         # evaluation, p after it - randn() only counts draws, so drawing both here keeps the tape aligned
         noise_q = self.randn(orig.shape, x_t.device) if step > 0 else None
         noise_p = self.randn(x_t.shape, x_t.device) if step > 0 else None
-        _lib.check(lib.pf_ddpm_step(x_t.data_ptr(), e_t.data_ptr(), _lib.ptr(noise_p), _lib.ptr(noise_q), orig.data_ptr(), mask.data_ptr(),
-                                    C.byref(coef), x.data_ptr(), n, _lib.current_stream()), "pf_ddpm_step")
-        return x
+        return _steps.ddpm_step(lib, x_t, e_t, x, coef=coef, noise_p=noise_p, noise_q=noise_q, orig=orig, mask=mask)
 
     @torch.no_grad()
     def paint(self, x, cond, t_start: int, orig=None, mask=None, orig_noise=None, uncond_scale: float = 1.0,
               uncond_cond=None, cond_concat=None, repaint_n: int = 1):
         """RePaint-style loop.  ``orig_noise`` is ignored exactly like the reference (fresh noise per step)."""
-        lib, stream = self._lib, _lib.current_stream
         x = x.contiguous()
         if orig is not None:
             assert mask is not None
             orig, mask = orig.contiguous().float(), mask.contiguous().float()
-        n = x.numel()
         steps = np.flip(self.time_steps[: t_start + 1])
         if self.graph and self.noise_fn is None and repaint_n == 1 and t_start >= 1 and self.on_step is None:
             x = self._paint_graph(x, cond, int(t_start), orig, mask, uncond_scale, uncond_cond, cond_concat)
@@ -406,9 +388,7 @@ class SDFSampler(DiffusionSampler):
                 if u < repaint_n - 1 and step > 0:
                     noise = self.randn(orig.shape, x.device)
                     b = self.model.beta[step - 1]
-                    x_t = torch.empty_like(x)
-                    _lib.check(lib.pf_axpby(x.data_ptr(), noise.data_ptr(), float((1 - b) ** 0.5), float(b),
-                                            x_t.data_ptr(), n, stream()), "pf_axpby")
+                    x_t = _steps.axpby(self._lib, x, noise, (1 - b) ** 0.5, b)
             if self.on_step is not None:
                 self.on_step(step, x)
         return x
@@ -447,48 +427,20 @@ class DDIMSampler(DiffusionSampler):
     def _paint_graph(self, x, cond, t_start, orig, mask, orig_noise, uncond_scale, uncond_cond, cond_concat, noisy: bool):
         """All t_start+1 steps of a DDIM loop as replays of one captured step.  ``noisy``: every step of the range has sigma != 0
         (eta > 0) and draws one noise tensor, in the eager loop's draw order; otherwise (eta = 0) no step draws."""
-        lib, dev, B, n = self._lib, x.device, x.shape[0], x.numel()
-        (table, taus), st = self._coef_table(dev), self._step_state(dev)
-        off = self.sample_offset * (n // B)
-        inputs = dict(x=x, cond=cond, orig=orig, mask=mask, orig_noise=orig_noise, uncond_cond=uncond_cond, cond_concat=cond_concat)
-
+        lib, off = self._lib, self._elem_offset(x.shape)
         rng = noisy and self._rng_ok(x)
 
-        def make_body(bf):
-            xb, tb = bf["x"], torch.empty(B, dtype=torch.long, device=dev)
-            nz = torch.empty_like(xb) if (noisy and not rng) else None
-            bf["_keep"] = (tb, nz)
+        def update(bf, e_t, table, st):
+            xb, known = bf["x"], dict(orig=bf["orig"], orig_noise=bf["orig_noise"], mask=bf["mask"])
+            if rng:
+                _steps.ddim_step(lib, xb, e_t, xb, table=table, state=st, rng=(self.seed, 0, off), **known)
+                return
+            nz = _steps.randn_dev(lib, bf["_noise"][0], self.seed, st, 0, off) if noisy else None
+            _steps.ddim_step(lib, xb, e_t, xb, table=table, state=st, noise=nz, **known)
 
-            def body():
-                stream = _lib.current_stream()
-                _lib.check(lib.pf_step_begin(st.data_ptr(), taus.data_ptr(), tb.data_ptr(), B, stream), "pf_step_begin")
-                xin = xb if bf["cond_concat"] is None else torch.cat([xb, bf["cond_concat"]], dim=1)
-                e_t = self.get_eps(xin, tb, bf["cond"], uncond_scale=uncond_scale, uncond_cond=bf["uncond_cond"], prep=bf["_prep"])
-                if rng:
-                    _lib.check(lib.pf_ddim_step_rng_dev(xb.data_ptr(), e_t.data_ptr(), _lib.ptr(bf["orig"]), _lib.ptr(bf["orig_noise"]),
-                                                        _lib.ptr(bf["mask"]), table.data_ptr(), st.data_ptr(), self.seed, off, xb.data_ptr(), n,
-                                                        stream), "pf_ddim_step_rng_dev")
-                else:
-                    if noisy:
-                        _lib.check(lib.pf_randn_dev(nz.data_ptr(), n, self.seed, st.data_ptr(), 0, off, stream), "pf_randn_dev")
-                    _lib.check(lib.pf_ddim_step_dev(xb.data_ptr(), e_t.data_ptr(), _lib.ptr(nz), _lib.ptr(bf["orig"]), _lib.ptr(bf["orig_noise"]),
-                                                    _lib.ptr(bf["mask"]), table.data_ptr(), st.data_ptr(), xb.data_ptr(), n, stream),
-                               "pf_ddim_step_dev")
-                _lib.check(lib.pf_step_end(st.data_ptr(), 1 if noisy else 0, stream), "pf_step_end")
-            return body
-
-        key = ("ddim", str(dev), float(uncond_scale), self.seed, off, bool(noisy)) + self._shape_key(**inputs)
-        ent = self._graph_for(key, inputs, make_body, lambda: self._set_state(st, t_start), uncond_scale)
-        g = ent["g"]
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        for _ in range(t_start + 1):
-            g.replay()
-        e1.record()
-        self.last_replay = (e0, e1, t_start + 1)
-        if noisy:
-            self._draws += t_start + 1
-        return ent["bufs"]["x"].clone()   # the static buffer is overwritten by the next paint() with these shapes
+        inputs = dict(x=x, cond=cond, orig=orig, mask=mask, orig_noise=orig_noise, uncond_cond=uncond_cond, cond_concat=cond_concat)
+        table, taus = self._coef_table(x.device)
+        return self._replay_loop("ddim", inputs, table, taus, int(noisy), int(noisy and not rng), t_start + 1, t_start, uncond_scale, update)
 
     def _coef(self, index: int) -> _lib.DdimCoef:
         a, ap, sg = self.ddim_alpha[index], self.ddim_alpha_prev[index], self.ddim_sigma[index]
@@ -504,15 +456,14 @@ class DDIMSampler(DiffusionSampler):
         orig, orig_noise, mask = (None if v is None else v.contiguous() for v in (orig, orig_noise, mask))
         noisy = float(self.ddim_sigma[index]) != 0.0
         if noisy and not repeat_noise and temperature == 1.0 and self._rng_ok(x, e_t, orig, orig_noise, mask):
-            # the step's draw happens inside the update kernel (same values as randn() + pf_ddim_step)
+            # the step's draw happens inside the update kernel (same values as randn() + the tensor form)
             draw = self._draws
             self._draws += 1
             if orig is not None and orig_noise is None:   # reference: a fresh q_sample noise per step, drawn after p_sample's
                 orig_noise = self.randn(orig.shape, x.device)
             out = torch.empty_like(x)
-            _lib.check(self._lib.pf_ddim_step_rng(x.data_ptr(), e_t.data_ptr(), _lib.ptr(orig), _lib.ptr(orig_noise), _lib.ptr(mask),
-                                                  C.byref(coef), self.seed, draw, self.sample_offset * (x.numel() // x.shape[0]),
-                                                  out.data_ptr(), x.numel(), _lib.current_stream()), "pf_ddim_step_rng")
+            _steps.ddim_step(self._lib, x, e_t, out, coef=coef, rng=(self.seed, draw, self._elem_offset(x.shape)),
+                             orig=orig, orig_noise=orig_noise, mask=mask)
             return out, coef
         if noisy:
             noise = self.randn((1, *x.shape[1:]) if repeat_noise else x.shape, x.device)
@@ -524,10 +475,7 @@ class DDIMSampler(DiffusionSampler):
             # reference: q_sample(orig, index, noise=None) draws randn_like per step, after p_sample's draw (sampler_ddim.py:355-359)
             orig_noise = self.randn(orig.shape, x.device)
         out = torch.empty_like(x)
-        _lib.check(self._lib.pf_ddim_step(x.data_ptr(), e_t.data_ptr(), _lib.ptr(noise), _lib.ptr(orig), _lib.ptr(orig_noise),
-                                          _lib.ptr(mask), C.byref(coef), out.data_ptr(), x.numel(), _lib.current_stream()),
-                   "pf_ddim_step")
-        return out, coef
+        return _steps.ddim_step(self._lib, x, e_t, out, coef=coef, noise=noise, orig=orig, orig_noise=orig_noise, mask=mask), coef
 
     @torch.no_grad()
     def get_x_prev_and_pred_x0(self, e_t, index: int, x, *, temperature: float = 1.0, repeat_noise: bool = False):
@@ -544,13 +492,7 @@ class DDIMSampler(DiffusionSampler):
 
     @torch.no_grad()
     def q_sample(self, x0, index: int, noise=None):
-        if noise is None:
-            noise = self.randn(x0.shape, x0.device)
-        out = torch.empty_like(x0)
-        _lib.check(self._lib.pf_axpby(x0.contiguous().data_ptr(), noise.contiguous().data_ptr(),
-                                      float(self.ddim_alpha_sqrt[index]), float(self.ddim_sqrt_one_minus_alpha[index]),
-                                      out.data_ptr(), out.numel(), _lib.current_stream()), "pf_axpby")
-        return out
+        return _steps.q_sample(self, x0, noise, self.ddim_alpha_sqrt[index], self.ddim_sqrt_one_minus_alpha[index], self._elem_offset(x0.shape))
 
     @torch.no_grad()
     def sample(self, shape, cond, repeat_noise=False, temperature=1.0, x_last=None, uncond_scale=1.0, uncond_cond=None,

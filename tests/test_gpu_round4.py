@@ -1,6 +1,6 @@
 """Round-4 additions (-m gpu): the hoisted step-invariant prefix (pf_unet_prepare_time / pf_unet_prepare_cond /
-pf_unet_forward_prepared), the update kernels that draw their noise themselves (pf_ddpm_step_rng / pf_ddim_step_rng and the
-device-state forms), the per-handle plan options (pf_unet_set_option), the 16x16-pixel conv tile at op level, and BASELINE
+pf_unet_forward_prepared), the update kernels that draw their noise themselves (the rng form of pf_ddpm_step / pf_ddim_step, with host
+coefficients and with the device table + state), the per-handle plan options (pf_unet_set_option), the 16x16-pixel conv tile at op level, and BASELINE
 configs[1] / configs[2] checked against the CPU oracle on ALL samples (configs[2]: a first / middle / last subset)."""
 import ctypes as C
 
@@ -12,7 +12,7 @@ import torch.nn.functional as F
 pytestmark = pytest.mark.gpu
 
 from oracle import sampler_ref, unet_ref  # noqa: E402
-from polyffusion_amd import _lib, synth  # noqa: E402
+from polyffusion_amd import _lib, _steps, synth  # noqa: E402
 from polyffusion_amd.arch import UNetConfig  # noqa: E402
 from polyffusion_amd.inference_sdf import synthetic_model  # noqa: E402
 from polyffusion_amd.params import preset  # noqa: E402
@@ -128,34 +128,25 @@ def test_ddpm_step_rng_equals_randn_plus_step(lib, with_orig):
     n, seed, off, dq, dp = 16 * 2 * 128 * 128, 1234, 3 * 32768, 40, 41
     g = torch.Generator().manual_seed(1)
     x, eps = torch.randn(n, generator=g).cuda(), torch.randn(n, generator=g).cuda()
-    orig = torch.randn(n, generator=g).cuda() if with_orig else None
-    mask = (torch.rand(n, generator=g) > 0.3).float().cuda() if with_orig else None
+    known = dict(orig=torch.randn(n, generator=g).cuda(), mask=(torch.rand(n, generator=g) > 0.3).float().cuda()) if with_orig else {}
     coef = _lib.DdpmCoef(1.3, 0.7, 0.2, 0.8, 0.05, 0.9, 0.43)
-    st = _lib.current_stream()
-    nq, npz = torch.empty(n, device="cuda"), torch.empty(n, device="cuda")
-    _lib.check(lib.pf_randn(nq.data_ptr(), n, seed, dq, off, st))
-    _lib.check(lib.pf_randn(npz.data_ptr(), n, seed, dp, off, st))
-    ref = torch.empty(n, device="cuda")
-    _lib.check(lib.pf_ddpm_step(x.data_ptr(), eps.data_ptr(), npz.data_ptr(), nq.data_ptr() if with_orig else None, _lib.ptr(orig), _lib.ptr(mask),
-                                C.byref(coef), ref.data_ptr(), n, st))
-    out = torch.empty(n, device="cuda")
-    _lib.check(lib.pf_ddpm_step_rng(x.data_ptr(), eps.data_ptr(), _lib.ptr(orig), _lib.ptr(mask), C.byref(coef), seed, dq, dp, off, out.data_ptr(), n, st))
+    nq, npz = _steps.randn(lib, (n,), "cuda", seed, dq, off), _steps.randn(lib, (n,), "cuda", seed, dp, off)
+    ref = _steps.ddpm_step(lib, x, eps, torch.empty(n, device="cuda"), coef=coef, noise_p=npz, noise_q=nq if with_orig else None, **known)
+    out = _steps.ddpm_step(lib, x, eps, torch.empty(n, device="cuda"), coef=coef, rng=(seed, dq, dp, off), **known)
     assert torch.equal(out, ref)
     # in place (the graph path updates x where it stands)
     xi = x.clone()
-    _lib.check(lib.pf_ddpm_step_rng(xi.data_ptr(), eps.data_ptr(), _lib.ptr(orig), _lib.ptr(mask), C.byref(coef), seed, dq, dp, off, xi.data_ptr(), n, st))
+    _steps.ddpm_step(lib, xi, eps, xi, coef=coef, rng=(seed, dq, dp, off), **known)
     assert torch.equal(xi, ref)
     # device-state form: draws (q, p) = (state.draws, state.draws + 1) with a known region, p = state.draws without
     table = torch.tensor([[0.0] * 7, [1.3, 0.7, 0.2, 0.8, 0.05, 0.9, 0.43]], device="cuda")
     state = torch.zeros(2, dtype=torch.int64, device="cuda")
-    _lib.check(lib.pf_step_state_set(state.data_ptr(), 1, dq if with_orig else dp, st))
-    out2 = torch.empty(n, device="cuda")
-    _lib.check(lib.pf_ddpm_step_rng_dev(x.data_ptr(), eps.data_ptr(), _lib.ptr(orig), _lib.ptr(mask), table.data_ptr(), state.data_ptr(), seed, off,
-                                        out2.data_ptr(), n, st))
+    _lib.check(lib.pf_step_state_set(state.data_ptr(), 1, dq if with_orig else dp, _lib.current_stream()))
+    out2 = _steps.ddpm_step(lib, x, eps, torch.empty(n, device="cuda"), table=table, state=state, rng=(seed, 0, 0, off), **known)
     assert torch.equal(out2, ref)
     # whole Philox groups only
     with pytest.raises(RuntimeError):
-        _lib.check(lib.pf_ddpm_step_rng(x.data_ptr(), eps.data_ptr(), None, None, C.byref(coef), seed, dq, dp, off + 2, out.data_ptr(), n, st))
+        _steps.ddpm_step(lib, x, eps, out, coef=coef, rng=(seed, dq, dp, off + 2))
 
 
 @pytest.mark.parametrize("with_orig", [True, False])
@@ -163,29 +154,22 @@ def test_ddim_step_rng_equals_randn_plus_step(lib, with_orig):
     n, seed, off, d = 4 * 2 * 128 * 128, 99, 32768, 7
     g = torch.Generator().manual_seed(3)
     x, eps = torch.randn(n, generator=g).cuda(), torch.randn(n, generator=g).cuda()
-    orig = torch.randn(n, generator=g).cuda() if with_orig else None
-    on = torch.randn(n, generator=g).cuda() if with_orig else None
-    mask = (torch.rand(n, generator=g) > 0.3).float().cuda() if with_orig else None
+    known = dict(orig=torch.randn(n, generator=g).cuda(), orig_noise=torch.randn(n, generator=g).cuda(),
+                 mask=(torch.rand(n, generator=g) > 0.3).float().cuda()) if with_orig else {}
     coef = _lib.DdimCoef(0.6, 0.8, 0.85, 0.5, 0.1, 0.8, 0.6)
-    st = _lib.current_stream()
-    nz = torch.empty(n, device="cuda")
-    _lib.check(lib.pf_randn(nz.data_ptr(), n, seed, d, off, st))
-    ref = torch.empty(n, device="cuda")
-    _lib.check(lib.pf_ddim_step(x.data_ptr(), eps.data_ptr(), nz.data_ptr(), _lib.ptr(orig), _lib.ptr(on), _lib.ptr(mask), C.byref(coef), ref.data_ptr(), n, st))
-    out = torch.empty(n, device="cuda")
-    _lib.check(lib.pf_ddim_step_rng(x.data_ptr(), eps.data_ptr(), _lib.ptr(orig), _lib.ptr(on), _lib.ptr(mask), C.byref(coef), seed, d, off, out.data_ptr(), n, st))
+    nz = _steps.randn(lib, (n,), "cuda", seed, d, off)
+    ref = _steps.ddim_step(lib, x, eps, torch.empty(n, device="cuda"), coef=coef, noise=nz, **known)
+    out = _steps.ddim_step(lib, x, eps, torch.empty(n, device="cuda"), coef=coef, rng=(seed, d, off), **known)
     assert torch.equal(out, ref)
     table = torch.tensor([[0.6, 0.8, 0.85, 0.5, 0.1, 0.8, 0.6]], device="cuda")
     state = torch.zeros(2, dtype=torch.int64, device="cuda")
-    _lib.check(lib.pf_step_state_set(state.data_ptr(), 0, d, st))
-    out2 = torch.empty(n, device="cuda")
-    _lib.check(lib.pf_ddim_step_rng_dev(x.data_ptr(), eps.data_ptr(), _lib.ptr(orig), _lib.ptr(on), _lib.ptr(mask), table.data_ptr(), state.data_ptr(), seed,
-                                        off, out2.data_ptr(), n, st))
+    _lib.check(lib.pf_step_state_set(state.data_ptr(), 0, d, _lib.current_stream()))
+    out2 = _steps.ddim_step(lib, x, eps, torch.empty(n, device="cuda"), table=table, state=state, rng=(seed, 0, off), **known)
     assert torch.equal(out2, ref)
 
 
 def test_ddim_eta1_paint_graph_equals_eager():
-    """eta = 1: every step draws; the eager loop (pf_ddim_step_rng) and the captured step (pf_ddim_step_rng_dev) agree bit for bit."""
+    """eta = 1: every step draws; the eager loop (host coefficients) and the captured step (device table + state) agree bit for bit."""
     m, _ = small_unet()
     g = torch.Generator().manual_seed(4)
     x, c = torch.randn(2, 2, 32, 32, generator=g).cuda(), torch.randn(2, 1, 32, generator=g).cuda()
