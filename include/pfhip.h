@@ -432,6 +432,21 @@ enum { PF_PAD_SAME = 0, PF_PAD_BOTTOM_RIGHT = 1 };
 size_t pf_conv_splitk_ws_bytes(const pf_conv_args* a);
 /* number of per-sample tiles a pf_conv2d launch with these arguments emits into stats_out (0 on error) */
 int pf_conv_stats_tiles(const pf_conv_args* a);
+/* What a pf_conv2d launch with these arguments runs (needs no device): the arguments are checked as pf_conv2d checks them (same code and
+ * pf_last_error() text on refusal, *out zero-filled), then *out says which kernel form they get, the pixels x channels one workgroup owns,
+ * the K split across workgroups they would like and the one they get with the splitk_ws they carry, and the two older queries' answers.
+ * Forms: fp32 MFMA direct | split precision direct (1x1, 3x3, strided, upsampling through the halo read) | the same on the 64 px x 64 ch tile with
+ * two wave groups of one workgroup halving K | on the 128 px x 128 ch tile with two wave groups half a tap apart | parity-folded upsampling (four
+ * 2x2 convs on the source grid) | planes GEMM (a_planes) | fused Winograd F(2x2, 3x3). */
+enum { PF_CONV_FORM_F32 = 0, PF_CONV_FORM_SPLIT, PF_CONV_FORM_SPLIT_KG2, PF_CONV_FORM_SPLIT_PINGPONG, PF_CONV_FORM_UPFOLD, PF_CONV_FORM_PLANES, PF_CONV_FORM_WINO };
+typedef struct pf_conv_plan_info {
+  int32_t form, tile_h, tile_w, tile_n;   /* PF_CONV_FORM_*; output pixels (rows x columns) x channels per workgroup */
+  int32_t wave_groups;                    /* 1, or 2 four-wave groups per workgroup */
+  int32_t ksplit_wanted, ksplit;          /* K slices across workgroups: wanted / granted (1 = none) */
+  int32_t stats_tiles; size_t splitk_ws_bytes;   /* = pf_conv_stats_tiles, pf_conv_splitk_ws_bytes */
+  double flops;                           /* operations the launch executes */
+} pf_conv_plan_info;
+int pf_conv_describe(const pf_conv_args* a, pf_conv_plan_info* out);
 /* GroupNorm scale/shift from per-tile statistics of up to two channel-concatenated producers (no pass over the tensors) */
 int pf_gn_finalize_tiles(const float* stats0, int tiles0, int c0, const float* stats1, int tiles1, int c1, int batch, int hw,
                          int groups, float eps, const float* gamma, const float* beta, float* scale, float* shift, void* stream);

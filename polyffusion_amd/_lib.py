@@ -118,6 +118,26 @@ class ConvArgs(C.Structure):
 PAD_SAME, PAD_BOTTOM_RIGHT = 0, 1   # pf_conv_args.pad_mode
 
 
+class ConvPlanInfo(C.Structure):   # pf_conv_plan_info: what pf_conv_describe says a pf_conv2d launch runs
+    _fields_ = [
+        ("form", C.c_int32), ("tile_h", C.c_int32), ("tile_w", C.c_int32), ("tile_n", C.c_int32), ("wave_groups", C.c_int32),
+        ("ksplit_wanted", C.c_int32), ("ksplit", C.c_int32), ("stats_tiles", C.c_int32),
+        ("splitk_ws_bytes", C.c_size_t), ("flops", C.c_double),
+    ]
+
+
+# PF_CONV_FORM_*, in the enum's order
+CONV_FORMS = ("f32", "split", "split_kg2", "split_pingpong", "upfold", "planes", "wino")
+
+
+def conv_form(lib, a: ConvArgs) -> str:
+    """'form THxTWxBN[ ks=S]': what pf_conv_describe says a pf_conv2d launch with these arguments runs ('refused' if it would not)"""
+    i = ConvPlanInfo()
+    if lib.pf_conv_describe(C.byref(a), C.byref(i)) != 0:
+        return "refused"
+    return f"{CONV_FORMS[i.form]} {i.tile_h}x{i.tile_w}x{i.tile_n}" + (f" ks={i.ksplit}" if i.ksplit > 1 else "")
+
+
 class AutoencCfg(C.Structure):
     _fields_ = [
         ("in_channels", C.c_int32), ("out_channels", C.c_int32), ("channels", C.c_int32), ("n_levels", C.c_int32),
@@ -216,6 +236,7 @@ SIGNATURES = {
     "pf_conv2d": (C.c_int, [C.POINTER(ConvArgs), C.c_void_p]),
     "pf_conv_stats_tiles": (C.c_int, [C.POINTER(ConvArgs)]),
     "pf_conv_splitk_ws_bytes": (C.c_size_t, [C.POINTER(ConvArgs)]),
+    "pf_conv_describe": (C.c_int, [C.POINTER(ConvArgs), C.POINTER(ConvPlanInfo)]),
     "pf_gn_finalize_tiles": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                        C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "pf_attention_bf16x3": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),

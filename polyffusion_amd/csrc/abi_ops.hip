@@ -3,6 +3,7 @@
 #include <stdarg.h>
 #include <vector>
 #include "plan.h"
+#include "conv_plan.h"
 
 namespace pf {
 
@@ -23,7 +24,7 @@ using namespace pf;
 
 extern "C" {
 
-int pf_version(void) { return 101; }
+int pf_version(void) { return 102; }
 const char* pf_last_error(void) { return g_err.c_str(); }
 int pf_x3_element(void) {
 #ifdef PF_X3_F16
@@ -85,8 +86,18 @@ int pf_ln_planes(const float* x, int rows, int c, float eps, const float* gamma,
 int pf_ln_stats(const float* x, int rows, int c, float eps, float* mean, float* rstd, void* stream) {
   return launch_ln_stats(x, rows, c, eps, mean, rstd, (hipStream_t)stream);
 }
-int pf_conv_stats_tiles(const pf_conv_args* a) { return a ? conv_stats_tiles(*a) : 0; }
-size_t pf_conv_splitk_ws_bytes(const pf_conv_args* a) { return a ? conv_splitk_ws_bytes(*a) : 0; }
+int pf_conv_stats_tiles(const pf_conv_args* a) { return a ? conv_plan(*a).stats_tiles : 0; }
+size_t pf_conv_splitk_ws_bytes(const pf_conv_args* a) { return a ? conv_plan(*a).splitk_ws_bytes : 0; }
+int pf_conv_describe(const pf_conv_args* a, pf_conv_plan_info* out) {
+  PF_REQUIRE(a && out, "pf_conv_describe: null argument");
+  memset(out, 0, sizeof *out);
+  if (int rc = conv_validate(*a)) return rc;
+  const ConvPlan pl = conv_plan(*a);
+  out->form = pl.form; out->tile_h = pl.th; out->tile_w = pl.tw; out->tile_n = pl.bn; out->wave_groups = pl.wave_groups;
+  out->ksplit_wanted = pl.ksplit_wanted; out->ksplit = pl.ksplit; out->stats_tiles = pl.stats_tiles;
+  out->splitk_ws_bytes = pl.splitk_ws_bytes; out->flops = pl.flops;
+  return PF_OK;
+}
 int pf_gn_finalize_tiles(const float* stats0, int tiles0, int c0, const float* stats1, int tiles1, int c1, int batch, int hw,
                          int groups, float eps, const float* gamma, const float* beta, float* scale, float* shift, void* stream) {
   return launch_gn_finalize_tiles(stats0, tiles0, c0, stats1, tiles1, c1, batch, hw, groups, eps, gamma, beta, scale, shift,

@@ -25,7 +25,7 @@
 //     split-K across workgroups (ksplit) and across two wave groups of one workgroup (KG == 2).
 #include <vector>
 
-#include "conv_common.h"
+#include "conv_plan.h"
 
 namespace pf {
 
@@ -894,10 +894,6 @@ static int launch3_cfg(ConvP& p, hipStream_t stream) {
   constexpr size_t lds_xch = KG == 2 ? (size_t)FMFN * 16 * NWM * 128 * 4 : 0;   // accumulator hand-over between the wave groups
   constexpr size_t lds = lds_groups > lds_xch ? lds_groups : lds_xch;
   static_assert(lds <= 160 * 1024, "LDS budget");
-  p.tiles_x = cdiv(p.Wout, TW);
-  p.tiles_y = cdiv(p.Hout, TH);
-  p.nt = cdiv(p.Npad, BN);
-  conv_fill_divs(p);
   auto kern = conv_bf3_kernel<KS, STRIDE, UPS, TH, TW, BN, PRO, NWM, SKIP, KG>;
   static std::atomic<uint64_t> attr_done{0};
   if (int rc = set_max_lds_once(reinterpret_cast<const void*>(kern), (int)lds, attr_done)) return rc;
@@ -908,7 +904,8 @@ static int launch3_cfg(ConvP& p, hipStream_t stream) {
 }
 
 template <int KS, int STRIDE, bool UPS, int PRO>
-static int dispatch_tile3(ConvP& p, int tile, hipStream_t s) {
+static int dispatch_tile3(ConvP& p, const ConvPlan& pl, hipStream_t s) {
+  const int tile = pl.tile;
   if constexpr (KS == 1) {
     if (tile == 0) return launch3_cfg<1, 1, false, 1, 128, 128, PRO>(p, s);
     if (tile == 1) return launch3_cfg<1, 1, false, 1, 128, 64, PRO>(p, s);
@@ -921,19 +918,11 @@ static int dispatch_tile3(ConvP& p, int tile, hipStream_t s) {
     return launch3_cfg<3, 2, false, 4, 16, 64, PRO>(p, s);
   } else {
     if constexpr (!UPS && PRO == 1) {
-      // no more tiles than CUs (and an even number of K chunks): two wave groups per workgroup split K (see the kernel)
-      const int blocks = p.B * cdiv(p.Hout, tile == 3 ? 16 : tile == 2 ? 4 : 8) * cdiv(p.Wout, 16) * cdiv(p.Npad, tile == 0 ? 128 : 64);
-      // (the 128x128 tile split the same way measured neutral - its two wave groups run in lockstep behind the shared barrier - DESIGN.md 3)
-      const int cus = num_cus();
-      const bool kg2 = tile == 2 && p.ksplit == 1 && blocks <= cus && ((p.c0 + p.c1) / 32) % 2 == 0 && (!p.sw || ((p.sc0 + p.sc1) / 32) % 2 == 0);
-      if (kg2) return p.sw ? launch3_cfg<3, 1, false, 4, 16, 64, 1, 2, true, 2>(p, s) : launch3_cfg<3, 1, false, 4, 16, 64, 1, 2, false, 2>(p, s);
-      // ... but run as two groups half a tap apart (conv_bf3_pingpong) it gains: one group's fragment reads / copies / halo arithmetic
-      // hide behind the other's MFMAs (B = 16: the 32x32 level; B = 8: the 64x64 level)
-      // (from K = 2304 up: at K = 576 ... 1728 the two-group form measured 3-6 % behind the four-wave one - r32_128_256, r64_128_128 at B = 8)
-      if (p.pp && tile == 0 && p.ksplit == 1 && blocks <= cus && (p.c0 + p.c1) >= 256 && ((p.c0 + p.c1) / 32) % 2 == 0 && (!p.sw || ((p.sc0 + p.sc1) / 32) % 2 == 0))
-        return p.sw ? launch3_cfg<3, 1, false, 8, 16, 128, 1, 2, true, 2>(p, s) : launch3_cfg<3, 1, false, 8, 16, 128, 1, 2, false, 2>(p, s);
-      if (tile == 3) return p.sw ? launch3_cfg<3, 1, false, 16, 16, 64, 1, 2, true>(p, s) : launch3_cfg<3, 1, false, 16, 16, 64, 1, 2, false>(p, s);
-      if (p.sw) {   // fused skip projection: only the ResBlock second-conv configurations are instantiated
+      if (pl.form == PF_CONV_FORM_SPLIT_KG2) return pl.skip ? launch3_cfg<3, 1, false, 4, 16, 64, 1, 2, true, 2>(p, s) : launch3_cfg<3, 1, false, 4, 16, 64, 1, 2, false, 2>(p, s);
+      if (pl.form == PF_CONV_FORM_SPLIT_PINGPONG)
+        return pl.skip ? launch3_cfg<3, 1, false, 8, 16, 128, 1, 2, true, 2>(p, s) : launch3_cfg<3, 1, false, 8, 16, 128, 1, 2, false, 2>(p, s);
+      if (tile == 3) return pl.skip ? launch3_cfg<3, 1, false, 16, 16, 64, 1, 2, true>(p, s) : launch3_cfg<3, 1, false, 16, 16, 64, 1, 2, false>(p, s);
+      if (pl.skip) {   // fused skip projection: only the ResBlock second-conv configurations are instantiated
         if (tile == 0) return launch3_cfg<3, 1, false, 8, 16, 128, 1, 2, true>(p, s);
         if (tile == 1) return launch3_cfg<3, 1, false, 8, 16, 64, 1, 2, true>(p, s);
         return launch3_cfg<3, 1, false, 4, 16, 64, 1, 2, true>(p, s);
@@ -945,50 +934,16 @@ static int dispatch_tile3(ConvP& p, int tile, hipStream_t s) {
   }
 }
 
-// same argument validation as launch_conv (done by the caller); w points to the bf16x3 packing
-int launch_conv_bf3(const pf_conv_args& a, hipStream_t stream) {
-  if (conv_wino_eligible(a)) return launch_conv_wino(a, stream);
-  ConvP p;
-  memset(&p, 0, sizeof p);
-  p.x0 = a.x0; p.x1 = a.x1; p.c0 = a.c0; p.c1 = a.c1;
-  p.B = a.batch; p.Hin = a.hin; p.Win = a.win;
-  p.Hout = a.hin; p.Wout = a.win;
-  if (a.ups) { p.Hout *= 2; p.Wout *= 2; }
-  if (a.stride == 2) { p.Hout = (p.Hout - 1) / 2 + 1; p.Wout = (p.Wout - 1) / 2 + 1; }
-  p.w = a.w; p.N = a.n; p.Npad = (a.n + 63) / 64 * 64;
-  p.sc = a.sc; p.sh = a.sh; p.mean = a.mean; p.rstd = a.rstd;
-  p.bias = a.bias; p.sbias = a.sbias; p.ld_sbias = a.ld_sbias; p.res = a.res; p.ld_res = a.ld_res;
-  p.sb_rows = reinterpret_cast<const long long*>(a.sbias_rows); p.sb_nrows = a.sbias_nrows;
-  p.geglu = a.geglu; p.out = a.out; p.ld_out = a.ld_out; p.stats = a.stats_out;
-  p.ksplit = conv_ksplit(a);
-  p.pp = !a.no_pp;
-  p.partial = p.ksplit > 1 ? static_cast<float*>(a.splitk_ws) : nullptr;
-  p.qkv = a.qkv_planes; p.out_planes = a.out_planes;
-  if (a.gn_stats0 && (a.prologue == 1 || a.prologue == 2)) {
-    p.gn_s0 = a.gn_stats0; p.gn_t0 = a.gn_tiles0; p.gn_s1 = a.gn_stats1; p.gn_t1 = a.gn_tiles1;
-    p.gn_gamma = a.gn_gamma; p.gn_beta = a.gn_beta; p.gn_eps = a.gn_eps; p.gn_groups = a.gn_groups;
-  }
-  p.sx0 = a.skip_x0; p.sc0 = a.skip_c0; p.sx1 = a.skip_x1; p.sc1 = a.skip_c1; p.sw = a.skip_w; p.bias2 = a.skip_w ? a.skip_bias : nullptr;
-  p.x1_bmod = a.x1_bmod;
-  p.amax = static_cast<unsigned*>(a.absmax_slot);
-  p.pad_br = a.pad_mode == PF_PAD_BOTTOM_RIGHT;
-  const int tile = conv_pick_tile(a);
-  if (a.ks == 1) {
-    switch (a.prologue) {
-      case 0: return dispatch_tile3<1, 1, false, 0>(p, tile, stream);
-      case 2: return dispatch_tile3<1, 1, false, 2>(p, tile, stream);
-      default: return dispatch_tile3<1, 1, false, 3>(p, tile, stream);
-    }
-  }
-  if (a.ups_fold) {   // tiles walk the source grid; every workgroup stores one parity of its pixels
-    p.Hout = a.hin; p.Wout = a.win; p.fold = 1;
-    return dispatch_tile3<2, 1, false, 0>(p, tile, stream);
-  }
-  if (a.stride == 2) return dispatch_tile3<3, 2, false, 0>(p, tile, stream);
-  int rc = a.ups ? dispatch_tile3<3, 1, true, 0>(p, tile, stream) : dispatch_tile3<3, 1, false, 1>(p, tile, stream);
-  if (rc != PF_OK || p.ksplit == 1) return rc;
+// p.w points to the bf16x3 packing
+int launch_conv_bf3(ConvP& p, const ConvPlan& pl, hipStream_t stream) {
+  if (pl.ks == 1)
+    return pl.pro == 0 ? dispatch_tile3<1, 1, false, 0>(p, pl, stream) : pl.pro == 2 ? dispatch_tile3<1, 1, false, 2>(p, pl, stream) : dispatch_tile3<1, 1, false, 3>(p, pl, stream);
+  if (pl.ks == 2) return dispatch_tile3<2, 1, false, 0>(p, pl, stream);
+  if (pl.stride == 2) return dispatch_tile3<3, 2, false, 0>(p, pl, stream);
+  int rc = pl.ups ? dispatch_tile3<3, 1, true, 0>(p, pl, stream) : dispatch_tile3<3, 1, false, 1>(p, pl, stream);
+  if (rc != PF_OK || pl.ksplit == 1) return rc;
   const int M = p.B * p.Hout * p.Wout;
-  hipLaunchKernelGGL(splitk_reduce_kernel, dim3(M / 64, cdiv(p.N, 64)), dim3(1024), 0, stream, static_cast<const float*>(a.splitk_ws), p.ksplit, M, p.N,
+  hipLaunchKernelGGL(splitk_reduce_kernel, dim3(M / 64, cdiv(p.N, 64)), dim3(1024), 0, stream, p.partial, p.ksplit, M, p.N,
                      p.Hout * p.Wout, p.bias, p.bias2, p.sbias, p.ld_sbias, p.sb_rows, p.sb_nrows, p.res, p.ld_res, p.out, p.ld_out, p.stats, p.amax);
   PF_CHECK_HIP(hipGetLastError());
   return PF_OK;
@@ -1005,13 +960,6 @@ extern "C" int pf_debug_trace_clear() {
 #endif
 
 // host: fp32 torch weight [N][K][taps] -> bf16x3 packing [tap][K/8][plane][Npad][8] at column col(n)
-static inline unsigned short f2bf_rne(float f) {
-  unsigned int u; memcpy(&u, &f, 4);
-  u += 0x7FFFu + ((u >> 16) & 1u);
-  return (unsigned short)(u >> 16);
-}
-static inline float bf2f(unsigned short h) { unsigned int u = (unsigned int)h << 16; float f; memcpy(&f, &u, 4); return f; }
-
 bool pack_gemm_bf3(void* dst_, const float* src, int n_src, int K, int taps, int Npad, int n_off, const int* colmap) {
   unsigned short* dst = (unsigned short*)dst_;
   bool fits = true;
@@ -1020,17 +968,8 @@ bool pack_gemm_bf3(void* dst_, const float* src, int n_src, int K, int taps, int
     const int col = colmap ? colmap[n] : n_off + n;
     for (int k = 0; k < K; ++k)
       for (int t = 0; t < taps; ++t) {
-        const float v = src[((size_t)n * K + k) * taps + t];
-#ifdef PF_X3_F16
-        const float vs = fminf(fmaxf(v * PF_X3_WS, -65504.f), 65504.f);
-        fits = fits && vs == v * PF_X3_WS;
-        const _Float16 fh = (_Float16)vs, fl = (_Float16)(vs - (float)fh);
         unsigned short hi, lo;
-        memcpy(&hi, &fh, 2); memcpy(&lo, &fl, 2);
-#else
-        const unsigned short hi = f2bf_rne(v);
-        const unsigned short lo = f2bf_rne(v - bf2f(hi));
-#endif
+        fits = split_hi_lo(src[((size_t)n * K + k) * taps + t], &hi, &lo) && fits;
         const size_t base = ((size_t)t * K8 + k / 8) * 2;
         dst[((base + 0) * Npad + col) * 8 + (k & 7)] = hi;
         dst[((base + 1) * Npad + col) * 8 + (k & 7)] = lo;
@@ -1038,7 +977,6 @@ bool pack_gemm_bf3(void* dst_, const float* src, int n_src, int K, int taps, int
   }
   return fits;
 }
-
 
 // UpSample = nearest x2 then conv3x3 (ref:unet.py:236-238).  Output pixel (2y+py, 2x+px) only ever sees a 2x2 block of SOURCE
 // pixels: rows {y-1, y} with weights {w[0], w[1]+w[2]} for py = 0, rows {y, y+1} with {w[0]+w[1], w[2]} for py = 1 (columns

@@ -21,7 +21,7 @@
 //   loads are in flight (registers) while the current tile's MFMAs run; one barrier per tile.
 #include <stdlib.h>
 #include <cstdlib>
-#include "conv_common.h"
+#include "conv_plan.h"
 
 namespace pf {
 
@@ -217,9 +217,6 @@ static int launch_cfg(ConvP& p, hipStream_t stream) {
   constexpr int THIN = (TH - 1) * STRIDE + KS, TWIN = (TW - 1) * STRIDE + KS;
   constexpr size_t lds = (size_t)(2 * THIN * TWIN * (BK + 4) + 2 * BK * BN) * sizeof(float);
   static_assert(lds <= 160 * 1024, "LDS budget");
-  p.tiles_x = cdiv(p.Wout, TW);
-  p.tiles_y = cdiv(p.Hout, TH);
-  p.nt = cdiv(p.Npad, BN);
   auto kern = conv_mfma_kernel<KS, STRIDE, UPS, TH, TW, BN, BK, PRO>;
   static std::atomic<uint64_t> attr_done{0};  // raise the dynamic-LDS cap once per instantiation and device
   if (int rc = set_max_lds_once(reinterpret_cast<const void*>(kern), (int)lds, attr_done)) return rc;
@@ -227,84 +224,6 @@ static int launch_cfg(ConvP& p, hipStream_t stream) {
   hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds, stream, p);
   PF_CHECK_HIP(hipGetLastError());
   return PF_OK;
-}
-
-// tile choice shared by both arithmetic modes: 0 = 128 px x 128 ch, 1 = 128 px x 64 ch, 2 = 64 px x 64 ch
-static void conv_out_dims(const pf_conv_args& a, int* hout, int* wout) {
-  int h = a.hin, w = a.win;
-  if (a.ups) { h *= 2; w *= 2; }
-  if (a.stride == 2) { h = (h - 1) / 2 + 1; w = (w - 1) / 2 + 1; }
-  *hout = h; *wout = w;
-}
-int conv_pick_tile(const pf_conv_args& a) {
-  if (a.geglu) return 0;
-  int hout, wout;
-  conv_out_dims(a, &hout, &wout);
-  const int npad = (a.n + 63) / 64 * 64;
-  const int mt128 = a.ks == 1 ? a.batch * hout * cdiv(wout, 128) : a.batch * cdiv(hout, 8) * cdiv(wout, 16);
-  if (a.ks == 3 && a.stride == 2) return 2;
-  if (a.force_tile >= 1 && a.force_tile <= 3 && a.precision == PF_PREC_BF16X3 && a.stride == 1 && !a.ups && !a.ups_fold &&
-      (a.ks == 3 || a.a_planes) && (a.force_tile != 1 || npad % 128 == 0)) return a.force_tile - 1;   // measurement aid (pf_conv_args.force_tile)
-  // bf16x3 3x3: the wide tile + split-K beats twice as many narrow tiles; planes GEMMs (both operands direct-to-LDS): one 128x128 workgroup
-  // per CU beats two 128x64 ones as soon as every CU gets one (measured at M = 16384, N = 256: K = 256 18.1 -> 16.1 us, K = 1024 37.5 -> 33.9 us)
-  // bf16x3 3x3 with 64 output channels in all (the 128x128 level): a 16x16-pixel tile when that still gives every CU two rounds of
-  // two workgroups - each wave then owns 128 pixels x 32 channels (four A fragments per weight fragment instead of two)
-  if (a.precision == PF_PREC_BF16X3 && a.ks == 3 && a.stride == 1 && !a.ups && !a.ups_fold && npad == 64 && hout % 16 == 0 && wout % 16 == 0 &&
-      a.batch * (hout / 16) * (wout / 16) >= 4 * num_cus() && !a.skip_w && a.c0 + a.c1 >= 128 && !a.no_t16) return 3;
-  // (the same 16x16-pixel footprint for the 128-channel tile - 128 x 64 per wave, one workgroup per CU - measured worse at the 64x64
-  // level: r64_128_128 55.3 -> 57 us, the fused-skip form 79 -> 82, only the K = 3456 conv gained 2.5 %)
-  const bool wide_at_256 = a.precision == PF_PREC_BF16X3 && (a.ks == 3 || a.a_planes);
-  const int cus = num_cus();   // (the thresholds were measured on 256 CUs; they are rounds of the chip, not literals)
-  if (npad % 128 == 0 && mt128 * (npad / 128) >= (wide_at_256 ? cus : 2 * cus)) return 0;
-  // bf16x3 3x3: the 128 px x 64 ch tile as soon as it gives every CU a workgroup - at B = 8 the 32x32 level has exactly 256 of them and they
-  // beat 512 narrow tiles by 6-10 % (tools/sweep_conv.py, profiles/r05_sweep_conv_before.log); below that the 64 px tile fills more CUs
-  const bool bf3x3 = a.precision == PF_PREC_BF16X3 && a.ks == 3 && a.stride == 1 && !a.ups;
-  if (mt128 * (npad / 64) >= (bf3x3 ? cus : 2 * cus)) return 1;
-  return 2;
-}
-void conv_tile_shape(const pf_conv_args& a, int tile, int* th, int* tw) {
-  if (a.ks == 1) { *th = 1; *tw = tile == 2 ? 64 : 128; }
-  else if (a.stride == 2) { *th = 4; *tw = 16; }
-  else { *th = tile == 3 ? 16 : tile == 2 ? 4 : 8; *tw = 16; }
-}
-// split-K (bf16x3 3x3 only): layers whose tile grid cannot fill the chip (the 16x16 level at batch 16, most levels at
-// small batch) run ksplit K-slices per tile and a reduce kernel that also applies the epilogue
-static int ksplit_wanted(const pf_conv_args& a) {
-  if (a.precision != PF_PREC_BF16X3 || a.ks != 3 || a.stride != 1 || a.geglu || a.ups_fold || conv_wino_eligible(a)) return 1;
-  int hout, wout, th, tw;
-  conv_out_dims(a, &hout, &wout);
-  if ((hout * wout) % 64 != 0) return 1;
-  conv_tile_shape(a, conv_pick_tile(a), &th, &tw);
-  const int blocks = a.batch * cdiv(hout, th) * cdiv(wout, tw) * cdiv((a.n + 63) / 64 * 64, 64);
-  const int nchunk = (a.c0 + a.c1) / 32;
-  if (a.force_ksplit >= 1 && nchunk % a.force_ksplit == 0) return a.force_ksplit;   // measurement aid (pf_conv_args.force_ksplit)
-  // Round 5, from a sweep of every layer shape at B = 1 / 8 / 16 (tools/sweep_conv.py, profiles/r05_sweep_conv_before.log): the split pays
-  // only for DEEP K on FEW workgroups - its fp32 partial sums and the reduce launch cost ~8 us, which a K = 2304 loop (25 us unsplit on
-  // any number of workgroups, 17 us with the intra-workgroup split) never earns back: B = 8, 16x16 level 22.9 -> 17.4 us, B = 1, 64x64
-  // level 19.5 -> 11.5 us without it.  K >= 4608 on at most half the CUs, or K >= 3456 on at most a quarter: four slices (+10 ... +30 %).
-  const int cus = num_cus();
-  if (nchunk % 4 == 0 && ((nchunk >= 16 && blocks <= cus / 2) || (nchunk >= 12 && blocks <= cus / 4))) return 4;
-  return 1;
-}
-size_t conv_splitk_ws_bytes(const pf_conv_args& a) {
-  const int s = ksplit_wanted(a);
-  if (s <= 1) return 0;
-  int hout, wout;
-  conv_out_dims(a, &hout, &wout);
-  return (size_t)s * a.batch * hout * wout * a.n * sizeof(float);
-}
-int conv_ksplit(const pf_conv_args& a) {
-  const size_t need = conv_splitk_ws_bytes(a);
-  return (need && a.splitk_ws && a.splitk_ws_bytes >= need) ? ksplit_wanted(a) : 1;
-}
-int conv_stats_tiles(const pf_conv_args& a) {
-  int hout, wout, th, tw;
-  conv_out_dims(a, &hout, &wout);
-  if (conv_wino_eligible(a)) return (hout / 16) * (wout / 16);   // the Winograd form: one statistics tile per 16x16-pixel workgroup
-  if (conv_ksplit(a) > 1) return hout * wout / 64;   // the reduce kernel emits one statistics tile per 64 rows
-  conv_tile_shape(a, conv_pick_tile(a), &th, &tw);
-  if (a.ups_fold) return cdiv(a.hin, th) * cdiv(a.win, tw) * 4;   // tiles walk the source grid, one statistics tile per parity
-  return cdiv(hout, th) * cdiv(wout, tw);
 }
 
 template <int KS, int STRIDE, bool UPS, int PRO>
@@ -322,86 +241,13 @@ static int dispatch_tile(ConvP& p, int tile, hipStream_t s) {
   }
 }
 
-double conv_flops(const pf_conv_args& a) {
-  const int cin = a.c0 + a.c1;
-  int hout = a.hin, wout = a.win;
-  if (a.ks == 3) {
-    if (a.ups) { hout *= 2; wout *= 2; }
-    if (a.stride == 2) { hout = (hout - 1) / 2 + 1; wout = (wout - 1) / 2 + 1; }
-  }
-  const double skip = a.skip_w ? (double)(a.skip_c0 + a.skip_c1) : 0.0;   // fused 1x1 projection of a second tensor
-  // folded upsampling conv: 2x2 taps per output pixel; Winograd F(2x2, 3x3): 16 products per 2x2 output pixels (work actually done)
-  const double taps = (a.ups_fold || conv_wino_eligible(a)) ? 4.0 : (double)(a.ks * a.ks);
-  return 2.0 * a.batch * hout * wout * (double)a.n * (cin * taps + skip);
-}
-
-int launch_conv(const pf_conv_args& a, hipStream_t stream) {
-  PF_REQUIRE(a.ks == 1 || a.ks == 3, "conv: ks must be 1 or 3 (got %d)", a.ks);
-  PF_REQUIRE(a.stride == 1 || a.stride == 2, "conv: stride must be 1 or 2");
-  PF_REQUIRE(!(a.ks == 1 && (a.stride != 1 || a.ups)), "conv: 1x1 supports stride 1 without upsampling only");
-  PF_REQUIRE(!(a.ups && a.stride != 1), "conv: upsample fold needs stride 1");
-  PF_REQUIRE(a.pad_mode == PF_PAD_SAME || (a.pad_mode == PF_PAD_BOTTOM_RIGHT && a.ks == 3 && a.stride == 2 && a.hin % 2 == 0 && a.win % 2 == 0),
-             "conv: pad_mode %d needs ks=3, stride 2 and an even input size", a.pad_mode);
-  PF_REQUIRE(a.c0 > 0 && a.c0 % 32 == 0 && a.c1 >= 0 && a.c1 % 32 == 0, "conv: channel counts must be multiples of 32 (c0=%d c1=%d)", a.c0, a.c1);
-  PF_REQUIRE(a.x0 && (a.c1 == 0 || a.x1), "conv: null input");
-  PF_REQUIRE(a.n > 0 && a.w && a.out, "conv: null weight/output");
-  PF_REQUIRE(a.prologue >= 0 && a.prologue <= 3, "conv: bad prologue %d", a.prologue);
-  PF_REQUIRE(a.prologue == 0 || (a.sc && a.sh), "conv: prologue needs sc/sh");
-  PF_REQUIRE(!a.gn_stats0 || (a.precision == PF_PREC_BF16X3 && (a.prologue == 1 || a.prologue == 2) && a.gn_gamma && a.gn_beta && a.gn_groups > 0 &&
-                              (a.c0 + a.c1) % a.gn_groups == 0 && a.c0 + a.c1 <= 1024 && a.gn_tiles0 > 0 && (a.c1 == 0 || (a.gn_stats1 && a.gn_tiles1 > 0))),
-             "conv: fused GroupNorm finalize needs the bf16x3 path, prologue 1/2, gamma/beta, statistics of every source and <= 1024 channels");
-  PF_REQUIRE(a.prologue != 3 || (a.mean && a.rstd && a.ks == 1), "conv: LayerNorm prologue needs mean/rstd and ks=1");
-  PF_REQUIRE(!a.geglu || (a.n % 64 == 0 && !a.sbias && !a.res), "conv: geglu needs N %% 64 == 0 and no residual");
-  PF_REQUIRE((a.ks == 3 && (a.prologue == 0 || a.prologue == 1)) || a.ks == 1, "conv: 3x3 supports prologue 0/1 only");
-  PF_REQUIRE(!(a.ks == 3 && a.prologue == 1 && (a.ups || a.stride == 2)), "conv: GN prologue only on plain 3x3");
-  PF_REQUIRE(!(a.ks == 3 && a.prologue == 0 && !a.ups && a.stride == 1), "conv: plain 3x3 without prologue is not instantiated");
-  PF_REQUIRE(!(a.ks == 1 && a.prologue == 1), "conv: 1x1 with SiLU prologue is not instantiated");
-  PF_REQUIRE(!(a.stats_out && a.geglu), "conv: statistics are not available with the GeGLU epilogue");
-  PF_REQUIRE(!a.qkv_planes || (a.ks == 1 && a.n % 192 == 0 && a.win % 16 == 0 && !a.geglu && !a.res && !a.sbias && !a.stats_out),
-             "conv: qkv planes need ks=1, N = 3*heads*64 and L %% 16 == 0");
-
-  PF_REQUIRE(a.precision == PF_PREC_F32 || a.precision == PF_PREC_BF16X3, "conv: bad precision %d", a.precision);
-  PF_REQUIRE(!a.ups_fold || (a.ups && a.precision == PF_PREC_BF16X3 && a.ks == 3 && a.stride == 1 && a.prologue == 0 && !a.res && !a.skip_w),
-             "conv: ups_fold needs ups=1, bf16x3, ks=3, no prologue / residual");
-  PF_REQUIRE(!a.skip_w || (a.precision == PF_PREC_BF16X3 && a.ks == 3 && a.stride == 1 && !a.ups && a.skip_x0 && a.skip_c0 > 0 &&
-                           a.skip_c0 % 32 == 0 && a.skip_c1 % 32 == 0 && (a.skip_c1 == 0 || a.skip_x1) && !a.geglu),
-             "conv: fused skip projection needs bf16x3, ks=3, stride 1, channel counts multiples of 32");
-  PF_REQUIRE(!a.out_planes || (a.precision == PF_PREC_BF16X3 && a.ks == 1 && !a.stats_out && a.ld_out % 8 == 0 &&
-                               (a.geglu ? a.n / 2 : a.n) % 8 == 0),
-             "conv: out_planes needs bf16x3, ks=1, no statistics, ld_out and n multiples of 8");
-  PF_REQUIRE(!a.a_planes || (a.precision == PF_PREC_BF16X3 && a.ks == 1 && a.prologue == 0 && a.c1 == 0),
-             "conv: a_planes needs bf16x3, ks=1, no prologue, single source");
-  if (a.a_planes) return launch_gemm_planes(a, stream);
-  if (a.precision == PF_PREC_BF16X3) return launch_conv_bf3(a, stream);
-
-  ConvP p;
-  memset(&p, 0, sizeof p);
-  p.x0 = a.x0; p.x1 = a.x1; p.c0 = a.c0; p.c1 = a.c1; p.x1_bmod = a.x1_bmod;
-  p.B = a.batch; p.Hin = a.hin; p.Win = a.win;
-  p.Hout = a.hin; p.Wout = a.win;
-  if (a.ups) { p.Hout *= 2; p.Wout *= 2; }
-  if (a.stride == 2) { p.Hout = (p.Hout - 1) / 2 + 1; p.Wout = (p.Wout - 1) / 2 + 1; }
-  p.w = a.w; p.N = a.n; p.Npad = (a.n + 63) / 64 * 64;
-  p.sc = a.sc; p.sh = a.sh; p.mean = a.mean; p.rstd = a.rstd;
-  p.bias = a.bias; p.sbias = a.sbias; p.ld_sbias = a.ld_sbias; p.res = a.res; p.ld_res = a.ld_res;
-  p.sb_rows = reinterpret_cast<const long long*>(a.sbias_rows); p.sb_nrows = a.sbias_nrows;
-  p.geglu = a.geglu; p.out = a.out; p.ld_out = a.ld_out; p.stats = a.stats_out;
-  p.ksplit = 1; p.partial = nullptr; p.qkv = a.qkv_planes; p.out_planes = a.out_planes;
-  p.amax = static_cast<unsigned*>(a.absmax_slot);
-  p.pad_br = a.pad_mode == PF_PAD_BOTTOM_RIGHT;
-
-  const int tile = conv_pick_tile(a);
-
-  if (a.ks == 1) {
-    switch (a.prologue) {
-      case 0: return dispatch_tile<1, 1, false, 0>(p, tile, stream);
-      case 2: return dispatch_tile<1, 1, false, 2>(p, tile, stream);
-      default: return dispatch_tile<1, 1, false, 3>(p, tile, stream);
-    }
-  }
-  if (a.stride == 2) return dispatch_tile<3, 2, false, 0>(p, tile, stream);
-  if (a.ups) return dispatch_tile<3, 1, true, 0>(p, tile, stream);
-  return dispatch_tile<3, 1, false, 1>(p, tile, stream);
+// validated arguments (conv_validate): a 1x1 has prologue 0, 2 or 3; a 3x3 is strided, upsampling, or plain with GroupNorm + SiLU fused
+int launch_conv_f32(ConvP& p, const ConvPlan& pl, hipStream_t stream) {
+  if (pl.ks == 1)
+    return pl.pro == 0 ? dispatch_tile<1, 1, false, 0>(p, pl.tile, stream) : pl.pro == 2 ? dispatch_tile<1, 1, false, 2>(p, pl.tile, stream) : dispatch_tile<1, 1, false, 3>(p, pl.tile, stream);
+  if (pl.stride == 2) return dispatch_tile<3, 2, false, 0>(p, pl.tile, stream);
+  if (pl.ups) return dispatch_tile<3, 1, true, 0>(p, pl.tile, stream);
+  return dispatch_tile<3, 1, false, 1>(p, pl.tile, stream);
 }
 
 }  // namespace pf

@@ -19,7 +19,7 @@
 // The output transform is separable: each wave applies the column half (S[i][q] = M[i][.] A) in registers, the four row partners
 // exchange S through the LDS (128 KB, once per workgroup) and each wave finishes one 32-tile x 32-channel block:
 // Y[p][q] = A^T[p][.] S[.][q], + bias + time bias + residual, 16-byte stores after a lane-quad transpose, tile statistics.
-#include "conv_common.h"
+#include "conv_plan.h"
 
 namespace pf {
 
@@ -523,34 +523,7 @@ __global__ __launch_bounds__(256, 1) void conv_wino_pipe_kernel(ConvP p) {
 #endif
 }
 
-bool conv_wino_eligible(const pf_conv_args& a) {
-  return a.wino > 0 && a.w_wino && a.precision == PF_PREC_BF16X3 && a.ks == 3 && a.stride == 1 && !a.ups && !a.ups_fold && a.prologue == 1 &&
-         a.hin % 16 == 0 && a.win % 16 == 0 && a.n % 64 == 0 && a.c0 % 32 == 0 && a.c1 % 32 == 0 && !a.geglu && !a.out_planes && !a.qkv_planes &&
-         a.c0 + a.c1 <= 1024 && a.hin * a.win < (1 << 20) &&
-         (long long)a.batch * a.hin * a.win * (a.c0 > a.c1 ? a.c0 : a.c1) * 4 < (1ll << 31) &&      // 32-bit buffer offsets
-         (long long)a.batch * a.hin * a.win * (a.ld_out > a.ld_res ? a.ld_out : a.ld_res) * 4 < (1ll << 31) &&
-         !a.skip_w && (a.ld_out & 3) == 0 && (!a.res || (a.ld_res & 3) == 0);
-}
-
-int launch_conv_wino(const pf_conv_args& a, hipStream_t stream) {
-  ConvP p;
-  memset(&p, 0, sizeof p);
-  p.x0 = a.x0; p.x1 = a.x1; p.c0 = a.c0; p.c1 = a.c1;
-  p.B = a.batch; p.Hin = a.hin; p.Win = a.win; p.Hout = a.hin; p.Wout = a.win;
-  p.w = a.w_wino; p.N = a.n; p.Npad = a.n;
-  p.sc = a.sc; p.sh = a.sh;
-  p.bias = a.bias; p.sbias = a.sbias; p.ld_sbias = a.ld_sbias; p.res = a.res; p.ld_res = a.ld_res;
-  p.sb_rows = reinterpret_cast<const long long*>(a.sbias_rows); p.sb_nrows = a.sbias_nrows;
-  p.out = a.out; p.ld_out = a.ld_out; p.stats = a.stats_out;
-  p.ksplit = 1;
-  if (a.gn_stats0) {
-    p.gn_s0 = a.gn_stats0; p.gn_t0 = a.gn_tiles0; p.gn_s1 = a.gn_stats1; p.gn_t1 = a.gn_tiles1;
-    p.gn_gamma = a.gn_gamma; p.gn_beta = a.gn_beta; p.gn_eps = a.gn_eps; p.gn_groups = a.gn_groups;
-  }
-  p.x1_bmod = a.x1_bmod;
-  p.amax = static_cast<unsigned*>(a.absmax_slot);
-  p.tiles_x = a.win / 16; p.tiles_y = a.hin / 16; p.nt = a.n / 64;
-  conv_fill_divs(p);
+int launch_conv_wino(ConvP& p, const ConvPlan&, hipStream_t stream) {
   const int grid = p.B * p.tiles_y * p.tiles_x * p.nt;
   auto kern = conv_wino_pipe_kernel<0>;
   static std::atomic<uint64_t> attr_done{0};
@@ -572,13 +545,6 @@ extern "C" int pf_debug_wino_trace_clear() {
 
 // host: fp32 torch weight [N][K][3][3] -> U = G g G^T per (n, k), split into hi | lo pieces, in MFMA B-operand order
 // [i][K/16][N/64][j][nb][plane][lane = (k % 16 / 8) * 32 + n % 32][k % 8]   (N % 64 == 0, K % 16 == 0)
-static inline unsigned short wf2bf_rne(float f) {
-  unsigned int u; memcpy(&u, &f, 4);
-  u += 0x7FFFu + ((u >> 16) & 1u);
-  return (unsigned short)(u >> 16);
-}
-static inline float wbf2f(unsigned short h) { unsigned int u = (unsigned int)h << 16; float f; memcpy(&f, &u, 4); return f; }
-
 bool pack_wino_bf3(void* dst_, const float* src, int N, int K) {
   unsigned short* dst = (unsigned short*)dst_;
   bool fits = true;
@@ -593,17 +559,8 @@ bool pack_wino_bf3(void* dst_, const float* src, int N, int K) {
       for (int i = 0; i < 4; ++i)
         for (int j = 0; j < 4; ++j) {
           const double ud = Gg[i][0] * G[j][0] + Gg[i][1] * G[j][1] + Gg[i][2] * G[j][2];
-          const float v = (float)ud;
-#ifdef PF_X3_F16
-          const float vs = fminf(fmaxf(v * PF_X3_WS, -65504.f), 65504.f);
-          fits = fits && vs == v * PF_X3_WS;
-          const _Float16 fh = (_Float16)vs, fl = (_Float16)(vs - (float)fh);
           unsigned short hi, lo;
-          memcpy(&hi, &fh, 2); memcpy(&lo, &fl, 2);
-#else
-          const unsigned short hi = wf2bf_rne(v);
-          const unsigned short lo = wf2bf_rne(v - wbf2f(hi));
-#endif
+          fits = split_hi_lo((float)ud, &hi, &lo) && fits;
           const int kk = k / 16, ln = ((k % 16) / 8) * 32 + (n % 32), e = k % 8, ntile = n / 64, nb = (n % 64) / 32;
           const size_t frag = ((((size_t)i * KK + kk) * NT + ntile) * 4 + j) * 2 + nb;
           dst[((frag * 2 + 0) * 64 + ln) * 8 + e] = hi;

@@ -7,7 +7,7 @@
 // the 16-byte slot is XOR-swizzled with (row>>2)&3 on the source address and on the fragment read, which makes
 // ds_read_b128 over 32 consecutive rows conflict-free.  Epilogue = conv_common.h (bias / residual / per-sample bias /
 // GroupNorm statistics / fp32 or split-plane output).
-#include "conv_common.h"
+#include "conv_plan.h"
 
 namespace pf {
 
@@ -177,8 +177,6 @@ template <int BM, int BN, int RING>
 static int launch_gp(ConvP& p, hipStream_t stream) {
   constexpr size_t ring = (size_t)RING * (2 * BM * 4 + 8 * BN) * 16, epi = (size_t)BM * (BN + 8) * 4;   // epi: planes-output transpose
   constexpr size_t lds = ring > epi ? ring : epi;
-  p.tiles_x = cdiv(p.Wout, BM); p.tiles_y = 1; p.nt = cdiv(p.Npad, BN);
-  conv_fill_divs(p);
   auto kern = gemm_planes_kernel<BM, BN, RING>;
   static std::atomic<uint64_t> attr_done{0};
   if (int rc = set_max_lds_once(reinterpret_cast<const void*>(kern), (int)lds, attr_done)) return rc;
@@ -187,23 +185,11 @@ static int launch_gp(ConvP& p, hipStream_t stream) {
   return PF_OK;
 }
 
-// a.x0 = A planes (bf16 hi [M][K] then lo [M][K]); everything else as pf_conv2d with ks = 1, prologue 0, bf16x3 weights
-int launch_gemm_planes(const pf_conv_args& a, hipStream_t stream) {
-  PF_REQUIRE((size_t)a.batch * a.win * a.c0 * 2 * 2 < ((size_t)1 << 31), "gemm_planes: the A plane pair must stay below 2 GiB (32-bit offsets of the direct-to-LDS loads)");
-  ConvP p;
-  memset(&p, 0, sizeof p);
-  p.x0 = a.x0; p.c0 = a.c0; p.B = a.batch; p.Hin = 1; p.Win = a.win; p.Hout = 1; p.Wout = a.win;
-  p.w = a.w; p.N = a.n; p.Npad = (a.n + 63) / 64 * 64;
-  p.bias = a.bias; p.sbias = a.sbias; p.ld_sbias = a.ld_sbias; p.res = a.res; p.ld_res = a.ld_res;
-  p.sb_rows = reinterpret_cast<const long long*>(a.sbias_rows); p.sb_nrows = a.sbias_nrows;
-  p.geglu = a.geglu; p.out = a.out; p.ld_out = a.ld_out; p.stats = a.stats_out; p.out_planes = a.out_planes; p.qkv = a.qkv_planes;
-  p.ksplit = 1;
-  p.amax = static_cast<unsigned*>(a.absmax_slot);
-  const int tile = conv_pick_tile(a);
-  // ring depth: the deepest that still lets two workgroups share a CU's 160 KB (a 128x128 stage is 32 KB)
-  if (tile == 0) return launch_gp<128, 128, 2>(p, stream);
-  if (tile == 1) return launch_gp<128, 64, 3>(p, stream);
-  return launch_gp<64, 64, 3>(p, stream);   // same row tiling as the register path: the GroupNorm statistics tiles must agree
+// p.x0 = A planes (bf16 hi [M][K] then lo [M][K]); everything else as pf_conv2d with ks = 1, prologue 0, bf16x3 weights; <pl.tw, pl.bn, pl.ring>
+int launch_gemm_planes(ConvP& p, const ConvPlan& pl, hipStream_t stream) {
+  if (pl.tile == 0) return launch_gp<128, 128, 2>(p, stream);
+  if (pl.tile == 1) return launch_gp<128, 64, 3>(p, stream);
+  return launch_gp<64, 64, 3>(p, stream);
 }
 
 }  // namespace pf

@@ -44,20 +44,11 @@ int num_cus();
 static inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
 // ---- launchers implemented in the .hip files (all enqueue on `stream`, never sync) ----
-int launch_conv(const pf_conv_args& a, hipStream_t stream);
-double conv_flops(const pf_conv_args& a);
-int launch_conv_bf3(const pf_conv_args& a, hipStream_t stream);  // called by launch_conv after validation
-int conv_pick_tile(const pf_conv_args& a);                        // 0: 128px x 128ch, 1: 128px x 64ch, 2: 64px x 64ch
-void conv_tile_shape(const pf_conv_args& a, int tile, int* th, int* tw);
-int conv_stats_tiles(const pf_conv_args& a);
-int conv_ksplit(const pf_conv_args& a);                           // K-split factor this launch uses (1 = none); needs a.splitk_ws
-size_t conv_splitk_ws_bytes(const pf_conv_args& a);              // scratch wanted for the split (0 = would not split)                      // per-sample tiles emitted into stats_out
+int launch_conv(const pf_conv_args& a, hipStream_t stream);      // validate, plan, parameter block, form launcher (conv_plan.h)
 // both return false when a weight does not fit the split's element type (fp16 build: |w| * 2^8 > 65504; the packing then holds the clamped value)
 bool pack_gemm_bf3(void* dst, const float* src, int n_src, int K, int taps, int Npad, int n_off, const int* colmap);
 bool pack_upfold_bf3(void* dst, const float* src, int N, int K, int Npad);   // UpSample conv weight -> 4 parities x 4 taps
-// fused Winograd F(2x2, 3x3) form of the stride-1 3x3 conv (conv_wino.hip): eligibility of a launch, the launch, the weight transform + packing
-bool conv_wino_eligible(const pf_conv_args& a);
-int launch_conv_wino(const pf_conv_args& a, hipStream_t stream);
+// fused Winograd F(2x2, 3x3) form of the stride-1 3x3 conv (conv_wino.hip): the weight transform + packing
 bool pack_wino_bf3(void* dst, const float* src, int N, int K);            // [N][K][3][3] -> U = G g G^T, hi | lo, MFMA B-operand order
 
 int launch_attention(const float* q, int ldq, const float* k, int ldk, const float* v, int ldv, float* o, int ldo,
@@ -68,7 +59,6 @@ int launch_attention(const float* q, int ldq, const float* k, int ldk, const flo
 int launch_attention_bf3(const void* planes, float* o, int ldo, void* o_planes, int batch, int n_heads, int l, int form, hipStream_t stream,
                          float* scratch = nullptr, size_t scratch_floats = 0);
 size_t attention_bf3_split_floats(int batch, int n_heads, int l, int* nsplit_out);
-int launch_gemm_planes(const pf_conv_args& a, hipStream_t stream);   // called by launch_conv when a.a_planes
 // out = x + ff2(GeGLU(ff1(LayerNorm(x)))) for C = 256, hidden 1024, as one launch (mlp_fused_bf3.hip); w1 / w2 = bf16x3 packings
 int launch_mlp_fused(const float* x, int batch, int l, const float* gamma, const float* beta, float eps, const void* w1, const float* b1,
                      const void* w2, const float* b2, float* out, void* out_planes, hipStream_t stream, const void* w3 = nullptr,

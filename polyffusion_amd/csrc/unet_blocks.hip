@@ -1,5 +1,6 @@
 // unet_blocks.hip - the block emitters shared by the pf_unet and pf_ddpm plans (unet_blocks.h).
 #include "unet_blocks.h"
+#include "conv_plan.h"
 
 namespace pf {
 
@@ -36,26 +37,26 @@ void BlockCtx::conv(pf_conv_args a, Tn* out, bool persist, const float* w_own) {
   a.absmax_slot = o.amax_slot;
   a.no_t16 = o.opt[PF_OPT_CONV_T16] == PF_OPT_OFF;
   a.no_pp = o.opt[PF_OPT_CONV_PP] == PF_OPT_OFF;
-  if (const size_t wsb = conv_splitk_ws_bytes(a)) {   // small-M layer: K-split partial sums live in the temp region
-    float* ws = talloc(wsb / 4);
-    a.splitk_ws = dry ? (void*)1 : (void*)ws; a.splitk_ws_bytes = wsb;
+  ConvPlan pl = conv_plan(a);   // (the args carry no K-split scratch yet: the plan says how much it wants, and is then told that it got it)
+  if (pl.splitk_ws_bytes) {     // small-M layer: K-split partial sums live in the temp region
+    float* ws = talloc(pl.splitk_ws_bytes / 4);
+    a.splitk_ws = dry ? (void*)1 : (void*)ws; a.splitk_ws_bytes = pl.splitk_ws_bytes;
+    conv_plan_grant_split(pl, a);
   }
   if (out) {
     *out = Tn{a.out, a.n};
     if (o.tile_stats) {
-      out->nt = conv_stats_tiles(a);
+      out->nt = pl.stats_tiles;
       float* sb = persist ? palloc((size_t)B * out->nt * a.n * 2) : talloc((size_t)B * out->nt * a.n * 2);
       a.stats_out = sb;
       out->st = sb;
     }
   }
-  double direct = -1.0;
-  if (a.wino) { pf_conv_args d = a; d.wino = 0; direct = conv_flops(d); }
-  launch(a.ks == 3 ? PF_K_CONV3 : PF_K_GEMM, conv_flops(a), [&] {
+  launch(a.ks == 3 ? PF_K_CONV3 : PF_K_GEMM, pl.flops, [&] {
     if (w_own) a.w = w_own;                                        // (folded upsampling conv)
     else if (bf3) a.w += split_offset(a.ks * a.ks, cin_, a.n);     // the region's split packing
     return launch_conv(a, s);
-  }, 1, direct);
+  }, 1, pl.direct_flops);
 }
 
 void BlockCtx::stats_pass(Tn& x, int hw, bool persist) {
@@ -95,18 +96,11 @@ void BlockCtx::gn_attach(pf_conv_args& a, const GnRef& r) {
   a.gn_gamma = w(r.g); a.gn_beta = w(r.b); a.gn_eps = r.eps; a.gn_groups = r.groups;
 }
 
-// the fused Winograd form of a ResBlock conv (PF_OPT_CONV_WINO).  AUTO follows the same-box A/B of profiles/r06_ab_winograd.md: the form
-// wins where the K loop is long enough to carry its per-tile exchange - 192 input channels and more, or 128 and more from the 32x32 level
-// down - and when its 16x16-pixel x 64-channel workgroups fill at least three quarters of the CUs.
+// the fused Winograd form of a ResBlock conv (PF_OPT_CONV_WINO; the AUTO rule: conv_wino_auto, conv_plan.hip)
 void BlockCtx::wino_attach(pf_conv_args& a, size_t wino_off) {
   const int v = o.opt[PF_OPT_CONV_WINO];
   if (!wino_off || v == PF_OPT_OFF || o.precision != PF_PREC_BF16X3) return;
-  const int cin_ = a.c0 + a.c1;
-  if (v == PF_OPT_AUTO) {
-    const int wgs = a.batch * (a.hin / 16) * (a.win / 16) * (a.n / 64);
-    const bool deep = cin_ >= 192 || (cin_ >= 128 && a.hin * a.win <= 1024);
-    if (!deep || wgs * 4 < num_cus() * 3) return;
-  }
+  if (v == PF_OPT_AUTO && !conv_wino_auto(a)) return;
   a.w_wino = dry ? (const void*)16 : (const void*)w(wino_off);
   a.wino = 1;
 }

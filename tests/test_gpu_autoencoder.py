@@ -90,6 +90,9 @@ def test_downsample_conv_pads_bottom_and_right_only(mode, x3):
         a = _lib.ConvArgs()
         a.x0, a.c0, a.batch, a.hin, a.win, a.ks, a.stride, a.pad_mode = xh.data_ptr(), C, B, H, W, 3, 2, pad_mode
         a.w, a.n, a.bias, a.out, a.ld_out, a.precision = wd.data_ptr(), C, bd.data_ptr(), out.data_ptr(), C, 0 if mode == "f32" else 1
+        info = _lib.ConvPlanInfo()   # a strided conv runs the direct form of its precision, 4x16-pixel x 64-channel tiles
+        _lib.check(lib.pf_conv_describe(ctypes.byref(a), ctypes.byref(info)), "pf_conv_describe", lib)
+        assert (_lib.CONV_FORMS[info.form], info.tile_h, info.tile_w, info.tile_n) == ("f32" if mode == "f32" else "split", 4, 16, 64)
         _lib.check(lib.pf_conv2d(ctypes.byref(a), _lib.current_stream()), "pf_conv2d", lib)
         torch.cuda.synchronize()
         return out.cpu().permute(0, 3, 1, 2).double()

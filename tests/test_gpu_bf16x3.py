@@ -48,7 +48,7 @@ def test_resblock_conv_gn_silu_bf16x3(lib, B, H, W, c0, c1, cout):
     out = torch.empty(B, H, W, cout, device="cuda")
     run_conv(lib, x0=x0, c0=c0, x1=x1, c1=c1, batch=B, hin=H, win=W, ks=3, stride=1, ups=0, w=pack3(lib, w), n=cout,
              prologue=1, sc=sc, sh=sh, bias=dev(bias), sbias=dev(sb), ld_sbias=cout, res=dev(nhwc(res)), ld_res=cout,
-             out=out, ld_out=cout, precision=1)
+             out=out, ld_out=cout, precision=1, form="split_kg2" if B == 16 else None)   # B = 16 at 16x16: two wave groups halve K
     err = (out.cpu() - nhwc(ref)).abs().max().item()
     assert err < TOL_OP, err
 
@@ -166,7 +166,8 @@ def test_split_k_small_m_layers(lib, B, H, W, c0, c1, cout, fk):
     assert nt == H * W // 64
     out = torch.empty(B, H, W, cout, device="cuda")
     stats = torch.full((B, nt, cout, 2), float("nan"), device="cuda")
-    run_conv(lib, out=out, ld_out=cout, stats_out=stats, splitk_ws=ws, splitk_ws_bytes=need, **kw)
+    info = run_conv(lib, out=out, ld_out=cout, stats_out=stats, splitk_ws=ws, splitk_ws_bytes=need, form="split", **kw)
+    assert info.ksplit == info.ksplit_wanted == (fk or 4) and info.stats_tiles == nt
     assert (out.cpu() - nhwc(ref)).abs().max() < TOL_OP
     o = out.cpu().double()
     tot = stats.cpu().double().sum(1)
@@ -222,7 +223,7 @@ def test_planes_gemm_chain(lib, B, L, k, n):
     ap = _split_planes(x)
     out = torch.empty(B, L, n, device="cuda")
     run_conv(lib, x0=ap, c0=k, batch=B, hin=1, win=L, ks=1, stride=1, ups=0, w=pack3(lib, w), n=n, bias=dev(bias),
-             res=dev(res), ld_res=n, out=out, ld_out=n, precision=1, a_planes=1)
+             res=dev(res), ld_res=n, out=out, ld_out=n, precision=1, a_planes=1, form="planes")
     assert (out.cpu() - ref).abs().max().item() < TOL_OP
     # same GEMM, result as planes
     op = torch.zeros(B * L * n, device="cuda")
@@ -356,7 +357,8 @@ def test_fused_skip_projection(lib, B, H, W, ch, c0, c1, cout):
         setattr(a, k, v.data_ptr() if isinstance(v, torch.Tensor) else (0 if v is None else v))
     ws_bytes = lib.pf_conv_splitk_ws_bytes(C.byref(a))
     scratch = torch.empty(max(ws_bytes, 4), dtype=torch.uint8, device="cuda")
-    run_conv(lib, splitk_ws=scratch, splitk_ws_bytes=ws_bytes, **{k: v for k, v in kw.items() if v is not None})
+    # (the fused projection rides on the direct split forms: two wave groups wherever the tiles are no more than the CUs and the chunks pair up)
+    run_conv(lib, splitk_ws=scratch, splitk_ws_bytes=ws_bytes, form="split" if H == 12 else "split_kg2", **{k: v for k, v in kw.items() if v is not None})
     err = (out.cpu() - nhwc(ref)).abs().max().item()
     assert err < TOL_OP, err
 
@@ -383,7 +385,7 @@ def test_upsample_conv_parity_folded(lib, B, H, W, c, cout):
         setattr(a, k, v.data_ptr() if isinstance(v, torch.Tensor) else v)
     nt = lib.pf_conv_stats_tiles(C.byref(a))
     stats = torch.zeros(B, nt, cout, 2, device="cuda")
-    run_conv(lib, stats_out=stats, **kw)
+    run_conv(lib, stats_out=stats, form="upfold", **kw)
     o = out.cpu()
     assert (o - nhwc(ref)).abs().max().item() < TOL_OP
     tot = stats.cpu().sum(1)

@@ -39,7 +39,8 @@ def nhwc(x):
     return x.permute(0, 2, 3, 1).contiguous()
 
 
-def run_conv(lib, **kw):
+def run_conv(lib, form=None, **kw):
+    """one pf_conv2d launch; `form`: the name (_lib.CONV_FORMS) pf_conv_describe must give these arguments"""
     a = _lib.ConvArgs()
     keep = []
     for k, v in kw.items():
@@ -47,8 +48,12 @@ def run_conv(lib, **kw):
             keep.append(v)
             v = v.data_ptr()
         setattr(a, k, v)
+    info = _lib.ConvPlanInfo()
+    _lib.check(lib.pf_conv_describe(C.byref(a), C.byref(info)), "pf_conv_describe")
+    assert form is None or _lib.CONV_FORMS[info.form] == form, (_lib.CONV_FORMS[info.form], form)
     _lib.check(lib.pf_conv2d(C.byref(a), _lib.current_stream()), "pf_conv2d")
     torch.cuda.synchronize()
+    return info
 
 
 def gn_scale_shift(lib, x0, x1, gamma, beta, eps):

@@ -241,7 +241,8 @@ def test_conv_16x16_pixel_tile_vs_torch(lib, c0, c1):
     assert lib.pf_conv_stats_tiles(C.byref(a)) == (H // 16) * (W // 16)      # the 16x16-pixel tile is what this shape gets
     out = torch.empty(B, H, W, cout, device="cuda")
     stats = torch.zeros(B, (H // 16) * (W // 16), cout, 2, device="cuda")
-    run_conv(lib, out=out, stats_out=stats, **kw)
+    info = run_conv(lib, out=out, stats_out=stats, form="split", **kw)
+    assert (info.tile_h, info.tile_w, info.tile_n, info.wave_groups) == (16, 16, 64, 1)
     o = out.cpu()
     assert (o - nhwc(ref)).abs().max().item() < 3e-4
     tot = stats.cpu().double().sum(1)
@@ -289,14 +290,14 @@ def test_conv_pingpong_form_vs_torch(lib, c0, c1, skip):
         kw.update(res=dev(nhwc(res)), ld_res=cout)
     out = torch.empty(B, H, W, cout, device="cuda")
     stats = torch.zeros(B, (H // 8) * (W // 16), cout, 2, device="cuda")
-    run_conv(lib, out=out, stats_out=stats, **kw)
+    run_conv(lib, out=out, stats_out=stats, form="split_pingpong", **kw)
     o = out.cpu()
     assert (o - nhwc(ref)).abs().max().item() < 3e-4
     tot = stats.cpu().double().sum(1)
     od = o.double()
     assert (tot[..., 0] - od.sum((1, 2))).abs().max() < 5e-2 and (tot[..., 1] - (od * od).sum((1, 2))).abs().max() < 5e-1
     out1 = torch.empty_like(out)
-    run_conv(lib, out=out1, no_pp=1, **kw)
+    run_conv(lib, out=out1, no_pp=1, form="split", **kw)
     d = (out1 - out).abs().max().item()
     assert 0 < d < 2e-5                              # the two forms differ (K summed in two halves), in the last bits only
     out2 = torch.empty_like(out)

@@ -55,7 +55,7 @@ def test_wino_conv_gn_silu_vs_torch(lib, B, H, W, c0, c1, cout):
     assert nt == (H // 16) * (W // 16)
     stats = torch.full((B, nt, cout, 2), float("nan"), device="cuda")
     out = torch.full((B, H, W, cout), float("nan"), device="cuda")
-    run_conv(lib, out=out, stats_out=stats, w_wino=ww, wino=1, **kw)
+    run_conv(lib, out=out, stats_out=stats, w_wino=ww, wino=1, form="wino", **kw)
     err = (out.cpu() - nhwc(ref)).abs().max().item()
     direct = torch.empty(B, H, W, cout, device="cuda")
     run_conv(lib, out=direct, **kw)

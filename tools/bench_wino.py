@@ -89,7 +89,7 @@ def main():
         gf = 2.0 * B * H * W * n * cin * 9 / 1e9
         diff = (args[0][1] - args[1][1]).abs().max().item()
         hbm = (B * H * W * (cin + n * (2 if has_res else 1)) * 4) / 1e6
-        print(f"{name:18s} B={B:2d} direct {d:7.1f} us ({gf / d * 1e3:6.1f} TF/s)   wino {wv:7.1f} us ({gf / wv * 1e3:6.1f} TF/s direct-equivalent)   "
+        print(f"{name:18s} B={B:2d} direct [{_lib.conv_form(lib, args[0][0])}] {d:7.1f} us ({gf / d * 1e3:6.1f} TF/s)   wino [{_lib.conv_form(lib, args[1][0])}] {wv:7.1f} us ({gf / wv * 1e3:6.1f} TF/s direct-equivalent)   "
               f"x{d / wv:4.2f}   |diff| {diff:.1e}   HBM floor {hbm / 5.0:5.1f} us @5TB/s", flush=True)
 
 

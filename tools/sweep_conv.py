@@ -14,6 +14,7 @@ sys.path.insert(0, os.path.join(REPO, "tests"))
 import ctypes as C  # noqa: E402
 
 import layer_launch  # noqa: E402
+from polyffusion_amd import _lib  # noqa: E402
 
 B = int(sys.argv[1]) if len(sys.argv) > 1 else 8
 flt = sys.argv[2] if len(sys.argv) > 2 else ""
@@ -74,5 +75,5 @@ for shape in SHAPES:
                     res.append((t, tile - 1, ks, nopp))
     res.sort()
     best = res[0]
-    print(f"{shape[0]:18s} B={B}: auto {t_auto:6.1f} us | best {best[0]:6.1f} (tile {best[1]} ks {best[2]}{' nopp' if best[3] else ''}) "
+    print(f"{shape[0]:18s} B={B}: auto {t_auto:6.1f} us [{_lib.conv_form(base.lib, base.args)}] | best {best[0]:6.1f} (tile {best[1]} ks {best[2]}{' nopp' if best[3] else ''}) "
           f"{(t_auto / best[0] - 1) * 100:+5.1f} % | " + "  ".join(f"t{r[1]}k{r[2]}{'n' if r[3] else ''}:{r[0]:.1f}" for r in res[:8]), flush=True)
