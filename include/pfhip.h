@@ -224,6 +224,52 @@ int pf_step_begin(const pf_step_state* dev_state, const int32_t* time_steps, int
 int pf_step_end(pf_step_state* dev_state, int draws_used, void* stream);          /* index -= 1; draws += draws_used */
 int pf_randn_dev(float* out, size_t n, uint64_t seed, const pf_step_state* dev_state, int slot, uint64_t elem_offset, void* stream);
 
+/* ---- the training objective, forward only: what LightningLearner.validation_step logs as val/loss (lightning_learner.py:41-52) through
+ * LatentDiffusion.loss / DenoiseDiffusion.loss (stable_diffusion/latent_diffusion.py:203-240, ddpm/__init__.py:90-111).  Two memory-bound
+ * launches around the denoiser; the caller zero-fills the structs and sets what it needs.  All memory is caller-owned device memory;
+ * nothing is allocated and nothing synchronises.
+ *
+ * pf_qsample_rows - q_xt_x0 + q_sample with one time step PER SAMPLE (latent_diffusion.py:149-177, ddpm/__init__.py:36-64):
+ *     x_t[b][i] = sqrt_ab[t[b]] * x0[b][i] + sqrt_1mab[t[b]] * noise[b][i]       rows samples of row_elems floats
+ *   each product rounded, then the sum, as the reference's tensor operations.  sqrt_ab / sqrt_1mab are device tables of n_steps floats
+ *   that the host builds in float32 as the reference does (alpha_bar ** 0.5, (1 - alpha_bar) ** 0.5); t[b] outside [0, n_steps) is
+ *   clamped for memory safety only.  Noise: a tensor (rng == 0), or drawn in the kernel (rng == 1): element i of the [rows][row_elems]
+ *   tensor is exactly what pf_randn(seed, draw, elem_offset) writes at i; rng needs row_elems and elem_offset to be multiples of 4 and
+ *   16-byte aligned tensors.  noise_out (optional, rng == 1) receives the drawn noise.  x_t may alias x0. */
+typedef struct pf_qsample_rows_args {
+  const float* x0;                    /* [rows][row_elems] */
+  const float* noise;                 /* [rows][row_elems]; rng == 0 only */
+  const int64_t* t;                   /* [rows] */
+  const float *sqrt_ab, *sqrt_1mab;   /* [n_steps] */
+  int32_t n_steps;
+  int rng;                            /* 1: the noise is drawn in the kernel; noise must be NULL */
+  uint64_t seed, draw, elem_offset;   /* rng only */
+  float* x_t;                         /* [rows][row_elems] */
+  float* noise_out;                   /* optional, rng only */
+  int32_t rows; size_t row_elems;
+} pf_qsample_rows_args;
+int pf_qsample_rows(const pf_qsample_rows_args* a, void* stream);
+/* pf_mse_rows - the reduction of F.mse_loss(noise, eps_theta) (latent_diffusion.py:239-240, ddpm/__init__.py:110-111), kept per sample:
+ *     row_sum[b] = sum_i (noise[b][i] - eps_theta[b][i])^2        into a device double[rows]
+ *   the difference formed in float32, squared and accumulated in float64.  Noise: a tensor, or (rng == 1) RE-DRAWN in the kernel from the
+ *   (seed, draw, elem_offset) that pf_qsample_rows used - a loss evaluation with library noise never writes or reads a noise tensor.
+ *   The result is a function of the row's values alone: workgroup j of a row owns elements [j * PF_MSE_CHUNK, (j + 1) * PF_MSE_CHUNK),
+ *   reduces them in a fixed order and leaves one partial in `workspace` (pf_mse_rows_workspace_bytes(rows, row_elems) bytes, 8-byte
+ *   aligned); a second launch adds each row's partials in index order.  No atomics: bit-identical from call to call, between the two
+ *   noise forms and however the batch is split into calls (with elem_offset advanced by the rows in front). */
+#define PF_MSE_CHUNK 2048
+typedef struct pf_mse_rows_args {
+  const float* eps_theta;             /* [rows][row_elems] */
+  const float* noise;                 /* [rows][row_elems]; rng == 0 only */
+  int rng;                            /* 1: the noise is re-drawn in the kernel; noise must be NULL */
+  uint64_t seed, draw, elem_offset;   /* rng only */
+  double* row_sum;                    /* [rows] */
+  void* workspace; size_t workspace_bytes;
+  int32_t rows; size_t row_elems;
+} pf_mse_rows_args;
+size_t pf_mse_rows_workspace_bytes(int rows, size_t row_elems);
+int pf_mse_rows(const pf_mse_rows_args* a, void* stream);
+
 /* ---- weight broadcast over RCCL / xGMI.  The path has ONE exchange: rank 0 ships the packed weight
  * blob at start-up; the step loop has no collective.  librccl.so is opened on first use (dlopen), so a single-GPU process
  * never loads it.  `unique_id` is the 128-byte ncclUniqueId: rank 0 obtains it with pf_comm_unique_id and hands it to the

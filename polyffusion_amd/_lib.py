@@ -71,6 +71,23 @@ class DdimStepArgs(C.Structure):
                 + [(n, C.c_uint64) for n in ("seed", "draw", "elem_offset")] + [("x_out", C.c_void_p), ("n", C.c_size_t)])
 
 
+class QsampleRowsArgs(C.Structure):
+    """pf_qsample_rows_args (include/pfhip.h); filled by ``_steps.qsample_rows`` only."""
+    _fields_ = ([(n, C.c_void_p) for n in ("x0", "noise", "t", "sqrt_ab", "sqrt_1mab")] + [("n_steps", C.c_int32), ("rng", C.c_int)]
+                + [(n, C.c_uint64) for n in ("seed", "draw", "elem_offset")] + [("x_t", C.c_void_p), ("noise_out", C.c_void_p)]
+                + [("rows", C.c_int32), ("row_elems", C.c_size_t)])
+
+
+class MseRowsArgs(C.Structure):
+    """pf_mse_rows_args (include/pfhip.h); filled by ``_steps.mse_rows`` only."""
+    _fields_ = ([("eps_theta", C.c_void_p), ("noise", C.c_void_p), ("rng", C.c_int)] + [(n, C.c_uint64) for n in ("seed", "draw", "elem_offset")]
+                + [("row_sum", C.c_void_p), ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t), ("rows", C.c_int32),
+                   ("row_elems", C.c_size_t)])
+
+
+MSE_CHUNK = 2048           # PF_MSE_CHUNK: elements of a row one workgroup of pf_mse_rows reduces
+
+
 class UNetPrepared(C.Structure):
     """pf_unet_prepared (include/pfhip.h): the step-invariant prefix a sampler computes once per loop."""
     _fields_ = [("time_table", C.c_void_p), ("n_time_rows", C.c_int32), ("cross_bias", C.c_void_p)]
@@ -189,6 +206,9 @@ SIGNATURES = {
     "pf_step_begin": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
     "pf_step_end": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p]),
     "pf_randn_dev": (C.c_int, [C.c_void_p, C.c_size_t, C.c_uint64, C.c_void_p, C.c_int, C.c_uint64, C.c_void_p]),
+    "pf_qsample_rows": (C.c_int, [C.POINTER(QsampleRowsArgs), C.c_void_p]),
+    "pf_mse_rows_workspace_bytes": (C.c_size_t, [C.c_int, C.c_size_t]),
+    "pf_mse_rows": (C.c_int, [C.POINTER(MseRowsArgs), C.c_void_p]),
     "pf_comm_unique_id": (C.c_int, [C.c_void_p]),
     "pf_comm_init": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_void_p)]),
     "pf_comm_bcast": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p]),

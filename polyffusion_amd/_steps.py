@@ -1,5 +1,7 @@
 """The sampler's elementwise launches: noise, ``a*x + b*y`` and the two reverse-step updates (``pf_randn`` / ``pf_randn_dev``, ``pf_axpby``,
-``pf_ddpm_step``, ``pf_ddim_step`` of include/pfhip.h).  The only place that fills ``pf_ddpm_step_args`` / ``pf_ddim_step_args``:
+``pf_ddpm_step``, ``pf_ddim_step`` of include/pfhip.h), and the two launches of the training objective (``pf_qsample_rows``,
+``pf_mse_rows``) with the loss evaluation both diffusion mirrors share (``diffusion_loss_rows``).  The only place that fills
+``pf_ddpm_step_args`` / ``pf_ddim_step_args`` / ``pf_qsample_rows_args`` / ``pf_mse_rows_args``:
 ``sampler.py`` and ``ddpm.py`` decide WHICH route a step takes (coefficients by value or from a device table, noise tensors or
 in-kernel draws) and say so with keyword arguments; every launch goes to the current stream.  Tensors are read as dense buffers
 through raw pointers: callers pass contiguous float32 tensors.
@@ -76,3 +78,83 @@ def ddim_step(lib, x, eps, out, *, coef=None, table=None, state=None, noise=None
     """One DDIM update into ``out`` (may be ``x``).  ``rng``: ``None`` (noise from ``noise``) or ``(seed, draw, elem_offset)``."""
     return _launch(lib.pf_ddim_step, "pf_ddim_step", lib, _lib.DdimStepArgs(), x, eps, out, coef, table, state, rng,
                    ("seed", "draw", "elem_offset"), dict(noise=noise, orig=orig, orig_noise=orig_noise, mask=mask))
+
+
+# ---- the training objective, forward only (LatentDiffusion.loss / DenoiseDiffusion.loss of the reference) -------------------------------
+def sqrt_tables(alpha_bar: torch.Tensor, device):
+    """``alpha_bar ** 0.5`` and ``(1 - alpha_bar) ** 0.5`` on the float32 ``alpha_bar``, as ``q_xt_x0`` / ``q_sample`` compute them
+    (latent_diffusion.py:157-159, 177; ddpm/__init__.py:44-46, 64), as device tables for ``pf_qsample_rows``."""
+    ab = alpha_bar.detach().to(device="cpu", dtype=torch.float32)
+    # x ** 0.5 is the correctly rounded float32 square root where the host's float32 pow is IEEE-exact - and on some CPUs torch's
+    # vectorised float32 pow is not (seen: one ulp at (1 - alpha_bar[999]) ** 0.5 of the ddpm schedule).  The float64 square root rounded
+    # to float32 IS that value on every host (53 >= 2 * 24 + 2 bits: the double rounding is innocuous); 1 - alpha_bar stays a float32 operation.
+    root = lambda v: torch.sqrt(v.double()).float()
+    return root(ab).to(device).contiguous(), root(1 - ab).to(device).contiguous()
+
+
+def time_steps(t, batch: int, n_steps: int, seed: int, device) -> torch.Tensor:
+    """The ``t`` of a loss evaluation as a device int64 ``[batch]``.  ``None``: ``randint(0, n_steps)`` from a CPU generator seeded with
+    ``seed`` (the reference draws on the device from the global generator, which nothing can pin).  A ``t`` held on the host - a
+    sequence, a CPU tensor, or the one drawn here - is range-checked; a device tensor is taken as it is (the kernel clamps)."""
+    if t is None:
+        t = torch.randint(0, n_steps, (batch,), generator=torch.Generator().manual_seed(int(seed)), dtype=torch.int64)
+    elif not isinstance(t, torch.Tensor):
+        t = torch.as_tensor(t, dtype=torch.int64)
+    if t.dim() != 1 or t.shape[0] != batch:
+        raise RuntimeError(f"time steps of shape {tuple(t.shape)} for a batch of {batch}")
+    if t.device.type == "cpu" and batch and (int(t.min()) < 0 or int(t.max()) >= n_steps):
+        raise RuntimeError(f"time step outside [0, {n_steps}): {t.tolist()}")
+    return t.to(device=device, dtype=torch.int64).contiguous()
+
+
+def _rng_fields(args, rng):
+    if rng is not None:
+        args.rng = 1
+        args.seed, args.draw, args.elem_offset = (int(v) for v in rng)
+
+
+def qsample_rows(lib, x0, t, sqrt_ab, sqrt_1mab, *, noise=None, rng=None, noise_out=None, out=None) -> torch.Tensor:
+    """``x_t[b] = sqrt_ab[t[b]] * x0[b] + sqrt_1mab[t[b]] * noise[b]`` (``pf_qsample_rows``).  ``noise``: a tensor like ``x0``, or
+    ``rng = (seed, draw, elem_offset)``: drawn in the kernel (``noise_out``, optional, receives it).  ``t``: device int64 ``[B]``."""
+    a = _lib.QsampleRowsArgs()
+    if out is None:
+        out = torch.empty_like(x0)
+    a.x0, a.noise, a.t, a.x_t, a.noise_out = x0.data_ptr(), _lib.ptr(noise), t.data_ptr(), out.data_ptr(), _lib.ptr(noise_out)
+    a.sqrt_ab, a.sqrt_1mab, a.n_steps = sqrt_ab.data_ptr(), sqrt_1mab.data_ptr(), sqrt_ab.numel()
+    a.rows, a.row_elems = x0.shape[0], x0.numel() // max(1, x0.shape[0])
+    _rng_fields(a, rng)
+    _lib.check(lib.pf_qsample_rows(C.byref(a), _lib.current_stream()), "pf_qsample_rows", lib)
+    return out
+
+
+def mse_rows(lib, eps_theta, *, noise=None, rng=None) -> torch.Tensor:
+    """``sum_i (noise[b, i] - eps_theta[b, i]) ** 2`` per sample as float64 ``[B]`` (``pf_mse_rows``); ``noise``: a tensor, or
+    ``rng = (seed, draw, elem_offset)``: re-drawn in the kernel."""
+    a = _lib.MseRowsArgs()
+    rows, row_elems = eps_theta.shape[0], eps_theta.numel() // max(1, eps_theta.shape[0])
+    out = torch.empty(rows, dtype=torch.float64, device=eps_theta.device)
+    nb = int(lib.pf_mse_rows_workspace_bytes(rows, row_elems))
+    ws = torch.empty(max(nb, 8) // 8, dtype=torch.float64, device=eps_theta.device)
+    a.eps_theta, a.noise, a.row_sum, a.workspace, a.workspace_bytes = eps_theta.data_ptr(), _lib.ptr(noise), out.data_ptr(), ws.data_ptr(), nb
+    a.rows, a.row_elems = rows, row_elems
+    _rng_fields(a, rng)
+    _lib.check(lib.pf_mse_rows(C.byref(a), _lib.current_stream()), "pf_mse_rows", lib)
+    return out
+
+
+def diffusion_loss_rows(lib, x0, t, tables, predict, *, noise=None, rng=None):
+    """The body both ``loss`` methods share (latent_diffusion.py:226-240, ddpm/__init__.py:105-111): ``x_t = q_sample(x0, t, noise)``,
+    ``eps_theta = predict(x_t)``, then the per-sample mean of ``(noise - eps_theta) ** 2`` as float64 ``[B]``.  Returns
+    ``(loss_rows, x_t, eps_theta)``.  With ``rng`` the noise exists only inside the two kernels."""
+    x0 = x0.contiguous().float()
+    if noise is not None:
+        noise = noise.to(device=x0.device, dtype=torch.float32).contiguous()
+        if noise.shape != x0.shape:
+            raise RuntimeError(f"noise of shape {tuple(noise.shape)} for x0 of shape {tuple(x0.shape)}")
+        rng = None
+    xt = qsample_rows(lib, x0, t, tables[0], tables[1], noise=noise, rng=rng)
+    eps_theta = predict(xt).contiguous()
+    if eps_theta.shape != x0.shape:
+        raise RuntimeError(f"the model predicts {tuple(eps_theta.shape)} for noise of shape {tuple(x0.shape)}")
+    rows = mse_rows(lib, eps_theta, noise=noise, rng=rng)
+    return rows / float(x0.numel() // x0.shape[0]), xt, eps_theta

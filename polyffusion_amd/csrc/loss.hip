@@ -1,0 +1,187 @@
+// loss.hip - the training objective, forward only (gfx950): the two memory-bound launches around the denoiser in
+// LatentDiffusion.loss / DenoiseDiffusion.loss (stable_diffusion/latent_diffusion.py:149-177, 203-240; ddpm/__init__.py:36-64, 90-111):
+//   qsample_rows - x_t = sqrt(alpha_bar_t) x0 + sqrt(1 - alpha_bar_t) noise with one t per sample,
+//   mse_rows     - per-sample sum of (noise - eps_theta)^2 in float64, as per-chunk partials + an in-order second pass.
+// Both read and write 16 bytes per lane and take one Philox call per four elements when the noise is drawn (or re-drawn) in the kernel.
+#include "noise.h"
+
+namespace pf {
+
+namespace {
+
+constexpr int kThreads = 256;
+constexpr int kQChunk = 4 * kThreads;            // elements of a row one qsample workgroup owns: one 16-byte group per lane
+constexpr int kMseGroups = PF_MSE_CHUNK / 4 / kThreads;   // 16-byte groups of a chunk per lane
+static_assert(PF_MSE_CHUNK == 4 * kThreads * kMseGroups, "PF_MSE_CHUNK must be a whole number of 16-byte groups per lane");
+
+// four consecutive elements of a row starting at element e (a multiple of 4): one 16-byte access when the tensor allows it (VEC),
+// else element by element; elements at or past `n` read as 0 / are not written
+template <bool VEC>
+__device__ __forceinline__ f32x4 load4(const float* __restrict__ p, size_t e, size_t n) {
+  if (VEC) return *reinterpret_cast<const f32x4*>(p + e);
+  f32x4 v = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+  for (int j = 0; j < 4; ++j)
+    if (e + j < n) v[j] = p[e + j];
+  return v;
+}
+template <bool VEC>
+__device__ __forceinline__ void store4(float* p, size_t e, size_t n, f32x4 v) {
+  if (VEC) { *reinterpret_cast<f32x4*>(p + e) = v; return; }
+#pragma unroll
+  for (int j = 0; j < 4; ++j)
+    if (e + j < n) p[e + j] = v[j];
+}
+
+// workgroup = (row, chunk of kQChunk elements); lane = one 16-byte group.  x_t and x0 carry no __restrict__: x_t may alias x0.
+template <bool VEC, bool RNG>
+__global__ __launch_bounds__(kThreads) void qsample_rows_kernel(const float* x0, const float* __restrict__ noise, const long long* __restrict__ t,
+                                                               const float* __restrict__ sqrt_ab, const float* __restrict__ sqrt_1mab, int n_steps,
+                                                               uint64_t seed, uint64_t draw, uint64_t off, float* xt, float* __restrict__ noise_out,
+                                                               size_t row_elems, unsigned chunks) {
+  const unsigned row = blockIdx.x / chunks, chunk = blockIdx.x - row * chunks;
+  const size_t e = (size_t)chunk * kQChunk + 4 * (size_t)threadIdx.x;
+  if (e >= row_elems) return;
+  long long tv = t[row];
+  tv = tv < 0 ? 0 : (tv >= n_steps ? n_steps - 1 : tv);       // memory safety only: the host mirror rejects a bad t it can see
+  const float a = sqrt_ab[tv], b = sqrt_1mab[tv];
+  const size_t base = (size_t)row * row_elems;
+  f32x4 nz;
+  if (RNG) {
+    nz = philox_normal4v((off + base + e) >> 2, draw, seed);
+    if (noise_out) store4<true>(noise_out + base, e, row_elems, nz);
+  } else {
+    nz = load4<VEC>(noise + base, e, row_elems);
+  }
+  const f32x4 xv = load4<VEC>(x0 + base, e, row_elems);
+  f32x4 o;
+#pragma unroll
+  for (int j = 0; j < 4; ++j) o[j] = add_rn(mul_rn(a, xv[j]), mul_rn(b, nz[j]));
+  store4<VEC>(xt + base, e, row_elems, o);
+}
+
+// workgroup = (row, chunk of PF_MSE_CHUNK elements).  Lane l owns groups l, l + 256, ... of the chunk and adds their squares in element
+// order; the lanes of a wave are combined by a butterfly (every lane ends with the same sum), the four waves in wave order.  The order is
+// fixed by (row_elems, element index) alone, so VEC and the element-by-element form give the same bits.
+template <bool VEC, bool RNG>
+__global__ __launch_bounds__(kThreads) void mse_partial_kernel(const float* __restrict__ eps, const float* __restrict__ noise, uint64_t seed,
+                                                              uint64_t draw, uint64_t off, double* __restrict__ partial, size_t row_elems,
+                                                              unsigned chunks) {
+  __shared__ double wave_sum[kThreads / 64];
+  const unsigned row = blockIdx.x / chunks, chunk = blockIdx.x - row * chunks;
+  const size_t base = (size_t)row * row_elems;
+  double acc = 0.0;
+#pragma unroll
+  for (int k = 0; k < kMseGroups; ++k) {
+    const size_t e = (size_t)chunk * PF_MSE_CHUNK + 4 * ((size_t)k * kThreads + threadIdx.x);
+    if (e < row_elems) {
+      const f32x4 nz = RNG ? philox_normal4v((off + base + e) >> 2, draw, seed) : load4<VEC>(noise + base, e, row_elems);
+      const f32x4 ev = load4<VEC>(eps + base, e, row_elems);
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const double d = (double)sub_rn(nz[j], ev[j]);      // the difference in float32, as the reference forms it
+        acc += d * d;                                       // exact product (48 bits), float64 sum
+      }
+    }
+  }
+#pragma unroll
+  for (int m = 32; m >= 1; m >>= 1) acc += __shfl_xor(acc, m, 64);
+  if ((threadIdx.x & 63) == 0) wave_sum[threadIdx.x >> 6] = acc;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    double s = wave_sum[0];
+#pragma unroll
+    for (int w = 1; w < kThreads / 64; ++w) s += wave_sum[w];
+    partial[(size_t)row * chunks + chunk] = s;
+  }
+}
+// one lane per row: the row's partials in index order
+__global__ void mse_finish_kernel(const double* __restrict__ partial, double* __restrict__ row_sum, int rows, unsigned chunks) {
+  const int row = blockIdx.x * blockDim.x + threadIdx.x;
+  if (row >= rows) return;
+  double s = 0.0;
+  for (unsigned c = 0; c < chunks; ++c) s += partial[(size_t)row * chunks + c];
+  row_sum[row] = s;
+}
+
+inline bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
+inline size_t chunks_of(size_t row_elems, size_t chunk) { return (row_elems + chunk - 1) / chunk; }
+
+}  // namespace
+
+size_t mse_rows_workspace_bytes(int rows, size_t row_elems) {
+  if (rows <= 0 || row_elems == 0) return 0;
+  return (size_t)rows * chunks_of(row_elems, PF_MSE_CHUNK) * sizeof(double);
+}
+
+int launch_qsample_rows(const pf_qsample_rows_args& a, hipStream_t s) {
+  PF_REQUIRE(a.x0 && a.t && a.sqrt_ab && a.sqrt_1mab && a.x_t && a.rows > 0 && a.row_elems > 0 && a.n_steps > 0, "qsample_rows: bad arguments");
+  const size_t chunks = chunks_of(a.row_elems, kQChunk);
+  PF_REQUIRE(chunks * (size_t)a.rows < (1ull << 31), "qsample_rows: %d rows of %zu elements are more workgroups than one launch holds", a.rows, a.row_elems);
+  const bool vec = a.row_elems % 4 == 0 && aligned16(a.x0) && aligned16(a.x_t) && aligned16(a.noise) && aligned16(a.noise_out);
+  const dim3 grid((unsigned)(chunks * a.rows)), block(kThreads);
+  const long long* t = reinterpret_cast<const long long*>(a.t);
+  if (a.rng) {
+    PF_REQUIRE(!a.noise, "qsample_rows_rng: the noise is drawn in the kernel, the noise tensor must be NULL");
+    PF_REQUIRE(a.row_elems % 4 == 0 && a.elem_offset % 4 == 0, "qsample_rows_rng: row_elems and elem_offset must be multiples of 4 (one Philox call yields four normals)");
+    PF_REQUIRE(vec, "qsample_rows_rng: tensors must be 16-byte aligned");
+    hipLaunchKernelGGL((qsample_rows_kernel<true, true>), grid, block, 0, s, a.x0, nullptr, t, a.sqrt_ab, a.sqrt_1mab, a.n_steps, a.seed, a.draw,
+                       a.elem_offset, a.x_t, a.noise_out, a.row_elems, (unsigned)chunks);
+  } else {
+    PF_REQUIRE(a.noise && !a.noise_out, "qsample_rows: a noise tensor is required without rng (and noise_out belongs to rng)");
+    if (vec)
+      hipLaunchKernelGGL((qsample_rows_kernel<true, false>), grid, block, 0, s, a.x0, a.noise, t, a.sqrt_ab, a.sqrt_1mab, a.n_steps, 0, 0, 0, a.x_t,
+                         nullptr, a.row_elems, (unsigned)chunks);
+    else
+      hipLaunchKernelGGL((qsample_rows_kernel<false, false>), grid, block, 0, s, a.x0, a.noise, t, a.sqrt_ab, a.sqrt_1mab, a.n_steps, 0, 0, 0, a.x_t,
+                         nullptr, a.row_elems, (unsigned)chunks);
+  }
+  PF_CHECK_HIP(hipGetLastError());
+  return PF_OK;
+}
+
+int launch_mse_rows(const pf_mse_rows_args& a, hipStream_t s) {
+  PF_REQUIRE(a.eps_theta && a.row_sum && a.rows > 0 && a.row_elems > 0, "mse_rows: bad arguments");
+  const size_t chunks = chunks_of(a.row_elems, PF_MSE_CHUNK), need = mse_rows_workspace_bytes(a.rows, a.row_elems);
+  PF_REQUIRE(chunks * (size_t)a.rows < (1ull << 31), "mse_rows: %d rows of %zu elements are more workgroups than one launch holds", a.rows, a.row_elems);
+  PF_REQUIRE(a.workspace && a.workspace_bytes >= need && ((uintptr_t)a.workspace & 7) == 0 && ((uintptr_t)a.row_sum & 7) == 0,
+             "mse_rows: workspace of %zu bytes (8-byte aligned) required, got %zu", need, a.workspace_bytes);
+  const bool vec = a.row_elems % 4 == 0 && aligned16(a.eps_theta) && aligned16(a.noise);
+  const dim3 grid((unsigned)(chunks * a.rows)), block(kThreads);
+  double* partial = reinterpret_cast<double*>(a.workspace);
+  if (a.rng) {
+    PF_REQUIRE(!a.noise, "mse_rows_rng: the noise is re-drawn in the kernel, the noise tensor must be NULL");
+    PF_REQUIRE(a.row_elems % 4 == 0 && a.elem_offset % 4 == 0, "mse_rows_rng: row_elems and elem_offset must be multiples of 4 (one Philox call yields four normals)");
+    PF_REQUIRE(vec, "mse_rows_rng: tensors must be 16-byte aligned");
+    hipLaunchKernelGGL((mse_partial_kernel<true, true>), grid, block, 0, s, a.eps_theta, nullptr, a.seed, a.draw, a.elem_offset, partial, a.row_elems,
+                       (unsigned)chunks);
+  } else {
+    PF_REQUIRE(a.noise, "mse_rows: a noise tensor is required without rng");
+    if (vec)
+      hipLaunchKernelGGL((mse_partial_kernel<true, false>), grid, block, 0, s, a.eps_theta, a.noise, 0, 0, 0, partial, a.row_elems, (unsigned)chunks);
+    else
+      hipLaunchKernelGGL((mse_partial_kernel<false, false>), grid, block, 0, s, a.eps_theta, a.noise, 0, 0, 0, partial, a.row_elems, (unsigned)chunks);
+  }
+  PF_CHECK_HIP(hipGetLastError());
+  hipLaunchKernelGGL(mse_finish_kernel, dim3((unsigned)cdiv(a.rows, 64)), dim3(64), 0, s, partial, a.row_sum, a.rows, (unsigned)chunks);
+  PF_CHECK_HIP(hipGetLastError());
+  return PF_OK;
+}
+
+}  // namespace pf
+
+using namespace pf;
+
+extern "C" {
+
+int pf_qsample_rows(const pf_qsample_rows_args* a, void* stream) {
+  PF_REQUIRE(a, "pf_qsample_rows: null arguments");
+  return launch_qsample_rows(*a, (hipStream_t)stream);
+}
+size_t pf_mse_rows_workspace_bytes(int rows, size_t row_elems) { return mse_rows_workspace_bytes(rows, row_elems); }
+int pf_mse_rows(const pf_mse_rows_args* a, void* stream) {
+  PF_REQUIRE(a, "pf_mse_rows: null arguments");
+  return launch_mse_rows(*a, (hipStream_t)stream);
+}
+
+}  // extern "C"

@@ -110,6 +110,10 @@ int launch_mfma_probe(float* sink, int iters, double* flops, hipStream_t s);
 int launch_step_state_set(pf_step_state* st, int64_t index, uint64_t draws, hipStream_t s);
 int launch_step_begin(const pf_step_state* st, const int* time_steps, int64_t* t_out, int batch, hipStream_t s);
 int launch_step_end(pf_step_state* st, int draws_used, hipStream_t s);
+// the training objective, forward only (loss.hip): forward noising with one t per sample, and the per-sample squared error in float64
+int launch_qsample_rows(const pf_qsample_rows_args& a, hipStream_t s);
+size_t mse_rows_workspace_bytes(int rows, size_t row_elems);
+int launch_mse_rows(const pf_mse_rows_args& a, hipStream_t s);
 
 // vanilla DDPM network (attention_wide.hip): single-head attention with a wide head (exact fp32; scratch = batch * l * l floats), the
 // ConvTranspose2d(4, 2, 1) parity fold (fold: [Cout][Cin][16], the pack_upfold_bf3 tap order; fp32 packing [4][4][Cin][Cout]) and its fp32

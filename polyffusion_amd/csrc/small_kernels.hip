@@ -6,6 +6,7 @@
 //   counter-based Gaussian noise, GRU gate update and the texture-encoder front end
 //   (dl_modules/chord_enc.py:15-22, txt_enc.py:23-27).
 #include "pf_internal.h"
+#include "noise.h"
 
 namespace pf {
 
@@ -434,14 +435,7 @@ int launch_matvec_exp(const float* x, int ldx, const float* w, const float* bias
 }
 
 // ------------------------------------------------------------------ sampler elementwise kernels
-// Individually rounded fp32 operations the optimiser cannot merge.  __fmul_rn / __fadd_rn are plain * and + in this toolchain (no
-// OCML_BASIC_ROUNDED_OPERATIONS) and `#pragma clang fp contract(off)` does not survive inlining + SLP vectorisation here (the *_step_rng
-// kernels came out with v_pk_fma_f32 where the scalar kernels had separate multiplies and adds: last-bit differences between two
-// kernels that must agree).  One opaque VALU instruction per operation: every kernel that inlines the update computes the same bits,
-// in the reference's operation order (each product rounded, then the sum).
-__device__ __forceinline__ float mul_rn(float a, float b) { float r; asm("v_mul_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b)); return r; }
-__device__ __forceinline__ float add_rn(float a, float b) { float r; asm("v_add_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b)); return r; }
-__device__ __forceinline__ float sub_rn(float a, float b) { float r; asm("v_sub_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b)); return r; }
+// (mul_rn / add_rn / sub_rn, the individually rounded fp32 operations of the updates below: noise.h)
 
 static inline dim3 ew_grid(size_t n) { return dim3((unsigned)min((size_t)2048, (n + 255) / 256)); }
 
@@ -552,37 +546,7 @@ int launch_step_end(pf_step_state* st, int draws_used, hipStream_t s) {
   return PF_OK;
 }
 
-// ------------------------------------------------------------------ Philox4x32-10 + Box-Muller
-__device__ __forceinline__ void philox_round(uint32_t& c0, uint32_t& c1, uint32_t& c2, uint32_t& c3, uint32_t k0, uint32_t k1) {
-  const uint64_t p0 = (uint64_t)0xD2511F53u * c0, p1 = (uint64_t)0xCD9E8D57u * c2;
-  const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c1 ^ k0, n1 = (uint32_t)p1;
-  const uint32_t n2 = (uint32_t)(p0 >> 32) ^ c3 ^ k1, n3 = (uint32_t)p0;
-  c0 = n0; c1 = n1; c2 = n2; c3 = n3;
-}
-// the four standard normals of group g (elements 4g .. 4g+3 of the global tensor) of draw `sid`.
-// NOT inlined: randn_kernel and the *_step_rng kernels must produce the same bits for the same (g, sid, seed), and the generated code
-// of logf / sincosf / the products around them depends on its surroundings when inlined (measured: two calls in one kernel differ from
-// the stand-alone kernel in the last bit of ~20 % of the draws) - one shared body is the same arithmetic by construction.
-__device__ __noinline__ f32x4 philox_normal4v(uint64_t g, uint64_t sid, uint64_t seed) {
-#pragma clang fp contract(off)
-  float z[4];
-  uint32_t c0 = (uint32_t)g, c1 = (uint32_t)(g >> 32), c2 = (uint32_t)sid, c3 = (uint32_t)(sid >> 32);
-  uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32);
-#pragma unroll
-  for (int r = 0; r < 10; ++r) { philox_round(c0, c1, c2, c3, k0, k1); k0 += 0x9E3779B9u; k1 += 0xBB67AE85u; }
-  const float u0 = ((float)(c0 >> 8) + 0.5f) * (1.0f / 16777216.0f), u1 = ((float)(c1 >> 8) + 0.5f) * (1.0f / 16777216.0f);
-  const float u2 = ((float)(c2 >> 8) + 0.5f) * (1.0f / 16777216.0f), u3 = ((float)(c3 >> 8) + 0.5f) * (1.0f / 16777216.0f);
-  const float ra = sqrtf(-2.0f * logf(u0)), rb = sqrtf(-2.0f * logf(u2));
-  float sa, ca, sb, cb;
-  sincosf(6.283185307179586f * u1, &sa, &ca);
-  sincosf(6.283185307179586f * u3, &sb, &cb);
-  z[0] = ra * ca; z[1] = ra * sa; z[2] = rb * cb; z[3] = rb * sb;
-  return f32x4{z[0], z[1], z[2], z[3]};
-}
-__device__ __forceinline__ void philox_normal4(uint64_t g, uint64_t sid, uint64_t seed, float (&z)[4]) {
-  const f32x4 v = philox_normal4v(g, sid, seed);
-  z[0] = v[0]; z[1] = v[1]; z[2] = v[2]; z[3] = v[3];
-}
+// ------------------------------------------------------------------ counter-based Gaussian noise (Philox4x32-10 + Box-Muller: noise.h)
 __device__ __forceinline__ void randn_body(float* __restrict__ out, size_t n, uint64_t seed, uint64_t sid, uint64_t off) {
   const uint64_t g0 = off >> 2, g1 = (off + n + 3) >> 2;
   for (uint64_t g = g0 + (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; g < g1; g += (uint64_t)gridDim.x * blockDim.x) {

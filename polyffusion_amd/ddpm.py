@@ -193,10 +193,55 @@ class DenoiseDiffusion:
     def _randn(self, shape, device) -> torch.Tensor:
         return _steps.draw(self, shape, device)
 
-    def q_sample(self, x0: torch.Tensor, t: int, eps: Optional[torch.Tensor] = None) -> torch.Tensor:
-        """x_t = sqrt(alpha_bar_t) x0 + sqrt(1 - alpha_bar_t) eps (``q_xt_x0`` + ``q_sample``), one ``t`` for the whole batch."""
-        ab = self.alpha_bar[t]
-        return _steps.q_sample(self, x0.contiguous().float(), eps, ab ** 0.5, (1 - ab) ** 0.5)
+    def _tables(self, device):
+        """``alpha_bar ** 0.5`` / ``(1 - alpha_bar) ** 0.5`` in float32 on ``device`` (built once per device)."""
+        key = str(device)
+        cache = self.__dict__.setdefault("_sqrt_tables", {})
+        if key not in cache:
+            cache[key] = _steps.sqrt_tables(self.alpha_bar, device)
+        return cache[key]
+
+    def q_xt_x0(self, x0: torch.Tensor, t: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+        """``(mean, var)`` of q(x_t | x_0) (ddpm/__init__.py:36-48): ``alpha_bar[t] ** 0.5 * x0`` and ``1 - alpha_bar[t]`` shaped
+        ``[B, 1, 1, 1]``.  An accessor kept for parity (two torch operations); ``q_sample`` / ``loss`` run the kernels."""
+        ab = self.alpha_bar.to(x0.device)[t.to(x0.device)].reshape(-1, *([1] * (x0.dim() - 1)))
+        return ab ** 0.5 * x0, 1 - ab
+
+    def q_sample(self, x0: torch.Tensor, t, eps: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """x_t = sqrt(alpha_bar_t) x0 + sqrt(1 - alpha_bar_t) eps (``q_xt_x0`` + ``q_sample``, ddpm/__init__.py:36-64).  ``t``: an
+        ``int`` - one time step for the whole batch, ``pf_axpby`` - or a tensor of one time step per sample (``pf_qsample_rows``).
+        ``eps=None``: the owner's next draw (``noise_fn``, else the library's generator: made inside the kernel on the tensor route)."""
+        if not isinstance(t, torch.Tensor):
+            ab = self.alpha_bar[t]
+            return _steps.q_sample(self, x0.contiguous().float(), eps, ab ** 0.5, (1 - ab) ** 0.5)
+        x0 = x0.contiguous().float()
+        tt = _steps.time_steps(t, x0.shape[0], self.n_steps, 0, x0.device)
+        sa, sb = self._tables(x0.device)
+        if eps is None and self.noise_fn is not None:
+            eps = _steps.draw(self, x0.shape, x0.device)
+        if eps is not None:
+            return _steps.qsample_rows(self._lib, x0, tt, sa, sb, noise=eps.to(device=x0.device, dtype=torch.float32).contiguous())
+        out = _steps.qsample_rows(self._lib, x0, tt, sa, sb, rng=(self.seed, self._draws, 0))
+        self._draws += 1
+        return out
+
+    def loss_rows(self, x0: torch.Tensor, noise: Optional[torch.Tensor] = None, *, t=None, seed: Optional[int] = None, draw: int = 0,
+                  elem_offset: int = 0, return_t: bool = False):
+        """The per-sample mean of ``(noise - eps_theta) ** 2`` as float64 ``[B]``; ``loss`` is its mean.  See ``loss``."""
+        dev = self.eps_model.device
+        seed = self.seed if seed is None else int(seed)
+        t = _steps.time_steps(t, x0.shape[0], self.n_steps, seed, dev)
+        rows = _steps.diffusion_loss_rows(self._lib, x0.to(dev), t, self._tables(dev), lambda xt: self.eps_model(xt, t), noise=noise,
+                                          rng=(seed, draw, elem_offset))[0]
+        return (rows, t) if return_t else rows
+
+    def loss(self, x0: torch.Tensor, noise: Optional[torch.Tensor] = None, *, t=None, seed: Optional[int] = None, draw: int = 0,
+             elem_offset: int = 0) -> torch.Tensor:
+        """``F.mse_loss(noise, eps_model(q_sample(x0, t, noise), t))`` (ddpm/__init__.py:90-111) as a 0-d float32 tensor.  ``t=None``:
+        ``randint(0, n_steps, (B,))`` from a CPU ``torch.Generator`` seeded with ``seed`` (default: the object's seed; the reference
+        draws on the device from the global generator).  ``noise=None``: draw ``draw`` of the library's generator under ``seed``, keyed
+        by the global element index ``elem_offset + i`` and made inside the two kernels - it never exists as a tensor."""
+        return self.loss_rows(x0, noise, t=t, seed=seed, draw=draw, elem_offset=elem_offset).mean().float()
 
     def coef(self, t: int) -> "_lib.DdpmCoef":
         """``p_sample``'s mean = 1/sqrt(a) (x - (1-a)/sqrt(1-ab) eps), sigma = sqrt(beta) as the library's step coefficients."""
@@ -238,6 +283,29 @@ class DenoiseDiffusion:
             if callback is not None:
                 callback(t_, t, xt)
         return xt
+
+
+class Polyffusion_DDPM:
+    """``models/model_ddpm.py``: the wrapper the reference's learner drives.  ``get_loss_dict`` (:32-37) is the whole of it here."""
+
+    def __init__(self, ddpm: DenoiseDiffusion, params: Optional[Mapping] = None, max_simu_note: int = 20):
+        self.ddpm, self.params = ddpm, params
+
+    def p_sample(self, xt: torch.Tensor, t: int) -> torch.Tensor:
+        return self.ddpm.p_sample(xt, t)
+
+    def q_sample(self, x0: torch.Tensor, t) -> torch.Tensor:
+        return self.ddpm.q_sample(x0, t)
+
+    def get_loss_dict(self, batch, step, *, detail: bool = False, **loss_kw):
+        """``{"loss": ddpm.loss(prmat2c)}`` for a reference-layout batch ``(prmat2c, pnotree, chord, prmat)``; ``loss_kw`` (``noise``,
+        ``t``, ``seed``, ``draw``, ``elem_offset``) go to ``DenoiseDiffusion.loss``; ``detail=True`` adds the per-sample ``"loss_rows"``
+        (float64 ``[B]``) and the ``"t"`` they were evaluated at."""
+        prmat2c = batch[0]
+        if not detail:
+            return {"loss": self.ddpm.loss(prmat2c, **loss_kw)}
+        rows, t = self.ddpm.loss_rows(prmat2c, return_t=True, **loss_kw)
+        return {"loss": rows.mean().float(), "loss_rows": rows, "t": t}
 
 
 def state_from_checkpoint(path: str) -> Tuple["OrderedDict[str, torch.Tensor]", Optional[torch.Tensor], Optional[dict]]:

@@ -7,11 +7,14 @@
   (:153-164) and ``load_trained`` (:59-84; legacy ``.pt`` with ``{"model": state_dict}``).
 * ``load_pretrained_chd_enc`` / ``load_pretrained_txt_enc``: the key-prefix remaps of
   ``utils.py:48-86`` (``chord_enc.`` / ``rhy_encoder.``).
+* ``get_loss_dict`` (:185-234): the condition of a training batch and ``ldm.loss`` on it - what the reference's learner logs as
+  ``val/loss``.
 * ``PianoTreeDecoder`` / ``ChordDecoder`` (``decoders.py``), ``_decode_pnotree`` (:166-183), ``_decode_chord`` (:108-136) and
   ``load_pretrained_pnotree_enc_dec`` / ``load_pretrained_chd_enc_dec`` (``utils.py:19-69``).
 """
 from __future__ import annotations
 
+import random
 from types import SimpleNamespace
 from typing import Mapping, Optional
 
@@ -246,3 +249,47 @@ class Polyffusion_SDF:
         # [B,128,128] -> [B*4,32,128] is a pure view and the means come back as [B, 4*z] = cat(dim=-1)
         segs = prmat.contiguous().view(B * 4, 32, prmat.shape[2])
         return self.txt_enc(segs).mean.view(B, 1, -1)
+
+    def get_loss_dict(self, batch, step, *, detail: bool = False, **loss_kw):
+        """models/model_sdf.py:185-234: the condition of a reference-layout batch ``(prmat2c, pnotree, chord, prmat)`` by ``cond_type``
+        (``chord`` | ``pnotree`` | ``txt`` | ``chord+txt``), replaced by all -1 under ``cond_mode`` ``uncond`` and, under ``mix`` /
+        ``mix2``, with probability 0.2 - Python's ``random.random() < 0.2`` in the reference's call order (``chord+txt`` with ``mix2``:
+        the chord draw, the texture draw, then the whole-condition draw), so a seeded ``random`` makes the reference's choices.  Returns
+        ``{"loss": ldm.loss(prmat2c, cond)}``.
+
+        ``concat_blurry``: at HEAD the reference calls ``exit(0)`` on this branch (:227-230); here it computes what the line after
+        that says, ``ldm.loss(prmat2c, cond, cond_concat=get_blurry_image(prmat2c, ratio=concat_ratio))``.
+
+        ``loss_kw`` (``noise``, ``t``, ``seed``, ``draw``, ``elem_offset``) go to ``ldm.loss``; ``detail=True`` adds the per-sample
+        ``"loss_rows"`` (float64 ``[B]``) and the ``"t"`` they were evaluated at."""
+        prmat2c, pnotree, chord, prmat = batch
+        if self.cond_type == "chord":
+            cond = self._encode_chord(chord)
+        elif self.cond_type == "pnotree":
+            cond = self._encode_pnotree(pnotree)
+        elif self.cond_type == "txt":
+            cond = self._encode_txt(prmat)
+        elif self.cond_type == "chord+txt":
+            zchd = self._encode_chord(chord)
+            ztxt = self._encode_txt(prmat)
+            if self.cond_mode == "mix2":
+                if random.random() < 0.2:
+                    zchd = -torch.ones_like(zchd)
+                if random.random() < 0.2:
+                    ztxt = -torch.ones_like(ztxt)
+            cond = torch.cat([zchd, ztxt], dim=-1)
+        else:
+            raise NotImplementedError(f"cond_type {self.cond_type!r}")
+        if self.cond_mode == "uncond":
+            cond = -torch.ones_like(cond)
+        elif self.cond_mode in ("mix", "mix2"):
+            if random.random() < 0.2:
+                cond = -torch.ones_like(cond)
+        cond_concat = None
+        if self.concat_blurry:
+            from .inference_sdf import get_blurry_image
+            cond_concat = get_blurry_image(prmat2c, ratio=self.concat_ratio)
+        if not detail:
+            return {"loss": self.ldm.loss(prmat2c, cond, cond_concat=cond_concat, **loss_kw)}
+        rows, t = self.ldm.loss_rows(prmat2c, cond, cond_concat=cond_concat, return_t=True, **loss_kw)
+        return {"loss": rows.mean().float(), "loss_rows": rows, "t": t}

@@ -17,7 +17,7 @@ from typing import Iterable, List, Optional, Tuple
 
 import torch
 
-from . import _lib
+from . import _lib, _steps
 from ._handle import ModelHandle
 from .arch import UNetConfig
 
@@ -280,6 +280,64 @@ class LatentDiffusion:
         if self.first_stage_model is None:
             return z
         return self.first_stage_model.decode(z, self.latent_scaling_factor)
+
+    # ---- the training objective, forward only (latent_diffusion.py:149-177, 203-240) -----------------------------------------------
+    def _tables(self, device):
+        """``alpha_bar ** 0.5`` / ``(1 - alpha_bar) ** 0.5`` in float32 on ``device`` (built once per device)."""
+        key = str(device)
+        cache = self.__dict__.setdefault("_sqrt_tables", {})
+        if key not in cache:
+            cache[key] = _steps.sqrt_tables(self.alpha_bar, device)
+        return cache[key]
+
+    def q_xt_x0(self, x0: torch.Tensor, t: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+        """``(mean, var)`` of q(x_t | x_0) (latent_diffusion.py:149-161): ``alpha_bar[t] ** 0.5 * x0`` and ``1 - alpha_bar[t]``, the
+        latter shaped ``[B, 1, 1, 1]``.  An accessor kept for parity (two torch operations); ``q_sample`` / ``loss`` run the kernel."""
+        ab = self.alpha_bar.to(x0.device)[t.to(x0.device)].reshape(-1, *([1] * (x0.dim() - 1)))
+        return ab ** 0.5 * x0, 1 - ab
+
+    def q_sample(self, x0: torch.Tensor, t, eps: Optional[torch.Tensor] = None, *, seed: int = 0, draw: int = 0,
+                 elem_offset: int = 0) -> torch.Tensor:
+        """``alpha_bar[t] ** 0.5 * x0 + (1 - alpha_bar[t]) ** 0.5 * eps`` with one ``t`` per sample (latent_diffusion.py:163-177), as one
+        ``pf_qsample_rows`` launch.  ``eps=None``: draw ``draw`` of the library's generator under ``seed``, made inside the kernel."""
+        x0 = x0.contiguous().float()
+        t = _steps.time_steps(t, x0.shape[0], self.n_steps, 0, x0.device)
+        sa, sb = self._tables(x0.device)
+        if eps is not None:
+            return _steps.qsample_rows(self.eps_model._lib, x0, t, sa, sb, noise=eps.to(device=x0.device, dtype=torch.float32).contiguous())
+        return _steps.qsample_rows(self.eps_model._lib, x0, t, sa, sb, rng=(seed, draw, elem_offset))
+
+    def loss_rows(self, x0: torch.Tensor, cond: torch.Tensor, noise: Optional[torch.Tensor] = None,
+                  cond_concat: Optional[torch.Tensor] = None, *, t=None, seed: int = 0, draw: int = 0, elem_offset: int = 0,
+                  return_t: bool = False):
+        """The per-sample mean of ``(noise - eps_theta) ** 2`` as float64 ``[B]``; ``loss`` is its mean.  See ``loss``."""
+        B = x0.shape[0]
+        dev = self.device
+        t = _steps.time_steps(t, B, self.n_steps, seed, dev)
+        x0 = x0.to(dev)
+        if self.first_stage_model is not None:
+            # the posterior sample's noise: a draw of its own under the same seed, keyed by the same global element index
+            x0 = self.autoencoder_encode(x0, seed=seed, stream_id=(1 << 32) + int(draw), offset=elem_offset)
+        cond = cond.to(dev)
+        if cond_concat is not None:
+            cc = cond_concat.to(device=dev, dtype=torch.float32)
+            predict = lambda xt: self.eps_model(torch.cat([xt, cc], dim=1), t, cond)      # latent_diffusion.py:229-232
+        else:
+            predict = lambda xt: self.eps_model(xt, t, cond)
+        rows = _steps.diffusion_loss_rows(self.eps_model._lib, x0, t, self._tables(dev), predict, noise=noise,
+                                          rng=(seed, draw, elem_offset))[0]
+        return (rows, t) if return_t else rows
+
+    def loss(self, x0: torch.Tensor, cond: torch.Tensor, noise: Optional[torch.Tensor] = None,
+             cond_concat: Optional[torch.Tensor] = None, *, t=None, seed: int = 0, draw: int = 0, elem_offset: int = 0) -> torch.Tensor:
+        """``F.mse_loss(noise, eps_model(q_sample(x0, t, noise), t, cond))`` (latent_diffusion.py:203-240) as a 0-d float32 tensor.
+        ``t=None``: ``randint(0, n_steps, (B,))`` from a CPU ``torch.Generator`` seeded with ``seed`` (the reference draws it on the
+        device from the global generator, which nothing can pin).  ``noise=None``: draw ``draw`` of the library's counter-based
+        generator under ``seed``; element ``i`` of ``x0`` uses global element ``elem_offset + i``, so a batch split into several calls
+        sees the noise of the unsplit batch.  The noise is then made inside ``pf_qsample_rows`` and made again inside ``pf_mse_rows``:
+        it never exists as a tensor.  ``cond_concat`` is concatenated to ``x_t`` on the channel axis in front of the UNet (:229-232).
+        With a first-stage model ``x0`` first goes through ``autoencoder_encode``."""
+        return self.loss_rows(x0, cond, noise, cond_concat, t=t, seed=seed, draw=draw, elem_offset=elem_offset).mean().float()
 
     supports_shared_x = True     # forward(..., shared_x=True): the guidance evaluation with its condition-independent prefix computed once
 
