@@ -215,11 +215,16 @@ __global__ __launch_bounds__(256, 2) void conv_mfma_kernel(ConvP p) {
 template <int KS, int STRIDE, bool UPS, int TH, int TW, int BN, int BK, int PRO>
 static int launch_cfg(ConvP& p, hipStream_t stream) {
   constexpr int THIN = (TH - 1) * STRIDE + KS, TWIN = (TW - 1) * STRIDE + KS;
-  constexpr size_t lds = (size_t)(2 * THIN * TWIN * (BK + 4) + 2 * BK * BN) * sizeof(float);
-  static_assert(lds <= 160 * 1024, "LDS budget");
+  constexpr size_t lds_loop = (size_t)(2 * THIN * TWIN * (BK + 4) + 2 * BK * BN) * sizeof(float);
+  // a plane store (qkv_planes; linear layers) transposes the finished tile through the LDS, TW rows of BN + 8 floats (conv_epilogue):
+  // more than the main loop's images on the 128-row tiles, where it ran past the allocation (tests/conv_matrix.py, the f32 qkv case)
+  constexpr size_t lds_planes = TH == 1 ? (size_t)TW * (BN + 8) * sizeof(float) : 0;
+  constexpr size_t lds_max = lds_loop > lds_planes ? lds_loop : lds_planes;
+  static_assert(lds_max <= 160 * 1024, "LDS budget");
+  const size_t lds = (p.qkv || p.out_planes) ? lds_max : lds_loop;
   auto kern = conv_mfma_kernel<KS, STRIDE, UPS, TH, TW, BN, BK, PRO>;
   static std::atomic<uint64_t> attr_done{0};  // raise the dynamic-LDS cap once per instantiation and device
-  if (int rc = set_max_lds_once(reinterpret_cast<const void*>(kern), (int)lds, attr_done)) return rc;
+  if (int rc = set_max_lds_once(reinterpret_cast<const void*>(kern), (int)lds_max, attr_done)) return rc;
   const int grid = p.B * p.tiles_y * p.tiles_x * p.nt;
   hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds, stream, p);
   PF_CHECK_HIP(hipGetLastError());
