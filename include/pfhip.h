@@ -269,6 +269,24 @@ typedef struct pf_mse_rows_args {
 } pf_mse_rows_args;
 size_t pf_mse_rows_workspace_bytes(int rows, size_t row_elems);
 int pf_mse_rows(const pf_mse_rows_args* a, void* stream);
+/* pf_chord_ce_rows - the three cross-entropies of Chord_8Bar.chord_loss (models/model_chd_8bar.py:21-39; ChordDecoder.recon_loss,
+ *   dl_modules/chord_dec.py:72-85), kept per sample and not yet divided: from the logits root [rows][n_step][12], chroma
+ *   [rows][n_step][12][2], bass [rows][n_step][12] and the chord matrix gt [rows][n_step][36],
+ *     ce_rows[b][0..2] = sum over the row's steps of -log_softmax(logits)[target]   for root (12-way), chroma (12 two-way items a step), bass
+ *   into a device double[rows][3]; the reference's means are ce_rows summed over b / (rows n_step), / (rows n_step 12) for chroma.
+ *   Targets are the reference's: root / bass = arg-max of gt[..., 0:12] / gt[..., 24:36] (ties to the lowest index: an all-zero row
+ *   targets 0), chroma = (long) gt[..., 12:24], clamped to {0, 1} for memory safety only.  hit_rows (optional, int32 [rows][3]): how
+ *   many arg-maxes of the logits equal their target.  Logits are widened to float64; log-sum-exp and the row sum are float64 in a fixed
+ *   order, one workgroup per row, no atomics: a row's result is a function of that row alone, bit-identical however the batch is
+ *   split into calls.  ce_rows 8-byte aligned. */
+int pf_chord_ce_rows(const float* root, const float* chroma, const float* bass, const float* gt, int rows, int n_step, double* ce_rows,
+                     int32_t* hit_rows, void* stream);
+/* pf_normal_rsample - Normal(mean, std).rsample() of torch.distributions, what Chord_8Bar.get_loss_dict draws from the encoder
+ *   (models/model_chd_8bar.py:44): z[i] = mean[i] + std[i] * noise[i], n elements, the product rounded, then the sum.  noise: a tensor,
+ *   or NULL - then element i uses what pf_randn(seed, stream_id, elem_offset) writes at i, bit-equal to pf_randn + the tensor form.
+ *   As for pf_gaussian_sample, any n, elem_offset and alignment are accepted. */
+int pf_normal_rsample(const float* mean, const float* std, const float* noise, uint64_t seed, uint64_t stream_id, uint64_t elem_offset,
+                      float* z, size_t n, void* stream);
 
 /* ---- weight broadcast over RCCL / xGMI.  The path has ONE exchange: rank 0 ships the packed weight
  * blob at start-up; the step loop has no collective.  librccl.so is opened on first use (dlopen), so a single-GPU process
@@ -353,6 +371,32 @@ int pf_decoder_launches(const pf_decoder* d, int rows);
  * result does not depend on the other rows of the call. */
 int pf_decoder_forward(pf_decoder* d, const float* z, int rows, float* out0, float* out1, float* out2, int32_t* est,
                        void* workspace, size_t workspace_bytes, void* stream);
+/* The chord walk with teacher forcing: ChordDecoder.forward(z_chd, False, tfr, gt_chd) (dl_modules/chord_dec.py:27-70), PF_DEC_CHORD
+ * only.  The reference's per-step coin `random.random() < tfr` (:55) is the caller's: bit t of force_mask (t < n_step - 1) set means the
+ * token fed to step t + 1 is gt[:, t] (:56-57), otherwise the arg-max token of step t is fed back (:59-64).  feedback says which
+ * arg-max token:
+ *   PF_FEEDBACK_ROW   - each row's own one-hot root | chroma bits | one-hot bass, as pf_decoder_forward feeds it: a row's result does
+ *                       not depend on the other rows of the call, and force_mask 0 gives pf_decoder_forward's bits;
+ *   PF_FEEDBACK_BATCH - what the reference computes at batch > 1: t_root[arange(bs), 0, idx] with idx of shape (bs, 1) (:59-63) sets
+ *                       the root and bass part of EVERY row's token to the union over the call's rows (one more small launch per
+ *                       fed-back step); the number Lightning logged as val/loss comes from this form at the logged batch size.
+ * Refused before anything is enqueued: n_step - 1 > 64, a null gt, an unknown feedback, a short workspace.  Everything is
+ * caller-owned device memory (workspace 16-byte aligned, pf_decoder_forced_workspace_bytes(d, rows) bytes); launches only: capturable.
+ * pf_decoder_forced_launches counts, by a dry run of the same walk with every step fed back (force_mask 0), the most launches a call
+ * enqueues: pf_decoder_launches under PF_FEEDBACK_ROW, at most n_step - 1 more under PF_FEEDBACK_BATCH; it does not depend on rows. */
+enum { PF_FEEDBACK_ROW = 0, PF_FEEDBACK_BATCH = 1 };
+typedef struct pf_chord_forced_args {
+  const float* z;                     /* [rows][z_dim] */
+  const float* gt;                    /* [rows][n_step][36], the batch's chord matrix */
+  int32_t rows;
+  int feedback;                       /* PF_FEEDBACK_* */
+  uint64_t force_mask;
+  float *root, *chroma, *bass;        /* [rows][n_step][12], [rows][n_step][12][2], [rows][n_step][12] */
+  void* workspace; size_t workspace_bytes;
+} pf_chord_forced_args;
+size_t pf_decoder_forced_workspace_bytes(const pf_decoder* d, int rows);
+int pf_decoder_forced_launches(const pf_decoder* d, int rows, int feedback);
+int pf_decoder_forward_forced(pf_decoder* d, const pf_chord_forced_args* a, void* stream);
 
 /* Arithmetic of the dense contractions (convs / linears):
  *   PF_PREC_F32    - v_mfma_f32_32x32x2_f32, exact fp32 FMA chains (157 TFLOP/s pipe);

@@ -85,6 +85,13 @@ class MseRowsArgs(C.Structure):
                    ("row_elems", C.c_size_t)])
 
 
+class ChordForcedArgs(C.Structure):
+    """pf_chord_forced_args (include/pfhip.h); filled by ``decoders.ChordDecoder.forward_forced`` only."""
+    _fields_ = [("z", C.c_void_p), ("gt", C.c_void_p), ("rows", C.c_int32), ("feedback", C.c_int), ("force_mask", C.c_uint64),
+                ("root", C.c_void_p), ("chroma", C.c_void_p), ("bass", C.c_void_p), ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t)]
+
+
+FEEDBACK = {"row": 0, "batch": 1}   # PF_FEEDBACK_ROW / PF_FEEDBACK_BATCH
 MSE_CHUNK = 2048           # PF_MSE_CHUNK: elements of a row one workgroup of pf_mse_rows reduces
 
 
@@ -209,6 +216,8 @@ SIGNATURES = {
     "pf_qsample_rows": (C.c_int, [C.POINTER(QsampleRowsArgs), C.c_void_p]),
     "pf_mse_rows_workspace_bytes": (C.c_size_t, [C.c_int, C.c_size_t]),
     "pf_mse_rows": (C.c_int, [C.POINTER(MseRowsArgs), C.c_void_p]),
+    "pf_chord_ce_rows": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "pf_normal_rsample": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_void_p, C.c_size_t, C.c_void_p]),
     "pf_comm_unique_id": (C.c_int, [C.c_void_p]),
     "pf_comm_init": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_void_p)]),
     "pf_comm_bcast": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p]),
@@ -237,6 +246,9 @@ SIGNATURES = {
     "pf_decoder_launches": (C.c_int, [C.c_void_p, C.c_int]),
     "pf_decoder_forward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                      C.c_size_t, C.c_void_p]),
+    "pf_decoder_forced_workspace_bytes": (C.c_size_t, [C.c_void_p, C.c_int]),
+    "pf_decoder_forced_launches": (C.c_int, [C.c_void_p, C.c_int, C.c_int]),
+    "pf_decoder_forward_forced": (C.c_int, [C.c_void_p, C.POINTER(ChordForcedArgs), C.c_void_p]),
     "pf_packed_gemm_weight_floats": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
     "pf_pack_gemm_weight": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "pf_pack_gemm_weight_bf16x3": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]),

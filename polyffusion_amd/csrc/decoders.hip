@@ -1,6 +1,7 @@
 // decoders.hip - the frozen decoders of Polyffusion_SDF in inference mode (greedy, arg-max fed back), plain fp32.
 //   pnotree: PianoTreeDecoder.decoder(z, inference=True, ...)            (dl_modules/pianotree_dec.py:155-332)
 //   chord:   ChordDecoder.forward(z_chd, inference=True, tfr=0)          (dl_modules/chord_dec.py:27-70)
+//            and the same walk with teacher forcing (inference=False): pf_decoder_forward_forced
 // A PianoTree decode is 32 time steps x (max_simu_note - 1) note slots, every slot depending on the arg-max of the one before it.
 // Per note slot there are two launches: one fused GRU step (W_hh.h mat-vec with the gate update in its epilogue; a workgroup owns four
 // hidden units and eight rows of the batch, so W_hh is read once per slot per 8-row tile) and one "heads" launch (a workgroup per row:
@@ -368,13 +369,14 @@ __global__ __launch_bounds__(3 * PN_HE) void pnotree_emb_gru_kernel(const float*
 }
 
 // ---- chord heads: root 12 | chroma 12x2 | bass 12 logits of one step, and the next token one-hot root | chroma bits | one-hot bass
-// (chord_dec.py:39-64).  One workgroup per row.
+// (chord_dec.py:39-64).  One workgroup per row.  forced (teacher forcing, chord_dec.py:56-57): the row's ground-truth token of this step,
+// rows ld_forced apart, written as the next token instead of the arg-max one; null on the greedy path.
 __global__ __launch_bounds__(256) void chord_heads_kernel(const float* __restrict__ h, int H, const float* __restrict__ w_root,
                                                           const float* __restrict__ b_root, const float* __restrict__ w_chroma,
                                                           const float* __restrict__ b_chroma, const float* __restrict__ w_bass,
                                                           const float* __restrict__ b_bass, float* __restrict__ root,
                                                           float* __restrict__ chroma, float* __restrict__ bass, float* __restrict__ token,
-                                                          int t, int n_step) {
+                                                          int t, int n_step, const float* __restrict__ forced, int ld_forced) {
   __shared__ float hs[1024], lg[48];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, row = blockIdx.x;
   for (int k = tid; k < H; k += 256) hs[k] = h[(size_t)row * H + k];
@@ -404,8 +406,21 @@ __global__ __launch_bounds__(256) void chord_heads_kernel(const float* __restric
         if (p[o] > p[bi]) bi = o;
       v = (tid < 12 ? tid : tid - 24) == bi ? 1.f : 0.f;
     }
-    token[(size_t)row * 36 + tid] = v;
+    token[(size_t)row * 36 + tid] = forced ? forced[(size_t)row * ld_forced + tid] : v;
   }
+}
+
+// The reference's fed-back token at batch > 1 (chord_dec.py:59-63): t_root[arange(bs), 0, idx] with idx of shape (bs, 1) sets, in EVERY
+// row, the root (and bass) columns of ALL rows' arg-maxes.  Token entries are 0 / 1, so that union is a maximum over the call's rows;
+// the chroma bits stay the row's own.  One wave per root / bass column: its lanes stride the rows, combine by a butterfly (a maximum of
+// 0 / 1 values: no order to keep) and write the column back.  No workgroup touches another's column.
+__global__ __launch_bounds__(64) void chord_union_kernel(float* __restrict__ token, int R) {
+  const int col = blockIdx.x < 12 ? blockIdx.x : blockIdx.x + 12, lane = threadIdx.x;
+  float m = 0.f;
+  for (int r = lane; r < R; r += 64) m = fmaxf(m, token[(size_t)r * 36 + col]);
+#pragma unroll
+  for (int o = 32; o; o >>= 1) m = fmaxf(m, __shfl_xor(m, o));
+  for (int r = lane; r < R; r += 64) token[(size_t)r * 36 + col] = m;
 }
 
 // ---- bind-time tables
@@ -478,9 +493,13 @@ struct pf_decoder {
 
 namespace {
 
+// teacher forcing of the chord walk: bit t of mask set = the token fed to step t + 1 is gt[:, t] (gt [R][n_step][36]); null = greedy
+struct ChordForce { const float* gt; uint64_t mask; int feedback; };
+
 // The decode of either kind, dry or live (c.B = rows).  The two halves of a ping-pong buffer are told apart inside the closures: a
 // dry run carries null pointers and does no arithmetic on them.
-int dec_run(const pf_decoder* d, PlanCtx& c, const float* z, float* out0, float* out1, float* out2, int32_t* est) {
+int dec_run(const pf_decoder* d, PlanCtx& c, const float* z, float* out0, float* out1, float* out2, int32_t* est,
+            const ChordForce* force = nullptr) {
   const int R = c.B;
   // one fused GRU step h[cur] -> h[cur ^ 1] of the ping-pong pair h [2][R][H]
   auto gru_step = [&](const GruOff& g, const float* x, int ldx, int Kx, int ldwx, float* h, int cur, int H, const float* add1, const float* add2, int ld2) {
@@ -508,12 +527,20 @@ int dec_run(const pf_decoder* d, PlanCtx& c, const float* z, float* out0, float*
     linear(z_in, ZI, d->gru.w_ih + IN, ldw, d->gru.b_ih, gi_z, 3 * H, ZI);
     for (int t = 0; t < d->n_step; ++t) {
       gru_step(d->gru, t == 0 ? c.w(d->init_input) : token, t == 0 ? 0 : 36, IN, ldw, h, t & 1, H, gi_z, nullptr, 0);
+      const bool fed = t < d->n_step - 1;   // a token follows this step
+      const bool forced = force && fed && ((force->mask >> t) & 1);
       c.launch(PF_K_SMALL, 0.0, [&] {
+        const float* gt_t = forced ? force->gt + (size_t)t * 36 : nullptr;
         hipLaunchKernelGGL(chord_heads_kernel, dim3(R), dim3(256), 0, c.s, (const float*)(h + (size_t)((t + 1) & 1) * R * H), H, c.w(d->root.w),
                            c.w(d->root.b), c.w(d->chroma.w), c.w(d->chroma.b), c.w(d->bass.w), c.w(d->bass.b), out0, out1, out2, token, t,
-                           d->n_step);
+                           d->n_step, gt_t, d->n_step * 36);
         return launched();
       });
+      if (force && force->feedback == PF_FEEDBACK_BATCH && fed && !forced)
+        c.launch(PF_K_SMALL, 0.0, [&] {
+          hipLaunchKernelGGL(chord_union_kernel, dim3(24), dim3(64), 0, c.s, token, R);
+          return launched();
+        });
     }
     return c.rc;
   }
@@ -572,6 +599,13 @@ PlanSize dec_plan(const pf_decoder* d, int rows) {
   PlanCtx c;
   c.B = rows;
   return plan_sizes(c, [d](PlanCtx& dry) { dec_run(d, dry, nullptr, nullptr, nullptr, nullptr, nullptr); });
+}
+// the forced chord walk with every step fed back (mask 0): the most launches any mask enqueues; the workspace is the greedy walk's
+PlanSize dec_plan_forced(const pf_decoder* d, int rows, int feedback) {
+  PlanCtx c;
+  c.B = rows;
+  const ChordForce f{nullptr, 0, feedback};
+  return plan_sizes(c, [d, &f](PlanCtx& dry) { dec_run(d, dry, nullptr, nullptr, nullptr, nullptr, nullptr, &f); });
 }
 
 }  // namespace
@@ -683,6 +717,32 @@ int pf_decoder_forward(pf_decoder* d, const float* z, int rows, float* out0, flo
   const int rc = c.use_workspace("pf_decoder_forward", workspace, workspace_bytes, dec_plan(d, rows), stream, d->wt.wdev, 16);
   if (rc != PF_OK) return rc;
   return dec_run(d, c, z, out0, out1, out2, est);
+}
+
+static bool chord_handle(const pf_decoder* d) { return d && d->kind == PF_DEC_CHORD; }
+static bool feedback_known(int f) { return f == PF_FEEDBACK_ROW || f == PF_FEEDBACK_BATCH; }
+size_t pf_decoder_forced_workspace_bytes(const pf_decoder* d, int rows) {
+  return (chord_handle(d) && rows > 0) ? dec_plan_forced(d, rows, PF_FEEDBACK_ROW).bytes() : 0;
+}
+int pf_decoder_forced_launches(const pf_decoder* d, int rows, int feedback) {
+  return (chord_handle(d) && rows > 0 && feedback_known(feedback)) ? dec_plan_forced(d, rows, feedback).n_launch : 0;
+}
+
+int pf_decoder_forward_forced(pf_decoder* d, const pf_chord_forced_args* a, void* stream) {
+  PF_REQUIRE(d && a, "pf_decoder_forward_forced: null argument");
+  PF_REQUIRE(d->kind == PF_DEC_CHORD, "pf_decoder_forward_forced: teacher forcing is built for the chord decoder only");
+  PF_REQUIRE(d->n_step - 1 <= 64, "pf_decoder_forward_forced: force_mask holds 64 steps, n_step - 1 = %d", d->n_step - 1);
+  PF_REQUIRE(a->gt, "pf_decoder_forward_forced: gt (the chord matrix [rows][n_step][36]) is null");
+  PF_REQUIRE(feedback_known(a->feedback), "pf_decoder_forward_forced: unknown feedback %d (PF_FEEDBACK_ROW or PF_FEEDBACK_BATCH)", a->feedback);
+  PF_REQUIRE(a->z && a->root && a->chroma && a->bass && a->workspace && a->rows > 0, "pf_decoder_forward_forced: bad arguments");
+  PlanCtx c;
+  c.B = a->rows;
+  const int rc = c.use_workspace("pf_decoder_forward_forced", a->workspace, a->workspace_bytes, dec_plan_forced(d, a->rows, a->feedback), stream,
+                                 d->wt.wdev, 16);
+  if (rc != PF_OK) return rc;
+  if (!d->wt.wdev) return set_error(PF_ESTATE, "pf_decoder_forward_forced: weights not bound");
+  const ChordForce f{a->gt, a->force_mask, a->feedback};
+  return dec_run(d, c, a->z, a->root, a->chroma, a->bass, nullptr, &f);
 }
 
 }  // extern "C"

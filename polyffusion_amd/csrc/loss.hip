@@ -3,6 +3,8 @@
 //   qsample_rows - x_t = sqrt(alpha_bar_t) x0 + sqrt(1 - alpha_bar_t) noise with one t per sample,
 //   mse_rows     - per-sample sum of (noise - eps_theta)^2 in float64, as per-chunk partials + an in-order second pass.
 // Both read and write 16 bytes per lane and take one Philox call per four elements when the noise is drawn (or re-drawn) in the kernel.
+// And the objective of the chord VAE (Chord_8Bar.chord_loss, models/model_chd_8bar.py:21-39):
+//   chord_ce_rows - per-sample sums of the three cross-entropies (root, chroma, bass) in float64, one workgroup per row.
 #include "noise.h"
 
 namespace pf {
@@ -104,6 +106,77 @@ __global__ void mse_finish_kernel(const double* __restrict__ partial, double* __
   row_sum[row] = s;
 }
 
+// ---- chord cross-entropy.  A row has 14 * n_step items (per step: the root, 12 chroma bits, the bass); lane l owns items l, l + 256, ...
+// in index order, the lanes of a wave are combined by a butterfly and the four waves in wave order: an order fixed by n_step alone.
+// -log_softmax(x)[target] = max + log(sum_j exp(x_j - max)) - x_target with x widened to float64 first.
+template <int N>
+__device__ __forceinline__ double ce_item(const float* __restrict__ x, int target, int& hit) {
+  double v[N], vm = (double)x[0], vt = (double)x[0];
+  int bi = 0;
+#pragma unroll
+  for (int j = 0; j < N; ++j) {
+    v[j] = (double)x[j];
+    if (v[j] > vm) { vm = v[j]; bi = j; }   // ties to the lowest index
+    if (j == target) vt = v[j];
+  }
+  double se = 0.0;
+#pragma unroll
+  for (int j = 0; j < N; ++j) se += exp(v[j] - vm);
+  hit = bi == target;
+  return (vm + log(se)) - vt;
+}
+__device__ __forceinline__ int argmax12(const float* __restrict__ g) {
+  int bi = 0;
+#pragma unroll
+  for (int j = 1; j < 12; ++j)
+    if (g[j] > g[bi]) bi = j;
+  return bi;
+}
+__global__ __launch_bounds__(kThreads) void chord_ce_rows_kernel(const float* __restrict__ root, const float* __restrict__ chroma,
+                                                                const float* __restrict__ bass, const float* __restrict__ gt, int n_step,
+                                                                double* __restrict__ ce_rows, int32_t* __restrict__ hit_rows) {
+  __shared__ double wsum[kThreads / 64][3];
+  __shared__ int whit[kThreads / 64][3];
+  const int row = blockIdx.x;
+  double acc[3] = {0.0, 0.0, 0.0};
+  int hits[3] = {0, 0, 0};
+  for (int i = threadIdx.x; i < 14 * n_step; i += kThreads) {
+    const int st = i / 14, k = i - st * 14;
+    const size_t step = (size_t)row * n_step + st;
+    const float* g = gt + step * 36;
+    int hit = 0;
+    if (k == 0) {
+      acc[0] += ce_item<12>(root + step * 12, argmax12(g), hit);
+      hits[0] += hit;
+    } else if (k == 13) {
+      acc[2] += ce_item<12>(bass + step * 12, argmax12(g + 24), hit);
+      hits[2] += hit;
+    } else {
+      const long long c = (long long)g[12 + (k - 1)];        // .long(); the clamp is for memory safety only
+      acc[1] += ce_item<2>(chroma + step * 24 + 2 * (k - 1), c < 0 ? 0 : (c > 1 ? 1 : (int)c), hit);
+      hits[1] += hit;
+    }
+  }
+#pragma unroll
+  for (int q = 0; q < 3; ++q) {
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) {
+      acc[q] += __shfl_xor(acc[q], m, 64);
+      hits[q] += __shfl_xor(hits[q], m, 64);
+    }
+    if ((threadIdx.x & 63) == 0) { wsum[threadIdx.x >> 6][q] = acc[q]; whit[threadIdx.x >> 6][q] = hits[q]; }
+  }
+  __syncthreads();
+  if (threadIdx.x < 3) {
+    double s = wsum[0][threadIdx.x];
+    int h = whit[0][threadIdx.x];
+#pragma unroll
+    for (int w = 1; w < kThreads / 64; ++w) { s += wsum[w][threadIdx.x]; h += whit[w][threadIdx.x]; }
+    ce_rows[(size_t)row * 3 + threadIdx.x] = s;
+    if (hit_rows) hit_rows[(size_t)row * 3 + threadIdx.x] = h;
+  }
+}
+
 inline bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 inline size_t chunks_of(size_t row_elems, size_t chunk) { return (row_elems + chunk - 1) / chunk; }
 
@@ -168,6 +241,15 @@ int launch_mse_rows(const pf_mse_rows_args& a, hipStream_t s) {
   return PF_OK;
 }
 
+int launch_chord_ce_rows(const float* root, const float* chroma, const float* bass, const float* gt, int rows, int n_step, double* ce_rows,
+                         int32_t* hit_rows, hipStream_t s) {
+  PF_REQUIRE(root && chroma && bass && gt && ce_rows && rows > 0 && n_step > 0, "chord_ce_rows: bad arguments");
+  PF_REQUIRE(((uintptr_t)ce_rows & 7) == 0 && ((uintptr_t)hit_rows & 3) == 0, "chord_ce_rows: ce_rows must be 8-byte and hit_rows 4-byte aligned");
+  hipLaunchKernelGGL(chord_ce_rows_kernel, dim3((unsigned)rows), dim3(kThreads), 0, s, root, chroma, bass, gt, n_step, ce_rows, hit_rows);
+  PF_CHECK_HIP(hipGetLastError());
+  return PF_OK;
+}
+
 }  // namespace pf
 
 using namespace pf;
@@ -182,6 +264,14 @@ size_t pf_mse_rows_workspace_bytes(int rows, size_t row_elems) { return mse_rows
 int pf_mse_rows(const pf_mse_rows_args* a, void* stream) {
   PF_REQUIRE(a, "pf_mse_rows: null arguments");
   return launch_mse_rows(*a, (hipStream_t)stream);
+}
+int pf_chord_ce_rows(const float* root, const float* chroma, const float* bass, const float* gt, int rows, int n_step, double* ce_rows,
+                     int32_t* hit_rows, void* stream) {
+  return launch_chord_ce_rows(root, chroma, bass, gt, rows, n_step, ce_rows, hit_rows, (hipStream_t)stream);
+}
+int pf_normal_rsample(const float* mean, const float* std, const float* noise, uint64_t seed, uint64_t stream_id, uint64_t elem_offset,
+                      float* z, size_t n, void* stream) {
+  return launch_normal_rsample(mean, std, noise, seed, stream_id, elem_offset, z, n, (hipStream_t)stream);
 }
 
 }  // extern "C"

@@ -114,6 +114,9 @@ int launch_step_end(pf_step_state* st, int draws_used, hipStream_t s);
 int launch_qsample_rows(const pf_qsample_rows_args& a, hipStream_t s);
 size_t mse_rows_workspace_bytes(int rows, size_t row_elems);
 int launch_mse_rows(const pf_mse_rows_args& a, hipStream_t s);
+// the chord VAE's objective (loss.hip): per-row sums of the root / chroma / bass cross-entropies in float64, and arg-max hits
+int launch_chord_ce_rows(const float* root, const float* chroma, const float* bass, const float* gt, int rows, int n_step, double* ce_rows,
+                         int32_t* hit_rows, hipStream_t s);
 
 // vanilla DDPM network (attention_wide.hip): single-head attention with a wide head (exact fp32; scratch = batch * l * l floats), the
 // ConvTranspose2d(4, 2, 1) parity fold (fold: [Cout][Cin][16], the pack_upfold_bf3 tap order; fp32 packing [4][4][Cin][Cout]) and its fp32
@@ -134,6 +137,9 @@ int launch_ddpm_time_embed(const int64_t* t, const float* w1, const float* b1, c
 // noise == nullptr: element i draws what launch_randn(seed, sid, off) writes at i
 int launch_gaussian_sample(const float* mean, const float* log_var, const float* noise, uint64_t seed, uint64_t sid, uint64_t off, float scale,
                            float* z, size_t n, hipStream_t s);
+// Normal(mean, sd).rsample(): z = mean + sd * noise, the product rounded, then the sum; noise as for launch_gaussian_sample
+int launch_normal_rsample(const float* mean, const float* sd, const float* noise, uint64_t seed, uint64_t sid, uint64_t off, float* z, size_t n,
+                          hipStream_t s);
 int launch_ae_tail(const float* x, const float* sc, const float* sh, const float* w /*[9][cin][z2]*/, const float* bias, const float* qw /*[e2][z2]*/,
                    const float* qb, int z2, int e2, const float* noise, uint64_t seed, uint64_t sid, uint64_t off, float scale, float* z, float* mean,
                    float* log_var, int batch, int cin, int h, int w_, hipStream_t stream);

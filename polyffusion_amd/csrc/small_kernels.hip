@@ -684,6 +684,20 @@ int launch_gaussian_sample(const float* mean, const float* log_var, const float*
   return PF_OK;
 }
 
+// Normal(mean, std).rsample() (torch.distributions: loc + eps * scale as two rounded tensor operations); noise as above
+__global__ void normal_rsample_kernel(const float* __restrict__ mean, const float* __restrict__ sd, const float* __restrict__ noise, uint64_t seed,
+                                      uint64_t sid, uint64_t off, float* __restrict__ z, size_t n) {
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x)
+    z[i] = add_rn(mean[i], mul_rn(noise_at(noise, i, seed, sid, off), sd[i]));
+}
+int launch_normal_rsample(const float* mean, const float* sd, const float* noise, uint64_t seed, uint64_t sid, uint64_t off, float* z, size_t n,
+                          hipStream_t s) {
+  PF_REQUIRE(mean && sd && z && n > 0, "normal_rsample: bad arguments");
+  hipLaunchKernelGGL(normal_rsample_kernel, ew_grid(n), dim3(256), 0, s, mean, sd, noise, seed, sid, off, z, n);
+  PF_CHECK_HIP(hipGetLastError());
+  return PF_OK;
+}
+
 // Encoder tail (autoencoder.py:198-201, 64-68, 316-324): moments = quant_conv(conv_out(swish(norm_out(x)))), mean | log_var = its halves,
 // log_var clamped to [-30, 20], z = scale * (mean + exp(0.5 log_var) * noise); x NHWC, outputs NCHW.  The layout of conv_out_kernel: a
 // workgroup owns 16x16 output pixels and stages the normalised + activated 18x18 halo in LDS 16 channels at a time; a thread owns one

@@ -3,10 +3,14 @@
 * ``PianoTreeDecoder``: ``dl_modules/pianotree_dec.py:10-99`` (constructor keywords and order kept), ``forward`` = ``:334-339``.
 * ``ChordDecoder``: ``dl_modules/chord_dec.py:7-25``, ``forward`` = ``:27-70``.
 
-Both are greedy decodes: every arg-max is fed back as the next token, on the device.  Teacher forcing (training) is not implemented.
+Both are greedy decodes: every arg-max is fed back as the next token, on the device.  Teacher forcing exists for the chord decoder
+only, as ``ChordDecoder.forward_forced`` (``chord_dec.py:27-70`` with ``inference=False``; forward pass, for the chd_8bar objective).
 No torch module takes part; without the library / a GPU ``forward`` raises.
 """
 from __future__ import annotations
+
+import ctypes as C
+from typing import Sequence, Union
 
 import torch
 
@@ -86,7 +90,8 @@ class ChordDecoder(_Decoder):
     def forward(self, z_chd, inference, tfr, gt_chd=None):
         """``z_chd`` [R, z_dim] -> ``(recon_root [R,n_step,12], recon_chroma [R,n_step,12,2], recon_bass [R,n_step,12])``."""
         if not inference:
-            raise NotImplementedError("ChordDecoder: teacher forcing (training) is not implemented; inference=True only")
+            raise NotImplementedError("ChordDecoder.forward: teacher forcing (training) is not implemented here, inference=True only; "
+                                      "ChordDecoder.forward_forced runs the teacher-forced decode")
         z = self._z(z_chd, self.z_dim)
         R = z.shape[0]
         root = torch.empty(R, self.n_step, 12, dtype=torch.float32, device=z.device)
@@ -96,3 +101,44 @@ class ChordDecoder(_Decoder):
         return root, chroma, bass
 
     __call__ = forward
+
+    def force_mask(self, force: Union[int, Sequence[bool]]) -> int:
+        """``force`` as the library's bit mask: a sequence of ``n_step - 1`` booleans (entry ``t``: feed ``gt[:, t]`` to step ``t + 1``)
+        or an int whose bit ``t`` says the same."""
+        n = self.n_step - 1
+        if isinstance(force, int) and not isinstance(force, bool):
+            if force < 0 or force >> max(n, 0):
+                raise ValueError(f"ChordDecoder: force mask {force:#x} has bits past step {n - 1}")
+            return force
+        flips = [bool(f) for f in force]
+        if len(flips) != n:
+            raise ValueError(f"ChordDecoder: force needs n_step - 1 = {n} entries, got {len(flips)}")
+        return sum(1 << t for t, f in enumerate(flips) if f)
+
+    def n_launches_forced(self, rows: int = 1, feedback: str = "row") -> int:
+        """The most launches one ``forward_forced`` enqueues (mask 0; a dry run, no GPU needed)."""
+        return int(self._lib.pf_decoder_forced_launches(self._h, rows, _lib.FEEDBACK[feedback]))
+
+    def forward_forced(self, z_chd, gt_chd, force: Union[int, Sequence[bool]] = 0, feedback: str = "row"):
+        """``ChordDecoder.forward(z_chd, False, tfr, gt_chd)`` of the reference with its coin flips handed in: where ``force[t]`` is set
+        the token fed to step ``t + 1`` is ``gt_chd[:, t]``, elsewhere the arg-max token of step ``t``.  ``feedback="row"``: each row
+        feeds back its own arg-max (batch-invariant; mask 0 is ``forward(z, True, 0)`` bit for bit).  ``feedback="batch"``: the
+        reference's token at batch > 1, whose root / bass part is the union over the rows of THIS call (``chord_dec.py:59-63``).
+        Returns ``(recon_root [R,n_step,12], recon_chroma [R,n_step,12,2], recon_bass [R,n_step,12])``."""
+        if feedback not in _lib.FEEDBACK:
+            raise ValueError(f"ChordDecoder: feedback must be 'row' or 'batch', got {feedback!r}")
+        mask = self.force_mask(force)
+        z = self._z(z_chd, self.z_dim)
+        R = z.shape[0]
+        if tuple(gt_chd.shape) != (R, self.n_step, 36):
+            raise RuntimeError(f"ChordDecoder: gt_chd must be [{R}, {self.n_step}, 36], got {tuple(gt_chd.shape)}")
+        gt = gt_chd.detach().to(device=z.device, dtype=torch.float32).contiguous()
+        root = torch.empty(R, self.n_step, 12, dtype=torch.float32, device=z.device)
+        chroma = torch.empty(R, self.n_step, 12, 2, dtype=torch.float32, device=z.device)
+        bass = torch.empty(R, self.n_step, 12, dtype=torch.float32, device=z.device)
+        ws = self.workspace_for(self._lib.pf_decoder_forced_workspace_bytes(self._h, R), z.device)
+        a = _lib.ChordForcedArgs(z=z.data_ptr(), gt=gt.data_ptr(), rows=R, feedback=_lib.FEEDBACK[feedback], force_mask=mask,
+                                 root=root.data_ptr(), chroma=chroma.data_ptr(), bass=bass.data_ptr(), workspace=ws.data_ptr(),
+                                 workspace_bytes=ws.numel())
+        self._check(self._lib.pf_decoder_forward_forced(self._h, C.byref(a), _lib.current_stream()), "pf_decoder_forward_forced")
+        return root, chroma, bass
