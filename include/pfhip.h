@@ -150,7 +150,7 @@ int pf_unet_n_launches(const pf_unet* u, int batch, int n_cond);
  *   eps = e_uncond + scale * (e_cond - e_uncond), where eps2 = [e_uncond ; e_cond] (2n elements). */
 int pf_cfg_combine(const float* eps2, float scale, float* eps, size_t n, void* stream);
 
-/* One reverse step of either sampler family as ONE elementwise kernel.  The caller zero-fills the struct and sets what it needs.
+/* One reverse step of a sampler family as ONE elementwise kernel (DDPM / RePaint and DDIM here; DPM-Solver++(2M) follows them below).  The caller zero-fills the struct and sets what it needs.
  *   DDPM / RePaint (SDFSampler.paint body + p_sample, sampler_sdf.py:80-171,307-336):
  *     x0    = c_recip*x - c_recipm1*eps ; mean = c_x0*x0 + c_xt*x ; x_unkn = mean + sigma*noise_p
  *     x_kn  = sqrt_ab*orig + sqrt_1mab*noise_q          (skipped when orig == NULL)
@@ -196,6 +196,38 @@ typedef struct pf_ddim_step_args {
 } pf_ddim_step_args;
 int pf_ddim_step(const pf_ddim_step_args* a, void* stream);
 
+/* DPM-Solver++(2M), the third family: the second-order multistep solver of the probability-flow ODE in its data-prediction form (Lu et al.,
+ * "DPM-Solver++", 2022, algorithm 2), one denoiser evaluation per step like DDIM.  With alpha = sqrt(ab), sigma = sqrt(1 - ab),
+ * lambda = log(alpha / sigma) and h = lambda(target) - lambda(current), one step is
+ *     x0    = (x - s1m*eps) / sqrt_a                      this step's data prediction (written to x0_out when that is set)
+ *     x_out = c_x*x + c_0*x0 + c_1*x0_prev                the c_1 term only when c_1 != 0
+ *     if orig: x_out = (q_sqrt_a*orig + q_s1m*orig_noise)*mask + x_out*(1-mask)         the known-region blend of the DDIM family
+ * The host folds everything else into the three coefficients, in float64, rounded once:
+ *     c_x = sigma_tgt / sigma_cur,  c_0 = -alpha_tgt*expm1(-h)*(1 + 1/(2r)),  c_1 = +alpha_tgt*expm1(-h)/(2r),  r = h_previous / h
+ * and a first-order step (the first of a loop, order 1, a repeated time step with h == 0, the lower-order last step) has c_1 == 0 and
+ * c_0 = -alpha_tgt*expm1(-h): it is the DDIM step with eta = 0.  c_1 == 0 means x0_prev is NOT READ (a select, not a product with zero:
+ * the history of a first step is uninitialised memory), so it may be NULL then; c_1 != 0 with x0_prev == NULL is refused when the
+ * coefficients come by value; with a device table the host cannot see the row, and the kernel leaves the term out (memory safety only).  The step draws no noise and uses
+ * state->draws for nothing.  Tensors that are all 16-byte aligned with n % 4 == 0 are moved as 16-byte vectors, anything else element by
+ * element; both evaluate the same individually rounded operations, so the bits do not depend on the path. */
+typedef struct pf_dpm_coef {
+  float s1m;                          /* sqrt(1 - ab) of the current time step */
+  float sqrt_a;                       /* sqrt(ab) of the current time step */
+  float c_x, c_0, c_1;                /* as above; c_1 == 0: first-order step */
+  float q_sqrt_a, q_s1m;              /* known-region forward noising at this index: sqrt(ab), sqrt(1 - ab) of the current time step, as pf_ddim_coef */
+} pf_dpm_coef;
+typedef struct pf_dpm_step_args {
+  const float *x, *eps;               /* [n] */
+  const float *x0_prev;               /* [n] the previous step's x0; read only when c_1 != 0 */
+  float* x0_out;                      /* [n] receives this step's x0; may alias x0_prev; NULL = not kept */
+  const float *orig, *orig_noise, *mask;   /* known region: all three or none */
+  const pf_dpm_coef* coef;            /* host coefficients, copied at the call ...            */
+  const pf_dpm_coef* table;           /* ... or a device table, row state->index              */
+  const pf_step_state* state;         /* device step state: required with table */
+  float* x_out; size_t n;             /* x_out may alias x */
+} pf_dpm_step_args;
+int pf_dpm_step(const pf_dpm_step_args* a, void* stream);
+
 /* RePaint re-noise between inner repeats (sampler_sdf.py:337-341; keeps the reference's beta-not-sqrt quirk):
  *   x_t = a*x + b*noise */
 int pf_axpby(const float* x, const float* noise, float a, float b, float* out, size_t n, void* stream);
@@ -217,8 +249,8 @@ int pf_mfma_probe(float* sink, int iters, double* flops_out, void* stream);
 
 /* ---- replayable reverse step: everything that changes from one step to the next - the table row, the
  * time-step value fed to the denoiser, the noise draw counter - lives in a small device-resident pf_step_state, so ONE captured
- * hipGraph of {begin, pf_unet_forward, step, end} is replayed for every step of the loop (pf_ddpm_step / pf_ddim_step with `table` and
- * `state`).  `time_steps` is the DDIM tau table (int32 per row; NULL: the row index itself is the time step, as in the DDPM sampler). */
+ * hipGraph of {begin, pf_unet_forward, step, end} is replayed for every step of the loop (pf_ddpm_step / pf_ddim_step / pf_dpm_step with
+ * `table` and `state`).  `time_steps` is the DDIM tau table (int32 per row; NULL: the row index itself is the time step, as in the DDPM sampler). */
 int pf_step_state_set(pf_step_state* dev_state, int64_t index, uint64_t draws, void* stream);
 int pf_step_begin(const pf_step_state* dev_state, const int32_t* time_steps, int64_t* t_out, int batch, void* stream);
 int pf_step_end(pf_step_state* dev_state, int draws_used, void* stream);          /* index -= 1; draws += draws_used */

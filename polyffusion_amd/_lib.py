@@ -56,6 +56,11 @@ class DdimCoef(C.Structure):
     _fields_ = [(n, C.c_float) for n in ("s1m", "sqrt_a", "sqrt_aprev", "dir_coef", "sigma", "q_sqrt_a", "q_s1m")]
 
 
+class DpmCoef(C.Structure):
+    """pf_dpm_coef (include/pfhip.h): one DPM-Solver++(2M) step; ``c_1 == 0`` marks a first-order step."""
+    _fields_ = [(n, C.c_float) for n in ("s1m", "sqrt_a", "c_x", "c_0", "c_1", "q_sqrt_a", "q_s1m")]
+
+
 _STEP_COMMON = [("rng", C.c_int), ("coef", C.c_void_p), ("table", C.c_void_p), ("state", C.c_void_p)]
 
 
@@ -69,6 +74,12 @@ class DdimStepArgs(C.Structure):
     """pf_ddim_step_args (include/pfhip.h); filled by ``_steps.ddim_step`` only."""
     _fields_ = ([(n, C.c_void_p) for n in ("x", "eps", "orig", "orig_noise", "mask", "noise")] + _STEP_COMMON
                 + [(n, C.c_uint64) for n in ("seed", "draw", "elem_offset")] + [("x_out", C.c_void_p), ("n", C.c_size_t)])
+
+
+class DpmStepArgs(C.Structure):
+    """pf_dpm_step_args (include/pfhip.h); filled by ``_steps.dpm_step`` only."""
+    _fields_ = ([(n, C.c_void_p) for n in ("x", "eps", "x0_prev", "x0_out", "orig", "orig_noise", "mask", "coef", "table", "state", "x_out")]
+                + [("n", C.c_size_t)])
 
 
 class QsampleRowsArgs(C.Structure):
@@ -206,6 +217,7 @@ SIGNATURES = {
     "pf_ddpm_step": (C.c_int, [C.POINTER(DdpmStepArgs), C.c_void_p]),
     "pf_axpby": (C.c_int, [C.c_void_p, C.c_void_p, C.c_float, C.c_float, C.c_void_p, C.c_size_t, C.c_void_p]),
     "pf_ddim_step": (C.c_int, [C.POINTER(DdimStepArgs), C.c_void_p]),
+    "pf_dpm_step": (C.c_int, [C.POINTER(DpmStepArgs), C.c_void_p]),
     "pf_randn": (C.c_int, [C.c_void_p, C.c_size_t, C.c_uint64, C.c_uint64, C.c_uint64, C.c_void_p]),
     "pf_clock_probe": (C.c_int, [C.c_void_p, C.c_void_p]),
     "pf_mfma_probe": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_double), C.c_void_p]),

@@ -1,7 +1,7 @@
-"""The sampler's elementwise launches: noise, ``a*x + b*y`` and the two reverse-step updates (``pf_randn`` / ``pf_randn_dev``, ``pf_axpby``,
-``pf_ddpm_step``, ``pf_ddim_step`` of include/pfhip.h), and the two launches of the training objective (``pf_qsample_rows``,
+"""The sampler's elementwise launches: noise, ``a*x + b*y`` and the three reverse-step updates (``pf_randn`` / ``pf_randn_dev``, ``pf_axpby``,
+``pf_ddpm_step``, ``pf_ddim_step``, ``pf_dpm_step`` of include/pfhip.h), and the two launches of the training objective (``pf_qsample_rows``,
 ``pf_mse_rows``) with the loss evaluation both diffusion mirrors share (``diffusion_loss_rows``).  The only place that fills
-``pf_ddpm_step_args`` / ``pf_ddim_step_args`` / ``pf_qsample_rows_args`` / ``pf_mse_rows_args``:
+``pf_ddpm_step_args`` / ``pf_ddim_step_args`` / ``pf_dpm_step_args`` / ``pf_qsample_rows_args`` / ``pf_mse_rows_args``:
 ``sampler.py`` and ``ddpm.py`` decide WHICH route a step takes (coefficients by value or from a device table, noise tensors or
 in-kernel draws) and say so with keyword arguments; every launch goes to the current stream.  Tensors are read as dense buffers
 through raw pointers: callers pass contiguous float32 tensors.
@@ -78,6 +78,13 @@ def ddim_step(lib, x, eps, out, *, coef=None, table=None, state=None, noise=None
     """One DDIM update into ``out`` (may be ``x``).  ``rng``: ``None`` (noise from ``noise``) or ``(seed, draw, elem_offset)``."""
     return _launch(lib.pf_ddim_step, "pf_ddim_step", lib, _lib.DdimStepArgs(), x, eps, out, coef, table, state, rng,
                    ("seed", "draw", "elem_offset"), dict(noise=noise, orig=orig, orig_noise=orig_noise, mask=mask))
+
+
+def dpm_step(lib, x, eps, out, *, coef=None, table=None, state=None, x0_prev=None, x0_out=None, orig=None, orig_noise=None, mask=None):
+    """One DPM-Solver++(2M) update into ``out`` (may be ``x``).  ``x0_prev``: the previous step's data prediction, read only by a
+    second-order step (``c_1 != 0``); ``x0_out``: receives this step's (may be ``x0_prev``; ``None`` = not kept).  No noise is drawn."""
+    return _launch(lib.pf_dpm_step, "pf_dpm_step", lib, _lib.DpmStepArgs(), x, eps, out, coef, table, state, None, (),
+                   dict(x0_prev=x0_prev, x0_out=x0_out, orig=orig, orig_noise=orig_noise, mask=mask))
 
 
 # ---- the training objective, forward only (LatentDiffusion.loss / DenoiseDiffusion.loss of the reference) -------------------------------

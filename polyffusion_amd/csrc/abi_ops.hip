@@ -132,6 +132,10 @@ int pf_ddim_step(const pf_ddim_step_args* a, void* stream) {
   PF_REQUIRE(a, "pf_ddim_step: null arguments");
   return launch_ddim_step(*a, (hipStream_t)stream);
 }
+int pf_dpm_step(const pf_dpm_step_args* a, void* stream) {
+  PF_REQUIRE(a, "pf_dpm_step: null arguments");
+  return launch_dpm_step(*a, (hipStream_t)stream);
+}
 int pf_axpby(const float* x, const float* noise, float a, float b, float* out, size_t n, void* stream) { return launch_axpby(x, noise, a, b, out, n, (hipStream_t)stream); }
 int pf_randn(float* out, size_t n, uint64_t seed, uint64_t stream_id, uint64_t elem_offset, void* stream) {
   return launch_randn(out, n, seed, stream_id, elem_offset, (hipStream_t)stream);

@@ -3,6 +3,7 @@
 //   timestep embedding MLP (unet.py:63-68,151-169), batched mat-vec (ResBlock emb_layers
 //   unet.py:286-289; n_cond==1 cross-attention collapse unet_attention.py:186-212),
 //   fused sampler updates (sampler_sdf.py:80-171,307-341; sampler_ddim.py:220-272,355-359),
+//   and the update of the sampler the reference does not have, DPM-Solver++(2M) (pf_dpm_step),
 //   counter-based Gaussian noise, GRU gate update and the texture-encoder front end
 //   (dl_modules/chord_enc.py:15-22, txt_enc.py:23-27).
 #include "pf_internal.h"
@@ -650,6 +651,80 @@ int launch_ddim_step(const pf_ddim_step_args& a, hipStream_t s) {
   } else {
     hipLaunchKernelGGL(ddim_step_kernel, ew_grid(a.n), dim3(256), 0, s, a.x, a.eps, a.noise, a.orig, a.orig_noise, a.mask, cv, a.table, a.state, a.x_out, a.n);
   }
+  PF_CHECK_HIP(hipGetLastError());
+  return PF_OK;
+}
+
+// ---- DPM-Solver++(2M) (include/pfhip.h): one element of the update on VALUES.  Every operation is individually rounded (noise.h), so the
+// scalar and the vector kernel give the same bits.  Roundings on the way to the result, which the tests' error budget counts:
+//   x0:           mul (s1m*e), sub, div                                  3   (what x0_out receives)
+//   first order:  those 3 + mul (c_x*x), mul (c_0*x0), add               6
+//   second order: those 6 + mul (c_1*x0_prev), add                       8
+//   known region: + mul, mul, add (the noised original), sub (1 - m), mul, mul, add (the blend)      + 7
+// `second` is uniform over the launch (c_1 != 0); x0p is a VALUE the caller loaded only when `second` holds.
+__device__ __forceinline__ float dpm_x0(float xv, float e, const pf_dpm_coef& c) { return __fdiv_rn(sub_rn(xv, mul_rn(c.s1m, e)), c.sqrt_a); }
+__device__ __forceinline__ float dpm_update_v(float xv, float x0, bool second, float x0p, bool has_orig, float ov, float onv, float m,
+                                              const pf_dpm_coef& c) {
+  float xp = add_rn(mul_rn(c.c_x, xv), mul_rn(c.c_0, x0));
+  if (second) xp = add_rn(xp, mul_rn(c.c_1, x0p));
+  if (has_orig) {
+    const float ot = add_rn(mul_rn(c.q_sqrt_a, ov), mul_rn(c.q_s1m, onv));
+    xp = add_rn(mul_rn(ot, m), mul_rn(xp, sub_rn(1.0f, m)));
+  }
+  return xp;
+}
+// x / out and x0p / x0o carry no __restrict__: x_out may alias x and x0_out may alias x0_prev (a thread reads element i of both before it
+// writes element i of either, and no other thread touches element i)
+__global__ void dpm_step_kernel(const float* x, const float* __restrict__ eps, const float* x0p, float* x0o, const float* __restrict__ orig,
+                                const float* __restrict__ on, const float* __restrict__ mask, pf_dpm_coef cv, const pf_dpm_coef* __restrict__ table,
+                                const pf_step_state* __restrict__ st, float* out, size_t n) {
+  const pf_dpm_coef c = coef_of(cv, table, st);
+  const bool second = c.c_1 != 0.f && x0p != nullptr;      // c_1 == 0: the history is not read at all (it may be uninitialised)
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
+    const float xv = x[i], x0 = dpm_x0(xv, eps[i], c);
+    const float o = dpm_update_v(xv, x0, second, second ? x0p[i] : 0.f, orig != nullptr, orig ? orig[i] : 0.f, orig ? on[i] : 0.f,
+                                 orig ? mask[i] : 0.f, c);
+    if (x0o) x0o[i] = x0;
+    out[i] = o;
+  }
+}
+// the same on four elements per thread, moved as 16-byte vectors (every tensor 16-byte aligned, n % 4 == 0: launch_dpm_step decides)
+__global__ void dpm_step_vec_kernel(const float* x, const float* __restrict__ eps, const float* x0p, float* x0o, const float* __restrict__ orig,
+                                    const float* __restrict__ on, const float* __restrict__ mask, pf_dpm_coef cv, const pf_dpm_coef* __restrict__ table,
+                                    const pf_step_state* __restrict__ st, float* out, size_t n) {
+  const pf_dpm_coef c = coef_of(cv, table, st);
+  const bool second = c.c_1 != 0.f && x0p != nullptr;
+  const size_t ng = n >> 2;
+  for (size_t g = (size_t)blockIdx.x * blockDim.x + threadIdx.x; g < ng; g += (size_t)gridDim.x * blockDim.x) {
+    const f32x4 xv = *reinterpret_cast<const f32x4*>(x + 4 * g), ev = *reinterpret_cast<const f32x4*>(eps + 4 * g);
+    f32x4 pv = {0.f, 0.f, 0.f, 0.f}, ov = pv, nv = pv, mv = pv, o, z;
+    if (second) pv = *reinterpret_cast<const f32x4*>(x0p + 4 * g);
+    if (orig) { ov = *reinterpret_cast<const f32x4*>(orig + 4 * g); nv = *reinterpret_cast<const f32x4*>(on + 4 * g); mv = *reinterpret_cast<const f32x4*>(mask + 4 * g); }
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      z[j] = dpm_x0(xv[j], ev[j], c);
+      o[j] = dpm_update_v(xv[j], z[j], second, pv[j], orig != nullptr, ov[j], nv[j], mv[j], c);
+    }
+    if (x0o) *reinterpret_cast<f32x4*>(x0o + 4 * g) = z;
+    *reinterpret_cast<f32x4*>(out + 4 * g) = o;
+  }
+}
+int launch_dpm_step(const pf_dpm_step_args& a, hipStream_t s) {
+  PF_REQUIRE(a.x && a.eps && a.x_out && a.n > 0, "dpm_step: bad arguments (x, eps and x_out must be set, n > 0)");
+  PF_REQUIRE((a.orig && a.orig_noise && a.mask) || (!a.orig && !a.orig_noise && !a.mask),
+             "dpm_step: the known region needs orig, orig_noise and mask - all three or none");
+  PF_REQUIRE(!(a.coef && (a.table || a.state)), "dpm_step: coefficients both by value (coef) and from the device (table / state)");
+  PF_REQUIRE(a.coef || (a.table && a.state), "dpm_step: null coefficients (set coef, or table and state)");
+  PF_REQUIRE(!a.coef || a.coef->c_1 == 0.f || a.x0_prev, "dpm_step: a second-order step (c_1 != 0) needs x0_prev");
+  const pf_dpm_coef cv = a.coef ? *a.coef : pf_dpm_coef{};
+  const uintptr_t bits = (uintptr_t)a.x | (uintptr_t)a.eps | (uintptr_t)a.x_out | (uintptr_t)a.x0_prev | (uintptr_t)a.x0_out | (uintptr_t)a.orig |
+                         (uintptr_t)a.orig_noise | (uintptr_t)a.mask;
+  if ((bits & 15) == 0 && a.n % 4 == 0)
+    hipLaunchKernelGGL(dpm_step_vec_kernel, ew_grid(a.n / 4), dim3(256), 0, s, a.x, a.eps, a.x0_prev, a.x0_out, a.orig, a.orig_noise, a.mask, cv, a.table,
+                       a.state, a.x_out, a.n);
+  else
+    hipLaunchKernelGGL(dpm_step_kernel, ew_grid(a.n), dim3(256), 0, s, a.x, a.eps, a.x0_prev, a.x0_out, a.orig, a.orig_noise, a.mask, cv, a.table,
+                       a.state, a.x_out, a.n);
   PF_CHECK_HIP(hipGetLastError());
   return PF_OK;
 }

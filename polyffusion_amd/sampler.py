@@ -5,11 +5,12 @@
 * ``SDFSampler``        - ``sampler_sdf.py`` (tables :52-78, ``p_sample`` :80-171, ``q_sample``
   :173-192, ``sample`` :194-255, ``paint`` :257-350 incl. the RePaint quirks of Appendix A).
 * ``DDIMSampler``       - ``sampler_ddim.py`` (tables :40-102, step :168-272, ``paint`` :301-362).
+* ``DPMSolverSampler``  - not in the reference: DPM-Solver++(2M), the second-order multistep solver, driven like ``DDIMSampler``.
 
 Same method names and argument meaning as the reference, so ``Experiments.predict`` drives
 them unchanged.  Differences, all host-side plumbing:
   - per-step scalars are read from host tables and passed by value into ONE fused HIP kernel
-    per step (``pf_ddpm_step`` / ``pf_ddim_step``, launched through ``_steps`` - this module decides the route, ``_steps`` fills
+    per step (``pf_ddpm_step`` / ``pf_ddim_step`` / ``pf_dpm_step``, launched through ``_steps`` - this module decides the route, ``_steps`` fills
     the argument struct) instead of ~20 elementwise launches and five device->host syncs per step;
   - noise comes from ``noise_fn(shape)`` when given (parity tests inject the reference's noise
     tape) and otherwise from the counter-based on-device generator keyed by (seed, draw counter,
@@ -528,4 +529,161 @@ class DDIMSampler(DiffusionSampler):
             x, _ = self._step(x, e_t, index, orig=orig, orig_noise=orig_noise, mask=mask)
             if self.on_step is not None:
                 self.on_step(int(step), x)
+        return x
+
+
+def dpm_time_steps(alpha_bar, n_steps: int, discretize: str = "logsnr") -> np.ndarray:
+    """The ascending time-step grid of ``DPMSolverSampler``.  ``uniform`` / ``quad``: DDIM's arrays (sampler_ddim.py:40-55).  ``logsnr``:
+    ``n_steps`` targets uniform in lambda = log(alpha / sigma) between the schedule's last and second time step, each mapped to the nearest
+    time step; duplicates and time step 0 (the end point of the last step) are dropped, so the grid can be shorter than asked for."""
+    ab = np.asarray(alpha_bar, dtype=np.float64)
+    n = len(ab)
+    if discretize == "uniform":
+        return np.asarray(list(range(0, n, n // n_steps))) + 1
+    if discretize == "quad":
+        return ((np.linspace(0, np.sqrt(n * 0.8), n_steps)) ** 2).astype(int) + 1
+    if discretize == "logsnr":
+        lam = 0.5 * np.log(ab / (1.0 - ab))
+        ts = {int(np.argmin(np.abs(lam - target))) for target in np.linspace(lam[n - 1], lam[1], n_steps)}
+        return np.asarray(sorted(ts - {0}), dtype=np.int64)
+    raise NotImplementedError(discretize)
+
+
+def dpm_coef_rows(alpha_bar, time_steps, t_start: int, order: int = 2, lower_order_final: bool = True) -> np.ndarray:
+    """float64 ``[t_start + 1, 7]``: row i = the ``pf_dpm_coef`` fields (s1m, sqrt_a, c_x, c_0, c_1, q_sqrt_a, q_s1m) of grid index i in a
+    loop that runs i = t_start .. 0.  Step i goes from ``time_steps[i]`` to ``time_steps[i - 1]`` (to time step 0 at i = 0, as DDIM ends).
+    First order (c_1 = 0): the loop's first step, ``order == 1``, a step of zero length or after one (a grid that repeats a time step), and
+    the last step of a loop of fewer than 15 steps when ``lower_order_final``."""
+    ab = np.asarray(alpha_bar, dtype=np.float64)
+    ts = np.asarray(time_steps)[: t_start + 1]
+    cur = ab[ts]
+    tgt = np.concatenate([ab[0:1], ab[ts[:-1]]])
+    lam = lambda a: 0.5 * np.log(a / (1.0 - a))
+    h = lam(tgt) - lam(cur)
+    rows = np.zeros((len(ts), 7), dtype=np.float64)
+    for i in range(len(ts)):
+        e = -np.sqrt(tgt[i]) * np.expm1(-h[i])                 # alpha_tgt * (1 - exp(-h))
+        second = (order == 2 and i < t_start and h[i] != 0.0 and h[i + 1] != 0.0
+                  and not (i == 0 and lower_order_final and len(ts) < 15))
+        k = 0.5 * h[i] / h[i + 1] if second else 0.0           # 1 / (2r), r = h_{i+1} / h_i
+        s1m, sqrt_a = np.sqrt(1.0 - cur[i]), np.sqrt(cur[i])
+        rows[i] = (s1m, sqrt_a, np.sqrt(1.0 - tgt[i]) / s1m, e * (1.0 + k), -e * k, sqrt_a, s1m)
+    return rows
+
+
+class DPMSolverSampler(DiffusionSampler):
+    """DPM-Solver++(2M) (Lu et al. 2022, algorithm 2; multistep, data prediction): a second-order solver of the probability-flow ODE that
+    DDIM with eta = 0 solves to first order, at the same cost per step - one denoiser evaluation and ONE update kernel (``pf_dpm_step``).
+    Not in the reference; it is driven like ``DDIMSampler`` (same ``paint`` / ``sample`` / ``q_sample`` / ``p_sample`` arguments, grid index
+    i counts up with the time step).  The update's coefficients are computed here in float64 and rounded once (``dpm_coef_rows``); the
+    previous step's data prediction lives in one buffer the kernel reads and overwrites.  Every ``paint()`` / ``sample()`` call starts a
+    fresh history: its first step is first order and never reads the buffer.  Deterministic: no step draws noise (a known region without
+    a fixed ``orig_noise`` draws a fresh one per step, as DDIM's paint does)."""
+
+    def __init__(self, model: LatentDiffusion, n_steps: int, discretize: str = "logsnr", order: int = 2, lower_order_final: bool = True,
+                 is_show_image: bool = False, **kw):
+        super().__init__(model, **kw)
+        if int(order) not in (1, 2):
+            raise ValueError(f"DPM-Solver++(2M): order {order!r}, expected 1 or 2")
+        self.is_show_image = is_show_image
+        self.n_steps = model.n_steps
+        self.order, self.lower_order_final, self.discretize = int(order), bool(lower_order_final), discretize
+        self._ab = model.alpha_bar.detach().cpu().double().numpy()
+        self.time_steps = dpm_time_steps(self._ab, n_steps, discretize)
+        self._rows = {}
+
+    def coef_rows(self, t_start: Optional[int] = None) -> np.ndarray:
+        """float32 ``[t_start + 1, 7]``: the coefficient rows of a loop that starts at grid index ``t_start`` (default: the whole grid)."""
+        t_start = len(self.time_steps) - 1 if t_start is None else int(t_start)
+        if t_start not in self._rows:
+            self._rows[t_start] = dpm_coef_rows(self._ab, self.time_steps, t_start, self.order, self.lower_order_final).astype(np.float32)
+        return self._rows[t_start]
+
+    def _coef(self, index: int, t_start: int) -> _lib.DpmCoef:
+        return _lib.DpmCoef(*(float(v) for v in self.coef_rows(t_start)[index]))
+
+    def _coef_table(self, device, t_start: int):
+        """([S, 7] fp32 rows of a loop starting at ``t_start`` - rows above it are zero and never read -, [S] int32 tau table) on the device."""
+        key = ("dpm_table", str(device), int(t_start))
+        if key not in self._dev_cache:
+            rows = np.zeros((len(self.time_steps), 7), dtype=np.float32)
+            rows[: t_start + 1] = self.coef_rows(t_start)
+            self._dev_cache[key] = torch.from_numpy(rows).to(device)
+        tk = ("dpm_taus", str(device))
+        if tk not in self._dev_cache:
+            self._dev_cache[tk] = torch.from_numpy(np.asarray(self.time_steps, dtype=np.int32)).to(device)
+        return self._dev_cache[key], self._dev_cache[tk]
+
+    def _paint_graph(self, x, cond, t_start, orig, mask, orig_noise, uncond_scale, uncond_cond, cond_concat):
+        """All t_start+1 steps as replays of one captured step.  The captured update reads its coefficient row from a STATIC table buffer
+        (its address is part of the graph): the rows of this call's ``t_start`` are copied into it with the other inputs, so one captured
+        step serves loops of every length.  The history buffer is static too; row ``t_start`` is first order and does not read it."""
+        lib = self._lib
+
+        def update(bf, e_t, _table, st):
+            hist = bf.get("_hist")
+            if hist is None:                       # first (warm-up) run of the body, before the capture
+                hist = bf["_hist"] = torch.empty_like(bf["x"])
+            xb = bf["x"]
+            _steps.dpm_step(lib, xb, e_t.contiguous(), xb, table=bf["dpm_table"], state=st, x0_prev=hist, x0_out=hist,
+                            orig=bf["orig"], orig_noise=bf["orig_noise"], mask=bf["mask"])
+
+        table, taus = self._coef_table(x.device, t_start)
+        inputs = dict(x=x, cond=cond, orig=orig, mask=mask, orig_noise=orig_noise, uncond_cond=uncond_cond, cond_concat=cond_concat,
+                      dpm_table=table)
+        return self._replay_loop("dpm", inputs, table, taus, 0, 0, t_start + 1, t_start, uncond_scale, update)
+
+    def _step(self, x, e_t, index, t_start, hist, orig=None, orig_noise=None, mask=None):
+        """Grid index ``index`` of a loop that started at ``t_start``; ``hist``: the history buffer (read unless the row is first order,
+        then overwritten with this step's x0)."""
+        coef = self._coef(index, t_start)
+        x, e_t = x.contiguous(), e_t.contiguous()
+        if orig is not None and orig_noise is None:      # DDIM's paint: a fresh q_sample noise per step (sampler_ddim.py:355-359)
+            orig_noise = self.randn(orig.shape, x.device)
+        out = torch.empty_like(x)
+        return _steps.dpm_step(self._lib, x, e_t, out, coef=coef, x0_prev=hist, x0_out=hist, orig=orig, orig_noise=orig_noise, mask=mask), coef
+
+    @torch.no_grad()
+    def p_sample(self, x, c, t, step: int, index: int, *, repeat_noise=False, temperature=1.0, uncond_scale=1.0,
+                 uncond_cond=None, cond_concat=None, prep: Optional[dict] = None, x0_prev: Optional[torch.Tensor] = None):
+        """One step on its own; returns (x_prev, pred_x0, e_t) like ``DDIMSampler.p_sample``.  Without ``x0_prev`` the step is first order;
+        with the ``pred_x0`` of the step at ``index + 1`` it is the second-order step of the full grid.  ``repeat_noise`` / ``temperature``
+        are accepted for the shared signature: there is no noise."""
+        e_t = self._eps(x, c, int(step), uncond_scale, uncond_cond, cond_concat, prep)
+        full = len(self.time_steps) - 1
+        second = x0_prev is not None and index < full
+        hist = x0_prev.contiguous().clone() if second else torch.empty_like(e_t)     # read by a second-order row only; receives this step's x0
+        x_prev, _ = self._step(x, e_t, index, full if second else index, hist)
+        return x_prev, hist, e_t
+
+    @torch.no_grad()
+    def q_sample(self, x0, index: int, noise=None):
+        row = self.coef_rows()[index]
+        return _steps.q_sample(self, x0, noise, float(row[5]), float(row[6]), self._elem_offset(x0.shape))
+
+    @torch.no_grad()
+    def sample(self, shape, cond, repeat_noise=False, temperature=1.0, x_last=None, uncond_scale=1.0, uncond_cond=None,
+               t_start: int = 0):
+        """From noise (or ``x_last``) down the grid, skipping its ``t_start`` highest entries like ``DDIMSampler.sample``."""
+        x = x_last if x_last is not None else self.randn(shape, cond.device)
+        return self.paint(x, cond, len(self.time_steps) - 1 - int(t_start), uncond_scale=uncond_scale, uncond_cond=uncond_cond)
+
+    @torch.no_grad()
+    def paint(self, x, cond, t_start: int, *, orig=None, mask=None, orig_noise=None, uncond_scale: float = 1.0,
+              uncond_cond=None, cond_concat=None, repaint_n: int = 1):
+        x, t_start = x.contiguous(), int(t_start)
+        if orig is not None:
+            assert mask is not None
+            orig, mask = orig.contiguous().float(), mask.contiguous().float()
+            orig_noise = None if orig_noise is None else orig_noise.contiguous().float()
+        if self.graph and self.noise_fn is None and (orig is None or orig_noise is not None) and self.on_step is None:
+            return self._paint_graph(x, cond, t_start, orig, mask, orig_noise, uncond_scale, uncond_cond, cond_concat)
+        prep = self.prepare(cond, uncond_scale=uncond_scale, uncond_cond=uncond_cond)
+        hist = torch.empty_like(x)          # the previous step's x0; uninitialised: the first step does not read it
+        for index in range(t_start, -1, -1):
+            step = int(self.time_steps[index])
+            e_t = self._eps(x, cond, step, uncond_scale, uncond_cond, cond_concat, prep)
+            x, _ = self._step(x, e_t, index, t_start, hist, orig=orig, orig_noise=orig_noise, mask=mask)
+            if self.on_step is not None:
+                self.on_step(step, x)
         return x
