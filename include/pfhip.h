@@ -108,6 +108,15 @@ size_t pf_unet_workspace_bytes_cfg(const pf_unet* u, int batch2, int n_cond);
 int pf_unet_forward_cfg(pf_unet* u, const float* x, const int64_t* t, const float* cond, int batch2, int n_cond,
                         const pf_unet_prepared* prep, float* eps2, void* workspace, size_t workspace_bytes, void* stream);
 int pf_unet_n_launches_cfg(const pf_unet* u, int batch2, int n_cond, int has_time, int has_cross);
+/* The same plan over `groups` stacked evaluations of one x (groups = 2: exactly the three entries above; groups = 3: dual guidance, the rows
+ * of cat([uncond, partial, cond]) - pf_cfg_combine3).  The shared prefix runs on batch_total / groups samples, the hand-over copies the running
+ * tensor (and its statistics) `groups` times, shared skips are read modulo batch_total / groups.  x: [batch_total / groups, ...]; t, cond (and
+ * prep->cross_bias): batch_total rows, every group carrying the same t.  groups outside {2, 3} or batch_total % groups != 0: PF_EINVAL from the
+ * forward (nothing is launched), 0 from the two queries. */
+size_t pf_unet_workspace_bytes_cfgn(const pf_unet* u, int batch_total, int groups, int n_cond);
+int pf_unet_forward_cfgn(pf_unet* u, const float* x, const int64_t* t, const float* cond, int batch_total, int groups, int n_cond,
+                         const pf_unet_prepared* prep, float* eps, void* workspace, size_t workspace_bytes, void* stream);
+int pf_unet_n_launches_cfgn(const pf_unet* u, int batch_total, int groups, int n_cond, int has_time, int has_cross);
 /* kernel launches of one forward; has_time / has_cross: with that member of pf_unet_prepared supplied */
 int pf_unet_n_launches_prepared(const pf_unet* u, int batch, int n_cond, int has_time, int has_cross);
 
@@ -149,6 +158,12 @@ int pf_unet_n_launches(const pf_unet* u, int batch, int n_cond);
  * Classifier-free guidance combine (DiffusionSampler.get_eps, stable_diffusion/sampler/__init__.py:69-77):
  *   eps = e_uncond + scale * (e_cond - e_uncond), where eps2 = [e_uncond ; e_cond] (2n elements). */
 int pf_cfg_combine(const float* eps2, float scale, float* eps, size_t n, void* stream);
+/* Dual guidance combine (not in the reference): eps3 = [e0 ; e1 ; e2] (3n elements) - both parts of a two-part condition dropped, the first
+ * part kept, both kept:
+ *   eps = (e0 + s1 * (e1 - e0)) + s2 * (e2 - e1)     five individually rounded fp32 operations in this order
+ * With e1 == e2 these are pf_cfg_combine's bits on [e0 ; e1] with scale s1 (finite values).  16-byte vectors when eps3 and eps are 16-byte
+ * aligned and n % 4 == 0, 4-byte elements otherwise: the same bits. */
+int pf_cfg_combine3(const float* eps3, float s1, float s2, float* eps, size_t n, void* stream);
 
 /* One reverse step of a sampler family as ONE elementwise kernel (DDPM / RePaint and DDIM here; DPM-Solver++(2M) follows them below).  The caller zero-fills the struct and sets what it needs.
  *   DDPM / RePaint (SDFSampler.paint body + p_sample, sampler_sdf.py:80-171,307-336):

@@ -199,6 +199,8 @@ SIGNATURES = {
                                            C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "pf_unet_forward_cfg": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.POINTER(UNetPrepared),
                                            C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "pf_unet_forward_cfgn": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(UNetPrepared),
+                                       C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "pf_unet_time_bias_width": (C.c_int, [C.c_void_p]),
     "pf_unet_cross_bias_width": (C.c_int, [C.c_void_p]),
     "pf_unet_prepare_time": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
@@ -206,6 +208,8 @@ SIGNATURES = {
     "pf_unet_n_launches_prepared": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int]),
     "pf_unet_workspace_bytes_cfg": (C.c_size_t, [C.c_void_p, C.c_int, C.c_int]),
     "pf_unet_n_launches_cfg": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int]),
+    "pf_unet_workspace_bytes_cfgn": (C.c_size_t, [C.c_void_p, C.c_int, C.c_int, C.c_int]),
+    "pf_unet_n_launches_cfgn": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
     "pf_unet_set_option": (C.c_int, [C.c_void_p, C.c_int, C.c_int]),
     "pf_unet_get_option": (C.c_int, [C.c_void_p, C.c_int]),
     "pf_unet_set_profiling": (C.c_int, [C.c_void_p, C.c_int]),
@@ -214,6 +218,7 @@ SIGNATURES = {
     "pf_unet_profile_read": (C.c_int, [C.c_void_p, C.POINTER(C.c_int), c_float_p, C.POINTER(C.c_double), C.c_int]),
     "pf_unet_n_launches": (C.c_int, [C.c_void_p, C.c_int, C.c_int]),
     "pf_cfg_combine": (C.c_int, [C.c_void_p, C.c_float, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "pf_cfg_combine3": (C.c_int, [C.c_void_p, C.c_float, C.c_float, C.c_void_p, C.c_size_t, C.c_void_p]),
     "pf_ddpm_step": (C.c_int, [C.POINTER(DdpmStepArgs), C.c_void_p]),
     "pf_axpby": (C.c_int, [C.c_void_p, C.c_void_p, C.c_float, C.c_float, C.c_void_p, C.c_size_t, C.c_void_p]),
     "pf_ddim_step": (C.c_int, [C.POINTER(DdimStepArgs), C.c_void_p]),

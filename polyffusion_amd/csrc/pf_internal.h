@@ -99,6 +99,7 @@ int launch_matvec_exp(const float* x, int ldx, const float* w, const float* bias
 
 // sampler elementwise kernels
 int launch_cfg_combine(const float* eps2, float scale, float* eps, size_t n, hipStream_t s);
+int launch_cfg_combine3(const float* eps3, float s1, float s2, float* eps, size_t n, hipStream_t s);
 // one reverse step per family: validates the arguments, then the tensor-noise or the in-kernel Philox kernel (include/pfhip.h)
 int launch_ddpm_step(const pf_ddpm_step_args& a, hipStream_t s);
 int launch_ddim_step(const pf_ddim_step_args& a, hipStream_t s);

@@ -453,6 +453,38 @@ int launch_cfg_combine(const float* eps2, float scale, float* eps, size_t n, hip
   return PF_OK;
 }
 
+// Dual guidance (DualScale in sampler.py): e3 = [e0 | e1 | e2], the evaluations with both parts of the condition dropped, one kept, both kept.
+//   e = e0 + s1 * (e1 - e0) + s2 * (e2 - e1)   as five rounded operations in this order (e1 == e2: cfg_combine_kernel's bits on [e0 | e1])
+__device__ __forceinline__ float cfg_combine3_v(float e0, float e1, float e2, float s1, float s2) {
+  return add_rn(add_rn(e0, mul_rn(s1, sub_rn(e1, e0))), mul_rn(s2, sub_rn(e2, e1)));
+}
+__global__ void cfg_combine3_kernel(const float* __restrict__ e3, float s1, float s2, float* __restrict__ e, size_t n) {
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x)
+    e[i] = cfg_combine3_v(e3[i], e3[n + i], e3[2 * n + i], s1, s2);
+}
+// the same on four elements per thread, moved as 16-byte vectors (e3 and e 16-byte aligned, n % 4 == 0 - so e3 + n and e3 + 2n are aligned
+// too and group g < n / 4 ends at float 4g + 3 < n of its third: launch_cfg_combine3 decides)
+__global__ void cfg_combine3_vec_kernel(const float* __restrict__ e3, float s1, float s2, float* __restrict__ e, size_t n) {
+  const size_t ng = n >> 2;
+  for (size_t g = (size_t)blockIdx.x * blockDim.x + threadIdx.x; g < ng; g += (size_t)gridDim.x * blockDim.x) {
+    const f32x4 a = *reinterpret_cast<const f32x4*>(e3 + 4 * g), b = *reinterpret_cast<const f32x4*>(e3 + n + 4 * g),
+                c = *reinterpret_cast<const f32x4*>(e3 + 2 * n + 4 * g);
+    f32x4 o;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) o[j] = cfg_combine3_v(a[j], b[j], c[j], s1, s2);
+    *reinterpret_cast<f32x4*>(e + 4 * g) = o;
+  }
+}
+int launch_cfg_combine3(const float* eps3, float s1, float s2, float* eps, size_t n, hipStream_t s) {
+  PF_REQUIRE(eps3 && eps && n > 0, "cfg_combine3: bad arguments");
+  if ((((uintptr_t)eps3 | (uintptr_t)eps) & 15) == 0 && n % 4 == 0)
+    hipLaunchKernelGGL(cfg_combine3_vec_kernel, ew_grid(n / 4), dim3(256), 0, s, eps3, s1, s2, eps, n);
+  else
+    hipLaunchKernelGGL(cfg_combine3_kernel, ew_grid(n), dim3(256), 0, s, eps3, s1, s2, eps, n);
+  PF_CHECK_HIP(hipGetLastError());
+  return PF_OK;
+}
+
 // one element of the DDPM / RePaint update on VALUES (has_*: which optional operands take part)
 __device__ __forceinline__ float ddpm_update_v(float xv, float ev, bool has_p, float np, bool has_orig, bool has_q, float nq, float ov, float m,
                                                const pf_ddpm_coef& c) {

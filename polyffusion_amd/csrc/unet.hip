@@ -248,8 +248,9 @@ struct Ctx : BlockCtx {
   // hoisted step-invariant prefix (pf_unet_prepared): supplied parts are not recomputed; dry runs only need to know WHETHER they are
   bool has_time = false, has_cross = false;
   const float* prep_time = nullptr; int prep_time_rows = 0; const float* prep_cross = nullptr;
-  // classifier-free guidance with a shared prefix (pf_unet_forward_cfg): while `shared` the plan runs on the first Bfull / 2 samples only
-  bool cfg_share = false, shared = false; int Bfull = 0;
+  // classifier-free guidance with a shared prefix (pf_unet_forward_cfg / _cfgn): while `shared` the plan runs on the first Bfull / groups samples only
+  int groups = 0;   // 0: plain forward; 2 / 3: that many stacked evaluations of one x
+  bool shared = false; int Bfull = 0;
 
   void lnp(const float* x, int rows, int c, size_t gamma, size_t beta, float* planes) {   // LayerNorm -> hi/lo planes
     launch(PF_K_LNSTAT, 0.0, [&] { return launch_ln_planes(x, rows, c, 1e-5f, w(gamma), w(beta), planes, s); });
@@ -458,15 +459,16 @@ static int run(pf_unet* u, Ctx& c, const float* x, const int64_t* t, const float
 
   std::vector<Tn> skips;
   Tn cur;
-  // Classifier-free guidance with a shared prefix: until the first SpatialTransformer the plan runs on the first half of the batch only
-  // (the two halves are identical there: the condition has not entered yet); right before it the running tensor and its statistics are
-  // duplicated and the plan continues on the whole batch.  Skip tensors produced in the shared phase keep their half size and are read
-  // with the sample index modulo the half (Tn::bmod -> pf_conv_args.x1_bmod).
-  if (c.cfg_share) { c.Bfull = c.B; c.B = c.B / 2; c.shared = true; }
-  auto dup_rows = [&](const float* src, size_t floats_per_half) -> const float* {
-    float* dst = c.palloc(2 * floats_per_half);
-    for (int h = 0; h < 2; ++h)
-      c.launch(PF_K_SMALL, 0, [&] { return device_copy(dst + h * floats_per_half, src, floats_per_half, c.s); });
+  // Classifier-free guidance with a shared prefix: until the first SpatialTransformer the plan runs on the first group of the batch only
+  // (the groups - two halves, or the three thirds of dual guidance - are identical there: the condition has not entered yet); right before it
+  // the running tensor and its statistics are copied once per group and the plan continues on the whole batch.  Skip tensors produced in the
+  // shared phase keep their one-group size and are read with the sample index modulo the group (Tn::bmod -> pf_conv_args.x1_bmod).
+  const int G = c.groups;
+  if (G) { c.Bfull = c.B; c.B = c.B / G; c.shared = true; }
+  auto dup_rows = [&](const float* src, size_t floats_per_group) -> const float* {
+    float* dst = c.palloc(G * floats_per_group);
+    for (int h = 0; h < G; ++h)
+      c.launch(PF_K_SMALL, 0, [&] { return device_copy(dst + h * floats_per_group, src, floats_per_group, c.s); });
     return dst;
   };
   auto leave_shared_phase = [&](Tn& a0, int h, int w_) {
@@ -521,19 +523,22 @@ static int run(pf_unet* u, Ctx& c, const float* x, const int64_t* t, const float
   }
   // out: GN + SiLU + conv3x3 -> NCHW
   c.head(cur, H, W_, 32, u->out_g, u->out_b, u->out_w, u->out_bias, cfg.out_channels, eps);
-  if (c.shared) {   // a UNet without any transformer block never looked at the condition: both halves of eps are the same image
+  if (c.shared) {   // a UNet without any transformer block never looked at the condition: every group of eps is the same image
     const size_t n = (size_t)c.B * cfg.out_channels * H * W_;
-    c.launch(PF_K_SMALL, 0, [&] { return device_copy(eps + n, eps, n, c.s); });
+    for (int h = 1; h < G; ++h)
+      c.launch(PF_K_SMALL, 0, [&] { return device_copy(eps + h * n, eps, n, c.s); });
     c.B = c.Bfull; c.shared = false;
   }
   return c.rc;
 }
 
-static Ctx make_ctx(const pf_unet* u, int batch, int n_cond, bool cfg_share, bool has_time = false, bool has_cross = false) {
+static Ctx make_ctx(const pf_unet* u, int batch, int n_cond, int groups, bool has_time = false, bool has_cross = false) {
   Ctx c;
-  c.u = const_cast<pf_unet*>(u); c.o = u->po; c.B = batch; c.n_cond = n_cond; c.cfg_share = cfg_share; c.has_time = has_time; c.has_cross = has_cross;
+  c.u = const_cast<pf_unet*>(u); c.o = u->po; c.B = batch; c.n_cond = n_cond; c.groups = groups; c.has_time = has_time; c.has_cross = has_cross;
   return c;
 }
+// a stacked guidance batch the shared-prefix plan accepts: two or three groups of the same size
+static bool groups_ok(int batch_total, int groups) { return (groups == 2 || groups == 3) && batch_total > 0 && batch_total % groups == 0; }
 static PlanSize unet_plan(const Ctx& c) { return plan_sizes(c, [](Ctx& d) { run(d.u, d, nullptr, nullptr, nullptr, nullptr); }); }
 
 }  // namespace pf
@@ -570,10 +575,10 @@ int pf_unet_bind_weights(pf_unet* u, const void* dev_blob) {
 }
 
 size_t pf_unet_workspace_bytes(const pf_unet* u, int batch, int n_cond) {
-  return (u && batch > 0 && n_cond > 0) ? unet_plan(make_ctx(u, batch, n_cond, false)).bytes() : 0;
+  return (u && batch > 0 && n_cond > 0) ? unet_plan(make_ctx(u, batch, n_cond, 0)).bytes() : 0;
 }
 int pf_unet_n_launches(const pf_unet* u, int batch, int n_cond) {
-  return (u && batch > 0 && n_cond > 0) ? unet_plan(make_ctx(u, batch, n_cond, false)).n_launch : 0;
+  return (u && batch > 0 && n_cond > 0) ? unet_plan(make_ctx(u, batch, n_cond, 0)).n_launch : 0;
 }
 
 int pf_unet_forward(pf_unet* u, const float* x, const int64_t* t, const float* cond, int batch, int n_cond, float* eps,
@@ -582,15 +587,15 @@ int pf_unet_forward(pf_unet* u, const float* x, const int64_t* t, const float* c
 }
 
 static int forward_impl(pf_unet* u, const float* x, const int64_t* t, const float* cond, int batch, int n_cond, const pf_unet_prepared* prep,
-                        float* eps, void* workspace, size_t workspace_bytes, void* stream, bool cfg_share) {
+                        float* eps, void* workspace, size_t workspace_bytes, void* stream, int groups) {
   PF_REQUIRE(u && x && t && cond && eps && workspace, "pf_unet_forward: null argument");
   PF_REQUIRE(!prep || !prep->time_table || prep->n_time_rows > 0, "pf_unet_forward: time table without rows");
   PF_REQUIRE(!prep || !prep->cross_bias || n_cond == 1, "pf_unet_forward: the collapsed cross-attention bias exists only for n_cond == 1");
   PF_REQUIRE(batch > 0 && n_cond > 0, "pf_unet_forward: batch and n_cond must be positive");
-  PF_REQUIRE(!cfg_share || batch % 2 == 0, "pf_unet_forward_cfg: the batch is the two guidance halves (got %d)", batch);
+  PF_REQUIRE(!groups || groups_ok(batch, groups), "pf_unet_forward_cfg: the batch is 2 or 3 guidance groups of one size (got %d rows, %d groups)", batch, groups);
   if (!u->wt.wdev) return set_error(PF_ESTATE, "pf_unet_forward: weights not bound (call pf_unet_bind_weights)");
   PF_REQUIRE(n_cond == 1 || u->cfg.d_cond % 32 == 0, "pf_unet_forward: n_cond > 1 needs d_cond %% 32 == 0");
-  Ctx c = make_ctx(u, batch, n_cond, cfg_share);
+  Ctx c = make_ctx(u, batch, n_cond, groups);
   const int rc = c.use_workspace("pf_unet_forward", workspace, workspace_bytes, unet_plan(c), stream, u->wt.wdev);   // (the layout does not depend on `prep`)
   if (rc != PF_OK) return rc;
   if (prep && prep->time_table) { c.has_time = true; c.prep_time = prep->time_table; c.prep_time_rows = prep->n_time_rows; }
@@ -601,20 +606,29 @@ static int forward_impl(pf_unet* u, const float* x, const int64_t* t, const floa
 
 int pf_unet_forward_prepared(pf_unet* u, const float* x, const int64_t* t, const float* cond, int batch, int n_cond, const pf_unet_prepared* prep,
                              float* eps, void* workspace, size_t workspace_bytes, void* stream) {
-  return forward_impl(u, x, t, cond, batch, n_cond, prep, eps, workspace, workspace_bytes, stream, false);
+  return forward_impl(u, x, t, cond, batch, n_cond, prep, eps, workspace, workspace_bytes, stream, 0);
 }
 
 int pf_unet_forward_cfg(pf_unet* u, const float* x, const int64_t* t, const float* cond, int batch2, int n_cond, const pf_unet_prepared* prep,
                         float* eps2, void* workspace, size_t workspace_bytes, void* stream) {
-  return forward_impl(u, x, t, cond, batch2, n_cond, prep, eps2, workspace, workspace_bytes, stream, true);
+  return pf_unet_forward_cfgn(u, x, t, cond, batch2, 2, n_cond, prep, eps2, workspace, workspace_bytes, stream);
+}
+size_t pf_unet_workspace_bytes_cfg(const pf_unet* u, int batch2, int n_cond) { return pf_unet_workspace_bytes_cfgn(u, batch2, 2, n_cond); }
+int pf_unet_n_launches_cfg(const pf_unet* u, int batch2, int n_cond, int has_time, int has_cross) {
+  return pf_unet_n_launches_cfgn(u, batch2, 2, n_cond, has_time, has_cross);
 }
 
-size_t pf_unet_workspace_bytes_cfg(const pf_unet* u, int batch2, int n_cond) {
-  return (u && batch2 > 0 && batch2 % 2 == 0 && n_cond > 0) ? unet_plan(make_ctx(u, batch2, n_cond, true)).bytes() : 0;
+int pf_unet_forward_cfgn(pf_unet* u, const float* x, const int64_t* t, const float* cond, int batch_total, int groups, int n_cond,
+                         const pf_unet_prepared* prep, float* eps, void* workspace, size_t workspace_bytes, void* stream) {
+  PF_REQUIRE(groups_ok(batch_total, groups), "pf_unet_forward_cfgn: the batch is 2 or 3 guidance groups of one size (got %d rows, %d groups)", batch_total, groups);
+  return forward_impl(u, x, t, cond, batch_total, n_cond, prep, eps, workspace, workspace_bytes, stream, groups);
 }
-int pf_unet_n_launches_cfg(const pf_unet* u, int batch2, int n_cond, int has_time, int has_cross) {
-  if (!u || batch2 <= 0 || batch2 % 2 || n_cond <= 0) return 0;
-  return unet_plan(make_ctx(u, batch2, n_cond, true, has_time != 0, has_cross != 0 && n_cond == 1)).n_launch;
+size_t pf_unet_workspace_bytes_cfgn(const pf_unet* u, int batch_total, int groups, int n_cond) {
+  return (u && groups_ok(batch_total, groups) && n_cond > 0) ? unet_plan(make_ctx(u, batch_total, n_cond, groups)).bytes() : 0;
+}
+int pf_unet_n_launches_cfgn(const pf_unet* u, int batch_total, int groups, int n_cond, int has_time, int has_cross) {
+  if (!u || !groups_ok(batch_total, groups) || n_cond <= 0) return 0;
+  return unet_plan(make_ctx(u, batch_total, n_cond, groups, has_time != 0, has_cross != 0 && n_cond == 1)).n_launch;
 }
 
 int pf_unet_time_bias_width(const pf_unet* u) { return u ? u->tbias.sum : 0; }
@@ -638,7 +652,7 @@ int pf_unet_prepare_cond(pf_unet* u, const float* cond, int batch, float* cross,
   if (!u->wt.wdev) return set_error(PF_ESTATE, "pf_unet_prepare_cond: weights not bound (call pf_unet_bind_weights)");
   PF_REQUIRE(u->cross_total > 0, "pf_unet_prepare_cond: this UNet has no transformer block");
   PF_REQUIRE(scratch_bytes >= (size_t)batch * u->cross_total * sizeof(float), "pf_unet_prepare_cond: scratch too small");
-  Ctx c = make_ctx(u, batch, 1, false);   // a live context without a workspace (and without the profiler)
+  Ctx c = make_ctx(u, batch, 1, 0);   // a live context without a workspace (and without the profiler)
   c.dry = false; c.s = (hipStream_t)stream; c.W = u->wt.wdev;
   cross_bias_launches(u, c, cond, batch, cross, static_cast<float*>(scratch));
   return c.rc;
@@ -646,7 +660,7 @@ int pf_unet_prepare_cond(pf_unet* u, const float* cond, int batch, float* cross,
 
 int pf_unet_n_launches_prepared(const pf_unet* u, int batch, int n_cond, int has_time, int has_cross) {
   if (!u || batch <= 0 || n_cond <= 0) return 0;
-  return unet_plan(make_ctx(u, batch, n_cond, false, has_time != 0, has_cross != 0 && n_cond == 1)).n_launch;
+  return unet_plan(make_ctx(u, batch, n_cond, 0, has_time != 0, has_cross != 0 && n_cond == 1)).n_launch;
 }
 
 int pf_unet_set_option(pf_unet* u, int option, int value) {

@@ -29,7 +29,7 @@ import torch
 from . import _lib, datasample, midi, synth
 from .model_sdf import ChordEncoder, Polyffusion_SDF, TextureEncoder
 from .params import Params, find_params, load_params, preset
-from .sampler import DDIMSampler, DiffusionSampler, DPMSolverSampler, SDFSampler
+from .sampler import GUIDANCE_ORDERS, DDIMSampler, DiffusionSampler, DPMSolverSampler, DualScale, SDFSampler
 from .unet import LatentDiffusion, UNetModel
 
 
@@ -345,7 +345,9 @@ def encode_conditions(model: Polyffusion_SDF, params, chd, prmat, autoreg: bool,
         assert chd is not None and prmat is not None
         n = min(chd.shape[0], prmat.shape[0])
         chd, prmat = chd[:n], prmat[:n]
-        cond = torch.cat([model._encode_chord(chd), model._encode_txt(prmat)], dim=-1)
+        zchd = model._encode_chord(chd)
+        model.cond_split = int(zchd.shape[-1])       # where the texture part begins (DualScale.split: read here, where the two are joined)
+        cond = torch.cat([zchd, model._encode_txt(prmat)], dim=-1)
         if autoreg:
             cond_mid = torch.cat([model._encode_chord(get_autoreg_data(chd)), model._encode_txt(get_autoreg_data(prmat))], dim=-1)
     else:
@@ -358,6 +360,15 @@ def make_parser() -> ArgumentParser:
     p.add_argument("--chkpt_path", help="the path of the checkpoint to be used")
     p.add_argument("--custom_params_path", help="params yaml/json; default <chkpt>/../../params.yaml")
     p.add_argument("--uncond_scale", type=float, default=1.0, help="unconditional scale for classifier-free guidance")
+    # extension: dual guidance for chord+txt models (sampler.DualScale) - what cond_mode mix2 trains for
+    p.add_argument("--uncond_scale_chd", type=float, default=None, metavar="X", help="extension, chord+txt models, together with "
+                   "--uncond_scale_txt: separate guidance scales for the chord and the texture part of the condition.  With the default "
+                   "--guidance_order chd,txt: eps = eps(-,-) + X * (eps(chd,-) - eps(-,-)) + Y * (eps(chd,txt) - eps(chd,-)); with txt,chd: "
+                   "eps = eps(-,-) + Y * (eps(-,txt) - eps(-,-)) + X * (eps(chd,txt) - eps(-,txt)) ('-' = that part dropped, as cond_mode "
+                   "mix2 trains it).  X == Y is --uncond_scale X; costs three denoiser evaluations per step instead of two")
+    p.add_argument("--uncond_scale_txt", type=float, default=None, metavar="Y", help="extension: the texture scale Y of --uncond_scale_chd")
+    p.add_argument("--guidance_order", choices=list(GUIDANCE_ORDERS), default="chd,txt", metavar="{chd,txt | txt,chd}", help="extension: which part the intermediate "
+                   "evaluation of --uncond_scale_chd / --uncond_scale_txt keeps (the part named first); default: chd,txt")
     p.add_argument("--seed", type=int, help="use a specific seed for inference")
     p.add_argument("--autoreg", action="store_true", help="autoregressively inpaint the music segments")
     p.add_argument("--from_dataset", default=None, help="choose condition from a dataset {pop909, musicalion} (validation half of its split)")
@@ -413,6 +424,28 @@ def make_parser() -> ArgumentParser:
     p.add_argument("--hip_graph", action="store_true", help="capture one reverse step as a hipGraph and replay it (same results; "
                    "removes the host-side launch cost that bounds small batches, e.g. the batch-1 runs of --autoreg)")
     return p
+
+
+def wants_dual_guidance(args, cond_type: str) -> bool:
+    """Whether the command line asks for dual guidance (``--uncond_scale_chd X --uncond_scale_txt Y``); every misuse is a ``SystemExit``."""
+    x, y = getattr(args, "uncond_scale_chd", None), getattr(args, "uncond_scale_txt", None)
+    if x is None and y is None:
+        return False
+    if x is None or y is None:
+        raise SystemExit("--uncond_scale_chd and --uncond_scale_txt go together: give both (equal values are --uncond_scale)")
+    if cond_type != "chord+txt":
+        raise SystemExit(f"--uncond_scale_chd / --uncond_scale_txt steer the two parts of a chord+txt condition; this model's cond_type is "
+                         f"{cond_type!r} (use --uncond_scale)")
+    if args.uncond_scale != make_parser().get_default("uncond_scale"):
+        raise SystemExit("--uncond_scale together with --uncond_scale_chd / --uncond_scale_txt: give the single scale or the two, not both")
+    return True
+
+
+def dual_scale(args, split: int) -> DualScale:
+    """The command line's ``DualScale``: X scales the term that brings the chord in and Y the texture's, whichever comes first."""
+    x, y = args.uncond_scale_chd, args.uncond_scale_txt
+    first, second = (x, y) if args.guidance_order == "chd,txt" else (y, x)
+    return DualScale(first, second, split, args.guidance_order)
 
 
 def polydis_aftertouch(args, say=print):
@@ -579,8 +612,10 @@ def make_sampler(model, args, seed: int, sample_offset: int = 0):
     return SDFSampler(model.ldm, seed=seed, sample_offset=sample_offset, graph=getattr(args, "hip_graph", False)), None
 
 
-def generate_songs(model, params, args, cond, cond_mid, orig, mask, seed: int, rank: int = 0, world: int = 1, cond_concat=None):
-    """This rank's share of ``args.num_generate`` independent generations of the same conditions.
+def generate_songs(model, params, args, cond, cond_mid, orig, mask, seed: int, rank: int = 0, world: int = 1, cond_concat=None,
+                   uncond_scale=None):
+    """This rank's share of ``args.num_generate`` independent generations of the same conditions.  ``uncond_scale``: the guidance scale
+    (``None``: ``args.uncond_scale``; a ``DualScale`` for dual guidance) - handed to the sampler as it is.
 
     The reference loops over the songs (``inference_sdf.py:774``); here they are ONE batch and the unit of multi-GPU
     sharding: rank r takes the songs ``shard_range(num_generate, r, world)``, keyed into the noise generator by their
@@ -593,16 +628,17 @@ def generate_songs(model, params, args, cond, cond_mid, orig, mask, seed: int, r
     per_song = 1 if args.autoreg else B   # images the sampler sees per song in one paint() call
     sampler, t_idx = make_sampler(model, args, seed, lo * per_song)
     expmt = Experiments(params.model_name, params, sampler, t_idx=t_idx, repaint_n=args.repaint_n)
+    scale = args.uncond_scale if uncond_scale is None else uncond_scale
     rep = lambda v: None if v is None else v.unsqueeze(0).expand(n_local, *v.shape).contiguous()
     C, H, W = params.out_channels, params.img_h, params.img_w
     if n_local == 0:
         gen = torch.empty(0, 2 * B if args.autoreg else B, C, H // 2 if args.autoreg else H, W, device=cond.device)
     elif args.autoreg:
-        gen = expmt.predict_songs(rep(cond), rep(cond_mid), args.uncond_scale, orig=rep(orig), mask=rep(mask),
+        gen = expmt.predict_songs(rep(cond), rep(cond_mid), scale, orig=rep(orig), mask=rep(mask),
                                   cond_concat=rep(cond_concat))   # [n,2B,C,H/2,W]
     else:
         flat = lambda v: None if v is None else rep(v).reshape(n_local * B, *v.shape[1:])
-        gen = expmt.predict(flat(cond), None, args.uncond_scale, False, flat(orig), flat(mask),
+        gen = expmt.predict(flat(cond), None, scale, False, flat(orig), flat(mask),
                             cond_concat=flat(cond_concat)).reshape(n_local, B, C, H, W)
     return gen, expmt
 
@@ -644,6 +680,7 @@ def main(argv=None):
             params.setdefault("cond_mode", "cond")
             params.setdefault("use_enc", True)
     say(f"model_label: {params.model_name}")
+    dual = wants_dual_guidance(args, params.cond_type)     # (refusals before any weight is loaded)
     try:
         model = load_model(params, args, rank, world)
     except SystemExit as e:
@@ -748,6 +785,8 @@ def main(argv=None):
     if args.polydis and rank == 0:
         write_polydis(args, chd, prmat, seed, say)
     cond, cond_mid = encode_conditions(model, params, chd, prmat, args.autoreg, pnotree=pnotree)
+    # the guidance scale every later stage passes on unchanged: the float, or the two scales with the chord part's width as just concatenated
+    scale = dual_scale(args, model.cond_split) if dual else args.uncond_scale
     if params.cond_type == "pnotree" and rank == 0 and not args.no_pnotree_recon:
         write_pnotree_recon(model, args, cond, say)
     if params.cond_mode == "uncond":
@@ -807,8 +846,8 @@ def main(argv=None):
     else:
         model.ldm.eps_model.set_precision(args.precision)
     S, B = args.num_generate, cond.shape[0]
-    say(f"generating {S} song(s) x {B} segment(s) with uncond_scale = {args.uncond_scale} on {world} GPU(s)")
-    gen, expmt = generate_songs(model, params, args, cond, cond_mid, orig, mask, seed, rank, world, cond_concat=cond_concat)
+    say(f"generating {S} song(s) x {B} segment(s) with uncond_scale = {scale} on {world} GPU(s)")
+    gen, expmt = generate_songs(model, params, args, cond, cond_mid, orig, mask, seed, rank, world, cond_concat=cond_concat, uncond_scale=scale)
     gen = pfdist.gather_rows(gen, S, rank, world)   # [S, ...] on every rank (131 KB per image; the only end-of-run exchange)
     if not bool(torch.isfinite(gen).all()):
         # the note threshold (> 0.5) would turn a NaN into silence: refuse instead.  The one known way to get here is an activation beyond
@@ -821,7 +860,7 @@ def main(argv=None):
         stamps = []
         for i in range(S):
             extra = "" if args.inpaint_type is None else f"_inp{args.repaint_n}_{args.inpaint_type}"
-            stamp = os.path.join(args.output_dir, expmt._stamp(args.uncond_scale, args.autoreg, extra) + (f"_{i}" if S > 1 else ""))
+            stamp = os.path.join(args.output_dir, expmt._stamp(scale, args.autoreg, extra) + (f"_{i}" if S > 1 else ""))
             stamps.append(stamp)
             np.save(stamp + ".npy", gen[i].cpu().numpy())
             # generated cells on their own track when inpainting (ref:inference_sdf.py:385-389)

@@ -5,6 +5,8 @@
 * ``SDFSampler``        - ``sampler_sdf.py`` (tables :52-78, ``p_sample`` :80-171, ``q_sample``
   :173-192, ``sample`` :194-255, ``paint`` :257-350 incl. the RePaint quirks of Appendix A).
 * ``DDIMSampler``       - ``sampler_ddim.py`` (tables :40-102, step :168-272, ``paint`` :301-362).
+* ``DualScale`` / ``guidance_plan`` - not in the reference: separate guidance scales for the chord and texture parts of a ``chord+txt``
+  condition, passed as ``uncond_scale``; the one function that decides what a guided eps evaluates.
 * ``DPMSolverSampler``  - not in the reference: DPM-Solver++(2M), the second-order multistep solver, driven like ``DDIMSampler``.
 
 Same method names and argument meaning as the reference, so ``Experiments.predict`` drives
@@ -26,7 +28,8 @@ them unchanged.  Differences, all host-side plumbing:
 """
 from __future__ import annotations
 
-from typing import Callable, List, Optional
+from dataclasses import dataclass
+from typing import Callable, List, Optional, Tuple, Union
 
 import numpy as np
 import torch
@@ -35,6 +38,88 @@ from . import _lib, _steps
 from .unet import LatentDiffusion
 
 NoiseFn = Callable[[tuple], torch.Tensor]
+
+GUIDANCE_ORDERS = ("chd,txt", "txt,chd")
+
+
+@dataclass(frozen=True)
+class DualScale:
+    """Two guidance scales for a condition token that concatenates a chord part (columns ``[:split]``) and a texture part (``[split:]``), as
+    the ``chord+txt`` models build it (``Polyffusion_SDF.get_loss_dict``: ``cat([zchd, ztxt], -1)``) and ``cond_mode: mix2`` trains it (each
+    part dropped on its own).  Not in the reference.  Passed wherever ``uncond_scale`` takes a float::
+
+        eps = eps(-, -) + first * (eps(a, -) - eps(-, -)) + second * (eps(a, b) - eps(a, -))
+
+    where ``a`` is the part ``order`` names first (``"chd,txt"``: the intermediate evaluation keeps the chord and drops the texture;
+    ``"txt,chd"``: the other way round) and a dropped part takes ``uncond_cond``'s columns.  Frozen and hashable: it is part of the key of a
+    captured step.  Exact-float reductions (``guidance_plan``): ``first == second`` is single-scale guidance with that scale, bit for bit;
+    ``second == 0`` is single-scale guidance towards the partial condition."""
+    first: float
+    second: float
+    split: int
+    order: str = "chd,txt"
+
+    def __post_init__(self):
+        if self.order not in GUIDANCE_ORDERS:
+            raise ValueError(f"DualScale: order {self.order!r}, expected one of {GUIDANCE_ORDERS}")
+        object.__setattr__(self, "first", float(self.first))
+        object.__setattr__(self, "second", float(self.second))
+        object.__setattr__(self, "split", int(self.split))
+
+    @property
+    def chd(self) -> float:
+        """The scale of the term that brings the chord in."""
+        return self.first if self.order == "chd,txt" else self.second
+
+    @property
+    def txt(self) -> float:
+        return self.second if self.order == "chd,txt" else self.first
+
+    def __str__(self):          # what Experiments._stamp writes after "scale="
+        return f"chd:{self.chd},txt:{self.txt}" + ("" if self.order == "chd,txt" else ",txt-first")
+
+    def partial(self, cond: torch.Tensor, uncond_cond: torch.Tensor) -> torch.Tensor:
+        """``cond`` with the columns of the part named second replaced by ``uncond_cond``'s."""
+        if not 0 < self.split < cond.shape[-1]:
+            raise ValueError(f"DualScale: split {self.split} is not inside (0, {cond.shape[-1]}), the condition's last dimension")
+        k, uc = self.split, uncond_cond.expand_as(cond)
+        if self.order == "chd,txt":
+            return torch.cat([cond[..., :k], uc[..., k:]], dim=-1)
+        return torch.cat([uc[..., :k], cond[..., k:]], dim=-1)
+
+
+Scale = Union[float, DualScale]
+
+
+def scale_key(uncond_scale: Scale):
+    """The guidance scale as part of a hashable key: the ``DualScale`` itself, or the float."""
+    return uncond_scale if isinstance(uncond_scale, DualScale) else float(uncond_scale)
+
+
+def guidance_plan(cond: torch.Tensor, uncond_scale: Scale, uncond_cond: Optional[torch.Tensor]) -> Tuple[torch.Tensor, int, tuple]:
+    """THE branch logic of guided eps, shared by ``prepare`` and ``get_eps``: ``(context batch, groups, combine arguments)``.
+      groups 1: the model on ``context`` is the result                                        (arguments ``()``)
+      groups 2: ``context = cat([uncond_cond, c])``, ``pf_cfg_combine`` with ``(scale,)``       (the reference's ``get_eps``)
+      groups 3: ``context = cat([uncond_cond, partial, cond])``, ``pf_cfg_combine3`` with ``(first, second)``
+    A float takes the reference's exact-float branches (``sampler/__init__.py:63-74``): no ``uncond_cond`` or scale 1 -> ``cond`` alone,
+    scale 0 -> ``uncond_cond`` alone.  A ``DualScale`` reduces first - ``first == second``: the float ``first`` with ``cond``;
+    ``second == 0``: the float ``first`` with the partial condition in place of ``cond`` - and takes the float's branches from there."""
+    if isinstance(uncond_scale, DualScale):
+        ds = uncond_scale
+        if uncond_cond is None:
+            raise ValueError("DualScale guidance needs uncond_cond (the columns a dropped part takes)")
+        partial = ds.partial(cond, uncond_cond)        # (validates split also where a reduction does not use the result)
+        if ds.first == ds.second:
+            uncond_scale = ds.first
+        elif ds.second == 0.0:
+            cond, uncond_scale = partial, ds.first
+        else:
+            return torch.cat([uncond_cond, partial, cond]), 3, (ds.first, ds.second)
+    if uncond_cond is None or uncond_scale == 1.0:
+        return cond, 1, ()
+    if uncond_scale == 0.0:
+        return uncond_cond, 1, ()
+    return torch.cat([uncond_cond, cond]), 2, (float(uncond_scale),)
 
 
 class DiffusionSampler:
@@ -160,7 +245,7 @@ class DiffusionSampler:
                 _lib.check(self._lib.pf_step_end(st.data_ptr(), ndraw, _lib.current_stream()), "pf_step_end")
             return body
 
-        key = (family, str(dev), float(uncond_scale), self.seed, self._elem_offset(x.shape), ndraw) + self._shape_key(**inputs)
+        key = (family, str(dev), scale_key(uncond_scale), self.seed, self._elem_offset(x.shape), ndraw) + self._shape_key(**inputs)
         ent = self._graph_for(key, inputs, make_body, lambda: self._set_state(st, t_start), uncond_scale)
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         e0.record()
@@ -186,16 +271,11 @@ class DiffusionSampler:
         ``time_table`` [n_steps, W] (time MLP + all ``emb_layers`` per time-step value, ``unet.py:181-182, 286-289``) and ``cross`` -
         the collapsed one-token cross-attention biases (``unet_attention.py:186-212``) of exactly the context batch ``get_eps`` feeds
         the model: ``cond``, ``uncond_cond`` or ``cat([uncond_cond, cond])`` by the reference's exact-float branches
-        (``sampler/__init__.py:63-74``).  ``None`` entries (several context tokens) are computed inside every forward as before.
+        (``sampler/__init__.py:63-74``; ``guidance_plan`` decides, for ``get_eps`` too).  ``None`` entries (several context tokens) are computed inside every forward as before.
         Called explicitly by the loops of this class; pass the result as ``prep=`` with the SAME cond / guidance arguments.
         ``out``: a previous result whose buffers are overwritten in place (captured-graph replay)."""
         m = self.model.eps_model
-        if uncond_cond is None or uncond_scale == 1.0:
-            ctx = cond
-        elif uncond_scale == 0.0:
-            ctx = uncond_cond
-        else:
-            ctx = torch.cat([uncond_cond, cond])
+        ctx = guidance_plan(cond, uncond_scale, uncond_cond)[0]     # (a DualScale: possibly the three groups of dual guidance)
         o = out or {}
         # one row more than the schedule has steps: the DDIM tau table is shifted by +1 (sampler_ddim.py:63-73)
         return {"time_table": m.prepare_time(self.model.n_steps + 1, out=o.get("time_table")),
@@ -206,24 +286,28 @@ class DiffusionSampler:
         return {} if prep is None else {"time_table": prep["time_table"], "cross_bias": prep["cross"]}
 
     # ---- eps with classifier-free guidance ----------------------------------------------------------
-    def get_eps(self, x: torch.Tensor, t: torch.Tensor, c: torch.Tensor, *, uncond_scale: float,
+    def get_eps(self, x: torch.Tensor, t: torch.Tensor, c: torch.Tensor, *, uncond_scale: Scale,
                 uncond_cond: Optional[torch.Tensor], prep: Optional[dict] = None):
+        """``uncond_scale``: the reference's float, or a ``DualScale`` (separate scales for the chord and texture parts of ``c``)."""
         kw = self._prep_kw(prep)
-        if uncond_cond is None or uncond_scale == 1.0:
-            return self.model(x, t, c, **kw)
-        elif uncond_scale == 0.0:
-            return self.model(x, t, uncond_cond, **kw)
-        # re-concatenated on every call like the reference (sampler/__init__.py:69-74): [2B,n_cond,d_cond] is a few KB, and a
+        # the context is re-concatenated on every call like the reference (sampler/__init__.py:69-74): [2B,n_cond,d_cond] is a few KB, and a
         # cache keyed on addresses could serve a stale tensor after an in-place update or an allocator address reuse
+        ctx, groups, scales = guidance_plan(c, uncond_scale, uncond_cond)
+        if groups == 1:
+            return self.model(x, t, ctx, **kw)
+        tg = torch.cat([t] * groups)
         if self.share_cfg_prefix and getattr(self.model, "supports_shared_x", False):
-            # the two halves see the same x and t and differ only in the condition, which enters the UNet at its first transformer
-            # block: everything in front of it is evaluated once for both (UNetModel.forward(shared_x=True), pf_unet_forward_cfg)
-            eps2 = self.model(x, torch.cat([t, t]), torch.cat([uncond_cond, c]), shared_x=True, **kw)
+            # the groups see the same x and t and differ only in the condition, which enters the UNet at its first transformer
+            # block: everything in front of it is evaluated once for all (UNetModel.forward(shared_x=), pf_unet_forward_cfg / _cfgn)
+            epsg = self.model(x, tg, ctx, shared_x=True if groups == 2 else groups, **kw)
         else:
-            eps2 = self.model(torch.cat([x, x]), torch.cat([t, t]), torch.cat([uncond_cond, c]), **kw)
-        e_t = torch.empty_like(eps2[: x.shape[0]])   # eps has out_channels; x may carry extra cond_concat channels
-        _lib.check(self._lib.pf_cfg_combine(eps2.data_ptr(), float(uncond_scale), e_t.data_ptr(), e_t.numel(),
-                                            _lib.current_stream()), "pf_cfg_combine")
+            epsg = self.model(torch.cat([x] * groups), tg, ctx, **kw)
+        e_t = torch.empty_like(epsg[: x.shape[0]])   # eps has out_channels; x may carry extra cond_concat channels
+        if groups == 2:
+            _lib.check(self._lib.pf_cfg_combine(epsg.data_ptr(), scales[0], e_t.data_ptr(), e_t.numel(), _lib.current_stream()), "pf_cfg_combine")
+        else:
+            _lib.check(self._lib.pf_cfg_combine3(epsg.data_ptr(), scales[0], scales[1], e_t.data_ptr(), e_t.numel(), _lib.current_stream()),
+                       "pf_cfg_combine3")
         return e_t
 
     def _t_of(self, step: int, batch: int, device) -> torch.Tensor:

@@ -58,12 +58,24 @@ class UNetModel(ModelHandle):
         return self
 
     # ---- forward --------------------------------------------------------------------------------
-    def workspace(self, batch: int, n_cond: int, shared_x: bool = False) -> torch.Tensor:
-        # tile choice (and buffer sizes) depend on the arithmetic mode and on the plan options; the shared-prefix guidance plan has a layout of its own
-        key = (batch, n_cond, shared_x, self._lib.pf_unet_get_precision(self._h)) + self.options_key()
+    @staticmethod
+    def _groups(shared_x) -> int:
+        """``shared_x`` as a group count: 0 for a plain forward, ``True`` = 2 (classifier-free guidance), 2 or 3 as given."""
+        if not shared_x:                # False, None, or a group count of 0 as this method returns it
+            return 0
+        g = 2 if shared_x is True else int(shared_x)
+        if g not in (2, 3):
+            raise ValueError(f"shared_x={shared_x!r}: the shared-prefix plan runs 2 or 3 stacked evaluations (True means 2)")
+        return g
+
+    def workspace(self, batch: int, n_cond: int, shared_x=False) -> torch.Tensor:
+        # tile choice (and buffer sizes) depend on the arithmetic mode and on the plan options; the shared-prefix guidance plan has a layout of
+        # its own per group count
+        g = self._groups(shared_x)
+        key = (batch, n_cond, g, self._lib.pf_unet_get_precision(self._h)) + self.options_key()
         if self._ws is None or self._ws_key != key:
-            size = self._lib.pf_unet_workspace_bytes_cfg if shared_x else self._lib.pf_unet_workspace_bytes
-            self.workspace_for(size(self._h, batch, n_cond), self.device)
+            nbytes = self._lib.pf_unet_workspace_bytes_cfgn(self._h, batch, g, n_cond) if g else self._lib.pf_unet_workspace_bytes(self._h, batch, n_cond)
+            self.workspace_for(nbytes, self.device)
             self._ws_key = key
         return self._ws
 
@@ -104,34 +116,36 @@ class UNetModel(ModelHandle):
 
     def forward(self, x: torch.Tensor, time_steps: torch.Tensor, cond: torch.Tensor, out: Optional[torch.Tensor] = None, *,
                 time_table: Optional[torch.Tensor] = None, cross_bias: Optional[torch.Tensor] = None, check_t: bool = False,
-                shared_x: bool = False):
+                shared_x=False):
         """``time_table`` / ``cross_bias``: results of ``prepare_time`` / ``prepare_cond(cond)`` - the caller vouches that they
         belong to these weights and this ``cond``; either may be ``None`` (computed here).  Bit-identical either way.
         ``shared_x=True`` - classifier-free guidance (``sampler/__init__.py:69-74``): ``x`` holds B samples while ``time_steps`` and
         ``cond`` hold the 2B rows of ``cat([t, t])`` / ``cat([uncond_cond, cond])``; the result equals ``forward(cat([x, x]), ...)`` up to
         tile-choice rounding, but everything in front of the first transformer block - where the two halves cannot differ - is computed
         once (``pf_unet_forward_cfg``).  PRECONDITION: ``time_steps[:B] == time_steps[B:]`` (the shared prefix uses the first half's rows;
-        verified under ``check_t``).
+        verified under ``check_t``).  ``shared_x=3``: the same over three groups - ``time_steps`` and ``cond`` hold the 3B rows of a dual-guidance
+        evaluation, ``cat([uncond_cond, partial, cond])`` (``pf_unet_forward_cfgn``); every group carries the same ``t``.
         The prepared path is valid for ``0 <= t < time_table.shape[0]`` only; ``check_t=True`` verifies that (one device->host
         sync - the samplers, whose t values are rows of a host-built table, do not ask for it)."""
         if self._blob_dev is None:
             raise RuntimeError("UNetModel.forward: weights not loaded")
-        B = x.shape[0] * (2 if shared_x else 1)
+        G = self._groups(shared_x)
+        B = x.shape[0] * (G or 1)
         if tuple(x.shape[1:]) != (self.cfg.in_channels, self.img_h, self.img_w):
             raise RuntimeError(f"UNetModel.forward: x has shape {tuple(x.shape)}, expected [B,{self.cfg.in_channels},{self.img_h},{self.img_w}]")
         if cond.dim() != 3 or cond.shape[0] != B or cond.shape[2] != self.cfg.d_cond:
-            raise RuntimeError(f"UNetModel.forward: cond has shape {tuple(cond.shape)}, expected [{'2B' if shared_x else 'B'},n_cond,{self.cfg.d_cond}]")
+            raise RuntimeError(f"UNetModel.forward: cond has shape {tuple(cond.shape)}, expected [{f'{G}B' if G else 'B'},n_cond,{self.cfg.d_cond}]")
         if time_steps.shape[0] != B:
             raise RuntimeError(f"UNetModel.forward: {time_steps.shape[0]} time steps for {B} condition rows")
         x = x.contiguous().float()
         cond = cond.contiguous().float()
         t = time_steps.to(torch.int64).contiguous()
-        if shared_x and check_t and not torch.equal(t[: B // 2], t[B // 2:]):
-            # the shared prefix is evaluated once, with the first half's time rows: the two halves of a guidance evaluation carry the same t
-            raise RuntimeError("UNetModel.forward(shared_x=True): the two halves of time_steps must be equal "
-                               "(the conditional and unconditional evaluations share everything in front of the first transformer block)")
+        if G and check_t and not all(torch.equal(t[: B // G], t[g * (B // G): (g + 1) * (B // G)]) for g in range(1, G)):
+            # the shared prefix is evaluated once, with the first group's time rows: all groups of a guidance evaluation carry the same t
+            raise RuntimeError(f"UNetModel.forward(shared_x={shared_x!r}): the {G} groups of time_steps must be equal "
+                               "(the evaluations of one guidance step share everything in front of the first transformer block)")
         n_cond = cond.shape[1]
-        ws = self.workspace(B, n_cond, shared_x)
+        ws = self.workspace(B, n_cond, G)
         if out is None:
             out = torch.empty(B, self.cfg.out_channels, self.img_h, self.img_w, dtype=torch.float32, device=x.device)
         prep = None
@@ -151,9 +165,12 @@ class UNetModel(ModelHandle):
             if cross_bias is not None:
                 assert n_cond == 1 and cross_bias.shape[0] == B and cross_bias.is_contiguous() and cross_bias.device == x.device
                 prep.cross_bias = cross_bias.data_ptr()
-        fn = self._lib.pf_unet_forward_cfg if shared_x else self._lib.pf_unet_forward_prepared
-        self._check(fn(self._h, x.data_ptr(), t.data_ptr(), cond.data_ptr(), B, n_cond, None if prep is None else C.byref(prep), out.data_ptr(),
-                      ws.data_ptr(), ws.numel(), _lib.current_stream()), "pf_unet_forward")
+        args = (None if prep is None else C.byref(prep), out.data_ptr(), ws.data_ptr(), ws.numel(), _lib.current_stream())
+        if G:
+            rc = self._lib.pf_unet_forward_cfgn(self._h, x.data_ptr(), t.data_ptr(), cond.data_ptr(), B, G, n_cond, *args)
+        else:
+            rc = self._lib.pf_unet_forward_prepared(self._h, x.data_ptr(), t.data_ptr(), cond.data_ptr(), B, n_cond, *args)
+        self._check(rc, "pf_unet_forward")
         return out
 
     __call__ = forward
@@ -230,9 +247,10 @@ class UNetModel(ModelHandle):
         n = self._check(self._lib.pf_unet_profile_read_direct(self._h, fl, cap))
         return [fl[i] for i in range(n)]
 
-    def n_launches(self, batch: int, n_cond: int = 1, prepared: bool = False, shared_x: bool = False) -> int:
-        if shared_x:     # batch = the 2B rows of a guidance evaluation
-            return int(self._lib.pf_unet_n_launches_cfg(self._h, batch, n_cond, int(prepared), int(prepared)))
+    def n_launches(self, batch: int, n_cond: int = 1, prepared: bool = False, shared_x=False) -> int:
+        g = self._groups(shared_x)
+        if g:            # batch = the 2B (3B) rows of a guidance evaluation
+            return int(self._lib.pf_unet_n_launches_cfgn(self._h, batch, g, n_cond, int(prepared), int(prepared)))
         if prepared:
             return int(self._lib.pf_unet_n_launches_prepared(self._h, batch, n_cond, 1, 1))
         return int(self._lib.pf_unet_n_launches(self._h, batch, n_cond))
