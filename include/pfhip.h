@@ -165,6 +165,35 @@ int pf_cfg_combine(const float* eps2, float scale, float* eps, size_t n, void* s
  * aligned and n % 4 == 0, 4-byte elements otherwise: the same bits. */
 int pf_cfg_combine3(const float* eps3, float s1, float s2, float* eps, size_t n, void* stream);
 
+/* Overlapping windows along the time axis (not in the reference; MultiDiffusion, Bar-Tal et al. 2023, on the rows of a piano roll): a song is
+ * a canvas [songs][channels][canvas_h][width], canvas_h = stride * (n_windows - 1) + win_h, and the denoiser sees it as the batch of its
+ * n_windows windows of win_h rows.  Window j of song s is batch row s * n_windows + j (song-major) and canvas rows [j * stride, j * stride + win_h).
+ * Canvas row y is covered by the windows j with 0 <= y - j * stride < win_h, taken in ascending j; k(y) is their number.
+ *   pf_window_split: windows[s * n_windows + j][c][r][w] = canvas[s][c][j * stride + r][w]      (a copy; `channels` is whatever the canvas carries)
+ *   pf_window_merge: the windows' noise predictions back onto the canvas, with the guidance combine folded in.  eps is
+ *     [groups][songs * n_windows][channels][win_h][width], group-major as the guided evaluation stacks it.  Per canvas element, in fp32, every
+ *     operation individually rounded and in this order:
+ *       e_j = eps                                     groups == 1
+ *           = pf_cfg_combine's expression (scale s1)   groups == 2      the same device functions, so the same bits as the combine
+ *           = pf_cfg_combine3's expression (s1, s2)    groups == 3      launch followed by a groups == 1 merge
+ *       k(y) == 1:  out = e_j                          a select, not w*e/w: a row one window owns comes through bit for bit
+ *       otherwise:  num = w_0*e_0, num += w_j*e_j ; den = w_0, den += w_j ; out = num / den        w_j = row_weight[y - j * stride]
+ *     row_weight: win_h floats on the device, all > 0 (ones: the plain mean).
+ * Both are gathers over their output - no atomics, no shared memory, nothing order-dependent - so a launch is bit-reproducible.  16-byte
+ * vectors along width when width % 4 == 0 and every pointer is 16-byte aligned, 4-byte elements otherwise: the same bits.  Refused before
+ * any launch (message prefix "window_split: " / "window_merge: "): a non-positive extent, stride < 1, stride > win_h (rows would belong to
+ * no window), ceil(win_h / stride) > 8, null pointers, an output that overlaps an input, groups outside 1..3. */
+int pf_window_split(const float* canvas, float* windows, int songs, int channels, int win_h, int width, int n_windows, int stride, void* stream);
+typedef struct pf_window_merge_args {
+  const float* eps;                   /* [groups][songs * n_windows][channels][win_h][width] */
+  const float* row_weight;            /* [win_h], device memory, every weight > 0 */
+  int groups;                         /* 1, 2 or 3 */
+  float s1, s2;                       /* guidance scales: s1 with groups >= 2, s2 with groups == 3 */
+  int songs, channels, win_h, width, n_windows, stride;
+  float* out;                         /* [songs][channels][canvas_h][width]; must not overlap eps or row_weight */
+} pf_window_merge_args;
+int pf_window_merge(const pf_window_merge_args* a, void* stream);
+
 /* One reverse step of a sampler family as ONE elementwise kernel (DDPM / RePaint and DDIM here; DPM-Solver++(2M) follows them below).  The caller zero-fills the struct and sets what it needs.
  *   DDPM / RePaint (SDFSampler.paint body + p_sample, sampler_sdf.py:80-171,307-336):
  *     x0    = c_recip*x - c_recipm1*eps ; mean = c_x0*x0 + c_xt*x ; x_unkn = mean + sigma*noise_p

@@ -82,6 +82,12 @@ class DpmStepArgs(C.Structure):
                 + [("n", C.c_size_t)])
 
 
+class WindowMergeArgs(C.Structure):
+    """pf_window_merge_args (include/pfhip.h); filled by ``_steps.window_merge`` only."""
+    _fields_ = ([("eps", C.c_void_p), ("row_weight", C.c_void_p), ("groups", C.c_int), ("s1", C.c_float), ("s2", C.c_float)]
+                + [(n, C.c_int) for n in ("songs", "channels", "win_h", "width", "n_windows", "stride")] + [("out", C.c_void_p)])
+
+
 class QsampleRowsArgs(C.Structure):
     """pf_qsample_rows_args (include/pfhip.h); filled by ``_steps.qsample_rows`` only."""
     _fields_ = ([(n, C.c_void_p) for n in ("x0", "noise", "t", "sqrt_ab", "sqrt_1mab")] + [("n_steps", C.c_int32), ("rng", C.c_int)]
@@ -219,6 +225,8 @@ SIGNATURES = {
     "pf_unet_n_launches": (C.c_int, [C.c_void_p, C.c_int, C.c_int]),
     "pf_cfg_combine": (C.c_int, [C.c_void_p, C.c_float, C.c_void_p, C.c_size_t, C.c_void_p]),
     "pf_cfg_combine3": (C.c_int, [C.c_void_p, C.c_float, C.c_float, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "pf_window_split": (C.c_int, [C.c_void_p, C.c_void_p] + [C.c_int] * 6 + [C.c_void_p]),
+    "pf_window_merge": (C.c_int, [C.POINTER(WindowMergeArgs), C.c_void_p]),
     "pf_ddpm_step": (C.c_int, [C.POINTER(DdpmStepArgs), C.c_void_p]),
     "pf_axpby": (C.c_int, [C.c_void_p, C.c_void_p, C.c_float, C.c_float, C.c_void_p, C.c_size_t, C.c_void_p]),
     "pf_ddim_step": (C.c_int, [C.POINTER(DdimStepArgs), C.c_void_p]),

@@ -1,5 +1,6 @@
 """The sampler's elementwise launches: noise, ``a*x + b*y`` and the three reverse-step updates (``pf_randn`` / ``pf_randn_dev``, ``pf_axpby``,
-``pf_ddpm_step``, ``pf_ddim_step``, ``pf_dpm_step`` of include/pfhip.h), and the two launches of the training objective (``pf_qsample_rows``,
+``pf_ddpm_step``, ``pf_ddim_step``, ``pf_dpm_step`` of include/pfhip.h), the two launches around the denoiser of a window plan
+(``pf_window_split``, ``pf_window_merge``), and the two launches of the training objective (``pf_qsample_rows``,
 ``pf_mse_rows``) with the loss evaluation both diffusion mirrors share (``diffusion_loss_rows``).  The only place that fills
 ``pf_ddpm_step_args`` / ``pf_ddim_step_args`` / ``pf_dpm_step_args`` / ``pf_qsample_rows_args`` / ``pf_mse_rows_args``:
 ``sampler.py`` and ``ddpm.py`` decide WHICH route a step takes (coefficients by value or from a device table, noise tensors or
@@ -85,6 +86,32 @@ def dpm_step(lib, x, eps, out, *, coef=None, table=None, state=None, x0_prev=Non
     second-order step (``c_1 != 0``); ``x0_out``: receives this step's (may be ``x0_prev``; ``None`` = not kept).  No noise is drawn."""
     return _launch(lib.pf_dpm_step, "pf_dpm_step", lib, _lib.DpmStepArgs(), x, eps, out, coef, table, state, None, (),
                    dict(x0_prev=x0_prev, x0_out=x0_out, orig=orig, orig_noise=orig_noise, mask=mask))
+
+
+def window_split(lib, canvas, n_windows: int, stride: int, win_h: int) -> torch.Tensor:
+    """Canvas ``[S, C, canvas_h, W]`` -> its windows ``[S * n_windows, C, win_h, W]``, song-major (``pf_window_split``)."""
+    S, ch, _, W = canvas.shape
+    out = torch.empty(S * n_windows, ch, win_h, W, dtype=torch.float32, device=canvas.device)
+    _lib.check(lib.pf_window_split(canvas.data_ptr(), out.data_ptr(), S, ch, win_h, W, n_windows, stride, _lib.current_stream()),
+               "pf_window_split", lib)
+    return out
+
+
+def window_merge(lib, eps, row_weight, songs: int, n_windows: int, stride: int, groups: int = 1, scales=(), out=None) -> torch.Tensor:
+    """The windows' eps ``[groups * S * n_windows, C, win_h, W]`` (group-major, as the guided evaluation stacks it) -> the canvas eps
+    ``[S, C, canvas_h, W]``, the guidance combine of ``groups`` evaluations folded in (``pf_window_merge``).  ``row_weight``: ``[win_h]``
+    float32 on the device; ``scales``: ``()``, ``(s,)`` or ``(s1, s2)`` as ``guidance_plan`` returns them."""
+    rows, ch, win_h, W = eps.shape
+    if rows != groups * songs * n_windows:
+        raise RuntimeError(f"window_merge: eps has {rows} rows, expected {groups} groups x {songs} songs x {n_windows} windows")
+    if out is None:
+        out = torch.empty(songs, ch, stride * (n_windows - 1) + win_h, W, dtype=torch.float32, device=eps.device)
+    a = _lib.WindowMergeArgs()
+    a.eps, a.row_weight, a.out, a.groups = eps.data_ptr(), row_weight.data_ptr(), out.data_ptr(), int(groups)
+    a.s1, a.s2 = (float(v) for v in (tuple(scales) + (0.0, 0.0))[:2])
+    a.songs, a.channels, a.win_h, a.width, a.n_windows, a.stride = songs, ch, win_h, W, int(n_windows), int(stride)
+    _lib.check(lib.pf_window_merge(C.byref(a), _lib.current_stream()), "pf_window_merge", lib)
+    return out
 
 
 # ---- the training objective, forward only (LatentDiffusion.loss / DenoiseDiffusion.loss of the reference) -------------------------------

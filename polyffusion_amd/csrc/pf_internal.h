@@ -100,6 +100,9 @@ int launch_matvec_exp(const float* x, int ldx, const float* w, const float* bias
 // sampler elementwise kernels
 int launch_cfg_combine(const float* eps2, float scale, float* eps, size_t n, hipStream_t s);
 int launch_cfg_combine3(const float* eps3, float s1, float s2, float* eps, size_t n, hipStream_t s);
+// overlapping windows along the time axis: canvas -> window batch, and window eps -> canvas eps with the guidance combine folded in
+int launch_window_split(const float* canvas, float* windows, int songs, int channels, int win_h, int width, int n_windows, int stride, hipStream_t s);
+int launch_window_merge(const pf_window_merge_args& a, hipStream_t s);
 // one reverse step per family: validates the arguments, then the tensor-noise or the in-kernel Philox kernel (include/pfhip.h)
 int launch_ddpm_step(const pf_ddpm_step_args& a, hipStream_t s);
 int launch_ddim_step(const pf_ddim_step_args& a, hipStream_t s);

@@ -4,6 +4,7 @@
 //   unet.py:286-289; n_cond==1 cross-attention collapse unet_attention.py:186-212),
 //   fused sampler updates (sampler_sdf.py:80-171,307-341; sampler_ddim.py:220-272,355-359),
 //   and the update of the sampler the reference does not have, DPM-Solver++(2M) (pf_dpm_step),
+//   the canvas <-> window-batch gathers of joint overlapping-window sampling (pf_window_split, pf_window_merge),
 //   counter-based Gaussian noise, GRU gate update and the texture-encoder front end
 //   (dl_modules/chord_enc.py:15-22, txt_enc.py:23-27).
 #include "pf_internal.h"
@@ -440,11 +441,11 @@ int launch_matvec_exp(const float* x, int ldx, const float* w, const float* bias
 
 static inline dim3 ew_grid(size_t n) { return dim3((unsigned)min((size_t)2048, (n + 255) / 256)); }
 
+// e_u + s * (e_c - e_u) as three rounded operations, like the reference's tensor ops (shared with window_merge_kernel below)
+__device__ __forceinline__ float cfg_combine_v(float u, float c, float s) { return add_rn(u, mul_rn(s, sub_rn(c, u))); }
 __global__ void cfg_combine_kernel(const float* __restrict__ e2, float s, float* __restrict__ e, size_t n) {
-  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
-    const float u = e2[i], c = e2[n + i];
-    e[i] = add_rn(u, mul_rn(s, sub_rn(c, u)));   // e_u + s * (e_c - e_u) as three rounded operations, like the reference's tensor ops
-  }
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x)
+    e[i] = cfg_combine_v(e2[i], e2[n + i], s);
 }
 int launch_cfg_combine(const float* eps2, float scale, float* eps, size_t n, hipStream_t s) {
   PF_REQUIRE(eps2 && eps && n > 0, "cfg_combine: bad arguments");
@@ -481,6 +482,139 @@ int launch_cfg_combine3(const float* eps3, float s1, float s2, float* eps, size_
     hipLaunchKernelGGL(cfg_combine3_vec_kernel, ew_grid(n / 4), dim3(256), 0, s, eps3, s1, s2, eps, n);
   else
     hipLaunchKernelGGL(cfg_combine3_kernel, ew_grid(n), dim3(256), 0, s, eps3, s1, s2, eps, n);
+  PF_CHECK_HIP(hipGetLastError());
+  return PF_OK;
+}
+
+// ---- overlapping windows along the time axis (include/pfhip.h: pf_window_split / pf_window_merge; WindowPlan in sampler.py).  A song is a
+// canvas [S][C][Hc][W], Hc = stride * (Wn - 1) + Hw; window j of song s - batch row s * Wn + j - is canvas rows [j * stride, j * stride + Hw).
+// Both kernels are gathers over their OUTPUT (split: a window element reads one canvas element; merge: a canvas element reads the <= 8
+// windows that cover its row, in ascending j): no atomics, no LDS, nothing order-dependent.  V = 4: 16-byte vectors along W (W % 4 == 0 and
+// aligned pointers, the launchers decide), V = 1: 4-byte elements; the same individually rounded operations, so the same bits.
+struct window_geom { int S, C, Hw, W, Wn, stride, Hc; };
+template <int V>
+__device__ __forceinline__ void window_ld(const float* p, float (&v)[V]) {
+  if constexpr (V == 4) {
+    const f32x4 t = *reinterpret_cast<const f32x4*>(p);
+    v[0] = t[0]; v[1] = t[1]; v[2] = t[2]; v[3] = t[3];
+  } else {
+    v[0] = *p;
+  }
+}
+template <int V>
+__device__ __forceinline__ void window_st(float* p, const float (&v)[V]) {
+  if constexpr (V == 4) {
+    const f32x4 t = {v[0], v[1], v[2], v[3]};
+    *reinterpret_cast<f32x4*>(p) = t;
+  } else {
+    *p = v[0];
+  }
+}
+template <int V>
+__global__ void window_split_kernel(const float* __restrict__ canvas, float* __restrict__ win, window_geom g) {
+  const size_t Wv = (size_t)(g.W / V), n = (size_t)g.S * g.Wn * g.C * g.Hw * Wv;
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
+    const size_t wv = i % Wv;
+    size_t r = i / Wv;
+    const size_t row = r % g.Hw; r /= g.Hw;
+    const size_t c = r % g.C; r /= g.C;
+    const size_t j = r % g.Wn, s = r / g.Wn;
+    float v[V];
+    window_ld<V>(canvas + ((s * g.C + c) * g.Hc + j * g.stride + row) * g.W + wv * V, v);
+    window_st<V>(win + i * V, v);
+  }
+}
+// eps = [groups][S * Wn][C][Hw][W]; per covering window e_j = the guidance combine of its groups (the device functions of pf_cfg_combine /
+// pf_cfg_combine3), then: one window - out = e_j (a select); several - num = w_0*e_0, num += w_j*e_j, den likewise from the weights, out = num / den
+template <int V>
+__global__ void window_merge_kernel(const float* __restrict__ eps, const float* __restrict__ rw, int groups, float s1, float s2, window_geom g,
+                                    float* __restrict__ out) {
+  const size_t Wv = (size_t)(g.W / V), n = (size_t)g.S * g.C * g.Hc * Wv;
+  const size_t gs = (size_t)g.S * g.Wn * g.C * g.Hw * g.W;       // elements of one group
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
+    const size_t wv = i % Wv;
+    size_t r = i / Wv;
+    const int y = (int)(r % g.Hc); r /= g.Hc;
+    const size_t c = r % g.C, s = r / g.C;
+    const int j0 = y < g.Hw ? 0 : (y - g.Hw) / g.stride + 1, j1 = min(g.Wn - 1, y / g.stride);    // 0 <= y - j * stride < Hw for j0 <= j <= j1
+    float num[V], den = 0.f;
+    for (int j = j0; j <= j1; ++j) {
+      const int row = y - j * g.stride;
+      const size_t src = (((s * g.Wn + j) * g.C + c) * g.Hw + row) * g.W + wv * V;
+      float e[V];
+      window_ld<V>(eps + src, e);
+      if (groups == 2) {
+        float b[V];
+        window_ld<V>(eps + gs + src, b);
+#pragma unroll
+        for (int q = 0; q < V; ++q) e[q] = cfg_combine_v(e[q], b[q], s1);
+      } else if (groups == 3) {
+        float b[V], d[V];
+        window_ld<V>(eps + gs + src, b);
+        window_ld<V>(eps + 2 * gs + src, d);
+#pragma unroll
+        for (int q = 0; q < V; ++q) e[q] = cfg_combine3_v(e[q], b[q], d[q], s1, s2);
+      }
+      if (j0 == j1) {
+#pragma unroll
+        for (int q = 0; q < V; ++q) num[q] = e[q];
+      } else {
+        const float w = rw[row];
+#pragma unroll
+        for (int q = 0; q < V; ++q) num[q] = j == j0 ? mul_rn(w, e[q]) : add_rn(num[q], mul_rn(w, e[q]));
+        den = j == j0 ? w : add_rn(den, w);
+      }
+    }
+    if (j0 != j1) {
+#pragma unroll
+      for (int q = 0; q < V; ++q) num[q] = __fdiv_rn(num[q], den);
+    }
+    window_st<V>(out + i * V, num);
+  }
+}
+static inline bool ranges_overlap(const void* a, size_t a_bytes, const void* b, size_t b_bytes) {
+  const uintptr_t pa = (uintptr_t)a, pb = (uintptr_t)b;
+  return pa < pb + b_bytes && pb < pa + a_bytes;
+}
+// the geometry both entries share; refused before any HIP call
+static int window_geom_of(const char* who, int songs, int channels, int win_h, int width, int n_windows, int stride, window_geom* g) {
+  PF_REQUIRE(songs > 0 && channels > 0 && win_h > 0 && width > 0 && n_windows > 0,
+             "%s: non-positive extent (songs %d, channels %d, win_h %d, width %d, n_windows %d)", who, songs, channels, win_h, width, n_windows);
+  PF_REQUIRE(stride >= 1, "%s: stride %d < 1", who, stride);
+  PF_REQUIRE(stride <= win_h, "%s: stride %d > win_h %d (rows between two windows would belong to none)", who, stride, win_h);
+  PF_REQUIRE((win_h + stride - 1) / stride <= 8, "%s: ceil(win_h / stride) = %d windows over one row, at most 8", who, (win_h + stride - 1) / stride);
+  const int64_t hc = (int64_t)stride * (n_windows - 1) + win_h;
+  PF_REQUIRE(hc <= INT32_MAX, "%s: canvas height %lld does not fit 32 bits", who, (long long)hc);
+  *g = window_geom{songs, channels, win_h, width, n_windows, stride, (int)hc};
+  return PF_OK;
+}
+int launch_window_split(const float* canvas, float* windows, int songs, int channels, int win_h, int width, int n_windows, int stride,
+                        hipStream_t s) {
+  window_geom g;
+  if (int rc = window_geom_of("window_split", songs, channels, win_h, width, n_windows, stride, &g)) return rc;
+  PF_REQUIRE(canvas && windows, "window_split: null pointer");
+  const size_t n = (size_t)g.S * g.Wn * g.C * g.Hw * g.W, nc = (size_t)g.S * g.C * g.Hc * g.W;
+  PF_REQUIRE(!ranges_overlap(windows, n * sizeof(float), canvas, nc * sizeof(float)), "window_split: windows aliases canvas");
+  if (g.W % 4 == 0 && (((uintptr_t)canvas | (uintptr_t)windows) & 15) == 0)
+    hipLaunchKernelGGL(window_split_kernel<4>, ew_grid(n / 4), dim3(256), 0, s, canvas, windows, g);
+  else
+    hipLaunchKernelGGL(window_split_kernel<1>, ew_grid(n), dim3(256), 0, s, canvas, windows, g);
+  PF_CHECK_HIP(hipGetLastError());
+  return PF_OK;
+}
+int launch_window_merge(const pf_window_merge_args& a, hipStream_t s) {
+  window_geom g;
+  if (int rc = window_geom_of("window_merge", a.songs, a.channels, a.win_h, a.width, a.n_windows, a.stride, &g)) return rc;
+  PF_REQUIRE(a.groups >= 1 && a.groups <= 3, "window_merge: groups %d, expected 1, 2 or 3", a.groups);
+  PF_REQUIRE(a.eps && a.row_weight && a.out, "window_merge: null pointer (eps, row_weight and out must be set)");
+  const size_t ne = (size_t)a.groups * g.S * g.Wn * g.C * g.Hw * g.W, n = (size_t)g.S * g.C * g.Hc * g.W;
+  PF_REQUIRE(!ranges_overlap(a.out, n * sizeof(float), a.eps, ne * sizeof(float)) &&
+                 !ranges_overlap(a.out, n * sizeof(float), a.row_weight, (size_t)g.Hw * sizeof(float)),
+             "window_merge: out aliases an input");
+  if (g.W % 4 == 0 && (((uintptr_t)a.eps | (uintptr_t)a.row_weight | (uintptr_t)a.out) & 15) == 0)
+    hipLaunchKernelGGL(window_merge_kernel<4>, ew_grid(n / 4), dim3(256), 0, s, a.eps, a.row_weight, a.groups, a.s1, a.s2, g, a.out);
+  else
+    hipLaunchKernelGGL(window_merge_kernel<1>, ew_grid(n), dim3(256), 0, s, a.eps, a.row_weight, a.groups, a.s1, a.s2, g, a.out);
   PF_CHECK_HIP(hipGetLastError());
   return PF_OK;
 }

@@ -12,7 +12,8 @@ extraction, Polydis comparison.  Conditions therefore come from ``--from_song_np
 segmented by ``polyffusion_amd.datasample``), from ``--cond_npz`` (arrays
 ``chord`` [B,32,36] and/or ``prmat`` [B,128,128], optional ``prmat2c`` for inpainting) or from the
 seeded synthetic generator (``--synthetic``); the result is written as ``.mid`` (polyffusion_amd.midi) and ``.npy`` ([B,2,128,128] piano
-roll, or [2B,2,64,128] half-segments for ``--autoreg``).  ``--synthetic_weights`` replaces the
+roll, or [2B,2,64,128] half-segments for ``--autoreg``; ``--joint``, an extension, denoises the 2B-1 half-overlapping windows of a song
+in one reverse loop and writes [B,2,128,128]).  ``--synthetic_weights`` replaces the
 checkpoint by the deterministic weight generator (no trained weights ship with the reference).
 """
 from __future__ import annotations
@@ -119,7 +120,13 @@ class Experiments:
 
     @torch.no_grad()
     def predict(self, cond: torch.Tensor, cond_mid: Optional[torch.Tensor] = None, uncond_scale=1.0, autoreg=False,
-                orig=None, mask=None, cond_concat=None, noise: Optional[torch.Tensor] = None):
+                orig=None, mask=None, cond_concat=None, noise: Optional[torch.Tensor] = None, joint: bool = False, blend: str = "mean"):
+        """``joint``: the one-song form of ``predict_joint`` - all 2B-1 half-overlapping windows in one reverse loop; returns ``[B, C, H, W]``."""
+        if joint:
+            if autoreg:
+                raise ValueError("predict: joint and autoreg are two ways to join the segments of a song: choose one")
+            one = lambda v: None if v is None else v.unsqueeze(0)
+            return self.predict_joint(one(cond), one(cond_mid), uncond_scale, one(orig), one(mask), one(cond_concat), one(noise), blend)[0]
         p, dev = self.params, cond.device
         B = cond.shape[0]
         shape = [B, p.out_channels, p.img_h, p.img_w]
@@ -207,8 +214,50 @@ class Experiments:
             gen.append(new_half)
         return torch.stack(gen, dim=1)
 
-    def _stamp(self, uncond_scale, autoreg, extra=""):
-        return (f"{self.model_label}{extra}[scale={uncond_scale}{',autoreg' if autoreg else ''}]"
+    @torch.no_grad()
+    def predict_joint(self, cond: torch.Tensor, cond_mid: Optional[torch.Tensor] = None, uncond_scale=1.0, orig=None, mask=None,
+                      cond_concat=None, noise: Optional[torch.Tensor] = None, blend: str = "mean"):
+        """All ``2B-1`` half-overlapping 8-bar windows of every song in ONE reverse loop on one canvas per song (``sampler.WindowPlan``;
+        MultiDiffusion along the time axis; not in the reference), where ``predict_songs`` makes ``2B-1`` sampling runs one after the other.
+
+        Inputs as ``predict_songs``: ``cond`` / ``cond_mid`` ``[S, B, n_cond, d_cond]`` as ``encode_conditions(..., autoreg=True)`` returns
+        them per song - window ``w`` of song ``s`` takes ``cond[s, w / 2]`` for even ``w`` (the aligned segments) and ``cond_mid[s, (w - 1) / 2]``
+        for odd ``w`` (the half-shifted ones; the wrapped last row of ``cond_mid`` is unused, as under ``--autoreg``); ``orig`` / ``mask`` /
+        ``noise`` / ``cond_concat``, when given, ``[S, B, C, H, W]``, stitched along the time axis into canvases of ``H * B`` rows.  The
+        sampler's draws are keyed by (seed, draw counter, global song index), so ranks that shard the songs reproduce the unsharded run.
+        A song of one segment is one window: the bits of ``predict``.  Returns ``[S, B, C, H, W]``."""
+        from .sampler import WindowPlan
+        p, dev = self.params, cond.device
+        S, B = cond.shape[0], cond.shape[1]
+        H = p.img_h
+        plan = WindowPlan(2 * B - 1, H // 2, H, blend)
+        if B > 1 and (cond_mid is None or cond_mid.shape[:2] != cond.shape[:2]):
+            raise ValueError("predict_joint: songs of more than one segment need cond_mid, the conditions of the half-shifted windows, shaped like cond")
+        wins = [cond[:, w // 2] if w % 2 == 0 else cond_mid[:, (w - 1) // 2] for w in range(plan.n_windows)]
+        cw = torch.stack(wins, dim=1).reshape(S * plan.n_windows, *cond.shape[2:]).contiguous()
+        # [S, B, C, H, W] -> the canvas [S, C, B * H, W] and back
+        stitch = lambda v: None if v is None else v.permute(0, 2, 1, 3, 4).reshape(S, v.shape[2], B * H, v.shape[4]).contiguous().float()
+        shape = [S, p.out_channels, plan.canvas_h, p.img_w]
+        if orig is None or mask is None:
+            orig, mask = torch.zeros(shape, device=dev), torch.zeros(shape, device=dev)
+        else:
+            orig, mask = stitch(orig), stitch(mask)
+        noise = self.sampler.randn(shape, dev) if noise is None else stitch(noise)
+        uc = -torch.ones([S * plan.n_windows, 1, p.d_cond], device=dev)
+        before = getattr(self.sampler, "windows", None)
+        self.sampler.windows = plan
+        try:
+            xt = self.sampler.q_sample(orig, self.t_idx, noise)
+            x0 = self.sampler.paint(xt, cw, self.t_idx, orig=orig, mask=mask, orig_noise=noise, uncond_scale=uncond_scale, uncond_cond=uc,
+                                    cond_concat=stitch(cond_concat), repaint_n=self.repaint_n)
+        finally:
+            self.sampler.windows = before
+        return x0.reshape(S, x0.shape[1], B, H, x0.shape[3]).permute(0, 2, 1, 3, 4).contiguous()
+
+    def _stamp(self, uncond_scale, autoreg, extra="", joint=None):
+        """``joint``: ``None``, or the blend of a joint run (``mean`` is written as plain ``joint``)."""
+        how = ",autoreg" if autoreg else "" if not joint else ",joint" if joint == "mean" else f",joint-{joint}"
+        return (f"{self.model_label}{extra}[scale={uncond_scale}{how}]"
                 f"_{datetime.now().strftime('%y-%m-%d_%H%M%S')}")
 
     def generate(self, cond, cond_mid=None, uncond_scale=1.0, autoreg=False, no_output=False, cond_concat=None,
@@ -370,7 +419,14 @@ def make_parser() -> ArgumentParser:
     p.add_argument("--guidance_order", choices=list(GUIDANCE_ORDERS), default="chd,txt", metavar="{chd,txt | txt,chd}", help="extension: which part the intermediate "
                    "evaluation of --uncond_scale_chd / --uncond_scale_txt keeps (the part named first); default: chd,txt")
     p.add_argument("--seed", type=int, help="use a specific seed for inference")
-    p.add_argument("--autoreg", action="store_true", help="autoregressively inpaint the music segments")
+    joins = p.add_mutually_exclusive_group()     # two ways to join the segments of a song: argparse refuses the pair
+    joins.add_argument("--autoreg", action="store_true", help="autoregressively inpaint the music segments")
+    # extension: all 2B-1 half-overlapping windows of a song denoised as one batch in ONE reverse loop (sampler.WindowPlan)
+    joins.add_argument("--joint", action="store_true", help="extension: denoise all 2B-1 half-overlapping 8-bar windows of a song jointly in one "
+                       "reverse loop, their noise predictions blended where they overlap (one sampling run where --autoreg makes 2B-1; "
+                       "not together with --autoreg)")
+    p.add_argument("--joint_blend", choices=["mean", "ramp"], default="mean", help="extension: how --joint weights two windows over the same "
+                   "rows: mean (default) or ramp (a window fades in and out linearly over its overlaps)")
     p.add_argument("--from_dataset", default=None, help="choose condition from a dataset {pop909, musicalion} (validation half of its split)")
     p.add_argument("--dataset_dir", help="extension: directory of the dataset's song .npz files (default: the reference's dirs.py paths)")
     p.add_argument("--split_dir", default=datasample.TRAIN_SPLIT_DIR, help="extension: directory of the <dataset>.pickle split files")
@@ -625,7 +681,8 @@ def generate_songs(model, params, args, cond, cond_mid, orig, mask, seed: int, r
     S, B = args.num_generate, cond.shape[0]
     lo, hi = pfdist.shard_range(S, rank, world)
     n_local = hi - lo
-    per_song = 1 if args.autoreg else B   # images the sampler sees per song in one paint() call
+    joint = getattr(args, "joint", False)
+    per_song = 1 if args.autoreg or joint else B   # images (--joint: canvases) the sampler sees per song in one paint() call
     sampler, t_idx = make_sampler(model, args, seed, lo * per_song)
     expmt = Experiments(params.model_name, params, sampler, t_idx=t_idx, repaint_n=args.repaint_n)
     scale = args.uncond_scale if uncond_scale is None else uncond_scale
@@ -636,6 +693,9 @@ def generate_songs(model, params, args, cond, cond_mid, orig, mask, seed: int, r
     elif args.autoreg:
         gen = expmt.predict_songs(rep(cond), rep(cond_mid), scale, orig=rep(orig), mask=rep(mask),
                                   cond_concat=rep(cond_concat))   # [n,2B,C,H/2,W]
+    elif joint:
+        gen = expmt.predict_joint(rep(cond), rep(cond_mid), scale, orig=rep(orig), mask=rep(mask), cond_concat=rep(cond_concat),
+                                  blend=args.joint_blend)         # [n,B,C,H,W]
     else:
         flat = lambda v: None if v is None else rep(v).reshape(n_local * B, *v.shape[1:])
         gen = expmt.predict(flat(cond), None, scale, False, flat(orig), flat(mask),
@@ -784,7 +844,7 @@ def main(argv=None):
         raise SystemExit("cond_type pnotree needs the piano-tree grid: --from_midi, --from_song_npz, pnotree in --cond_npz or --synthetic")
     if args.polydis and rank == 0:
         write_polydis(args, chd, prmat, seed, say)
-    cond, cond_mid = encode_conditions(model, params, chd, prmat, args.autoreg, pnotree=pnotree)
+    cond, cond_mid = encode_conditions(model, params, chd, prmat, args.autoreg or args.joint, pnotree=pnotree)   # --joint: the same two streams
     # the guidance scale every later stage passes on unchanged: the float, or the two scales with the chord part's width as just concatenated
     scale = dual_scale(args, model.cond_split) if dual else args.uncond_scale
     if params.cond_type == "pnotree" and rank == 0 and not args.no_pnotree_recon:
@@ -860,7 +920,8 @@ def main(argv=None):
         stamps = []
         for i in range(S):
             extra = "" if args.inpaint_type is None else f"_inp{args.repaint_n}_{args.inpaint_type}"
-            stamp = os.path.join(args.output_dir, expmt._stamp(scale, args.autoreg, extra) + (f"_{i}" if S > 1 else ""))
+            stamp = os.path.join(args.output_dir, expmt._stamp(scale, args.autoreg, extra, args.joint_blend if args.joint else None)
+                                 + (f"_{i}" if S > 1 else ""))
             stamps.append(stamp)
             np.save(stamp + ".npy", gen[i].cpu().numpy())
             # generated cells on their own track when inpainting (ref:inference_sdf.py:385-389)

@@ -8,6 +8,8 @@
 * ``DualScale`` / ``guidance_plan`` - not in the reference: separate guidance scales for the chord and texture parts of a ``chord+txt``
   condition, passed as ``uncond_scale``; the one function that decides what a guided eps evaluates.
 * ``DPMSolverSampler``  - not in the reference: DPM-Solver++(2M), the second-order multistep solver, driven like ``DDIMSampler``.
+* ``WindowPlan``        - not in the reference: a song as one canvas whose half-overlapping windows are denoised as ONE batch per step, their
+  noise predictions blended where they overlap (``DiffusionSampler.windows``; ``pf_window_split`` / ``pf_window_merge``).
 
 Same method names and argument meaning as the reference, so ``Experiments.predict`` drives
 them unchanged.  Differences, all host-side plumbing:
@@ -122,12 +124,71 @@ def guidance_plan(cond: torch.Tensor, uncond_scale: Scale, uncond_cond: Optional
     return torch.cat([uncond_cond, cond]), 2, (float(uncond_scale),)
 
 
+BLENDS = ("mean", "ramp")
+MAX_COVER = 8           # windows over one canvas row that pf_window_merge accepts: ceil(win_h / stride)
+
+
+@dataclass(frozen=True)
+class WindowPlan:
+    """A song as ONE canvas of ``canvas_h = stride * (n_windows - 1) + win_h`` rows that the denoiser sees as the batch of its ``n_windows``
+    windows of ``win_h`` rows, ``stride`` rows apart (MultiDiffusion, Bar-Tal et al. 2023, along the time axis; not in the reference).  Window
+    ``j`` of song ``s`` is batch row ``s * n_windows + j`` and canvas rows ``[j * stride, j * stride + win_h)``.  Where windows overlap their
+    noise predictions are blended per row with ``weights()``: ``mean`` - ones; ``ramp`` - with ``ov = win_h - stride`` and
+    ``r = row + 0.5``, ``min(1, r / ov, (win_h - r) / ov)``: a window fades in over the rows it shares with its left neighbour and out over
+    those it shares with its right one (at ``stride == win_h / 2`` the weights of the two windows over a row sum to exactly 1).  Set as
+    ``DiffusionSampler.windows``.  Frozen and hashable: ``key`` is part of the key of a captured step."""
+    n_windows: int
+    stride: int
+    win_h: int
+    blend: str = "mean"
+
+    def __post_init__(self):
+        for f in ("n_windows", "stride", "win_h"):
+            object.__setattr__(self, f, int(getattr(self, f)))
+        if self.blend not in BLENDS:
+            raise ValueError(f"WindowPlan: blend {self.blend!r}, expected one of {BLENDS}")
+        if self.n_windows < 1 or self.win_h < 1:
+            raise ValueError(f"WindowPlan: {self.n_windows} windows of {self.win_h} rows")
+        if not 1 <= self.stride <= self.win_h:
+            raise ValueError(f"WindowPlan: stride {self.stride} outside [1, win_h = {self.win_h}] (beyond it rows would belong to no window)")
+        if -(-self.win_h // self.stride) > MAX_COVER:
+            raise ValueError(f"WindowPlan: stride {self.stride} puts {-(-self.win_h // self.stride)} windows of {self.win_h} rows over one row, "
+                             f"at most {MAX_COVER}")
+
+    @property
+    def canvas_h(self) -> int:
+        return self.stride * (self.n_windows - 1) + self.win_h
+
+    @property
+    def key(self) -> tuple:
+        return (self.n_windows, self.stride, self.win_h, self.blend)
+
+    def cover(self, y: int) -> List[int]:
+        """The windows over canvas row ``y``, ascending: every ``j`` with ``0 <= y - j * stride < win_h``."""
+        if not 0 <= y < self.canvas_h:
+            raise IndexError(f"WindowPlan: row {y} outside a canvas of {self.canvas_h} rows")
+        lo = 0 if y < self.win_h else (y - self.win_h) // self.stride + 1
+        return list(range(lo, min(self.n_windows - 1, y // self.stride) + 1))
+
+    def weights(self) -> np.ndarray:
+        """float32 ``[win_h]``, every weight > 0: what ``pf_window_merge`` receives as ``row_weight``."""
+        ov = self.win_h - self.stride
+        if self.blend == "mean" or ov == 0:
+            return np.ones(self.win_h, dtype=np.float32)
+        r = np.arange(self.win_h, dtype=np.float64) + 0.5
+        return np.minimum(1.0, np.minimum(r / ov, (self.win_h - r) / ov)).astype(np.float32)
+
+
 class DiffusionSampler:
     model: LatentDiffusion
 
     def __init__(self, model: LatentDiffusion, noise_fn: Optional[NoiseFn] = None, seed: int = 0, sample_offset: int = 0,
-                 graph: bool = False):
+                 graph: bool = False, windows: Optional[WindowPlan] = None):
         self.model = model
+        # windows: x, orig, mask, orig_noise and cond_concat are song canvases [S, ., canvas_h, W], cond / uncond_cond have S * n_windows rows
+        # in the plan's window order, and get_eps evaluates the denoiser on the batch of windows (pf_window_split), blending its predictions
+        # back onto the canvas (pf_window_merge).  Everything behind get_eps is elementwise on the canvas.  None: no windows, today's launches.
+        self.windows = windows
         self.n_steps = model.n_steps
         self.noise_fn = noise_fn
         self.seed = int(seed)
@@ -231,7 +292,7 @@ class DiffusionSampler:
         the time step), `ndraw`: noise draws per step, `n_noise`: how many of them need a tensor (bufs["_noise"]; none when they are made in
         the update kernel), `update(bufs, e_t, table, state)`: the family's in-place update of bufs["x"]."""
         x = inputs["x"]
-        dev, B, st = x.device, x.shape[0], self._step_state(x.device)
+        dev, B, st = x.device, self._eps_rows(x), self._step_state(x.device)      # B: rows the denoiser sees (one per window under a plan)
 
         def make_body(bf):
             tb = bf["_t"] = torch.empty(B, dtype=torch.long, device=dev)
@@ -245,7 +306,8 @@ class DiffusionSampler:
                 _lib.check(self._lib.pf_step_end(st.data_ptr(), ndraw, _lib.current_stream()), "pf_step_end")
             return body
 
-        key = (family, str(dev), scale_key(uncond_scale), self.seed, self._elem_offset(x.shape), ndraw) + self._shape_key(**inputs)
+        wkey = None if self.windows is None else self.windows.key
+        key = (family, str(dev), scale_key(uncond_scale), self.seed, self._elem_offset(x.shape), ndraw, wkey) + self._shape_key(**inputs)
         ent = self._graph_for(key, inputs, make_body, lambda: self._set_state(st, t_start), uncond_scale)
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         e0.record()
@@ -288,20 +350,15 @@ class DiffusionSampler:
     # ---- eps with classifier-free guidance ----------------------------------------------------------
     def get_eps(self, x: torch.Tensor, t: torch.Tensor, c: torch.Tensor, *, uncond_scale: Scale,
                 uncond_cond: Optional[torch.Tensor], prep: Optional[dict] = None):
-        """``uncond_scale``: the reference's float, or a ``DualScale`` (separate scales for the chord and texture parts of ``c``)."""
-        kw = self._prep_kw(prep)
-        # the context is re-concatenated on every call like the reference (sampler/__init__.py:69-74): [2B,n_cond,d_cond] is a few KB, and a
-        # cache keyed on addresses could serve a stale tensor after an in-place update or an allocator address reuse
-        ctx, groups, scales = guidance_plan(c, uncond_scale, uncond_cond)
+        """``uncond_scale``: the reference's float, or a ``DualScale`` (separate scales for the chord and texture parts of ``c``).
+        With a window plan (``self.windows``): ``x`` is the canvas ``[S, C, canvas_h, W]``, ``t`` / ``c`` / ``uncond_cond`` have one row per
+        window, and the result is the canvas eps - split, the same evaluation on the windows, and ONE merge launch that also combines the groups."""
+        wp = getattr(self, "windows", None)
+        if wp is not None:
+            return self._get_eps_windows(wp, x, t, c, uncond_scale, uncond_cond, prep)
+        epsg, groups, scales = self._eps_groups(x, t, c, uncond_scale, uncond_cond, prep)
         if groups == 1:
-            return self.model(x, t, ctx, **kw)
-        tg = torch.cat([t] * groups)
-        if self.share_cfg_prefix and getattr(self.model, "supports_shared_x", False):
-            # the groups see the same x and t and differ only in the condition, which enters the UNet at its first transformer
-            # block: everything in front of it is evaluated once for all (UNetModel.forward(shared_x=), pf_unet_forward_cfg / _cfgn)
-            epsg = self.model(x, tg, ctx, shared_x=True if groups == 2 else groups, **kw)
-        else:
-            epsg = self.model(torch.cat([x] * groups), tg, ctx, **kw)
+            return epsg
         e_t = torch.empty_like(epsg[: x.shape[0]])   # eps has out_channels; x may carry extra cond_concat channels
         if groups == 2:
             _lib.check(self._lib.pf_cfg_combine(epsg.data_ptr(), scales[0], e_t.data_ptr(), e_t.numel(), _lib.current_stream()), "pf_cfg_combine")
@@ -309,6 +366,47 @@ class DiffusionSampler:
             _lib.check(self._lib.pf_cfg_combine3(epsg.data_ptr(), scales[0], scales[1], e_t.data_ptr(), e_t.numel(), _lib.current_stream()),
                        "pf_cfg_combine3")
         return e_t
+
+    def _eps_groups(self, x, t, c, uncond_scale, uncond_cond, prep):
+        """The denoiser on what ``guidance_plan`` decides: ``(eps of every group stacked group-major, groups, combine arguments)``."""
+        kw = self._prep_kw(prep)
+        # the context is re-concatenated on every call like the reference (sampler/__init__.py:69-74): [2B,n_cond,d_cond] is a few KB, and a
+        # cache keyed on addresses could serve a stale tensor after an in-place update or an allocator address reuse
+        ctx, groups, scales = guidance_plan(c, uncond_scale, uncond_cond)
+        if groups == 1:
+            return self.model(x, t, ctx, **kw), 1, scales
+        tg = torch.cat([t] * groups)
+        if self.share_cfg_prefix and getattr(self.model, "supports_shared_x", False):
+            # the groups see the same x and t and differ only in the condition, which enters the UNet at its first transformer
+            # block: everything in front of it is evaluated once for all (UNetModel.forward(shared_x=), pf_unet_forward_cfg / _cfgn)
+            epsg = self.model(x, tg, ctx, shared_x=True if groups == 2 else groups, **kw)
+        else:
+            epsg = self.model(torch.cat([x] * groups), tg, ctx, **kw)
+        return epsg, groups, scales
+
+    def _eps_rows(self, x) -> int:
+        """Rows of the batch the denoiser sees for ``x``: its own, or one per window of every song under a window plan."""
+        wp = getattr(self, "windows", None)
+        return x.shape[0] * (1 if wp is None else wp.n_windows)
+
+    def _window_weights(self, wp: WindowPlan, device) -> torch.Tensor:
+        key = ("window_weights", wp.key, str(device))
+        if key not in self._dev_cache:
+            self._dev_cache[key] = torch.from_numpy(wp.weights()).to(device)
+        return self._dev_cache[key]
+
+    def _get_eps_windows(self, wp: WindowPlan, x, t, c, uncond_scale, uncond_cond, prep):
+        x = x.contiguous()
+        S, rows = x.shape[0], x.shape[0] * wp.n_windows
+        if x.dim() != 4 or x.shape[2] != wp.canvas_h:
+            raise ValueError(f"get_eps: x of shape {tuple(x.shape)} is not a canvas of {wp.canvas_h} rows ({wp.n_windows} windows of "
+                             f"{wp.win_h}, stride {wp.stride})")
+        if c.shape[0] != rows or t.shape[0] != rows or (uncond_cond is not None and uncond_cond.shape[0] != rows):
+            raise ValueError(f"get_eps: {S} songs of {wp.n_windows} windows need {rows} rows of t, cond and uncond_cond, got {t.shape[0]}, "
+                             f"{c.shape[0]}" + ("" if uncond_cond is None else f", {uncond_cond.shape[0]}"))
+        xw = _steps.window_split(self._lib, x, wp.n_windows, wp.stride, wp.win_h)
+        epsg, groups, scales = self._eps_groups(xw, t, c, uncond_scale, uncond_cond, prep)
+        return _steps.window_merge(self._lib, epsg.contiguous(), self._window_weights(wp, x.device), S, wp.n_windows, wp.stride, groups, scales)
 
     def _t_of(self, step: int, batch: int, device) -> torch.Tensor:
         """[batch] int64 on the device, all == step: a row of a constant [n_steps, batch] table (no fill launch per step)."""
@@ -318,7 +416,7 @@ class DiffusionSampler:
         return tr[int(step)]
 
     def _eps(self, x, c, step, uncond_scale, uncond_cond, cond_concat, prep=None):
-        t = self._t_of(step, x.shape[0], x.device)
+        t = self._t_of(step, self._eps_rows(x), x.device)
         xin = x if cond_concat is None else torch.cat([x, cond_concat], dim=1)
         return self.get_eps(xin, t, c, uncond_scale=uncond_scale, uncond_cond=uncond_cond, prep=prep)
 
