@@ -272,6 +272,43 @@ typedef struct pf_dpm_step_args {
 } pf_dpm_step_args;
 int pf_dpm_step(const pf_dpm_step_args* a, void* stream);
 
+/* Exact DDIM inversion (DESIGN.md 0, row "edit by inversion", and 3, "Exact DDIM inversion"; not in the reference): one iterate of one
+ * UPWARD step of the eta = 0 DDIM ODE.  The DDIM step from x at level a down to level ap is F(x) = (x - c_e*eps(x)) / c_y with
+ *     c_y = sqrt(a / ap),   c_e = sqrt(1 - a) - sqrt(a * (1 - ap) / ap)
+ * (the host forms both in float64 and rounds once).  The x whose step lands exactly on y solves x = c_y*y + c_e*eps(x), and
+ *     x_out = c_y*y + c_e*eps                              two products and one sum, each individually rounded
+ * is one iterate of that fixed-point iteration, elementwise on [rows][row_elems]; eps is the denoiser at the previous iterate (at y for
+ * the first one).  y, the state at the lower level, is fixed over the iterates: it is never written and may not alias x_out.  Coefficients
+ * by value or from a device table, row state->index - exactly one of the two, as pf_ddim_step.  Tensors that are all 16-byte aligned with
+ * row_elems % 4 == 0 are moved as 16-byte vectors, anything else element by element; the same operations, so the same bits.
+ *   Fused residual (resid != NULL): the same launch also forms, per row b,
+ *     resid[(slot * rows + b) * 2 + 0] = sum_i (x_out[b][i] - x_iter[b][i])^2        x_iter == NULL: the iterate is y
+ *     resid[(slot * rows + b) * 2 + 1] = sum_i x_out[b][i]^2
+ *   the difference in float32, squares and sums in float64.  x_iter is the previous iterate (read for the residual only; x_out may alias
+ *   it).  A workgroup owns one PF_MSE_CHUNK of one row, reduces in a fixed order and writes one partial pair into `workspace`
+ *   (pf_invert_step_workspace_bytes(rows, row_elems) bytes, 8-byte aligned); a second small launch adds a row's pairs in index order.  No
+ *   atomics: a row's two sums depend on that row alone, bit-identical from call to call and however the batch is split into calls.
+ *   slot = state->index * iters + k with a table (k, the iterate number, is a constant of a captured node), else `slot` by value; resid
+ *   holds n_slots slots of [rows][2] doubles and a slot outside [0, n_slots) is refused (by value) or not written (from the device).
+ *   The forward step's round-trip defect is the next residual over c_y: F(x_K) - y = (x_K - x_{K+1}) / c_y.
+ * Refused before any launch: two coefficient sources or none, resid without workspace or with one too small, y overlapping x_out. */
+typedef struct pf_invert_coef { float c_y, c_e; } pf_invert_coef;
+typedef struct pf_invert_step_args {
+  const float *y, *eps;               /* [rows][row_elems]: the lower state, the denoiser's output at the previous iterate */
+  const float *x_iter;                /* [rows][row_elems] the previous iterate, read for the residual only; NULL: it is y */
+  const pf_invert_coef* coef;         /* host coefficients, copied at the call ...            */
+  const pf_invert_coef* table;        /* ... or a device table, row state->index              */
+  const pf_step_state* state;         /* device step state: required with table; it also names the residual's slot */
+  float* x_out;                       /* [rows][row_elems]; may alias x_iter, not y */
+  double* resid;                      /* [n_slots][rows][2] device doubles; NULL: no residual, one launch */
+  void* workspace; size_t workspace_bytes;      /* resid only */
+  int32_t iters, k;                   /* resid with state: slot = state->index * iters + k */
+  int64_t slot, n_slots;              /* resid: the slot by value (without state), and how many slots resid holds */
+  int32_t rows; size_t row_elems;
+} pf_invert_step_args;
+size_t pf_invert_step_workspace_bytes(int rows, size_t row_elems);
+int pf_invert_step(const pf_invert_step_args* a, void* stream);
+
 /* RePaint re-noise between inner repeats (sampler_sdf.py:337-341; keeps the reference's beta-not-sqrt quirk):
  *   x_t = a*x + b*noise */
 int pf_axpby(const float* x, const float* noise, float a, float b, float* out, size_t n, void* stream);
@@ -298,6 +335,8 @@ int pf_mfma_probe(float* sink, int iters, double* flops_out, void* stream);
 int pf_step_state_set(pf_step_state* dev_state, int64_t index, uint64_t draws, void* stream);
 int pf_step_begin(const pf_step_state* dev_state, const int32_t* time_steps, int64_t* t_out, int batch, void* stream);
 int pf_step_end(pf_step_state* dev_state, int draws_used, void* stream);          /* index -= 1; draws += draws_used */
+/* the end of a captured UPWARD step (pf_invert_step walks its table from row 0 up): index += delta; draws += draws_used */
+int pf_step_advance(pf_step_state* dev_state, int64_t delta, int draws_used, void* stream);
 int pf_randn_dev(float* out, size_t n, uint64_t seed, const pf_step_state* dev_state, int slot, uint64_t elem_offset, void* stream);
 
 /* ---- the training objective, forward only: what LightningLearner.validation_step logs as val/loss (lightning_learner.py:41-52) through

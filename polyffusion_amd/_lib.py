@@ -82,6 +82,18 @@ class DpmStepArgs(C.Structure):
                 + [("n", C.c_size_t)])
 
 
+class InvertCoef(C.Structure):
+    """pf_invert_coef (include/pfhip.h): one upward step of exact DDIM inversion, ``x = c_y*y + c_e*eps``."""
+    _fields_ = [("c_y", C.c_float), ("c_e", C.c_float)]
+
+
+class InvertStepArgs(C.Structure):
+    """pf_invert_step_args (include/pfhip.h); filled by ``_steps.invert_step`` only."""
+    _fields_ = ([(n, C.c_void_p) for n in ("y", "eps", "x_iter", "coef", "table", "state", "x_out", "resid", "workspace")]
+                + [("workspace_bytes", C.c_size_t), ("iters", C.c_int32), ("k", C.c_int32), ("slot", C.c_int64), ("n_slots", C.c_int64),
+                   ("rows", C.c_int32), ("row_elems", C.c_size_t)])
+
+
 class WindowMergeArgs(C.Structure):
     """pf_window_merge_args (include/pfhip.h); filled by ``_steps.window_merge`` only."""
     _fields_ = ([("eps", C.c_void_p), ("row_weight", C.c_void_p), ("groups", C.c_int), ("s1", C.c_float), ("s2", C.c_float)]
@@ -231,6 +243,9 @@ SIGNATURES = {
     "pf_axpby": (C.c_int, [C.c_void_p, C.c_void_p, C.c_float, C.c_float, C.c_void_p, C.c_size_t, C.c_void_p]),
     "pf_ddim_step": (C.c_int, [C.POINTER(DdimStepArgs), C.c_void_p]),
     "pf_dpm_step": (C.c_int, [C.POINTER(DpmStepArgs), C.c_void_p]),
+    "pf_invert_step_workspace_bytes": (C.c_size_t, [C.c_int, C.c_size_t]),
+    "pf_invert_step": (C.c_int, [C.POINTER(InvertStepArgs), C.c_void_p]),
+    "pf_step_advance": (C.c_int, [C.c_void_p, C.c_int64, C.c_int, C.c_void_p]),
     "pf_randn": (C.c_int, [C.c_void_p, C.c_size_t, C.c_uint64, C.c_uint64, C.c_uint64, C.c_void_p]),
     "pf_clock_probe": (C.c_int, [C.c_void_p, C.c_void_p]),
     "pf_mfma_probe": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_double), C.c_void_p]),

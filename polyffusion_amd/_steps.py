@@ -1,5 +1,6 @@
 """The sampler's elementwise launches: noise, ``a*x + b*y`` and the three reverse-step updates (``pf_randn`` / ``pf_randn_dev``, ``pf_axpby``,
-``pf_ddpm_step``, ``pf_ddim_step``, ``pf_dpm_step`` of include/pfhip.h), the two launches around the denoiser of a window plan
+``pf_ddpm_step``, ``pf_ddim_step``, ``pf_dpm_step`` of include/pfhip.h), the upward iterate of exact DDIM inversion (``pf_invert_step``),
+the two launches around the denoiser of a window plan
 (``pf_window_split``, ``pf_window_merge``), and the two launches of the training objective (``pf_qsample_rows``,
 ``pf_mse_rows``) with the loss evaluation both diffusion mirrors share (``diffusion_loss_rows``).  The only place that fills
 ``pf_ddpm_step_args`` / ``pf_ddim_step_args`` / ``pf_dpm_step_args`` / ``pf_qsample_rows_args`` / ``pf_mse_rows_args``:
@@ -86,6 +87,33 @@ def dpm_step(lib, x, eps, out, *, coef=None, table=None, state=None, x0_prev=Non
     second-order step (``c_1 != 0``); ``x0_out``: receives this step's (may be ``x0_prev``; ``None`` = not kept).  No noise is drawn."""
     return _launch(lib.pf_dpm_step, "pf_dpm_step", lib, _lib.DpmStepArgs(), x, eps, out, coef, table, state, None, (),
                    dict(x0_prev=x0_prev, x0_out=x0_out, orig=orig, orig_noise=orig_noise, mask=mask))
+
+
+def invert_workspace(lib, rows: int, row_elems: int, device) -> torch.Tensor:
+    """The float64 workspace ``invert_step`` needs for the residual of ``rows`` rows of ``row_elems`` floats."""
+    nb = int(lib.pf_invert_step_workspace_bytes(int(rows), int(row_elems)))
+    return torch.empty(max(nb, 8) // 8, dtype=torch.float64, device=device)
+
+
+def invert_step(lib, y, eps, out, *, coef=None, table=None, state=None, x_iter=None, resid=None, workspace=None, iters: int = 1, k: int = 0,
+                slot: int = 0):
+    """One fixed-point iterate of one upward DDIM step into ``out`` (``pf_invert_step``): ``out = c_y*y + c_e*eps`` on ``[rows, ...]`` tensors,
+    rows = ``y.shape[0]``.  ``out`` may be ``x_iter``, never ``y``.  ``coef`` (a host ``InvertCoef``) or ``table`` + ``state`` (device).
+    ``resid``: float64 ``[..., rows, 2]`` on the device, its leading dimensions the slots - the launch then also writes the row sums of
+    ``(out - x_iter) ** 2`` (``x_iter = None``: ``y``) and ``out ** 2`` into slot ``state.index * iters + k`` (with ``state``) or ``slot``;
+    it needs ``workspace`` (``invert_workspace``)."""
+    a = _lib.InvertStepArgs()
+    rows = int(y.shape[0])
+    a.y, a.eps, a.x_iter, a.x_out = y.data_ptr(), eps.data_ptr(), _lib.ptr(x_iter), out.data_ptr()
+    a.coef = None if coef is None else C.addressof(coef)        # copied by the library during the call
+    a.table, a.state = _lib.ptr(table), _lib.ptr(state)
+    a.rows, a.row_elems = rows, y.numel() // max(1, rows)
+    if resid is not None:
+        a.resid, a.n_slots = resid.data_ptr(), resid.numel() // (2 * rows)
+        a.workspace, a.workspace_bytes = _lib.ptr(workspace), 0 if workspace is None else workspace.numel() * workspace.element_size()
+        a.iters, a.k, a.slot = int(iters), int(k), int(slot)
+    _lib.check(lib.pf_invert_step(C.byref(a), _lib.current_stream()), "pf_invert_step", lib)
+    return out
 
 
 def window_split(lib, canvas, n_windows: int, stride: int, win_h: int) -> torch.Tensor:

@@ -116,6 +116,10 @@ int launch_mfma_probe(float* sink, int iters, double* flops, hipStream_t s);
 int launch_step_state_set(pf_step_state* st, int64_t index, uint64_t draws, hipStream_t s);
 int launch_step_begin(const pf_step_state* st, const int* time_steps, int64_t* t_out, int batch, hipStream_t s);
 int launch_step_end(pf_step_state* st, int draws_used, hipStream_t s);
+int launch_step_advance(pf_step_state* st, int64_t delta, int draws_used, hipStream_t s);
+// exact DDIM inversion: one fixed-point iterate of one upward step, optionally with the per-row residual sums (a second, in-order launch)
+size_t invert_step_workspace_bytes(int rows, size_t row_elems);
+int launch_invert_step(const pf_invert_step_args& a, hipStream_t s);
 // the training objective, forward only (loss.hip): forward noising with one t per sample, and the per-sample squared error in float64
 int launch_qsample_rows(const pf_qsample_rows_args& a, hipStream_t s);
 size_t mse_rows_workspace_bytes(int rows, size_t row_elems);

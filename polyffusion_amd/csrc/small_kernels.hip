@@ -4,6 +4,7 @@
 //   unet.py:286-289; n_cond==1 cross-attention collapse unet_attention.py:186-212),
 //   fused sampler updates (sampler_sdf.py:80-171,307-341; sampler_ddim.py:220-272,355-359),
 //   and the update of the sampler the reference does not have, DPM-Solver++(2M) (pf_dpm_step),
+//   one fixed-point iterate of exact DDIM inversion with its fused residual (pf_invert_step) and the upward step state (pf_step_advance),
 //   the canvas <-> window-batch gathers of joint overlapping-window sampling (pf_window_split, pf_window_merge),
 //   counter-based Gaussian noise, GRU gate update and the texture-encoder front end
 //   (dl_modules/chord_enc.py:15-22, txt_enc.py:23-27).
@@ -891,6 +892,168 @@ int launch_dpm_step(const pf_dpm_step_args& a, hipStream_t s) {
   else
     hipLaunchKernelGGL(dpm_step_kernel, ew_grid(a.n), dim3(256), 0, s, a.x, a.eps, a.x0_prev, a.x0_out, a.orig, a.orig_noise, a.mask, cv, a.table,
                        a.state, a.x_out, a.n);
+  PF_CHECK_HIP(hipGetLastError());
+  return PF_OK;
+}
+
+// ---- exact DDIM inversion (include/pfhip.h: pf_invert_step; DESIGN.md 3, "Exact DDIM inversion"): one iterate of one UPWARD step,
+//   x_out = c_y*y + c_e*eps          mul, mul, add - 3 roundings, which the tests' budget counts on |c_y*y| + |c_e*eps|
+// Every operation is individually rounded (noise.h), so the three kernels below give the same bits.  y is never written and never aliases
+// x_out (refused); eps, x_iter and out carry no __restrict__: x_out may alias x_iter (a thread reads element i before it writes element i,
+// and no other thread touches element i).
+__device__ __forceinline__ float invert_update_v(float yv, float e, const pf_invert_coef& c) { return add_rn(mul_rn(c.c_y, yv), mul_rn(c.c_e, e)); }
+__global__ void invert_step_kernel(const float* __restrict__ y, const float* eps, pf_invert_coef cv, const pf_invert_coef* __restrict__ table,
+                                   const pf_step_state* __restrict__ st, float* out, size_t n) {
+  const pf_invert_coef c = coef_of(cv, table, st);
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) out[i] = invert_update_v(y[i], eps[i], c);
+}
+// the same on four elements per thread, moved as 16-byte vectors (every tensor 16-byte aligned, n % 4 == 0: launch_invert_step decides)
+__global__ void invert_step_vec_kernel(const float* __restrict__ y, const float* eps, pf_invert_coef cv, const pf_invert_coef* __restrict__ table,
+                                       const pf_step_state* __restrict__ st, float* out, size_t n) {
+  const pf_invert_coef c = coef_of(cv, table, st);
+  const size_t ng = n >> 2;
+  for (size_t g = (size_t)blockIdx.x * blockDim.x + threadIdx.x; g < ng; g += (size_t)gridDim.x * blockDim.x) {
+    const f32x4 yv = *reinterpret_cast<const f32x4*>(y + 4 * g), ev = *reinterpret_cast<const f32x4*>(eps + 4 * g);
+    f32x4 o;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) o[j] = invert_update_v(yv[j], ev[j], c);
+    *reinterpret_cast<f32x4*>(out + 4 * g) = o;
+  }
+}
+// With the residual: workgroup = (row, chunk of PF_MSE_CHUNK elements), the layout of mse_partial_kernel (loss.hip).  Lane l owns the 16-byte
+// groups l, l + 256, ... of the chunk, updates them and adds (x_out - x_iter)^2 and x_out^2 in element order - the difference in float32, the
+// squares (exact in float64) and the sums in float64; the lanes of a wave are combined by a butterfly, the four waves in wave order.  The
+// order is fixed by (row_elems, element index) alone: VEC and the element-by-element form give the same bits, and a row's two sums do not
+// depend on the rows around it.  One partial pair per workgroup; invert_resid_finish_kernel adds a row's pairs in index order.
+constexpr int kInvThreads = 256;
+constexpr int kInvGroups = PF_MSE_CHUNK / 4 / kInvThreads;
+static_assert(PF_MSE_CHUNK == 4 * kInvThreads * kInvGroups, "PF_MSE_CHUNK must be a whole number of 16-byte groups per lane");
+template <bool VEC>
+__device__ __forceinline__ f32x4 inv_load4(const float* p, size_t e, size_t n) {
+  if (VEC) return *reinterpret_cast<const f32x4*>(p + e);
+  f32x4 v = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+  for (int j = 0; j < 4; ++j)
+    if (e + j < n) v[j] = p[e + j];
+  return v;
+}
+template <bool VEC>
+__global__ __launch_bounds__(kInvThreads) void invert_step_resid_kernel(const float* __restrict__ y, const float* eps, const float* xi,
+                                                                       pf_invert_coef cv, const pf_invert_coef* __restrict__ table,
+                                                                       const pf_step_state* __restrict__ st, float* out,
+                                                                       double* __restrict__ partial, size_t row_elems, unsigned chunks) {
+  __shared__ double wave_sum[kInvThreads / 64][2];
+  const pf_invert_coef c = coef_of(cv, table, st);
+  const unsigned row = blockIdx.x / chunks, chunk = blockIdx.x - row * chunks;
+  const size_t base = (size_t)row * row_elems;
+  double acc_d = 0.0, acc_x = 0.0;
+#pragma unroll
+  for (int k = 0; k < kInvGroups; ++k) {
+    const size_t e = (size_t)chunk * PF_MSE_CHUNK + 4 * ((size_t)k * kInvThreads + threadIdx.x);
+    if (e < row_elems) {
+      const f32x4 yv = inv_load4<VEC>(y + base, e, row_elems), ev = inv_load4<VEC>(eps + base, e, row_elems);
+      const f32x4 pv = xi ? inv_load4<VEC>(xi + base, e, row_elems) : yv;     // no previous iterate: the iteration starts from y
+      f32x4 o;
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        o[j] = invert_update_v(yv[j], ev[j], c);
+        if (VEC || e + j < row_elems) {
+          const double d = (double)sub_rn(o[j], pv[j]), q = (double)o[j];
+          acc_d += d * d;
+          acc_x += q * q;
+        }
+      }
+      if (VEC) {
+        *reinterpret_cast<f32x4*>(out + base + e) = o;
+      } else {
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+          if (e + j < row_elems) out[base + e + j] = o[j];
+      }
+    }
+  }
+#pragma unroll
+  for (int m = 32; m >= 1; m >>= 1) {
+    acc_d += __shfl_xor(acc_d, m, 64);
+    acc_x += __shfl_xor(acc_x, m, 64);
+  }
+  if ((threadIdx.x & 63) == 0) { wave_sum[threadIdx.x >> 6][0] = acc_d; wave_sum[threadIdx.x >> 6][1] = acc_x; }
+  __syncthreads();
+  if (threadIdx.x < 2) {
+    double s = wave_sum[0][threadIdx.x];
+#pragma unroll
+    for (int w = 1; w < kInvThreads / 64; ++w) s += wave_sum[w][threadIdx.x];
+    partial[((size_t)row * chunks + chunk) * 2 + threadIdx.x] = s;
+  }
+}
+// one lane per row: the row's partial pairs in index order into slot `slot` of resid [n_slots][rows][2]; with a step state the slot is
+// state->index * iters + k.  A slot outside the table is not written (memory safety only: the host refuses the ones it can see).
+__global__ void invert_resid_finish_kernel(const double* __restrict__ partial, double* __restrict__ resid, int rows, unsigned chunks,
+                                           const pf_step_state* __restrict__ st, int iters, int k, long long slot, long long n_slots) {
+  const int row = blockIdx.x * blockDim.x + threadIdx.x;
+  if (row >= rows) return;
+  if (st) slot = (long long)st->index * iters + k;
+  if (slot < 0 || slot >= n_slots) return;
+  double sd = 0.0, sx = 0.0;
+  for (unsigned c = 0; c < chunks; ++c) {
+    sd += partial[((size_t)row * chunks + c) * 2 + 0];
+    sx += partial[((size_t)row * chunks + c) * 2 + 1];
+  }
+  double* dst = resid + ((size_t)slot * rows + row) * 2;
+  dst[0] = sd;
+  dst[1] = sx;
+}
+size_t invert_step_workspace_bytes(int rows, size_t row_elems) {
+  if (rows <= 0 || row_elems == 0) return 0;
+  return (size_t)rows * ((row_elems + PF_MSE_CHUNK - 1) / PF_MSE_CHUNK) * 2 * sizeof(double);
+}
+int launch_invert_step(const pf_invert_step_args& a, hipStream_t s) {
+  PF_REQUIRE(a.y && a.eps && a.x_out && a.rows > 0 && a.row_elems > 0, "invert_step: bad arguments (y, eps and x_out must be set, rows and row_elems > 0)");
+  PF_REQUIRE(!(a.coef && (a.table || a.state)), "invert_step: coefficients both by value (coef) and from the device (table / state)");
+  PF_REQUIRE(a.coef || (a.table && a.state), "invert_step: null coefficients (set coef, or table and state)");
+  const size_t n = (size_t)a.rows * a.row_elems, bytes = n * sizeof(float);
+  PF_REQUIRE(!ranges_overlap(a.y, bytes, a.x_out, bytes), "invert_step: y aliases x_out (y is the fixed lower state of every iterate)");
+  PF_REQUIRE(!ranges_overlap(a.eps, bytes, a.x_out, bytes), "invert_step: eps aliases x_out");
+  PF_REQUIRE(!a.x_iter || a.x_iter == a.x_out || !ranges_overlap(a.x_iter, bytes, a.x_out, bytes), "invert_step: x_iter overlaps x_out without being it");
+  const pf_invert_coef cv = a.coef ? *a.coef : pf_invert_coef{};
+  const uintptr_t bits = (uintptr_t)a.y | (uintptr_t)a.eps | (uintptr_t)a.x_out | (uintptr_t)a.x_iter;
+  const bool vec = (bits & 15) == 0 && a.row_elems % 4 == 0;
+  if (!a.resid) {          // one launch, no workspace (one that is given is not touched)
+    if (vec)
+      hipLaunchKernelGGL(invert_step_vec_kernel, ew_grid(n / 4), dim3(256), 0, s, a.y, a.eps, cv, a.table, a.state, a.x_out, n);
+    else
+      hipLaunchKernelGGL(invert_step_kernel, ew_grid(n), dim3(256), 0, s, a.y, a.eps, cv, a.table, a.state, a.x_out, n);
+    PF_CHECK_HIP(hipGetLastError());
+    return PF_OK;
+  }
+  const size_t chunks = (a.row_elems + PF_MSE_CHUNK - 1) / PF_MSE_CHUNK, need = invert_step_workspace_bytes(a.rows, a.row_elems);
+  PF_REQUIRE(chunks * (size_t)a.rows < (1ull << 31), "invert_step: %d rows of %zu elements are more workgroups than one launch holds", a.rows, a.row_elems);
+  PF_REQUIRE(a.workspace, "invert_step: resid without a workspace (pf_invert_step_workspace_bytes)");
+  PF_REQUIRE(a.workspace_bytes >= need, "invert_step: workspace of %zu bytes required, got %zu", need, a.workspace_bytes);
+  PF_REQUIRE(((uintptr_t)a.workspace & 7) == 0 && ((uintptr_t)a.resid & 7) == 0, "invert_step: workspace and resid must be 8-byte aligned");
+  PF_REQUIRE(a.n_slots > 0, "invert_step: resid needs n_slots > 0, the slots the table holds");
+  if (a.state) {
+    PF_REQUIRE(a.iters >= 1 && a.k >= 0 && a.k < a.iters, "invert_step: iterate k = %d outside [0, iters = %d)", a.k, a.iters);
+  } else {
+    PF_REQUIRE(a.slot >= 0 && a.slot < a.n_slots, "invert_step: slot %lld outside [0, n_slots = %lld)", (long long)a.slot, (long long)a.n_slots);
+  }
+  const dim3 grid((unsigned)(chunks * a.rows)), block(kInvThreads);
+  double* partial = reinterpret_cast<double*>(a.workspace);
+  if (vec)
+    hipLaunchKernelGGL(invert_step_resid_kernel<true>, grid, block, 0, s, a.y, a.eps, a.x_iter, cv, a.table, a.state, a.x_out, partial, a.row_elems, (unsigned)chunks);
+  else
+    hipLaunchKernelGGL(invert_step_resid_kernel<false>, grid, block, 0, s, a.y, a.eps, a.x_iter, cv, a.table, a.state, a.x_out, partial, a.row_elems, (unsigned)chunks);
+  PF_CHECK_HIP(hipGetLastError());
+  hipLaunchKernelGGL(invert_resid_finish_kernel, dim3((unsigned)cdiv(a.rows, 64)), dim3(64), 0, s, partial, a.resid, a.rows, (unsigned)chunks, a.state, a.iters,
+                     a.k, (long long)a.slot, (long long)a.n_slots);
+  PF_CHECK_HIP(hipGetLastError());
+  return PF_OK;
+}
+// the upward walk's counterpart of step_end_kernel: index += delta; draws += draws_used
+__global__ void step_advance_kernel(pf_step_state* st, long long delta, int draws_used) { st->index += delta; st->draws += (unsigned long long)draws_used; }
+int launch_step_advance(pf_step_state* st, int64_t delta, int draws_used, hipStream_t s) {
+  PF_REQUIRE(st && draws_used >= 0, "step_advance: bad arguments");
+  hipLaunchKernelGGL(step_advance_kernel, dim3(1), dim3(1), 0, s, st, (long long)delta, draws_used);
   PF_CHECK_HIP(hipGetLastError());
   return PF_OK;
 }

@@ -13,7 +13,8 @@ segmented by ``polyffusion_amd.datasample``), from ``--cond_npz`` (arrays
 ``chord`` [B,32,36] and/or ``prmat`` [B,128,128], optional ``prmat2c`` for inpainting) or from the
 seeded synthetic generator (``--synthetic``); the result is written as ``.mid`` (polyffusion_amd.midi) and ``.npy`` ([B,2,128,128] piano
 roll, or [2B,2,64,128] half-segments for ``--autoreg``; ``--joint``, an extension, denoises the 2B-1 half-overlapping windows of a song
-in one reverse loop and writes [B,2,128,128]).  ``--synthetic_weights`` replaces the
+in one reverse loop and writes [B,2,128,128]; ``--edit``, an extension, changes the condition song itself by exact DDIM inversion -
+``Experiments.edit`` - instead of generating from noise).  ``--synthetic_weights`` replaces the
 checkpoint by the deterministic weight generator (no trained weights ship with the reference).
 """
 from __future__ import annotations
@@ -254,6 +255,48 @@ class Experiments:
             self.sampler.windows = before
         return x0.reshape(S, x0.shape[1], B, H, x0.shape[3]).permute(0, 2, 1, 3, 4).contiguous()
 
+    @torch.no_grad()
+    def edit(self, orig: torch.Tensor, cond_src: torch.Tensor, cond_tgt: torch.Tensor, uncond_scale=1.0, *, iters: int = 3,
+             depth: Optional[int] = None, invert_scale=None, cond_mid_src: Optional[torch.Tensor] = None,
+             cond_mid_tgt: Optional[torch.Tensor] = None, joint: bool = False, blend: str = "mean", roundtrip: bool = False):
+        """Edit a given song by exact DDIM inversion (``DDIMSampler.invert``; not in the reference): walk ``orig`` ``[B, C, H, W]`` up the
+        eta = 0 ODE under its own condition ``cond_src`` to index ``depth`` (default: the run's start index), then ``paint`` back down under
+        ``cond_tgt``.  Where inpainting keeps a masked region and invents the rest, this keeps the whole song recognisable and changes what
+        the condition changes.  ``iters``: fixed-point iterates per upward step; ``invert_scale``: the guidance scale of the upward walk
+        (default: ``uncond_scale``, which also makes ``cond_tgt == cond_src`` the round trip).  ``joint``: the song as ONE canvas with the
+        window plan of ``predict_joint`` (``cond_mid_*``: the conditions of the half-shifted windows).  Returns the edited image
+        ``[B, C, H, W]``; with ``roundtrip`` also the repaint under ``cond_src`` at the inversion's scale, which a converged inversion
+        brings back to ``orig``.  The residuals of the walk stay in ``self.sampler.last_inversion``."""
+        s, p = self.sampler, self.params
+        if not isinstance(s, DDIMSampler):
+            raise ValueError("edit: exact inversion exists for the DDIM sampler with eta = 0 only")
+        depth = self.t_idx if depth is None else int(depth)
+        inv_scale = uncond_scale if invert_scale is None else invert_scale
+        orig = orig.contiguous().float()
+        B, H, dev = orig.shape[0], p.img_h, orig.device
+        if not joint:
+            uc = -torch.ones([B, 1, p.d_cond], device=dev)
+            x = s.invert(orig, cond_src, depth, iters=iters, uncond_scale=inv_scale, uncond_cond=uc)
+            out = s.paint(x, cond_tgt, depth, uncond_scale=uncond_scale, uncond_cond=uc)
+            return (out, s.paint(x, cond_src, depth, uncond_scale=inv_scale, uncond_cond=uc)) if roundtrip else out
+        from .sampler import WindowPlan
+        plan = WindowPlan(2 * B - 1, H // 2, H, blend)
+        if B > 1 and (cond_mid_src is None or cond_mid_tgt is None):
+            raise ValueError("edit: a joint edit of more than one segment needs cond_mid_src and cond_mid_tgt, the conditions of the half-shifted windows")
+        windows = lambda c, m: torch.stack([c[w // 2] if w % 2 == 0 else m[(w - 1) // 2] for w in range(plan.n_windows)]).contiguous()
+        canvas = orig.permute(1, 0, 2, 3).reshape(1, orig.shape[1], B * H, orig.shape[3]).contiguous()
+        uc = -torch.ones([plan.n_windows, 1, p.d_cond], device=dev)
+        back = lambda v: v.reshape(v.shape[1], B, H, v.shape[3]).permute(1, 0, 2, 3).contiguous()
+        before = getattr(s, "windows", None)
+        s.windows = plan
+        try:
+            cs, ct = windows(cond_src, cond_mid_src), windows(cond_tgt, cond_mid_tgt)
+            x = s.invert(canvas, cs, depth, iters=iters, uncond_scale=inv_scale, uncond_cond=uc)
+            out = back(s.paint(x, ct, depth, uncond_scale=uncond_scale, uncond_cond=uc))
+            return (out, back(s.paint(x, cs, depth, uncond_scale=inv_scale, uncond_cond=uc))) if roundtrip else out
+        finally:
+            s.windows = before
+
     def _stamp(self, uncond_scale, autoreg, extra="", joint=None):
         """``joint``: ``None``, or the blend of a joint run (``mean`` is written as plain ``joint``)."""
         how = ",autoreg" if autoreg else "" if not joint else ",joint" if joint == "mean" else f",joint-{joint}"
@@ -450,6 +493,21 @@ def make_parser() -> ArgumentParser:
     p.add_argument("--dpm_order", type=int, choices=[1, 2], default=2, help="solver order, default: 2 (1 = DDIM with eta 0 on the same grid)")
     p.add_argument("--dpm_discretize", choices=["logsnr", "uniform", "quad"], default="logsnr", help="time-step grid: uniform in log-SNR "
                    "(default; what the second-order update needs to pay off) or DDIM's two grids")
+    # extension: edit the condition song itself by exact DDIM inversion (DDIMSampler.invert) - e.g. re-harmonise it
+    p.add_argument("--edit", action="store_true", help="extension: edit the condition song's own image (from --from_midi, --from_dataset, "
+                   "--from_song_npz or prmat2c in --cond_npz) instead of generating from noise: invert it up the eta = 0 DDIM ODE under its own "
+                   "condition, sample back down with its chords replaced (--edit_chord_shift / --edit_chords_from_midi).  Needs --ddim with "
+                   "--ddim_eta 0 and a chord or chord+txt model")
+    p.add_argument("--edit_iters", type=int, default=3, metavar="K", help="fixed-point iterates (denoiser evaluations) per upward step, "
+                   "default: 3 (1 = the naive explicit inversion, which falls apart under guidance above 1)")
+    p.add_argument("--edit_depth", type=int, default=None, metavar="D", help="grid index to invert to, default: the full range "
+                   "(--ddim_steps - 1); lower keeps more of the song")
+    p.add_argument("--edit_invert_scale", type=float, default=None, metavar="S", help="guidance scale of the upward walk, default: the run's scale")
+    p.add_argument("--edit_roundtrip", action="store_true", help="also sample back under the song's own condition and print max |x - x_rec| "
+                   "and the number of note cells > 0.5 that differ")
+    p.add_argument("--edit_chord_shift", type=int, default=None, metavar="N", help="target chords: the song's own with each of the three "
+                   "12-wide blocks (root, chroma, bass) rolled by N semitones")
+    p.add_argument("--edit_chords_from_midi", default=None, metavar="FILE", help="target chords: those of another midi file")
     p.add_argument("--repaint_n", type=int, default=1, help="n sampling steps in RePaint")
     p.add_argument("--length", type=int, default=0, help="the generated length (in 8-bars)")
     p.add_argument("--show_image", action="store_true", help="(ignored: no image writer on this path)")
@@ -502,6 +560,58 @@ def dual_scale(args, split: int) -> DualScale:
     x, y = args.uncond_scale_chd, args.uncond_scale_txt
     first, second = (x, y) if args.guidance_order == "chd,txt" else (y, x)
     return DualScale(first, second, split, args.guidance_order)
+
+
+EDIT_COND_TYPES = ("chord", "chord+txt")
+
+
+def check_edit_args(args, cond_type: Optional[str] = None, world: int = 1) -> bool:
+    """Whether the command line asks for ``--edit``; every misuse is a ``SystemExit`` with a message, raised before any weight is loaded.
+    ``cond_type`` / ``world``: checked once they are known (``None`` / 1: the flags alone)."""
+    if not getattr(args, "edit", False):
+        given = [f"--{k}" for k in ("edit_roundtrip", "edit_chord_shift", "edit_chords_from_midi", "edit_depth", "edit_invert_scale")
+                 if getattr(args, k, None) not in (None, False)]
+        if given:
+            raise SystemExit(f"{', '.join(given)}: these belong to --edit, which was not given")
+        return False
+    if cond_type is not None and cond_type not in EDIT_COND_TYPES:
+        raise SystemExit(f"--edit replaces the chords of a song: it needs a model of cond_type chord or chord+txt, this one's is {cond_type!r}")
+    if getattr(args, "dpm", False):
+        raise SystemExit("--edit with --dpm: the 2M step's history makes its exact inverse a different problem; use --ddim")
+    if not args.ddim:
+        raise SystemExit("--edit needs --ddim: only the deterministic DDIM loop (eta 0) has an inverse to walk")
+    if args.ddim_eta != 0.0:
+        raise SystemExit(f"--edit needs --ddim_eta 0 (got {args.ddim_eta}): a loop that draws noise has no inverse")
+    if args.autoreg:
+        raise SystemExit("--edit with --autoreg: the autoregressive schedule inpaints from noise; use --joint to edit a song as one canvas")
+    if args.inpaint_type is not None:
+        raise SystemExit("--edit with --inpaint_type: two different ways to change a song, choose one")
+    if args.from_midi2 is not None:
+        raise SystemExit("--edit with --from_midi2: the song edited must be described by its own condition (chords and texture of one file)")
+    if args.num_generate > 1:
+        raise SystemExit("--edit is deterministic: --num_generate > 1 would write the same song again")
+    if world > 1:
+        raise SystemExit("--edit runs on one rank (one song, one loop)")
+    if args.edit_chord_shift is None and args.edit_chords_from_midi is None:
+        raise SystemExit("--edit needs the target chords: --edit_chord_shift N or --edit_chords_from_midi FILE")
+    if args.edit_chord_shift is not None and args.edit_chords_from_midi is not None:
+        raise SystemExit("--edit_chord_shift and --edit_chords_from_midi both name the target chords: give one of them")
+    if args.edit_iters < 1:
+        raise SystemExit(f"--edit_iters {args.edit_iters}: at least one iterate per step")
+    if args.edit_depth is not None and not 0 <= args.edit_depth < args.ddim_steps:
+        raise SystemExit(f"--edit_depth {args.edit_depth} outside [0, --ddim_steps - 1 = {args.ddim_steps - 1}]")
+    has_image = (args.uncond_scale != 0.0 and (args.from_midi is not None or args.from_dataset is not None)) or args.from_song_npz is not None
+    if not has_image and args.cond_npz is not None:        # (main reads --cond_npz only when none of the song sources above is taken)
+        with np.load(args.cond_npz) as z:
+            has_image = "prmat2c" in z
+    if not has_image:
+        raise SystemExit("--edit needs the song to edit: --from_midi, --from_dataset, --from_song_npz, or prmat2c in --cond_npz")
+    return True
+
+
+def shift_chords(chd: torch.Tensor, n: int) -> torch.Tensor:
+    """``chd [..., 36]`` with each of its three 12-wide blocks (root, chroma, bass) rolled by ``n``: the chords transposed by n semitones."""
+    return torch.cat([chd[..., 12 * j: 12 * j + 12].roll(int(n), dims=-1) for j in range(3)], dim=-1)
 
 
 def polydis_aftertouch(args, say=print):
@@ -703,11 +813,45 @@ def generate_songs(model, params, args, cond, cond_mid, orig, mask, seed: int, r
     return gen, expmt
 
 
+def edit_song(model, params, args, image, cond, cond_tgt, cond_mid, cond_mid_tgt, scale, seed: int, say=print) -> int:
+    """``--edit``: the condition song's own image through ``Experiments.edit``; writes ``<stamp>.mid`` / ``.npy`` with ``_edit<K>`` in the
+    stamp and prints the largest relative residual of the last iterate over all steps (and, with ``--edit_roundtrip``, how far the repaint
+    under the song's own condition lands from it)."""
+    n = min(cond.shape[0], cond_tgt.shape[0], image.shape[0])
+    cut = lambda v: None if v is None else v[:n].contiguous()
+    sampler, t_idx = make_sampler(model, args, seed, 0)
+    expmt = Experiments(params.model_name, params, sampler, t_idx=t_idx)
+    depth = t_idx if args.edit_depth is None else args.edit_depth
+    say(f"editing {n} segment(s): {depth + 1} upward steps x {args.edit_iters} iterates at scale "
+        f"{scale if args.edit_invert_scale is None else args.edit_invert_scale}, then {depth + 1} steps down at uncond_scale = {scale}")
+    orig = cut(image).float()
+    res = expmt.edit(orig, cut(cond), cut(cond_tgt), scale, iters=args.edit_iters, depth=depth, invert_scale=args.edit_invert_scale,
+                     cond_mid_src=cut(cond_mid), cond_mid_tgt=cut(cond_mid_tgt), joint=args.joint, blend=args.joint_blend,
+                     roundtrip=args.edit_roundtrip)
+    gen, rec = res if args.edit_roundtrip else (res, None)
+    if not bool(torch.isfinite(gen).all()):
+        raise SystemExit(f"non-finite values in the edited piano roll (precision {model.ldm.eps_model.precision})")
+    last = sampler.last_inversion.residuals()[:, -1]
+    say(f"inversion: largest relative residual of the last iterate over all steps: {float(np.nanmax(last)):.3e}")
+    if rec is not None:
+        differ = int(((rec > 0.5) != (orig > 0.5)).sum())
+        say(f"round trip: max |x - x_rec| = {float((rec - orig).abs().max()):.3e}, note cells > 0.5 that differ: {differ} of {orig.numel()}")
+    os.makedirs(args.output_dir, exist_ok=True)
+    stamp = os.path.join(args.output_dir, expmt._stamp(scale, False, f"_edit{args.edit_iters}", args.joint_blend if args.joint else None))
+    np.save(stamp + ".npy", gen.cpu().numpy())
+    if rec is not None:
+        np.save(stamp + "_roundtrip.npy", rec.cpu().numpy())
+    midi.prmat2c_to_midi_file(gen, stamp + ".mid")
+    say(f"edited song: piano_roll {tuple(gen.shape)}  onsets>0.5: {int((gen[:, 0] > 0.5).sum())}  -> {stamp}.mid")
+    return 0
+
+
 def main(argv=None):
     from . import dist as pfdist
     args = make_parser().parse_args(argv)
     if args.dpm and args.ddim:
         raise SystemExit("--dpm and --ddim name two different samplers: give one of them")
+    check_edit_args(args)                                  # what the flags alone decide, before anything else
     if not torch.cuda.is_available():
         raise SystemExit("inference_sdf needs an AMD GPU (no CPU fallback on this path)")
     rank, world, _ = pfdist.init_from_env()
@@ -741,6 +885,9 @@ def main(argv=None):
             params.setdefault("use_enc", True)
     say(f"model_label: {params.model_name}")
     dual = wants_dual_guidance(args, params.cond_type)     # (refusals before any weight is loaded)
+    editing = check_edit_args(args, params.cond_type, world)
+    if editing and params.get("concat_blurry", False):
+        raise SystemExit("--edit does not cover the concat_blurry variant (its blurred image describes the song being changed)")
     try:
         model = load_model(params, args, rank, world)
     except SystemExit as e:
@@ -849,11 +996,25 @@ def main(argv=None):
     scale = dual_scale(args, model.cond_split) if dual else args.uncond_scale
     if params.cond_type == "pnotree" and rank == 0 and not args.no_pnotree_recon:
         write_pnotree_recon(model, args, cond, say)
+    cond_tgt = cond_mid_tgt = None
+    if editing:
+        # the song's own condition is the source; the target is the same condition with the chords replaced
+        if chd is None or prmat2c_cond is None or cond_is_dummy:
+            raise SystemExit("--edit needs the song to edit with its chords: --from_midi, --from_dataset, --from_song_npz, or chord and prmat2c in --cond_npz")
+        if args.edit_chord_shift is not None:
+            chd_tgt = shift_chords(chd, args.edit_chord_shift)
+        else:
+            chd_tgt = song_from_midi(args.edit_chords_from_midi, "_edit")[2].to(_dev())
+            say(f"target chords from midi file: {args.edit_chords_from_midi}")
+        n = min(chd.shape[0], chd_tgt.shape[0])
+        cond_tgt, cond_mid_tgt = encode_conditions(model, params, chd_tgt[:n], prmat, args.joint, pnotree=pnotree)
     if params.cond_mode == "uncond":
         cond = -torch.ones_like(cond)
     if length > 0:
         cond = cond[:length]
         cond_mid = cond_mid[:length] if cond_mid is not None else None
+        cond_tgt = None if cond_tgt is None else cond_tgt[:length]
+        cond_mid_tgt = None if cond_mid_tgt is None else cond_mid_tgt[:length]
     orig = mask = None
     # the image to inpaint: --inpaint_from_midi, else (an extension of the reference, whose dataset branches are absent here) the condition song
     prmat2c_inp = inp_from_midi if inp_from_midi is not None else (None if cond_is_dummy else prmat2c_cond)
@@ -905,6 +1066,8 @@ def main(argv=None):
                 model = model16
     else:
         model.ldm.eps_model.set_precision(args.precision)
+    if editing:
+        return edit_song(model, params, args, prmat2c_cond, cond, cond_tgt, cond_mid, cond_mid_tgt, scale, seed, say)
     S, B = args.num_generate, cond.shape[0]
     say(f"generating {S} song(s) x {B} segment(s) with uncond_scale = {scale} on {world} GPU(s)")
     gen, expmt = generate_songs(model, params, args, cond, cond_mid, orig, mask, seed, rank, world, cond_concat=cond_concat, uncond_scale=scale)

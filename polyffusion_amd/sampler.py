@@ -7,6 +7,8 @@
 * ``DDIMSampler``       - ``sampler_ddim.py`` (tables :40-102, step :168-272, ``paint`` :301-362).
 * ``DualScale`` / ``guidance_plan`` - not in the reference: separate guidance scales for the chord and texture parts of a ``chord+txt``
   condition, passed as ``uncond_scale``; the one function that decides what a guided eps evaluates.
+* ``DDIMSampler.invert`` - not in the reference: the eta = 0 loop walked upwards, each step solved implicitly by fixed-point iterates
+  (``pf_invert_step``), so that ``paint`` under another condition edits a given song; ``invert_coef_rows``, ``InversionRecord``.
 * ``DPMSolverSampler``  - not in the reference: DPM-Solver++(2M), the second-order multistep solver, driven like ``DDIMSampler``.
 * ``WindowPlan``        - not in the reference: a song as one canvas whose half-overlapping windows are denoised as ONE batch per step, their
   noise predictions blended where they overlap (``DiffusionSampler.windows``; ``pf_window_split`` / ``pf_window_merge``).
@@ -286,17 +288,21 @@ class DiffusionSampler:
         restore()
         return g
 
-    def _replay_loop(self, family, inputs, table, taus, ndraw, n_noise, replays, t_start, uncond_scale, update):
+    def _replay_loop(self, family, inputs, table, taus, ndraw, n_noise, replays, t_start, uncond_scale, update, body_of=None):
         """`replays` reverse steps from table row `t_start` down as replays of ONE captured step; returns the resulting x.  `inputs`: name ->
         tensor or None (x, cond, uncond_cond, cond_concat and what `update` reads), `taus`: the device tau table (None: the row index is
         the time step), `ndraw`: noise draws per step, `n_noise`: how many of them need a tensor (bufs["_noise"]; none when they are made in
-        the update kernel), `update(bufs, e_t, table, state)`: the family's in-place update of bufs["x"]."""
+        the update kernel), `update(bufs, e_t, table, state)`: the family's in-place update of bufs["x"].  `body_of(bufs, t_buf, state)`: a
+        step of another shape than {begin, eps, update, end} (the upward step of `DDIMSampler.invert`) - it returns the closure to capture and
+        `update` is not used; the static buffers of the call stay reachable as `self._last_bufs`."""
         x = inputs["x"]
         dev, B, st = x.device, self._eps_rows(x), self._step_state(x.device)      # B: rows the denoiser sees (one per window under a plan)
 
         def make_body(bf):
             tb = bf["_t"] = torch.empty(B, dtype=torch.long, device=dev)
             bf["_noise"] = [torch.empty_like(bf["x"]) for _ in range(n_noise)]
+            if body_of is not None:
+                return body_of(bf, tb, st)
 
             def body():
                 _lib.check(self._lib.pf_step_begin(st.data_ptr(), _lib.ptr(taus), tb.data_ptr(), B, _lib.current_stream()), "pf_step_begin")
@@ -315,6 +321,7 @@ class DiffusionSampler:
             ent["g"].replay()
         e1.record()
         self.last_replay = (e0, e1, replays)     # bench.py reads the per-step replay time from these events
+        self._last_bufs = ent["bufs"]
         self._draws += ndraw * replays
         return ent["bufs"]["x"].clone()   # the static buffer is overwritten by the next paint() with these shapes
 
@@ -712,6 +719,126 @@ class DDIMSampler(DiffusionSampler):
             if self.on_step is not None:
                 self.on_step(int(step), x)
         return x
+
+
+    # ---- exact inversion of the eta = 0 loop (not in the reference) -------------------------------------------------------------
+    def invert_rows(self) -> np.ndarray:
+        """float32 ``[len(time_steps), 2]``: ``invert_coef_rows`` of this sampler's own float32 tables, rounded once."""
+        if getattr(self, "_inv_rows", None) is None:
+            self._inv_rows = invert_coef_rows(self.ddim_alpha.numpy(), self.ddim_alpha_prev.numpy()).astype(np.float32)
+        return self._inv_rows
+
+    def _invert_table(self, device):
+        """([S, 2] fp32 rows, [S] int32 tau table) on the device: row i = the pf_invert_coef of upward step i."""
+        key = ("invert_table", str(device))
+        if key not in self._dev_cache:
+            self._dev_cache[key] = (torch.from_numpy(self.invert_rows()).to(device), self._coef_table(device)[1])
+        return self._dev_cache[key]
+
+    def _invert_graph(self, x, cond, t_end, iters, resid, uncond_scale, uncond_cond, cond_concat):
+        """Steps 0 .. t_end as replays of ONE captured upward step {begin, iters x (eps, iterate), advance}.  The iterate lives in the
+        static x buffer (x_iter = x_out), the step's lower state y in a second one that every replay first refills from x."""
+        lib = self._lib
+        table, taus = self._invert_table(x.device)
+
+        def body_of(bf, tb, st):
+            yb = bf["_y"] = torch.empty_like(bf["x"])
+            ws = bf["_ws"] = _steps.invert_workspace(lib, yb.shape[0], yb.numel() // yb.shape[0], yb.device)
+
+            def body():
+                _lib.check(lib.pf_step_begin(st.data_ptr(), taus.data_ptr(), tb.data_ptr(), tb.numel(), _lib.current_stream()), "pf_step_begin")
+                yb.copy_(bf["x"])
+                for k in range(iters):
+                    cur = yb if k == 0 else bf["x"]
+                    xin = cur if bf["cond_concat"] is None else torch.cat([cur, bf["cond_concat"]], dim=1)
+                    e_t = self.get_eps(xin, tb, bf["cond"], uncond_scale=uncond_scale, uncond_cond=bf["uncond_cond"], prep=bf["_prep"])
+                    _steps.invert_step(lib, yb, e_t.contiguous(), bf["x"], table=table, state=st, x_iter=None if k == 0 else bf["x"],
+                                       resid=bf["resid"], workspace=ws, iters=iters, k=k)
+                _lib.check(lib.pf_step_advance(st.data_ptr(), 1, 0, _lib.current_stream()), "pf_step_advance")
+            return body
+
+        inputs = dict(x=x, cond=cond, uncond_cond=uncond_cond, cond_concat=cond_concat, resid=resid)
+        out = self._replay_loop(("ddim_invert", int(iters)), inputs, table, taus, 0, 0, t_end + 1, 0, uncond_scale, None, body_of=body_of)
+        return out, self._last_bufs["resid"].clone()      # the static table is overwritten by the next call with these shapes
+
+    @torch.no_grad()
+    def invert(self, x0, cond, t_end: Optional[int] = None, *, iters: int = 3, uncond_scale: Scale = 1.0, uncond_cond=None, cond_concat=None,
+               keep_iterates: bool = False):
+        """Walk the eta = 0 DDIM ODE UPWARDS from ``x0`` - taken at the level ``paint`` ends at, ``ddim_alpha_prev[0]`` - through indices
+        0 .. ``t_end`` (default: the last) to the noise ``x`` that ``paint(x, cond, t_end)`` brings back to ``x0``; a different ``cond`` in
+        that ``paint`` edits the image.  Step i goes from ``ddim_alpha_prev[i]`` to ``ddim_alpha[i]`` and is IMPLICIT: it looks for the x
+        whose DDIM step lands exactly on the state below, y, by ``iters`` fixed-point iterates ``x <- c_y*y + c_e*eps(x, time_steps[i])``
+        from ``x = y``, one denoiser evaluation each (``pf_invert_step``).  ``iters = 1`` is the naive explicit inversion, which falls apart
+        under guidance above 1.  Everything goes through ``get_eps``: float or ``DualScale`` guidance, ``cond_concat`` and a window plan
+        (``x0`` a canvas) work as in ``paint``.  ``graph=True``: one captured step replayed ``t_end + 1`` times, bit-identical to this loop.
+
+        No host sync: the per-row sums (x_K+1 - x_K)^2 and x_K+1^2 of every iterate are left in a device table, ``self.last_inversion``
+        (``.table`` float64 ``[t_end + 1, iters, rows, 2]``, ``.shape``, ``.residuals()`` -> sqrt of their ratio as numpy); the round-trip defect
+        of step i after k iterates is residual k+1 over c_y.  ``keep_iterates`` (eager, for tests): every iterate in ``last_inversion.iterates[i][k]``."""
+        n = len(self.time_steps)
+        t_end = n - 1 if t_end is None else int(t_end)
+        iters = int(iters)
+        if not 0 <= t_end < n:
+            raise ValueError(f"invert: t_end {t_end} outside [0, {n - 1}], the indices of this sampler's grid")
+        if iters < 1:
+            raise ValueError(f"invert: iters {iters} < 1 (one iterate is the explicit inversion)")
+        if bool((self.ddim_sigma[: t_end + 1] != 0).any()):
+            raise ValueError("invert: the loop is stochastic over this range (ddim_sigma != 0, eta > 0): only the eta = 0 ODE has an inverse")
+        y = x0.contiguous().float()
+        rows, dev = y.shape[0], y.device
+        use_graph = self.graph and self.noise_fn is None and self.on_step is None and not keep_iterates
+        # graph mode keeps one table of the whole grid's size in the captured step, so that one capture serves every t_end
+        resid = torch.zeros((n if use_graph else t_end + 1), iters, rows, 2, dtype=torch.float64, device=dev)
+        its = [] if keep_iterates else None
+        if use_graph:
+            y, full = self._invert_graph(y, cond, t_end, iters, resid, uncond_scale, uncond_cond, cond_concat)
+            resid = full[: t_end + 1]
+        else:
+            ws = _steps.invert_workspace(self._lib, rows, y.numel() // rows, dev)
+            prep = self.prepare(cond, uncond_scale=uncond_scale, uncond_cond=uncond_cond)
+            rws = self.invert_rows()
+            for i in range(t_end + 1):
+                step, coef = int(self.time_steps[i]), _lib.InvertCoef(float(rws[i, 0]), float(rws[i, 1]))
+                cur = y
+                if its is not None:
+                    its.append([])
+                for k in range(iters):
+                    e_t = self._eps(cur, cond, step, uncond_scale, uncond_cond, cond_concat, prep).contiguous()
+                    out = torch.empty_like(y)
+                    _steps.invert_step(self._lib, y, e_t, out, coef=coef, x_iter=None if k == 0 else cur, resid=resid, workspace=ws,
+                                       slot=i * iters + k)
+                    cur = out
+                    if its is not None:
+                        its[-1].append(out)
+                y = cur
+        self.last_inversion = InversionRecord(resid, (t_end + 1, iters, rows, 2), its)
+        return y
+
+
+@dataclass
+class InversionRecord:
+    """What ``DDIMSampler.invert`` leaves behind without a host sync: ``table`` - device float64 of ``shape`` ``[steps, iters, rows, 2]``, the
+    row sums (x_k+1 - x_k)^2 and x_k+1^2 of every iterate; ``iterates`` - ``[step][k]`` tensors under ``keep_iterates``, else ``None``."""
+    table: torch.Tensor
+    shape: tuple
+    iterates: Optional[list] = None
+
+    def residuals(self) -> np.ndarray:
+        """``sqrt(sum diff^2 / sum x^2)`` as numpy ``[steps, iters, rows]`` (copies the table: the one host sync)."""
+        t = self.table.detach().cpu().numpy().reshape(self.shape)
+        with np.errstate(divide="ignore", invalid="ignore"):
+            return np.sqrt(t[..., 0] / t[..., 1])
+
+
+def invert_coef_rows(alpha, alpha_prev) -> np.ndarray:
+    """float64 ``[n, 2]``: row i = ``(c_y, c_e)`` of the upward step from level ``alpha_prev[i]`` to ``alpha[i]`` (``pf_invert_coef``):
+    ``c_y = sqrt(a / ap)``, ``c_e = sqrt(1 - a) - sqrt(a * (1 - ap) / ap)`` - the DDIM step with eta = 0, ``x_prev = sqrt(ap) * (x -
+    sqrt(1 - a) * eps) / sqrt(a) + sqrt(1 - ap) * eps``, solved for x.  A repeated time step (``a == ap``, as on the ``quad`` grid) is the
+    identity: ``(1, 0)`` exactly."""
+    a, ap = np.asarray(alpha, dtype=np.float64), np.asarray(alpha_prev, dtype=np.float64)
+    rows = np.stack([np.sqrt(a / ap), np.sqrt(1.0 - a) - np.sqrt(a * (1.0 - ap) / ap)], axis=1)
+    rows[a == ap] = (1.0, 0.0)
+    return rows
 
 
 def dpm_time_steps(alpha_bar, n_steps: int, discretize: str = "logsnr") -> np.ndarray:
