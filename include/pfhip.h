@@ -420,6 +420,50 @@ int pf_comm_destroy(pf_comm* comm);
  * Rounding is the reference's int(round(v)) > 0 (== v > 0.5); custom_round != 0 selects utils.py:395-399 for the onset. */
 int pf_prmat2c_durations(const float* prmat2c, int n, int steps, int custom_round, int32_t* dur, void* stream);
 
+/* ---- scoring a roll against its chords ("Roll statistics"; not in the reference) ----
+ * One pass over n onset/sustain images and, optionally, the chords they were conditioned on: integer counters per image, the number of
+ * sounding cells per pitch class per beat, the number of onset cells per step.  Everything is a comparison or an integer count, so the
+ * result is exact and does not depend on any order.  It is a fixed statistic, not a chord extractor: no voicing, no key, no inversion.
+ *   Cells.  r(v) = v > 0.5 (custom_round: 0.95 < v < 1.05); on = r(onset), sus = r(sustain), sounding = on | sus; a NaN is silent.  With
+ *   `mask`, only cells whose mask (channel 0) == 0 - the generated ones - count: any other cell is silent for every counter and table,
+ *   but its raw values still serve as predecessor.  Predecessor occupied: v > 0.5 || v < -0.5 on either channel of the same key one step
+ *   earlier (custom_round: r(v) on either channel) - check_prmat2c_integrity's rule; step 0 has no predecessor.  Pitch class = key % 12,
+ *   beat j = step / 4.
+ *   Chords.  Row j of `chord` is root one-hot [0:12] | chroma bits [12:24] | bass one-hot [24:36].  C = {k : chord[12 + k] > 0.5}; a beat
+ *   with empty C enters no chord counter.  Bass class = arg-max of chord[24:36] (ties to the lowest index; no entry > 0: the beat has no
+ *   bass); with bass_relative it becomes (bass + arg-max of chord[0:12]) % 12.  chord == NULL: every chord counter is 0.
+ *   Every word of the three outputs is written by the call (unused counter slots as 0): the caller does not pre-zero.  One launch, one
+ *   workgroup per image, no atomics, nothing allocated, nothing synchronised: capturable.  Refused before any launch: null prmat2c or
+ *   outputs, pointers not 4-byte aligned, n <= 0, steps <= 0, steps % 4 != 0. */
+enum {
+  PF_ROLL_N_ONSET = 0,         /* onset cells */
+  PF_ROLL_N_SOUNDING = 1,      /* sounding cells */
+  PF_ROLL_N_ORPHAN = 2,        /* sus cells whose predecessor is not occupied */
+  PF_ROLL_CHORD_BEATS = 3,     /* beats with non-empty C */
+  PF_ROLL_SOUND_ON_CHORD = 4,  /* sounding cells on those beats */
+  PF_ROLL_SOUND_IN_CHORD = 5,  /* of those, class in C */
+  PF_ROLL_ONSET_IN_CHORD = 6,  /* onset cells on those beats, class in C */
+  PF_ROLL_ONSET_ON_CHORD = 7,  /* onset cells on those beats */
+  PF_ROLL_CHORD_CLASSES = 8,   /* sum over those beats of |C| */
+  PF_ROLL_CHORD_HEARD = 9,     /* sum over those beats of how many classes of C sound at all in the beat */
+  PF_ROLL_BASS_BEATS = 10,     /* chord beats that have a bass and at least one sounding cell */
+  PF_ROLL_BASS_HIT = 11,       /* of those, the lowest sounding key of the beat has the bass class */
+  PF_ROLL_LOW_KEY = 12,        /* lowest sounding key of the image, -1 if silent */
+  PF_ROLL_HIGH_KEY = 13        /* highest sounding key of the image, -1 if silent */
+};
+#define PF_ROLL_NCOUNT 16
+typedef struct pf_roll_stats_args {
+  const float* prmat2c;               /* [n][2][steps][128]: channel 0 onset, 1 sustain (as pf_prmat2c_durations) */
+  const float* chord;                 /* [n][steps/4][36]; NULL: the chord counters stay 0 */
+  const float* mask;                  /* optional, shape of prmat2c, channel 0 read: only cells with mask == 0 count */
+  int32_t n, steps;                   /* steps > 0, steps % 4 == 0 (a beat is 4 steps) */
+  int32_t custom_round, bass_relative;
+  int32_t* counters;                  /* [n][PF_ROLL_NCOUNT] */
+  int32_t* chroma;                    /* [n][steps/4][12]: sounding cells per pitch class per beat */
+  int32_t* onsets;                    /* [n][steps]: onset cells per step */
+} pf_roll_stats_args;
+int pf_roll_stats(const pf_roll_stats_args* a, void* stream);
+
 /* ---- condition encoders (replace RnnEncoder.forward dl_modules/chord_enc.py:15-22, TextureEncoder.forward
  *      dl_modules/txt_enc.py:23-35 and PianoTreeEncoder.forward dl_modules/pianotree_enc.py:97-121; only the Normal's mean is produced)
  *      PF_ENC_PNOTREE: input_dim = pitch classes + 5 duration digits (135), emb_size = note embedding (128), num_channel = hidden size

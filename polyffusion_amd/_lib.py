@@ -120,6 +120,18 @@ class ChordForcedArgs(C.Structure):
                 ("root", C.c_void_p), ("chroma", C.c_void_p), ("bass", C.c_void_p), ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t)]
 
 
+class RollStatsArgs(C.Structure):
+    """pf_roll_stats_args (include/pfhip.h); filled by ``score.roll_stats`` only."""
+    _fields_ = ([(n, C.c_void_p) for n in ("prmat2c", "chord", "mask")] + [(n, C.c_int32) for n in ("n", "steps", "custom_round", "bass_relative")]
+                + [(n, C.c_void_p) for n in ("counters", "chroma", "onsets")])
+
+
+# PF_ROLL_*, in the enum's order; PF_ROLL_NCOUNT slots per image (the rest are written as 0)
+ROLL_COUNTERS = ("N_ONSET", "N_SOUNDING", "N_ORPHAN", "CHORD_BEATS", "SOUND_ON_CHORD", "SOUND_IN_CHORD", "ONSET_IN_CHORD", "ONSET_ON_CHORD",
+                 "CHORD_CLASSES", "CHORD_HEARD", "BASS_BEATS", "BASS_HIT", "LOW_KEY", "HIGH_KEY")
+ROLL_NCOUNT = 16
+
+
 FEEDBACK = {"row": 0, "batch": 1}   # PF_FEEDBACK_ROW / PF_FEEDBACK_BATCH
 MSE_CHUNK = 2048           # PF_MSE_CHUNK: elements of a row one workgroup of pf_mse_rows reduces
 
@@ -263,6 +275,7 @@ SIGNATURES = {
     "pf_comm_bcast": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p]),
     "pf_comm_destroy": (C.c_int, [C.c_void_p]),
     "pf_prmat2c_durations": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "pf_roll_stats": (C.c_int, [C.POINTER(RollStatsArgs), C.c_void_p]),
     "pf_encoder_create": (C.c_int, [C.c_int] * 6 + [C.POINTER(C.c_void_p)]),
     "pf_encoder_create_dist": (C.c_int, [C.c_int] * 7 + [C.POINTER(C.c_void_p)]),
     "pf_encoder_destroy": (None, [C.c_void_p]),

@@ -68,6 +68,10 @@ int pf_pack_wino_weight_bf16x3(const float* w, int n, int k, void* dst) {
 int pf_prmat2c_durations(const float* prmat2c, int n, int steps, int custom_round, int32_t* dur, void* stream) {
   return launch_prmat2c_durations(prmat2c, n, steps, custom_round, dur, (hipStream_t)stream);
 }
+int pf_roll_stats(const pf_roll_stats_args* a, void* stream) {
+  PF_REQUIRE(a, "pf_roll_stats: null arguments");
+  return launch_roll_stats(*a, (hipStream_t)stream);
+}
 int pf_mlp_geglu_fused(const float* x, int batch, int l, const float* ln_gamma, const float* ln_beta, float ln_eps,
                        const void* w1_bf16x3, const float* b1, const void* w2_bf16x3, const float* b2,
                        float* out, void* out_planes, void* stream) {

@@ -6,6 +6,7 @@
 //   and the update of the sampler the reference does not have, DPM-Solver++(2M) (pf_dpm_step),
 //   one fixed-point iterate of exact DDIM inversion with its fused residual (pf_invert_step) and the upward step state (pf_step_advance),
 //   the canvas <-> window-batch gathers of joint overlapping-window sampling (pf_window_split, pf_window_merge),
+//   note durations of a generated roll (pf_prmat2c_durations) and its integer statistics against the run's chords (pf_roll_stats),
 //   counter-based Gaussian noise, GRU gate update and the texture-encoder front end
 //   (dl_modules/chord_enc.py:15-22, txt_enc.py:23-27).
 #include "pf_internal.h"
@@ -297,6 +298,155 @@ __global__ __launch_bounds__(128) void prmat2c_durations_kernel(const float* __r
 int launch_prmat2c_durations(const float* x, int n, int steps, int custom_round, int32_t* dur, hipStream_t stream) {
   PF_REQUIRE(x && dur && n > 0 && steps > 0, "prmat2c_durations: bad arguments");
   hipLaunchKernelGGL(prmat2c_durations_kernel, dim3(n), dim3(128), 0, stream, x, steps, custom_round, dur);
+  PF_CHECK_HIP(hipGetLastError());
+  return PF_OK;
+}
+
+// ------------------------------------------------------------------ roll statistics: onset/sustain image (+ chords, + mask) -> integers
+// include/pfhip.h, pf_roll_stats; DESIGN.md 3, "Roll statistics".  One workgroup per image, one wave per beat at a time: lane l of a wave is
+// key l, then key 64 + l, of each of the beat's four steps (a 256-byte coalesced read per channel and half), and a __ballot turns the
+// wave's 64 predicates into one word.  Everything a beat contributes is then popcounts and bit tests of those words - wave-uniform
+// integers - except the per-class counts, which lane k < 12 keeps for class k as popcount(word & class_mask[k]): the keys of class k
+// among the lower 64 are bits k, k + 12, ..., and among the upper 64 (key = 64 + bit, 64 % 12 == 4) the bits of class (k + 8) % 12.
+// A beat is owned by one wave, so its rows of `chroma` and `onsets` are written without any combination; the image's counters are added
+// over the waves through a few LDS integers.  No atomics, no floating-point arithmetic at all: exact and order-free.
+constexpr int kRollMaxWaves = 16;
+__device__ __forceinline__ bool roll_round(float v, int custom) { return custom ? (v > 0.95f && v < 1.05f) : (v > 0.5f); }
+__device__ __forceinline__ bool roll_occupied(float v, int custom) { return custom ? (v > 0.95f && v < 1.05f) : (v > 0.5f || v < -0.5f); }
+// arg-max of twelve floats, ties (and a NaN, which never compares greater) to the lowest index; *any: some entry is > 0
+__device__ __forceinline__ int roll_argmax12(const float* __restrict__ v, bool* any) {
+  float best = v[0];
+  int bi = 0;
+  bool pos = best > 0.0f;
+  for (int i = 1; i < 12; ++i) {
+    const float c = v[i];
+    pos = pos || c > 0.0f;
+    if (c > best) { best = c; bi = i; }
+  }
+  *any = pos;
+  return bi;
+}
+
+__global__ __launch_bounds__(64 * kRollMaxWaves) void roll_stats_kernel(const float* __restrict__ x, const float* __restrict__ chord,
+                                                                        const float* __restrict__ mask, int steps, int custom, int bass_rel,
+                                                                        int32_t* __restrict__ counters, int32_t* __restrict__ chroma,
+                                                                        int32_t* __restrict__ onsets) {
+  __shared__ int32_t part[kRollMaxWaves][PF_ROLL_NCOUNT];
+  const int n = blockIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nwaves = blockDim.x >> 6, beats = steps >> 2;
+  const float* on = x + (size_t)n * 2 * steps * 128;
+  const float* su = on + (size_t)steps * 128;
+  const float* mk = mask ? mask + (size_t)n * 2 * steps * 128 : nullptr;
+  constexpr unsigned long long kClass0 = 0x1001001001001001ull;                 // keys 0, 12, ..., 60
+  const unsigned long long cm[2] = {lane < 12 ? kClass0 << lane : 0ull, lane < 12 ? kClass0 << ((lane + 8) % 12) : 0ull};
+  const int cls[2] = {lane % 12, (lane + 4) % 12};                              // class of this lane's key in the lower / upper half
+  int cnt[PF_ROLL_NCOUNT] = {0};
+  int low = 128, high = -1;
+  for (int j = wave; j < beats; j += nwaves) {
+    // the beat's chord: the class set as 12 bits, the same set as key bits of the two halves, the bass class (-1: none)
+    unsigned cset = 0;
+    int bass = -1;
+    if (chord) {
+      const float* cd = chord + ((size_t)n * beats + j) * 36;
+      cset = (unsigned)__ballot(lane < 12 && cd[12 + (lane < 12 ? lane : 0)] > 0.5f);
+      bool any;
+      int b = roll_argmax12(cd + 24, &any);
+      if (bass_rel) {
+        bool unused;
+        b = (b + roll_argmax12(cd, &unused)) % 12;
+      }
+      bass = any ? b : -1;
+    }
+    const unsigned long long cw[2] = {__ballot((cset >> cls[0]) & 1u), __ballot((cset >> cls[1]) & 1u)};
+    // every value of the beat first (the loads are independent), then the words
+    const int t0 = 4 * j;
+    float a[4][2], s[4][2], m[4][2], pa[2], ps[2];
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+      const size_t p = (size_t)(t0 > 0 ? t0 - 1 : 0) * 128 + 64 * h + lane;
+      pa[h] = t0 > 0 ? on[p] : 0.0f;                                            // 0 is unoccupied under both rules
+      ps[h] = t0 > 0 ? su[p] : 0.0f;
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        const size_t i = (size_t)(t0 + k) * 128 + 64 * h + lane;
+        a[k][h] = on[i];
+        s[k][h] = su[i];
+        m[k][h] = mk ? mk[i] : 0.0f;
+      }
+    }
+    int mine = 0, snd_beat = 0, on_beat = 0, snd_in = 0, on_in = 0, orphan = 0;
+    unsigned long long heard[2] = {0ull, 0ull};
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      int on_step = 0;
+#pragma unroll
+      for (int h = 0; h < 2; ++h) {
+        const bool live = m[k][h] == 0.0f;
+        const bool is_on = live && roll_round(a[k][h], custom), is_su = live && roll_round(s[k][h], custom);
+        const bool occ = roll_occupied(pa[h], custom) || roll_occupied(ps[h], custom);
+        const unsigned long long w_on = __ballot(is_on), w_snd = __ballot(is_on || is_su), w_orph = __ballot(is_su && !occ);
+        pa[h] = a[k][h];
+        ps[h] = s[k][h];
+        on_step += __popcll(w_on);
+        snd_beat += __popcll(w_snd);
+        snd_in += __popcll(w_snd & cw[h]);
+        on_in += __popcll(w_on & cw[h]);
+        orphan += __popcll(w_orph);
+        mine += __popcll(w_snd & cm[h]);
+        heard[h] |= w_snd;
+      }
+      on_beat += on_step;
+      if (lane == 0) onsets[(size_t)n * steps + t0 + k] = on_step;
+    }
+    if (lane < 12) chroma[((size_t)n * beats + j) * 12 + lane] = mine;
+    const int n_heard = __popcll(__ballot(lane < 12 && ((cset >> (lane & 15)) & 1u) && mine > 0));
+    cnt[PF_ROLL_N_ONSET] += on_beat;
+    cnt[PF_ROLL_N_SOUNDING] += snd_beat;
+    cnt[PF_ROLL_N_ORPHAN] += orphan;
+    const bool sounds = (heard[0] | heard[1]) != 0ull;
+    const int lowest = heard[0] ? __builtin_ctzll(heard[0]) : heard[1] ? 64 + __builtin_ctzll(heard[1]) : 128;
+    const int highest = heard[1] ? 127 - __builtin_clzll(heard[1]) : heard[0] ? 63 - __builtin_clzll(heard[0]) : -1;
+    low = min(low, lowest);
+    high = max(high, highest);
+    if (cset) {
+      cnt[PF_ROLL_CHORD_BEATS] += 1;
+      cnt[PF_ROLL_SOUND_ON_CHORD] += snd_beat;
+      cnt[PF_ROLL_SOUND_IN_CHORD] += snd_in;
+      cnt[PF_ROLL_ONSET_IN_CHORD] += on_in;
+      cnt[PF_ROLL_ONSET_ON_CHORD] += on_beat;
+      cnt[PF_ROLL_CHORD_CLASSES] += __popc(cset);
+      cnt[PF_ROLL_CHORD_HEARD] += n_heard;
+      if (bass >= 0 && sounds) {
+        cnt[PF_ROLL_BASS_BEATS] += 1;
+        cnt[PF_ROLL_BASS_HIT] += (lowest % 12 == bass) ? 1 : 0;
+      }
+    }
+  }
+  cnt[PF_ROLL_LOW_KEY] = low;
+  cnt[PF_ROLL_HIGH_KEY] = high;
+  if (lane == 0) {
+#pragma unroll
+    for (int c = 0; c < PF_ROLL_NCOUNT; ++c) part[wave][c] = cnt[c];
+  }
+  __syncthreads();
+  if (threadIdx.x < PF_ROLL_NCOUNT) {
+    const int c = threadIdx.x;
+    int v = part[0][c];
+    for (int w = 1; w < nwaves; ++w) v = c == PF_ROLL_LOW_KEY ? min(v, part[w][c]) : c == PF_ROLL_HIGH_KEY ? max(v, part[w][c]) : v + part[w][c];
+    if (c == PF_ROLL_LOW_KEY && v == 128) v = -1;
+    counters[(size_t)n * PF_ROLL_NCOUNT + c] = v;
+  }
+}
+
+int launch_roll_stats(const pf_roll_stats_args& a, hipStream_t stream) {
+  PF_REQUIRE(a.prmat2c && a.n > 0 && a.steps > 0, "roll_stats: bad arguments (prmat2c %p, n = %d, steps = %d)", (const void*)a.prmat2c, a.n, a.steps);
+  PF_REQUIRE(a.steps % 4 == 0, "roll_stats: steps = %d is not a whole number of beats (4 steps each)", a.steps);
+  PF_REQUIRE(a.counters && a.chroma && a.onsets, "roll_stats: null output (counters %p, chroma %p, onsets %p)", (void*)a.counters, (void*)a.chroma,
+             (void*)a.onsets);
+  const uintptr_t all = (uintptr_t)a.prmat2c | (uintptr_t)a.chord | (uintptr_t)a.mask | (uintptr_t)a.counters | (uintptr_t)a.chroma | (uintptr_t)a.onsets;
+  PF_REQUIRE(all % 4 == 0, "roll_stats: every pointer must be 4-byte aligned");
+  const int waves = min(kRollMaxWaves, a.steps / 4);
+  hipLaunchKernelGGL(roll_stats_kernel, dim3(a.n), dim3(64 * waves), 0, stream, a.prmat2c, a.chord, a.mask, a.steps, a.custom_round != 0,
+                     a.bass_relative != 0, a.counters, a.chroma, a.onsets);
   PF_CHECK_HIP(hipGetLastError());
   return PF_OK;
 }

@@ -19,6 +19,7 @@ checkpoint by the deterministic weight generator (no trained weights ship with t
 """
 from __future__ import annotations
 
+import json
 import os
 import random
 from argparse import ArgumentParser
@@ -29,6 +30,7 @@ import numpy as np
 import torch
 
 from . import _lib, datasample, midi, synth
+from . import score as pfscore
 from .model_sdf import ChordEncoder, Polyffusion_SDF, TextureEncoder
 from .params import Params, find_params, load_params, preset
 from .sampler import GUIDANCE_ORDERS, DDIMSampler, DiffusionSampler, DPMSolverSampler, DualScale, SDFSampler
@@ -537,7 +539,40 @@ def make_parser() -> ArgumentParser:
                    "--synthetic_weights selects the synthetic Polydis state instead")
     p.add_argument("--hip_graph", action="store_true", help="capture one reverse step as a hipGraph and replay it (same results; "
                    "removes the host-side launch cost that bounds small batches, e.g. the batch-1 runs of --autoreg)")
+    # extension: score the generated rolls against the chords of the run (polyffusion_amd.score; one HIP launch over the images on the device)
+    p.add_argument("--score", action="store_true", help="extension: after generation print per song chord_f1, chord_fit, chord_cover, bass_fit, "
+                   "integrity and the onset count against the chords the run conditioned on (without chords: the chord-free numbers; when "
+                   "inpainting: of the invented cells only) and write <stamp>_score.json.  With --edit: chord_f1 of the source and of the "
+                   "edited image, each against the source and against the target chords")
+    p.add_argument("--best_of", type=int, default=1, metavar="N", help="extension: generate --num_generate x N candidates (the same songs as "
+                   "--num_generate of that product would give), score them and keep the best --num_generate, files named by rank; implies --score")
+    p.add_argument("--rank_by", choices=list(pfscore.RANK_BY), default="chord", help="what --best_of ranks by: chord (chord_f1, default), bass "
+                   "(bass_fit), integrity (lowest first) or texture (rhythm against the texture song; chord+txt models only)")
+    p.add_argument("--score_bass_relative", action="store_true", help="read the bass block of a chord row as an offset from the root "
+                   "(default: an absolute pitch class, as --from_midi writes it)")
     return p
+
+
+def check_score_args(args, cond_type: Optional[str] = None) -> bool:
+    """Whether the command line asks for scores (``--score`` or ``--best_of N > 1``); every misuse is a ``SystemExit`` with a message, raised
+    before any weight is loaded.  ``cond_type``: checked once it is known (``None``: the flags alone)."""
+    best_of = getattr(args, "best_of", 1)
+    if best_of < 1:
+        raise SystemExit(f"--best_of {best_of}: at least one candidate per song kept")
+    if best_of > 1 and getattr(args, "edit", False):
+        raise SystemExit("--best_of with --edit: --edit is deterministic, every candidate would be the same song")
+    scoring = bool(getattr(args, "score", False)) or best_of > 1
+    if not scoring:
+        given = [f"--{k}" for k in ("score_bass_relative",) if getattr(args, k, False)] + (["--rank_by"] if args.rank_by != "chord" else [])
+        if given:
+            raise SystemExit(f"{', '.join(given)}: these belong to --score / --best_of, which were not given")
+        return False
+    if cond_type is not None:
+        if args.rank_by == "texture" and cond_type != "chord+txt":
+            raise SystemExit(f"--rank_by texture compares against the texture song of a chord+txt model; this model's cond_type is {cond_type!r}")
+        if best_of > 1 and args.rank_by in ("chord", "bass") and "chord" not in cond_type.split("+"):
+            raise SystemExit(f"--rank_by {args.rank_by} needs the chords of the run; this model's cond_type is {cond_type!r} (use --rank_by integrity)")
+    return True
 
 
 def wants_dual_guidance(args, cond_type: str) -> bool:
@@ -780,7 +815,8 @@ def make_sampler(model, args, seed: int, sample_offset: int = 0):
 
 def generate_songs(model, params, args, cond, cond_mid, orig, mask, seed: int, rank: int = 0, world: int = 1, cond_concat=None,
                    uncond_scale=None):
-    """This rank's share of ``args.num_generate`` independent generations of the same conditions.  ``uncond_scale``: the guidance scale
+    """This rank's share of ``args.num_generate`` (times ``args.best_of``, the candidates of ``--best_of``) independent generations of the
+    same conditions.  ``uncond_scale``: the guidance scale
     (``None``: ``args.uncond_scale``; a ``DualScale`` for dual guidance) - handed to the sampler as it is.
 
     The reference loops over the songs (``inference_sdf.py:774``); here they are ONE batch and the unit of multi-GPU
@@ -788,7 +824,7 @@ def generate_songs(model, params, args, cond, cond_mid, orig, mask, seed: int, r
     GLOBAL index (``sample_offset``), so the result does not depend on the number of GPUs, and the step loop has no
     collective.  Returns (``[n_local, B, C, H, W]`` - or ``[n_local, 2B, C, H/2, W]`` with ``--autoreg`` -, the Experiments)."""
     from . import dist as pfdist
-    S, B = args.num_generate, cond.shape[0]
+    S, B = args.num_generate * getattr(args, "best_of", 1), cond.shape[0]      # --best_of N: N candidates per song kept, all of them songs here
     lo, hi = pfdist.shard_range(S, rank, world)
     n_local = hi - lo
     joint = getattr(args, "joint", False)
@@ -813,10 +849,45 @@ def generate_songs(model, params, args, cond, cond_mid, orig, mask, seed: int, r
     return gen, expmt
 
 
-def edit_song(model, params, args, image, cond, cond_tgt, cond_mid, cond_mid_tgt, scale, seed: int, say=print) -> int:
+def autoreg_halves(v: torch.Tensor) -> torch.Tensor:
+    """``[B, C, H, W]`` -> ``[2B, C, H/2, W]``: the segments cut into the halves ``--autoreg`` returns, in its order"""
+    B, C, H, W = v.shape
+    return v.reshape(B, C, 2, H // 2, W).permute(0, 2, 1, 3, 4).reshape(2 * B, C, H // 2, W)
+
+
+def score_songs(gen: torch.Tensor, chd, mask, args, txt_prmat=None):
+    """``--score`` on this rank's songs where they live: ``gen`` ``[n, B, C, H, W]`` (``[n, 2B, C, H/2, W]`` with ``--autoreg``) against the
+    run's chords ``chd [B, 32, 36]`` (``None``: the chord-free numbers), of the cells ``mask [B, C, H, W]`` marks as invented when inpainting.
+    Returns the per-song counters ``[n, 16]`` int32 (a song's segments summed) and, with ``txt_prmat`` ``[B, H, W]`` (the texture song of a
+    chord+txt model), ``texture_fit`` per song, float64 ``[n]``, else ``None``.  Two launches at most, no host synchronisation."""
+    n, per = gen.shape[0], gen.shape[1]
+    if n == 0:
+        return (torch.empty(0, _lib.ROLL_NCOUNT, dtype=torch.int32, device=gen.device),
+                None if txt_prmat is None else torch.empty(0, dtype=torch.float64, device=gen.device))
+    rep = lambda v: None if v is None else v.unsqueeze(0).expand(n, *v.shape)
+    if mask is not None and args.autoreg:
+        mask = autoreg_halves(mask)
+    st = pfscore.roll_stats(gen, rep(chd), rep(mask), bass_relative=args.score_bass_relative).songs(per)
+    if txt_prmat is None:
+        return st.counters, None
+    onset = (txt_prmat > 0).float()
+    img = torch.stack([onset, torch.zeros_like(onset)], dim=1)                      # the texture song as an image of onsets alone
+    ref = pfscore.roll_stats(autoreg_halves(img) if args.autoreg else img).songs(per)
+    ref = pfscore.RollStats(ref.counters.expand(n, -1), ref.chroma.expand(n, -1, -1), ref.onsets.expand(n, -1))
+    return st.counters, pfscore.texture_fit(st, ref)
+
+
+def score_line(c: dict) -> str:
+    return (f"chord_f1 {c['chord_f1']:.4f}  chord_fit {c['chord_fit']:.4f}  chord_cover {c['chord_cover']:.4f}  bass_fit {c['bass_fit']:.4f}  "
+            f"integrity {c['integrity']:.4f}  onsets {c['counters']['N_ONSET']}" + (f"  texture_fit {c['texture_fit']:.4f}" if "texture_fit" in c else ""))
+
+
+def edit_song(model, params, args, image, cond, cond_tgt, cond_mid, cond_mid_tgt, scale, seed: int, say=print, score_chords=None) -> int:
     """``--edit``: the condition song's own image through ``Experiments.edit``; writes ``<stamp>.mid`` / ``.npy`` with ``_edit<K>`` in the
     stamp and prints the largest relative residual of the last iterate over all steps (and, with ``--edit_roundtrip``, how far the repaint
-    under the song's own condition lands from it)."""
+    under the song's own condition lands from it).  ``score_chords``: ``--score`` - the (source, target) chords ``[B, 32, 36]``; chord_f1 of the
+    source image and of the edited one against each is printed and written to ``<stamp>_score.json`` (the edit took if the edited image
+    scores higher on the target chords than on the source's)."""
     n = min(cond.shape[0], cond_tgt.shape[0], image.shape[0])
     cut = lambda v: None if v is None else v[:n].contiguous()
     sampler, t_idx = make_sampler(model, args, seed, 0)
@@ -843,6 +914,16 @@ def edit_song(model, params, args, image, cond, cond_tgt, cond_mid, cond_mid_tgt
         np.save(stamp + "_roundtrip.npy", rec.cpu().numpy())
     midi.prmat2c_to_midi_file(gen, stamp + ".mid")
     say(f"edited song: piano_roll {tuple(gen.shape)}  onsets>0.5: {int((gen[:, 0] > 0.5).sum())}  -> {stamp}.mid")
+    if score_chords is not None:
+        doc = {"bass_relative": bool(args.score_bass_relative), "segments": n}
+        for img_name, img in (("source", orig), ("edited", gen)):
+            for chd_name, c in zip(("source_chords", "target_chords"), score_chords):
+                doc[f"{img_name}_on_{chd_name}"] = pfscore.roll_stats(img, c[:n], bass_relative=args.score_bass_relative).songs(n).report()[0]
+        f1 = lambda k: repr(doc[k]["chord_f1"])
+        say(f"edit score (chord_f1): source image on source chords {f1('source_on_source_chords')}, on target chords {f1('source_on_target_chords')}; "
+            f"edited image on source chords {f1('edited_on_source_chords')}, on target chords {f1('edited_on_target_chords')}")
+        with open(stamp + "_score.json", "w") as f:
+            json.dump(doc, f, indent=1)
     return 0
 
 
@@ -852,6 +933,7 @@ def main(argv=None):
     if args.dpm and args.ddim:
         raise SystemExit("--dpm and --ddim name two different samplers: give one of them")
     check_edit_args(args)                                  # what the flags alone decide, before anything else
+    check_score_args(args)
     if not torch.cuda.is_available():
         raise SystemExit("inference_sdf needs an AMD GPU (no CPU fallback on this path)")
     rank, world, _ = pfdist.init_from_env()
@@ -886,6 +968,7 @@ def main(argv=None):
     say(f"model_label: {params.model_name}")
     dual = wants_dual_guidance(args, params.cond_type)     # (refusals before any weight is loaded)
     editing = check_edit_args(args, params.cond_type, world)
+    scoring = check_score_args(args, params.cond_type)
     if editing and params.get("concat_blurry", False):
         raise SystemExit("--edit does not cover the concat_blurry variant (its blurred image describes the song being changed)")
     try:
@@ -996,7 +1079,7 @@ def main(argv=None):
     scale = dual_scale(args, model.cond_split) if dual else args.uncond_scale
     if params.cond_type == "pnotree" and rank == 0 and not args.no_pnotree_recon:
         write_pnotree_recon(model, args, cond, say)
-    cond_tgt = cond_mid_tgt = None
+    cond_tgt = cond_mid_tgt = chd_tgt = None
     if editing:
         # the song's own condition is the source; the target is the same condition with the chords replaced
         if chd is None or prmat2c_cond is None or cond_is_dummy:
@@ -1067,11 +1150,23 @@ def main(argv=None):
     else:
         model.ldm.eps_model.set_precision(args.precision)
     if editing:
-        return edit_song(model, params, args, prmat2c_cond, cond, cond_tgt, cond_mid, cond_mid_tgt, scale, seed, say)
+        return edit_song(model, params, args, prmat2c_cond, cond, cond_tgt, cond_mid, cond_mid_tgt, scale, seed, say,
+                         score_chords=(chd, chd_tgt) if scoring else None)
     S, B = args.num_generate, cond.shape[0]
+    S_all = S * args.best_of                        # --best_of N: N candidates per song kept, each a song of its own until the ranking
     say(f"generating {S} song(s) x {B} segment(s) with uncond_scale = {scale} on {world} GPU(s)")
+    if args.best_of > 1:
+        say(f"best of {args.best_of}: {S_all} candidates, the best {S} by {pfscore.RANK_BY[args.rank_by][0]} are kept")
     gen, expmt = generate_songs(model, params, args, cond, cond_mid, orig, mask, seed, rank, world, cond_concat=cond_concat, uncond_scale=scale)
-    gen = pfdist.gather_rows(gen, S, rank, world)   # [S, ...] on every rank (131 KB per image; the only end-of-run exchange)
+    counters = texture = None
+    if scoring:
+        # scored where the songs live, against the chords the run conditioned on (a model without a chord condition, or a run on the dummy
+        # condition, gets the chord-free numbers); 64 bytes of counters per song travel beside the rows
+        chd_score = chd[:B] if chd is not None and not cond_is_dummy and "chord" in params.cond_type.split("+") else None
+        counters, texture = score_songs(gen, chd_score, mask, args, prmat[:B] if params.cond_type == "chord+txt" and prmat is not None else None)
+        counters = pfdist.gather_rows(counters, S_all, rank, world)
+        texture = None if texture is None else pfdist.gather_rows(texture, S_all, rank, world)
+    gen = pfdist.gather_rows(gen, S_all, rank, world)   # [S, ...] on every rank (131 KB per image; the only end-of-run exchange)
     if not bool(torch.isfinite(gen).all()):
         # the note threshold (> 0.5) would turn a NaN into silence: refuse instead.  The one known way to get here is an activation beyond
         # fp16's range in the f16x3 mode on a checkpoint the probe inputs did not exercise (include/pfhip.h pf_x3_element)
@@ -1081,8 +1176,18 @@ def main(argv=None):
     if rank == 0:
         os.makedirs(args.output_dir, exist_ok=True)
         stamps = []
+        extra = "" if args.inpaint_type is None else f"_inp{args.repaint_n}_{args.inpaint_type}"
+        order, cands = list(range(S)), None         # which candidate file i holds: itself, or with --best_of the one ranked i
+        if scoring:
+            cands = pfscore.report_of(counters, gen.shape[1] * gen.shape[-2])
+            for c, t in zip(cands, [] if texture is None else texture.tolist()):
+                c["texture_fit"] = t
+            if args.best_of > 1:
+                key, descending = pfscore.RANK_BY[args.rank_by]
+                order = pfscore.rank([c[key] for c in cands], S, descending)
+            score_stamp = os.path.join(args.output_dir, expmt._stamp(scale, args.autoreg, extra, args.joint_blend if args.joint else None))
+        gen = gen[torch.tensor(order, device=gen.device)] if order != list(range(S_all)) else gen
         for i in range(S):
-            extra = "" if args.inpaint_type is None else f"_inp{args.repaint_n}_{args.inpaint_type}"
             stamp = os.path.join(args.output_dir, expmt._stamp(scale, args.autoreg, extra, args.joint_blend if args.joint else None)
                                  + (f"_{i}" if S > 1 else ""))
             stamps.append(stamp)
@@ -1090,6 +1195,16 @@ def main(argv=None):
             # generated cells on their own track when inpainting (ref:inference_sdf.py:385-389)
             midi.prmat2c_to_midi_file(gen[i], stamp + ".mid", inp_mask=None if args.autoreg else mask)
             say(f"song {i}: piano_roll {tuple(gen[i].shape)}  onsets>0.5: {int((gen[i][:, 0] > 0.5).sum())}  -> {stamp}.mid")
+            if scoring:
+                say(f"song {i} score: {score_line(cands[order[i]])}" + (f"  (candidate {order[i]} of {S_all})" if args.best_of > 1 else ""))
+        if scoring:
+            doc = {"best_of": args.best_of, "rank_by": args.rank_by if args.best_of > 1 else None, "bass_relative": bool(args.score_bass_relative),
+                   "chords": chd_score is not None, "masked": mask is not None, "steps": int(gen.shape[1] * gen.shape[-2]),
+                   "songs": [dict(cands[order[i]], candidate=order[i], file=os.path.basename(stamps[i]) + ".npy") for i in range(S)],
+                   "candidates": cands}
+            with open(score_stamp + "_score.json", "w") as f:
+                json.dump(doc, f, indent=1)
+            say(f"scores -> {score_stamp}_score.json")
         if args.polydis_recon:
             if params.cond_type in ("chord", "chord+txt") and args.inpaint_type is None and chd is not None:
                 n_seg = min(chd.shape[0], prmat.shape[0]) if params.cond_type == "chord+txt" and prmat is not None else chd.shape[0]
