@@ -309,6 +309,42 @@ typedef struct pf_invert_step_args {
 size_t pf_invert_step_workspace_bytes(int rows, size_t row_elems);
 int pf_invert_step(const pf_invert_step_args* a, void* stream);
 
+/* A path between two noises (DESIGN.md 0, row "morph", and 3, "Morph"; not in the reference): `frames` points between the rows of a and
+ * the rows of b, on the great circle through them (mode 0, slerp) or on the chord (mode 1, lerp),
+ *     out[k][r][i] = fl(fl(w0*a[r][i]) + fl(w1*b[r][i]))      two products and one sum, each individually rounded
+ * with one weight pair (w0, w1) per (frame k, row r).  Mode slerp forms them from the row's three sums
+ *     aa = sum a*a, ab = sum a*b, bb = sum b*b                products exact in float64, sums in float64
+ *     c = ab / sqrt(aa*bb), theta = acos(c), w0 = sin((1 - t[k])*theta) / sin(theta), w1 = sin(t[k]*theta) / sin(theta)
+ * in float64 on the device, each weight rounded to float once; mode lerp takes (1 - t[k], t[k]) rounded to float.  A slerp row with
+ * aa == 0, bb == 0 or 1 - |c| < 2^-20 takes the lerp weights: parallel rows, where slerp and lerp agree to O(theta^2) and sin(theta) has
+ * no digits left, and antiparallel rows, where no great circle is defined.  A frame with t[k] == 0 is a copy of a and one with
+ * t[k] == 1 a copy of b (a select, not arithmetic: bit-identical, -0.0f included).
+ *   Mode slerp is two launches without a host sync.  Reduce: a workgroup owns one PF_MSE_CHUNK of one row, adds its three sums in the
+ *   lane / butterfly / wave order of pf_invert_step's residual and writes one partial triple into `workspace`
+ *   (pf_slerp_rows_workspace_bytes(rows, row_elems) bytes, 8-byte aligned); no atomics.  Combine: a workgroup owns one (row, chunk), adds
+ *   its row's triples in chunk order - every workgroup of a row forms the same three doubles -, forms the weights and writes its chunk
+ *   of ALL frames: a and b are read once, (2 + frames) * n * 4 bytes move.  The chunk-0 workgroup of a row also writes stats[row] and
+ *   weights[:, row].  Mode lerp is the combine launch alone: no workspace, stats is not written.
+ *   A row's outputs depend on that row alone: bit-identical from call to call and however the rows are split into calls.  Tensors that
+ *   are all 16-byte aligned with row_elems % 4 == 0 are moved as 16-byte vectors, anything else element by element; the same operations,
+ *   so the same bits.
+ * Refused before any launch: null a, b, out or t; rows <= 0 or row_elems == 0; frames outside [1, PF_SLERP_MAX_FRAMES]; a t[k] that is
+ * NaN or outside [0, 1]; another mode; out overlapping a or b, partially too; mode slerp without workspace, with one too small or not
+ * 8-byte aligned; stats not 8-byte aligned; more workgroups than one launch holds. */
+#define PF_SLERP_MAX_FRAMES 64
+typedef struct pf_slerp_args {
+  const float *a, *b;                 /* [rows][row_elems] the two endpoints */
+  const double* t;                    /* HOST array of `frames` fractions in [0, 1], copied at the call */
+  float* out;                         /* [frames][rows][row_elems]; may not overlap a or b */
+  double* stats;                      /* [rows][3] device doubles: sum a*a, sum a*b, sum b*b; may be NULL; not written in mode lerp */
+  float* weights;                     /* [frames][rows][2] device floats: the (w0, w1) actually used; may be NULL */
+  void* workspace; size_t workspace_bytes;      /* mode slerp only */
+  int32_t mode;                       /* 0 slerp, 1 lerp */
+  int32_t frames, rows; size_t row_elems;
+} pf_slerp_args;
+size_t pf_slerp_rows_workspace_bytes(int rows, size_t row_elems);
+int pf_slerp_rows(const pf_slerp_args* a, void* stream);
+
 /* RePaint re-noise between inner repeats (sampler_sdf.py:337-341; keeps the reference's beta-not-sqrt quirk):
  *   x_t = a*x + b*noise */
 int pf_axpby(const float* x, const float* noise, float a, float b, float* out, size_t n, void* stream);

@@ -94,6 +94,12 @@ class InvertStepArgs(C.Structure):
                    ("rows", C.c_int32), ("row_elems", C.c_size_t)])
 
 
+class SlerpArgs(C.Structure):
+    """pf_slerp_args (include/pfhip.h); filled by ``_steps.slerp_rows`` only."""
+    _fields_ = ([(n, C.c_void_p) for n in ("a", "b", "t", "out", "stats", "weights", "workspace")]
+                + [("workspace_bytes", C.c_size_t), ("mode", C.c_int32), ("frames", C.c_int32), ("rows", C.c_int32), ("row_elems", C.c_size_t)])
+
+
 class WindowMergeArgs(C.Structure):
     """pf_window_merge_args (include/pfhip.h); filled by ``_steps.window_merge`` only."""
     _fields_ = ([("eps", C.c_void_p), ("row_weight", C.c_void_p), ("groups", C.c_int), ("s1", C.c_float), ("s2", C.c_float)]
@@ -134,6 +140,8 @@ ROLL_NCOUNT = 16
 
 FEEDBACK = {"row": 0, "batch": 1}   # PF_FEEDBACK_ROW / PF_FEEDBACK_BATCH
 MSE_CHUNK = 2048           # PF_MSE_CHUNK: elements of a row one workgroup of pf_mse_rows reduces
+SLERP_MAX_FRAMES = 64      # PF_SLERP_MAX_FRAMES: frames one pf_slerp_rows call writes
+SLERP_MODES = {"slerp": 0, "lerp": 1}
 
 
 class UNetPrepared(C.Structure):
@@ -257,6 +265,8 @@ SIGNATURES = {
     "pf_dpm_step": (C.c_int, [C.POINTER(DpmStepArgs), C.c_void_p]),
     "pf_invert_step_workspace_bytes": (C.c_size_t, [C.c_int, C.c_size_t]),
     "pf_invert_step": (C.c_int, [C.POINTER(InvertStepArgs), C.c_void_p]),
+    "pf_slerp_rows_workspace_bytes": (C.c_size_t, [C.c_int, C.c_size_t]),
+    "pf_slerp_rows": (C.c_int, [C.POINTER(SlerpArgs), C.c_void_p]),
     "pf_step_advance": (C.c_int, [C.c_void_p, C.c_int64, C.c_int, C.c_void_p]),
     "pf_randn": (C.c_int, [C.c_void_p, C.c_size_t, C.c_uint64, C.c_uint64, C.c_uint64, C.c_void_p]),
     "pf_clock_probe": (C.c_int, [C.c_void_p, C.c_void_p]),

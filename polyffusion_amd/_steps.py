@@ -1,5 +1,6 @@
 """The sampler's elementwise launches: noise, ``a*x + b*y`` and the three reverse-step updates (``pf_randn`` / ``pf_randn_dev``, ``pf_axpby``,
 ``pf_ddpm_step``, ``pf_ddim_step``, ``pf_dpm_step`` of include/pfhip.h), the upward iterate of exact DDIM inversion (``pf_invert_step``),
+the frames between two tensors of a morph (``pf_slerp_rows``),
 the two launches around the denoiser of a window plan
 (``pf_window_split``, ``pf_window_merge``), and the two launches of the training objective (``pf_qsample_rows``,
 ``pf_mse_rows``) with the loss evaluation both diffusion mirrors share (``diffusion_loss_rows``).  The only place that fills
@@ -114,6 +115,47 @@ def invert_step(lib, y, eps, out, *, coef=None, table=None, state=None, x_iter=N
         a.iters, a.k, a.slot = int(iters), int(k), int(slot)
     _lib.check(lib.pf_invert_step(C.byref(a), _lib.current_stream()), "pf_invert_step", lib)
     return out
+
+
+def slerp_workspace(lib, rows: int, row_elems: int, device) -> torch.Tensor:
+    """The float64 workspace mode slerp of ``slerp_rows`` needs for ``rows`` rows of ``row_elems`` floats."""
+    nb = int(lib.pf_slerp_rows_workspace_bytes(int(rows), int(row_elems)))
+    return torch.empty(max(nb, 8) // 8, dtype=torch.float64, device=device)
+
+
+def slerp_rows(lib, a, b, fracs, *, mode: str = "slerp", out=None, want_stats: bool = True, workspace=None):
+    """``len(fracs)`` points between the rows of ``a`` and ``b`` (``pf_slerp_rows``): ``out[k] = w0[k]*a + w1[k]*b`` with one weight pair per
+    (frame, row), rows = ``a.shape[0]`` - on the great circle through the two rows (``mode="slerp"``: a reduce and a combine launch) or on
+    the chord (``"lerp"``: the combine launch alone).  ``fracs``: host floats in [0, 1]; 0 and 1 give copies of ``a`` and ``b``.  ``a`` and
+    ``b`` are made contiguous float32.  Returns ``(out [K, rows, ...], stats, weights)``: ``stats`` float64 ``[rows, 3]`` (the sums a*a, a*b,
+    b*b; slerp only) and ``weights`` float32 ``[K, rows, 2]`` on the device, both ``None`` without ``want_stats``.  No host sync."""
+    a, b = a.contiguous().float(), b.contiguous().float()
+    if a.shape != b.shape or a.dim() < 1:
+        raise ValueError(f"slerp_rows: endpoints of shapes {tuple(a.shape)} and {tuple(b.shape)}")
+    if mode not in _lib.SLERP_MODES:
+        raise ValueError(f"slerp_rows: mode {mode!r}, expected one of {tuple(_lib.SLERP_MODES)}")
+    fr = [float(v) for v in fracs]
+    K, rows = len(fr), int(a.shape[0])
+    row_elems = a.numel() // max(1, rows)
+    if out is None:
+        out = torch.empty((K,) + tuple(a.shape), dtype=torch.float32, device=a.device)
+    elif out.dtype != torch.float32 or not out.is_contiguous() or out.numel() != K * a.numel():
+        raise ValueError(f"slerp_rows: out must be contiguous float32 of {K} x {tuple(a.shape)}")
+    stats = weights = None
+    if want_stats:
+        stats = torch.zeros(rows, 3, dtype=torch.float64, device=a.device) if mode == "slerp" else None
+        weights = torch.empty(K, rows, 2, dtype=torch.float32, device=a.device)
+    args = _lib.SlerpArgs()
+    tarr = (C.c_double * max(1, K))(*fr)                            # copied by the library during the call
+    args.a, args.b, args.t, args.out = a.data_ptr(), b.data_ptr(), C.addressof(tarr), out.data_ptr()
+    args.stats, args.weights = _lib.ptr(stats), _lib.ptr(weights)
+    args.mode, args.frames, args.rows, args.row_elems = _lib.SLERP_MODES[mode], K, rows, row_elems
+    if mode == "slerp":
+        if workspace is None and rows > 0:
+            workspace = slerp_workspace(lib, rows, row_elems, a.device)
+        args.workspace, args.workspace_bytes = _lib.ptr(workspace), 0 if workspace is None else workspace.numel() * workspace.element_size()
+    _lib.check(lib.pf_slerp_rows(C.byref(args), _lib.current_stream()), "pf_slerp_rows", lib)
+    return out, stats, weights
 
 
 def window_split(lib, canvas, n_windows: int, stride: int, win_h: int) -> torch.Tensor:

@@ -153,6 +153,11 @@ int pf_invert_step(const pf_invert_step_args* a, void* stream) {
   PF_REQUIRE(a, "pf_invert_step: null arguments");
   return launch_invert_step(*a, (hipStream_t)stream);
 }
+size_t pf_slerp_rows_workspace_bytes(int rows, size_t row_elems) { return slerp_rows_workspace_bytes(rows, row_elems); }
+int pf_slerp_rows(const pf_slerp_args* a, void* stream) {
+  PF_REQUIRE(a, "slerp_rows: null arguments");
+  return launch_slerp_rows(*a, (hipStream_t)stream);
+}
 int pf_step_advance(pf_step_state* st, int64_t delta, int draws_used, void* stream) { return launch_step_advance(st, delta, draws_used, (hipStream_t)stream); }
 int pf_axpby(const float* x, const float* noise, float a, float b, float* out, size_t n, void* stream) { return launch_axpby(x, noise, a, b, out, n, (hipStream_t)stream); }
 int pf_randn(float* out, size_t n, uint64_t seed, uint64_t stream_id, uint64_t elem_offset, void* stream) {

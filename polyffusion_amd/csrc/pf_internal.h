@@ -122,6 +122,9 @@ int launch_step_advance(pf_step_state* st, int64_t delta, int draws_used, hipStr
 // exact DDIM inversion: one fixed-point iterate of one upward step, optionally with the per-row residual sums (a second, in-order launch)
 size_t invert_step_workspace_bytes(int rows, size_t row_elems);
 int launch_invert_step(const pf_invert_step_args& a, hipStream_t s);
+// a path between two noises: per-row slerp (a reduce launch + a combine launch) or lerp (the combine launch alone) of `frames` points
+size_t slerp_rows_workspace_bytes(int rows, size_t row_elems);
+int launch_slerp_rows(const pf_slerp_args& a, hipStream_t s);
 // the training objective, forward only (loss.hip): forward noising with one t per sample, and the per-sample squared error in float64
 int launch_qsample_rows(const pf_qsample_rows_args& a, hipStream_t s);
 size_t mse_rows_workspace_bytes(int rows, size_t row_elems);

@@ -5,6 +5,7 @@
 //   fused sampler updates (sampler_sdf.py:80-171,307-341; sampler_ddim.py:220-272,355-359),
 //   and the update of the sampler the reference does not have, DPM-Solver++(2M) (pf_dpm_step),
 //   one fixed-point iterate of exact DDIM inversion with its fused residual (pf_invert_step) and the upward step state (pf_step_advance),
+//   the frames of a path between two noises, per-row slerp as a reduce and a combine launch (pf_slerp_rows),
 //   the canvas <-> window-batch gathers of joint overlapping-window sampling (pf_window_split, pf_window_merge),
 //   note durations of a generated roll (pf_prmat2c_durations) and its integer statistics against the run's chords (pf_roll_stats),
 //   counter-based Gaussian noise, GRU gate update and the texture-encoder front end
@@ -1196,6 +1197,169 @@ int launch_invert_step(const pf_invert_step_args& a, hipStream_t s) {
   PF_CHECK_HIP(hipGetLastError());
   hipLaunchKernelGGL(invert_resid_finish_kernel, dim3((unsigned)cdiv(a.rows, 64)), dim3(64), 0, s, partial, a.resid, a.rows, (unsigned)chunks, a.state, a.iters,
                      a.k, (long long)a.slot, (long long)a.n_slots);
+  PF_CHECK_HIP(hipGetLastError());
+  return PF_OK;
+}
+// ---- a path between two noises (include/pfhip.h: pf_slerp_rows; DESIGN.md 3, "Morph"): per row, `frames` points on the great circle from
+// a to b, out[k] = w0[k]*a + w1[k]*b.  Two launches in the layout of invert_step_resid_kernel, a workgroup = (row, chunk of PF_MSE_CHUNK):
+//   reduce   the row's sum a*a, a*b, b*b - the products exact in float64, per lane in element order, the lanes of a wave by a butterfly,
+//            the four waves in wave order; one partial triple per workgroup, no atomics
+//   combine  EVERY workgroup of a row adds the row's triples in chunk order (the same three doubles in each of them), lane k < frames forms
+//            frame k's two weights in float64 and rounds each to float once; then a and b are read once and all frames written.
+// Mode lerp runs the combine launch alone with (1 - t, t).  VEC and the element-by-element form do the same operations: the same bits.
+struct slerp_fracs { double t[PF_SLERP_MAX_FRAMES]; };      // by value in the launch: the host array is copied at the call
+template <bool VEC>
+__global__ __launch_bounds__(kInvThreads) void slerp_reduce_kernel(const float* __restrict__ a, const float* __restrict__ b,
+                                                                  double* __restrict__ partial, size_t row_elems, unsigned chunks) {
+  __shared__ double wave_sum[kInvThreads / 64][3];
+  const unsigned row = blockIdx.x / chunks, chunk = blockIdx.x - row * chunks;
+  const size_t base = (size_t)row * row_elems;
+  double acc[3] = {0.0, 0.0, 0.0};
+#pragma unroll
+  for (int k = 0; k < kInvGroups; ++k) {
+    const size_t e = (size_t)chunk * PF_MSE_CHUNK + 4 * ((size_t)k * kInvThreads + threadIdx.x);
+    if (e < row_elems) {
+      const f32x4 av = inv_load4<VEC>(a + base, e, row_elems), bv = inv_load4<VEC>(b + base, e, row_elems);
+#pragma unroll
+      for (int j = 0; j < 4; ++j)
+        if (VEC || e + j < row_elems) {
+          const double p = (double)av[j], q = (double)bv[j];
+          acc[0] += p * p;
+          acc[1] += p * q;
+          acc[2] += q * q;
+        }
+    }
+  }
+#pragma unroll
+  for (int m = 32; m >= 1; m >>= 1) {
+#pragma unroll
+    for (int c = 0; c < 3; ++c) acc[c] += __shfl_xor(acc[c], m, 64);
+  }
+  if ((threadIdx.x & 63) == 0) {
+#pragma unroll
+    for (int c = 0; c < 3; ++c) wave_sum[threadIdx.x >> 6][c] = acc[c];
+  }
+  __syncthreads();
+  if (threadIdx.x < 3) {
+    double s = wave_sum[0][threadIdx.x];
+#pragma unroll
+    for (int w = 1; w < kInvThreads / 64; ++w) s += wave_sum[w][threadIdx.x];
+    partial[((size_t)row * chunks + chunk) * 3 + threadIdx.x] = s;
+  }
+}
+// Lerp weights (1 - t, t) stand in for the slerp weights when aa == 0, bb == 0 or 1 - |c| < 2^-20: parallel rows, where the two agree to
+// O(theta^2) and sin(theta) has lost its digits, and antiparallel rows, where the great circle is not defined (the path then goes
+// through the origin).  A frame at t == 0 / t == 1 is a COPY of a / b, by a select: bit-identical, a negative zero included.
+template <bool VEC>
+__global__ __launch_bounds__(kInvThreads) void slerp_combine_kernel(const float* __restrict__ a, const float* __restrict__ b, slerp_fracs fr,
+                                                                   int frames, int mode, const double* __restrict__ partial,
+                                                                   float* __restrict__ out, double* __restrict__ stats,
+                                                                   float* __restrict__ weights, int rows, size_t row_elems, unsigned chunks) {
+  __shared__ float w_sh[PF_SLERP_MAX_FRAMES][2];
+  __shared__ int sel_sh[PF_SLERP_MAX_FRAMES];
+  const unsigned row = blockIdx.x / chunks, chunk = blockIdx.x - row * chunks;
+  if ((int)threadIdx.x < frames) {
+    const double t = fr.t[threadIdx.x];
+    double w0 = 1.0 - t, w1 = t;
+    if (mode == 0) {
+      double aa = 0.0, ab = 0.0, bb = 0.0;
+      for (unsigned c = 0; c < chunks; ++c) {
+        const double* p = partial + ((size_t)row * chunks + c) * 3;
+        aa += p[0];
+        ab += p[1];
+        bb += p[2];
+      }
+      const double c = ab / sqrt(aa * bb);
+      if (!(aa == 0.0 || bb == 0.0 || 1.0 - fabs(c) < 0x1p-20)) {
+        const double theta = acos(c), sn = sin(theta);
+        w0 = sin((1.0 - t) * theta) / sn;
+        w1 = sin(t * theta) / sn;
+      }
+      if (chunk == 0 && threadIdx.x == 0 && stats) {
+        stats[(size_t)row * 3 + 0] = aa;
+        stats[(size_t)row * 3 + 1] = ab;
+        stats[(size_t)row * 3 + 2] = bb;
+      }
+    }
+    const float f0 = (float)w0, f1 = (float)w1;
+    w_sh[threadIdx.x][0] = f0;
+    w_sh[threadIdx.x][1] = f1;
+    sel_sh[threadIdx.x] = t == 0.0 ? 1 : t == 1.0 ? 2 : 0;
+    if (chunk == 0 && weights) {
+      weights[((size_t)threadIdx.x * rows + row) * 2 + 0] = f0;
+      weights[((size_t)threadIdx.x * rows + row) * 2 + 1] = f1;
+    }
+  }
+  __syncthreads();
+  const size_t base = (size_t)row * row_elems, frame_elems = (size_t)rows * row_elems;
+#pragma unroll
+  for (int g = 0; g < kInvGroups; ++g) {
+    const size_t e = (size_t)chunk * PF_MSE_CHUNK + 4 * ((size_t)g * kInvThreads + threadIdx.x);
+    if (e < row_elems) {
+      const f32x4 av = inv_load4<VEC>(a + base, e, row_elems), bv = inv_load4<VEC>(b + base, e, row_elems);
+      for (int k = 0; k < frames; ++k) {
+        const float w0 = w_sh[k][0], w1 = w_sh[k][1];
+        const int sel = sel_sh[k];
+        f32x4 o;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          const float v = add_rn(mul_rn(w0, av[j]), mul_rn(w1, bv[j]));
+          o[j] = sel == 1 ? av[j] : sel == 2 ? bv[j] : v;
+        }
+        float* dst = out + (size_t)k * frame_elems + base + e;
+        if (VEC) {
+          *reinterpret_cast<f32x4*>(dst) = o;
+        } else {
+#pragma unroll
+          for (int j = 0; j < 4; ++j)
+            if (e + j < row_elems) dst[j] = o[j];
+        }
+      }
+    }
+  }
+}
+size_t slerp_rows_workspace_bytes(int rows, size_t row_elems) {
+  if (rows <= 0 || row_elems == 0) return 0;
+  return (size_t)rows * ((row_elems + PF_MSE_CHUNK - 1) / PF_MSE_CHUNK) * 3 * sizeof(double);
+}
+int launch_slerp_rows(const pf_slerp_args& a, hipStream_t s) {
+  PF_REQUIRE(a.a && a.b && a.out && a.t, "slerp_rows: null a, b, out or t");
+  PF_REQUIRE(a.rows > 0 && a.row_elems > 0, "slerp_rows: %d rows of %zu elements", a.rows, a.row_elems);
+  PF_REQUIRE(a.frames >= 1 && a.frames <= PF_SLERP_MAX_FRAMES, "slerp_rows: %d frames outside [1, %d]", a.frames, PF_SLERP_MAX_FRAMES);
+  PF_REQUIRE(a.mode == 0 || a.mode == 1, "slerp_rows: mode %d, expected 0 (slerp) or 1 (lerp)", a.mode);
+  slerp_fracs fr = {};
+  for (int k = 0; k < a.frames; ++k) {
+    PF_REQUIRE(a.t[k] >= 0.0 && a.t[k] <= 1.0, "slerp_rows: fraction t[%d] = %g outside [0, 1]", k, a.t[k]);     // (a NaN fails both)
+    fr.t[k] = a.t[k];
+  }
+  const size_t n = (size_t)a.rows * a.row_elems, bytes = n * sizeof(float);
+  PF_REQUIRE(!ranges_overlap(a.out, bytes * a.frames, a.a, bytes), "slerp_rows: out overlaps a");
+  PF_REQUIRE(!ranges_overlap(a.out, bytes * a.frames, a.b, bytes), "slerp_rows: out overlaps b");
+  PF_REQUIRE(((uintptr_t)a.stats & 7) == 0, "slerp_rows: stats must be 8-byte aligned");
+  const size_t chunks = (a.row_elems + PF_MSE_CHUNK - 1) / PF_MSE_CHUNK, need = slerp_rows_workspace_bytes(a.rows, a.row_elems);
+  PF_REQUIRE(chunks * (size_t)a.rows < (1ull << 31), "slerp_rows: %d rows of %zu elements are more workgroups than one launch holds", a.rows, a.row_elems);
+  if (a.mode == 0) {
+    PF_REQUIRE(a.workspace, "slerp_rows: mode slerp without a workspace (pf_slerp_rows_workspace_bytes)");
+    PF_REQUIRE(a.workspace_bytes >= need, "slerp_rows: workspace of %zu bytes required, got %zu", need, a.workspace_bytes);
+    PF_REQUIRE(((uintptr_t)a.workspace & 7) == 0, "slerp_rows: workspace must be 8-byte aligned");
+  }
+  const uintptr_t bits = (uintptr_t)a.a | (uintptr_t)a.b | (uintptr_t)a.out;
+  const bool vec = (bits & 15) == 0 && a.row_elems % 4 == 0;
+  const dim3 grid((unsigned)(chunks * a.rows)), block(kInvThreads);
+  double* partial = a.mode == 0 ? reinterpret_cast<double*>(a.workspace) : nullptr;
+  if (a.mode == 0) {
+    if (vec)
+      hipLaunchKernelGGL(slerp_reduce_kernel<true>, grid, block, 0, s, a.a, a.b, partial, a.row_elems, (unsigned)chunks);
+    else
+      hipLaunchKernelGGL(slerp_reduce_kernel<false>, grid, block, 0, s, a.a, a.b, partial, a.row_elems, (unsigned)chunks);
+    PF_CHECK_HIP(hipGetLastError());
+  }
+  if (vec)
+    hipLaunchKernelGGL(slerp_combine_kernel<true>, grid, block, 0, s, a.a, a.b, fr, a.frames, a.mode, partial, a.out, a.stats, a.weights, a.rows,
+                       a.row_elems, (unsigned)chunks);
+  else
+    hipLaunchKernelGGL(slerp_combine_kernel<false>, grid, block, 0, s, a.a, a.b, fr, a.frames, a.mode, partial, a.out, a.stats, a.weights, a.rows,
+                       a.row_elems, (unsigned)chunks);
   PF_CHECK_HIP(hipGetLastError());
   return PF_OK;
 }

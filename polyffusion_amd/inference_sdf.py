@@ -14,7 +14,8 @@ segmented by ``polyffusion_amd.datasample``), from ``--cond_npz`` (arrays
 seeded synthetic generator (``--synthetic``); the result is written as ``.mid`` (polyffusion_amd.midi) and ``.npy`` ([B,2,128,128] piano
 roll, or [2B,2,64,128] half-segments for ``--autoreg``; ``--joint``, an extension, denoises the 2B-1 half-overlapping windows of a song
 in one reverse loop and writes [B,2,128,128]; ``--edit``, an extension, changes the condition song itself by exact DDIM inversion -
-``Experiments.edit`` - instead of generating from noise).  ``--synthetic_weights`` replaces the
+``Experiments.edit`` - instead of generating from noise; ``--morph``, an extension, writes the frames of a path between the condition
+song and a second one - ``Experiments.morph`` - as [K,B,2,128,128]).  ``--synthetic_weights`` replaces the
 checkpoint by the deterministic weight generator (no trained weights ship with the reference).
 """
 from __future__ import annotations
@@ -33,7 +34,7 @@ from . import _lib, datasample, midi, synth
 from . import score as pfscore
 from .model_sdf import ChordEncoder, Polyffusion_SDF, TextureEncoder
 from .params import Params, find_params, load_params, preset
-from .sampler import GUIDANCE_ORDERS, DDIMSampler, DiffusionSampler, DPMSolverSampler, DualScale, SDFSampler
+from .sampler import GUIDANCE_ORDERS, MORPH_CONDS, MORPH_EASES, DDIMSampler, DiffusionSampler, DPMSolverSampler, DualScale, SDFSampler
 from .unet import LatentDiffusion, UNetModel
 
 
@@ -299,6 +300,50 @@ class Experiments:
         finally:
             s.windows = before
 
+    @torch.no_grad()
+    def morph(self, orig_a: Optional[torch.Tensor], cond_a: torch.Tensor, orig_b: Optional[torch.Tensor], cond_b: torch.Tensor,
+              frames: int = 5, uncond_scale=1.0, *, iters: int = 3, depth: Optional[int] = None, ease: str = "linear", cond_how: str = "lerp",
+              joint: bool = False, blend: str = "mean", cond_mid_a: Optional[torch.Tensor] = None, cond_mid_b: Optional[torch.Tensor] = None):
+        """``frames`` songs on a path from song A to song B (``DDIMSampler.morph``; not in the reference): ``orig_a`` / ``orig_b`` ``[B, C, H,
+        W]`` are walked up the eta = 0 ODE under their own conditions to index ``depth`` (default: the run's start index), the noises
+        interpolated on the sphere and the conditions as ``cond_how`` says, every frame painted back down.  Without the two images
+        (``None``) the end noises are two fresh draws (``morph_from_noise``: DDIM with eta 0 or DPM-Solver++).  ``joint``: each song as
+        ONE canvas with the window plan of ``predict_joint`` (``cond_mid_*``: the conditions of the half-shifted windows).  Returns
+        ``[K, B, C, H, W]``; the slerp tables and the inversion's residuals stay in ``self.sampler.last_morph``."""
+        s, p = self.sampler, self.params
+        if (orig_a is None) != (orig_b is None):
+            raise ValueError("morph: both songs' images, or neither (a path between two noise draws)")
+        if orig_a is not None and not isinstance(s, DDIMSampler):
+            raise ValueError("morph: exact inversion exists for the DDIM sampler with eta = 0 only")
+        depth = self.t_idx if depth is None else int(depth)
+        B, H, dev = cond_a.shape[0], p.img_h, cond_a.device
+        kw = dict(ease=ease, cond_how=cond_how, uncond_scale=uncond_scale)
+        if not joint:
+            uc = -torch.ones([B, 1, p.d_cond], device=dev)
+            if orig_a is None:
+                return s.morph_from_noise([B, p.out_channels, H, p.img_w], cond_a, cond_b, frames, t_start=depth, uncond_cond=uc, **kw)
+            return s.morph(orig_a.contiguous().float(), cond_a, orig_b.contiguous().float(), cond_b, frames, t_end=depth, iters=iters,
+                           uncond_cond=uc, **kw)
+        from .sampler import WindowPlan
+        plan = WindowPlan(2 * B - 1, H // 2, H, blend)
+        if B > 1 and (cond_mid_a is None or cond_mid_b is None):
+            raise ValueError("morph: a joint morph of more than one segment needs cond_mid_a and cond_mid_b, the conditions of the half-shifted windows")
+        windows = lambda c, m: torch.stack([c[w // 2] if w % 2 == 0 else m[(w - 1) // 2] for w in range(plan.n_windows)]).contiguous()
+        canvas = lambda v: v.contiguous().float().permute(1, 0, 2, 3).reshape(1, v.shape[1], B * H, v.shape[3]).contiguous()
+        uc = -torch.ones([plan.n_windows, 1, p.d_cond], device=dev)
+        before = getattr(s, "windows", None)
+        s.windows = plan
+        try:
+            ca, cb = windows(cond_a, cond_mid_a), windows(cond_b, cond_mid_b)
+            if orig_a is None:
+                out = s.morph_from_noise([1, p.out_channels, plan.canvas_h, p.img_w], ca, cb, frames, t_start=depth, uncond_cond=uc, **kw)
+            else:
+                out = s.morph(canvas(orig_a), ca, canvas(orig_b), cb, frames, t_end=depth, iters=iters, uncond_cond=uc, **kw)
+        finally:
+            s.windows = before
+        K = out.shape[0]                                                     # [K, 1, C, B * H, W] -> [K, B, C, H, W]
+        return out.reshape(K, out.shape[2], B, H, out.shape[4]).permute(0, 2, 1, 3, 4).contiguous()
+
     def _stamp(self, uncond_scale, autoreg, extra="", joint=None):
         """``joint``: ``None``, or the blend of a joint run (``mean`` is written as plain ``joint``)."""
         how = ",autoreg" if autoreg else "" if not joint else ",joint" if joint == "mean" else f",joint-{joint}"
@@ -510,6 +555,23 @@ def make_parser() -> ArgumentParser:
     p.add_argument("--edit_chord_shift", type=int, default=None, metavar="N", help="target chords: the song's own with each of the three "
                    "12-wide blocks (root, chroma, bass) rolled by N semitones")
     p.add_argument("--edit_chords_from_midi", default=None, metavar="FILE", help="target chords: those of another midi file")
+    # extension: a path between two songs - invert both, interpolate their noises on the sphere and their conditions, sample every point
+    p.add_argument("--morph", action="store_true", help="extension: write --morph_frames songs on a path from the condition song (A) to a "
+                   "second one (B: --morph_to_midi, --morph_to_song_index or --morph_to_npz): both are inverted up the eta = 0 DDIM ODE under "
+                   "their own conditions, the noises interpolated spherically, the encoded conditions as --morph_cond says, every frame "
+                   "sampled back down.  Needs --ddim with --ddim_eta 0.  With --synthetic (no song images) the path runs between two "
+                   "fresh noise draws under two synthetic conditions; that also works with --dpm")
+    p.add_argument("--morph_frames", type=int, default=5, metavar="K", help="frames of the path, both songs included: 2..64, default 5")
+    p.add_argument("--morph_ease", choices=list(MORPH_EASES), default="linear", help="where the frames sit between A and B: evenly (linear, "
+                   "default) or slow at both ends (cosine)")
+    p.add_argument("--morph_iters", type=int, default=3, metavar="N", help="fixed-point iterates per upward step of the two inversions, default: 3")
+    p.add_argument("--morph_depth", type=int, default=None, metavar="D", help="grid index to invert to and sample from, default: the full range")
+    p.add_argument("--morph_cond", choices=list(MORPH_CONDS), default="lerp", help="the frames' conditions: the two encoded conditions "
+                   "interpolated linearly (lerp, default) or A's up to the middle and B's from there (switch)")
+    p.add_argument("--morph_to_midi", default=None, metavar="FILE", help="song B: a midi file")
+    p.add_argument("--morph_to_song_index", type=int, default=None, metavar="N", help="song B: index into the validation list of --from_dataset")
+    p.add_argument("--morph_to_npz", default=None, metavar="FILE", help="song B: an npz with chord [B,32,36] and prmat2c [B,2,128,128] "
+                   "(and prmat [B,128,128] for chord+txt models; default: song A's texture)")
     p.add_argument("--repaint_n", type=int, default=1, help="n sampling steps in RePaint")
     p.add_argument("--length", type=int, default=0, help="the generated length (in 8-bars)")
     p.add_argument("--show_image", action="store_true", help="(ignored: no image writer on this path)")
@@ -641,6 +703,71 @@ def check_edit_args(args, cond_type: Optional[str] = None, world: int = 1) -> bo
             has_image = "prmat2c" in z
     if not has_image:
         raise SystemExit("--edit needs the song to edit: --from_midi, --from_dataset, --from_song_npz, or prmat2c in --cond_npz")
+    return True
+
+
+MORPH_TO = ("morph_to_midi", "morph_to_song_index", "morph_to_npz")
+
+
+def check_morph_args(args, cond_type: Optional[str] = None, world: int = 1) -> bool:
+    """Whether the command line asks for ``--morph``; every misuse is a ``SystemExit`` with a message, raised before any weight is loaded.
+    ``cond_type`` / ``world``: checked once they are known (``None`` / 1: the flags alone)."""
+    dflt = make_parser().get_default
+    if not getattr(args, "morph", False):
+        given = [f"--{k}" for k in ("morph_frames", "morph_ease", "morph_iters", "morph_depth", "morph_cond") + MORPH_TO
+                 if getattr(args, k, dflt(k)) != dflt(k)]
+        if given:
+            raise SystemExit(f"{', '.join(given)}: these belong to --morph, which was not given")
+        return False
+    dpm = getattr(args, "dpm", False)
+    if not args.ddim and not dpm:
+        raise SystemExit("--morph needs --ddim (eta 0) or, between two synthetic conditions, --dpm: the frames of a loop that draws noise are not a path")
+    if args.ddim and args.ddim_eta != 0.0:
+        raise SystemExit(f"--morph needs --ddim_eta 0 (got {args.ddim_eta}): the frames of a loop that draws noise are not a path")
+    if args.autoreg:
+        raise SystemExit("--morph with --autoreg: the autoregressive schedule inpaints from noise; use --joint to morph songs as canvases")
+    if args.inpaint_type is not None:
+        raise SystemExit("--morph with --inpaint_type: a morph has no known region, choose one")
+    if getattr(args, "edit", False):
+        raise SystemExit("--morph with --edit: two different things to do with a song's inversion, choose one")
+    if getattr(args, "best_of", 1) > 1:
+        raise SystemExit("--best_of with --morph: --morph is deterministic, every candidate would be the same path")
+    if args.num_generate > 1:
+        raise SystemExit("--morph is deterministic: --num_generate > 1 would write the same path again")
+    if world > 1:
+        raise SystemExit("--morph runs on one rank (one path, one batch of frames)")
+    if not 2 <= args.morph_frames <= _lib.SLERP_MAX_FRAMES:
+        raise SystemExit(f"--morph_frames {args.morph_frames} outside [2, {_lib.SLERP_MAX_FRAMES}]")
+    if args.morph_iters < 1:
+        raise SystemExit(f"--morph_iters {args.morph_iters}: at least one iterate per step")
+    steps = args.dpm_steps if dpm else args.ddim_steps
+    if args.morph_depth is not None and not 0 <= args.morph_depth < steps:
+        raise SystemExit(f"--morph_depth {args.morph_depth} outside [0, {steps - 1}], the sampler's steps")
+    to = [f"--{k}" for k in MORPH_TO if getattr(args, k) is not None]
+    has_image = (args.uncond_scale != 0.0 and (args.from_midi is not None or args.from_dataset is not None)) or args.from_song_npz is not None
+    from_npz = not has_image and args.cond_npz is not None     # (main reads --cond_npz only when none of the song sources above is taken)
+    if from_npz:
+        with np.load(args.cond_npz) as z:
+            has_image = "prmat2c" in z
+    if not has_image and not from_npz:
+        # no song at all: the path runs between two fresh noise draws under two synthetic conditions
+        if not args.synthetic:
+            raise SystemExit("--morph needs song A: --from_midi, --from_dataset, --from_song_npz or --cond_npz (or --synthetic for a path "
+                             "between two synthetic conditions)")
+        if to:
+            raise SystemExit(f"{', '.join(to)} with --synthetic: --synthetic morphs between two synthetic conditions, song B is a second draw")
+        return True
+    if len(to) != 1:
+        raise SystemExit(f"--morph needs song B from exactly one of --morph_to_midi, --morph_to_song_index, --morph_to_npz (got {len(to)})")
+    if args.morph_to_song_index is not None and args.from_dataset is None:
+        raise SystemExit("--morph_to_song_index names a song of --from_dataset, which was not given")
+    if not has_image:
+        raise SystemExit("--morph needs song A's image: prmat2c in --cond_npz (or --from_midi, --from_dataset, --from_song_npz)")
+    if dpm:
+        raise SystemExit("--morph with --dpm and a song image: the 2M step has no inverse to walk; use --ddim (or --synthetic, which starts from noise)")
+    if cond_type is not None and cond_type not in EDIT_COND_TYPES:
+        raise SystemExit(f"--morph between two songs describes each by its chords: it needs a model of cond_type chord or chord+txt, this "
+                         f"one's is {cond_type!r}")
     return True
 
 
@@ -927,12 +1054,64 @@ def edit_song(model, params, args, image, cond, cond_tgt, cond_mid, cond_mid_tgt
     return 0
 
 
+def morph_songs(model, params, args, image_a, image_b, cond_a, cond_b, cond_mid_a, cond_mid_b, scale, seed: int, say=print,
+                score_chords=None) -> int:
+    """``--morph``: the path from song A to song B through ``Experiments.morph``; writes ``<stamp>_morph.npy`` ``[K, B, 2, H, W]``, one
+    ``<stamp>_morph_<k>.mid`` per frame and ``<stamp>_morph.mid`` with the frames one after the other, and prints the largest relative
+    residual of the inversions' last iterate and the angle between the two end noises per row.  Without the images the path runs between
+    two fresh noise draws.  ``score_chords``: ``--score`` - (A's, B's) chords ``[B, 32, 36]``; chord_f1 of every frame against each is printed
+    and written to ``<stamp>_score.json`` (the crossover is where the second column overtakes the first)."""
+    n = min(cond_a.shape[0], cond_b.shape[0], *(v.shape[0] for v in (image_a, image_b) if v is not None))
+    if any(v.shape[0] != n for v in (cond_a, cond_b, image_a, image_b) if v is not None):
+        say(f"morph: both songs cut to {n} segment(s), the shorter one's")
+    cut = lambda v: None if v is None else v[:n].contiguous()
+    sampler, t_idx = make_sampler(model, args, seed, 0)
+    expmt = Experiments(params.model_name, params, sampler, t_idx=t_idx)
+    depth = t_idx if args.morph_depth is None else args.morph_depth
+    K = args.morph_frames
+    if image_a is None:
+        say(f"morphing {n} segment(s) between two noise draws: {K} frames x {depth + 1} steps down at uncond_scale = {scale}")
+    else:
+        say(f"morphing {n} segment(s): {depth + 1} upward steps x {args.morph_iters} iterates on both songs, {K} frames ({args.morph_ease}, "
+            f"conditions: {args.morph_cond}), then {depth + 1} steps down at uncond_scale = {scale}")
+    gen = expmt.morph(cut(image_a), cut(cond_a), cut(image_b), cut(cond_b), K, scale, iters=args.morph_iters, depth=depth, ease=args.morph_ease,
+                      cond_how=args.morph_cond, joint=args.joint, blend=args.joint_blend, cond_mid_a=cut(cond_mid_a), cond_mid_b=cut(cond_mid_b))
+    if not bool(torch.isfinite(gen).all()):
+        raise SystemExit(f"non-finite values in the morphed piano rolls (precision {model.ldm.eps_model.precision})")
+    rec = sampler.last_morph
+    if rec.inversion is not None:
+        say(f"inversion: largest relative residual of the last iterate over all steps: {float(np.nanmax(rec.inversion.residuals()[:, -1])):.3e}")
+    say("angle between the two end noises per " + ("song canvas" if args.joint else "segment") + " (radians): "
+        + ", ".join(f"{v:.4f}" for v in rec.angles().tolist()))
+    os.makedirs(args.output_dir, exist_ok=True)
+    stamp = os.path.join(args.output_dir, expmt._stamp(scale, False, "", args.joint_blend if args.joint else None))
+    np.save(stamp + "_morph.npy", gen.cpu().numpy())
+    for k in range(K):
+        midi.prmat2c_to_midi_file(gen[k], f"{stamp}_morph_{k}.mid")
+    midi.prmat2c_to_midi_file(gen.reshape(K * n, *gen.shape[2:]), stamp + "_morph.mid")
+    say(f"morph: {K} frames, piano_roll {tuple(gen.shape)}  onsets>0.5 per frame: {[int((gen[k][:, 0] > 0.5).sum()) for k in range(K)]}  "
+        f"-> {stamp}_morph.mid, {stamp}_morph_<k>.mid")
+    if score_chords is not None:
+        doc = {"bass_relative": bool(args.score_bass_relative), "segments": n, "frames": K, "fractions": [float(t) for t in rec.fractions]}
+        flat = gen.reshape(K * n, *gen.shape[2:])
+        for name, c in zip(("chord_f1_on_a", "chord_f1_on_b"), score_chords):
+            rep = pfscore.roll_stats(flat, c[:n].repeat(K, 1, 1), bass_relative=args.score_bass_relative).songs(n).report()
+            doc[name] = [r["chord_f1"] for r in rep]
+        for k in range(K):
+            say(f"frame {k} (t = {rec.fractions[k]:.3f}) chord_f1: on A's chords {doc['chord_f1_on_a'][k]:.4f}, on B's chords {doc['chord_f1_on_b'][k]:.4f}")
+        with open(stamp + "_score.json", "w") as f:
+            json.dump(doc, f, indent=1)
+        say(f"scores -> {stamp}_score.json")
+    return 0
+
+
 def main(argv=None):
     from . import dist as pfdist
     args = make_parser().parse_args(argv)
     if args.dpm and args.ddim:
         raise SystemExit("--dpm and --ddim name two different samplers: give one of them")
     check_edit_args(args)                                  # what the flags alone decide, before anything else
+    check_morph_args(args)
     check_score_args(args)
     if not torch.cuda.is_available():
         raise SystemExit("inference_sdf needs an AMD GPU (no CPU fallback on this path)")
@@ -968,7 +1147,10 @@ def main(argv=None):
     say(f"model_label: {params.model_name}")
     dual = wants_dual_guidance(args, params.cond_type)     # (refusals before any weight is loaded)
     editing = check_edit_args(args, params.cond_type, world)
+    morphing = check_morph_args(args, params.cond_type, world)
     scoring = check_score_args(args, params.cond_type)
+    if morphing and params.get("concat_blurry", False):
+        raise SystemExit("--morph does not cover the concat_blurry variant (its blurred image describes one song, a frame lies between two)")
     if editing and params.get("concat_blurry", False):
         raise SystemExit("--edit does not cover the concat_blurry variant (its blurred image describes the song being changed)")
     try:
@@ -1091,9 +1273,36 @@ def main(argv=None):
             say(f"target chords from midi file: {args.edit_chords_from_midi}")
         n = min(chd.shape[0], chd_tgt.shape[0])
         cond_tgt, cond_mid_tgt = encode_conditions(model, params, chd_tgt[:n], prmat, args.joint, pnotree=pnotree)
+    cond_b = cond_mid_b = chd_b = image_b = None
+    if morphing:
+        # song B: its own chords (and texture, where it brings one), encoded like song A's
+        prmat_b, pnotree_b = prmat, pnotree
+        if args.morph_to_midi is not None:
+            image_b, pnotree_b, chd_b, prmat_b = (v.to(_dev()) for v in song_from_midi(args.morph_to_midi, "_morph"))
+            say(f"morphing to midi file: {args.morph_to_midi}")
+        elif args.morph_to_song_index is not None:
+            (image_b, pnotree_b, chd_b, prmat_b), fn_b = song_from_dataset(args.from_dataset, args.morph_to_song_index)
+            image_b, pnotree_b, chd_b, prmat_b = (v.to(_dev()) for v in (image_b, pnotree_b, chd_b, prmat_b))
+            say(f"morphing to midi file: {fn_b}")
+        elif args.morph_to_npz is not None:
+            with np.load(args.morph_to_npz) as zb:
+                if "chord" not in zb or "prmat2c" not in zb:
+                    raise SystemExit(f"--morph_to_npz {args.morph_to_npz}: needs the arrays chord [B,32,36] and prmat2c [B,2,128,128]")
+                chd_b, image_b = (torch.from_numpy(zb[k]).float().to(_dev()) for k in ("chord", "prmat2c"))
+                prmat_b = torch.from_numpy(zb["prmat"]).float().to(_dev()) if "prmat" in zb else prmat
+        else:                  # --synthetic: a second draw of the synthetic conditions, no images
+            n_b = cond.shape[0]
+            chd_b = torch.from_numpy(synth.chords(n_b, seed + 101)).to(_dev())
+            prmat_b = torch.from_numpy(synth.prmat(n_b, seed + 201)).to(_dev())
+            pnotree_b = torch.from_numpy(synth.pnotree(n_b, seed + 301)).to(_dev()) if params.cond_type == "pnotree" else None
+        if image_b is not None and (chd is None or prmat2c_cond is None):
+            raise SystemExit("--morph needs song A with its chords and its image: --from_midi, --from_dataset, --from_song_npz, or chord and prmat2c in --cond_npz")
+        cond_b, cond_mid_b = encode_conditions(model, params, chd_b, prmat_b, args.joint, pnotree=pnotree_b)
     if params.cond_mode == "uncond":
         cond = -torch.ones_like(cond)
     if length > 0:
+        cond_b = None if cond_b is None else cond_b[:length]
+        cond_mid_b = None if cond_mid_b is None else cond_mid_b[:length]
         cond = cond[:length]
         cond_mid = cond_mid[:length] if cond_mid is not None else None
         cond_tgt = None if cond_tgt is None else cond_tgt[:length]
@@ -1149,6 +1358,9 @@ def main(argv=None):
                 model = model16
     else:
         model.ldm.eps_model.set_precision(args.precision)
+    if morphing:
+        return morph_songs(model, params, args, None if image_b is None else prmat2c_cond, image_b, cond, cond_b, cond_mid, cond_mid_b, scale, seed, say,
+                           score_chords=(chd, chd_b) if scoring and chd is not None and chd_b is not None else None)
     if editing:
         return edit_song(model, params, args, prmat2c_cond, cond, cond_tgt, cond_mid, cond_mid_tgt, scale, seed, say,
                          score_chords=(chd, chd_tgt) if scoring else None)

@@ -9,6 +9,9 @@
   condition, passed as ``uncond_scale``; the one function that decides what a guided eps evaluates.
 * ``DDIMSampler.invert`` - not in the reference: the eta = 0 loop walked upwards, each step solved implicitly by fixed-point iterates
   (``pf_invert_step``), so that ``paint`` under another condition edits a given song; ``invert_coef_rows``, ``InversionRecord``.
+* ``DDIMSampler.morph`` / ``DiffusionSampler.morph_from_noise`` - not in the reference: a path between two songs - both inverted as one
+  batch, their noises interpolated on the sphere (``pf_slerp_rows``) and their conditions linearly, every point painted back down;
+  ``morph_fractions``, ``MorphRecord``.
 * ``DPMSolverSampler``  - not in the reference: DPM-Solver++(2M), the second-order multistep solver, driven like ``DDIMSampler``.
 * ``WindowPlan``        - not in the reference: a song as one canvas whose half-overlapping windows are denoised as ONE batch per step, their
   noise predictions blended where they overlap (``DiffusionSampler.windows``; ``pf_window_split`` / ``pf_window_merge``).
@@ -32,6 +35,7 @@ them unchanged.  Differences, all host-side plumbing:
 """
 from __future__ import annotations
 
+import math
 from dataclasses import dataclass
 from typing import Callable, List, Optional, Tuple, Union
 
@@ -437,6 +441,118 @@ class DiffusionSampler:
         return all(v is None or (v.is_contiguous() and v.data_ptr() % 16 == 0) for v in (x,) + others)
 
 
+    # ---- a path between two songs (not in the reference) -------------------------------------------------------------------------------
+    def morph_noise(self, xa: torch.Tensor, xb: torch.Tensor, fracs):
+        """``len(fracs)`` noises on the great circle from ``xa`` to ``xb``, one circle per batch entry (a ``WindowPlan`` canvas is one row):
+        ``(x [K, rows, ...], stats [rows, 3] float64, weights [K, rows, 2] float32)``, all on the device (``pf_slerp_rows``, mode slerp).
+        A linear mix of two Gaussian noises has the wrong norm (``sqrt((1 - t)^2 + t^2)`` of it at an angle of pi / 2); this one keeps it."""
+        return _steps.slerp_rows(self._lib, xa, xb, fracs, mode="slerp")
+
+    def morph_cond(self, ca: torch.Tensor, cb: torch.Tensor, fracs, how: str = "lerp") -> torch.Tensor:
+        """The conditions of the frames, ``[K, rows, n_cond, d_cond]``: ``lerp`` - ``(1 - t)*ca + t*cb`` on the encoded conditions (mode lerp
+        of the same kernel; ``t = 0`` and ``t = 1`` are copies); ``switch`` - ``ca`` where ``t < 0.5``, else ``cb``."""
+        if how not in MORPH_CONDS:
+            raise ValueError(f"morph_cond: how {how!r}, expected one of {MORPH_CONDS}")
+        if ca.shape != cb.shape:
+            raise ValueError(f"morph_cond: conditions of shapes {tuple(ca.shape)} and {tuple(cb.shape)}")
+        if how == "lerp":
+            return _steps.slerp_rows(self._lib, ca, cb, fracs, mode="lerp", want_stats=False)[0]
+        ca, cb = ca.contiguous().float(), cb.contiguous().float()
+        return torch.stack([ca if float(t) < 0.5 else cb for t in fracs])
+
+    def _morph_refusal(self) -> Optional[str]:
+        """Why this sampler has no morph, or ``None``.  A loop that draws noise maps neighbouring starts to unrelated images."""
+        return f"{type(self).__name__} draws noise in every step: the frames of such a loop are not a path (use DDIMSampler with eta 0 or DPMSolverSampler)"
+
+    def _morph_paint(self, xs, cs, t_start: int, batch: int, uncond_scale, uncond_cond, cond_concat) -> torch.Tensor:
+        """``paint`` of the ``K * R`` starts ``xs [K, R, ...]`` under the conditions ``cs [K, Rc, ...]`` (``Rc = R``, or ``R`` times the windows
+        of the plan), frame-major, at most ``batch`` rows of ``xs`` per call; ``uncond_cond`` ``[Rc, ...]`` and ``cond_concat`` ``[R, ...]`` are
+        those of one frame.  Returns ``[K, R, C, H, W]``."""
+        K, R = xs.shape[0], xs.shape[1]
+        per = cs.shape[1] // R                                  # condition rows per row of x
+        tile = lambda v: None if v is None else v.repeat(K, *([1] * (v.dim() - 1))).contiguous()
+        x, c, uc, cc = xs.reshape(K * R, *xs.shape[2:]), cs.reshape(K * cs.shape[1], *cs.shape[2:]), tile(uncond_cond), tile(cond_concat)
+        cut = lambda v, i0, i1, m=1: None if v is None else v[i0 * m: i1 * m].contiguous()
+        outs = [self.paint(cut(x, i, min(i + batch, K * R)), cut(c, i, min(i + batch, K * R), per), t_start, uncond_scale=uncond_scale,
+                           uncond_cond=cut(uc, i, min(i + batch, K * R), per), cond_concat=cut(cc, i, min(i + batch, K * R)))
+                for i in range(0, K * R, batch)]
+        out = outs[0] if len(outs) == 1 else torch.cat(outs)
+        return out.reshape(K, R, *out.shape[1:])
+
+    def _morph_conds(self, cond_a, cond_b, fracs, cond_how, conds, rows: int) -> torch.Tensor:
+        K = len(fracs)
+        if conds is None:
+            conds = self.morph_cond(cond_a, cond_b, fracs, cond_how)
+        else:
+            conds = conds.contiguous().float()
+            if conds.numel() != K * cond_a.numel():
+                raise ValueError(f"morph: conds of shape {tuple(conds.shape)} for {K} frames of conditions of shape {tuple(cond_a.shape)}")
+            conds = conds.reshape(K, *cond_a.shape)
+        if conds.shape[1] % rows != 0:
+            raise ValueError(f"morph: {conds.shape[1]} condition rows for {rows} rows of x")
+        return conds
+
+    @torch.no_grad()
+    def morph_from_noise(self, shape, cond_a, cond_b, frames: int = 5, *, t_start: Optional[int] = None, ease: str = "linear",
+                         cond_how: str = "lerp", conds=None, uncond_scale: Scale = 1.0, uncond_cond=None, cond_concat=None, batch: int = 16):
+        """A path between two GENERATED songs: the end noises are two fresh draws of this sampler's own generator (``shape`` each), the
+        frames between them ``morph_noise`` / ``morph_cond`` at ``morph_fractions(frames, ease)``, every frame painted from ``t_start``
+        (default: the whole grid) - the rest as ``DDIMSampler.morph``.  For deterministic loops only: ``DDIMSampler`` with eta 0 and
+        ``DPMSolverSampler``; anything else is a ``ValueError``.  Returns ``[K, R, C, H, W]`` and leaves ``self.last_morph``."""
+        why = self._morph_refusal()
+        if why is not None:
+            raise ValueError(f"morph_from_noise: {why}")
+        fracs = morph_fractions(frames, ease)
+        t_start = len(self.time_steps) - 1 if t_start is None else int(t_start)
+        if int(batch) < 1:
+            raise ValueError(f"morph: batch {batch} < 1")
+        xa, xb = self.randn(shape, cond_a.device), self.randn(shape, cond_a.device)
+        xs, stats, weights = self.morph_noise(xa, xb, fracs)
+        cs = self._morph_conds(cond_a, cond_b, fracs, cond_how, conds, xa.shape[0])
+        self.last_morph = MorphRecord(fracs, stats, weights, None, (xa, xb))
+        return self._morph_paint(xs, cs, t_start, int(batch), uncond_scale, uncond_cond, cond_concat)
+
+
+MORPH_EASES = ("linear", "cosine")
+MORPH_CONDS = ("lerp", "switch")
+
+
+def morph_fractions(frames: int, ease: str = "linear") -> np.ndarray:
+    """float64 ``[frames]``: where the frames of a morph sit between song A (0) and song B (1), the endpoints included.  ``linear``:
+    ``k / (frames - 1)``; ``cosine``: ``(1 - cos(pi * k / (frames - 1))) / 2`` - slow at both ends.  One frame sits in the middle."""
+    frames = int(frames)
+    if ease not in MORPH_EASES:
+        raise ValueError(f"morph_fractions: ease {ease!r}, expected one of {MORPH_EASES}")
+    if not 1 <= frames <= _lib.SLERP_MAX_FRAMES:
+        raise ValueError(f"morph_fractions: {frames} frames outside [1, {_lib.SLERP_MAX_FRAMES}]")
+    if frames == 1:
+        return np.asarray([0.5], dtype=np.float64)
+    lin = np.arange(frames, dtype=np.float64) / (frames - 1)
+    if ease == "cosine":
+        # libm's cos, one value at a time: numpy's vectorised cos may differ in the last bit from host to host.  cos(0) and cos(pi) are
+        # exact, so the end points are 0 and 1
+        lin = np.asarray([(1.0 - math.cos(math.pi * float(v))) / 2.0 for v in lin], dtype=np.float64)
+    return lin
+
+
+@dataclass
+class MorphRecord:
+    """What a morph leaves behind without a host sync: ``fractions`` (host float64 ``[K]``), the device tables of ``pf_slerp_rows`` -
+    ``stats`` float64 ``[rows, 3]`` (sum a*a, a*b, b*b of the two end noises per row) and ``weights`` float32 ``[K, rows, 2]`` -, the
+    ``InversionRecord`` of the upward walk (rows: A's, then B's; ``None`` for ``morph_from_noise``) and the two end noises."""
+    fractions: np.ndarray
+    stats: torch.Tensor
+    weights: torch.Tensor
+    inversion: Optional["InversionRecord"] = None
+    end_noises: Optional[tuple] = None
+
+    def angles(self) -> np.ndarray:
+        """The angle between the two end noises of every row, radians, as numpy ``[rows]`` (copies the table: the one host sync)."""
+        s = self.stats.detach().cpu().numpy()
+        with np.errstate(divide="ignore", invalid="ignore"):
+            return np.arccos(np.clip(s[:, 1] / np.sqrt(s[:, 0] * s[:, 2]), -1.0, 1.0))
+
+
 class SDFSampler(DiffusionSampler):
     def __init__(self, model: LatentDiffusion, is_show_image: bool = False, **kw):
         super().__init__(model, **kw)
@@ -814,6 +930,42 @@ class DDIMSampler(DiffusionSampler):
         self.last_inversion = InversionRecord(resid, (t_end + 1, iters, rows, 2), its)
         return y
 
+    # ---- a path between two given songs (not in the reference) ------------------------------------------------------------------------------
+    def _morph_refusal(self) -> Optional[str]:
+        if bool((self.ddim_sigma != 0).any()):
+            return "this DDIM loop is stochastic (ddim_sigma != 0, eta > 0): the frames of a loop that draws noise are not a path"
+        return None
+
+    @torch.no_grad()
+    def morph(self, x0_a, cond_a, x0_b, cond_b, frames: int = 5, *, t_end: Optional[int] = None, iters: int = 3, ease: str = "linear",
+              cond_how: str = "lerp", conds=None, uncond_scale: Scale = 1.0, invert_scale: Optional[Scale] = None, uncond_cond=None,
+              cond_concat=None, batch: int = 16):
+        """``frames`` songs on a path from ``x0_a`` to ``x0_b`` (``[R, C, H, W]`` each; canvases under a window plan): both are taken to their
+        noises by ONE ``invert`` of the ``2R`` stacked rows under their own conditions (``invert_scale``: its guidance, default
+        ``uncond_scale``), the noises are interpolated on the sphere (``morph_noise``) and the conditions as ``cond_how`` says (``morph_cond``;
+        ``conds`` ``[K, rows of cond_a, ...]`` overrides them) at ``morph_fractions(frames, ease)``, and the ``K * R`` points are painted back
+        down from ``t_end`` in batches of at most ``batch`` rows, frame-major.  ``uncond_cond`` / ``cond_concat``: those of ONE song, shaped
+        like ``cond_a`` / ``x0_a``'s rows.  Everything ``invert`` and ``paint`` support carries over (float / ``DualScale`` guidance, a window
+        plan, ``graph=True``), and eta != 0 is refused by ``invert``.  With a converged inversion the first and last frame are the two
+        songs.  Returns ``[K, R, C, H, W]``.  No host sync: the fractions, the slerp tables and the inversion's residuals stay in
+        ``self.last_morph`` (``MorphRecord``)."""
+        fracs = morph_fractions(frames, ease)
+        if x0_a.shape != x0_b.shape or cond_a.shape != cond_b.shape:
+            raise ValueError(f"morph: songs of shapes {tuple(x0_a.shape)} / {tuple(x0_b.shape)} under conditions of shapes "
+                             f"{tuple(cond_a.shape)} / {tuple(cond_b.shape)}")
+        if int(batch) < 1:
+            raise ValueError(f"morph: batch {batch} < 1")
+        R = x0_a.shape[0]
+        t_end = len(self.time_steps) - 1 if t_end is None else int(t_end)
+        two = lambda v: None if v is None else torch.cat([v, v])
+        x = self.invert(torch.cat([x0_a.float(), x0_b.float()]), torch.cat([cond_a, cond_b]), t_end, iters=iters,
+                        uncond_scale=uncond_scale if invert_scale is None else invert_scale, uncond_cond=two(uncond_cond),
+                        cond_concat=two(cond_concat))
+        xs, stats, weights = self.morph_noise(x[:R], x[R:], fracs)
+        cs = self._morph_conds(cond_a, cond_b, fracs, cond_how, conds, R)
+        self.last_morph = MorphRecord(fracs, stats, weights, self.last_inversion, (x[:R], x[R:]))
+        return self._morph_paint(xs, cs, t_end, int(batch), uncond_scale, uncond_cond, cond_concat)
+
 
 @dataclass
 class InversionRecord:
@@ -900,6 +1052,9 @@ class DPMSolverSampler(DiffusionSampler):
         self._ab = model.alpha_bar.detach().cpu().double().numpy()
         self.time_steps = dpm_time_steps(self._ab, n_steps, discretize)
         self._rows = {}
+
+    def _morph_refusal(self) -> Optional[str]:
+        return None             # no step draws noise: morph_from_noise is a path
 
     def coef_rows(self, t_start: Optional[int] = None) -> np.ndarray:
         """float32 ``[t_start + 1, 7]``: the coefficient rows of a loop that starts at grid index ``t_start`` (default: the whole grid)."""
