@@ -629,6 +629,29 @@ int pf_gn_scale_shift(const float* x0, int c0, const float* x1, int c1, int batc
                       void* scratch, size_t scratch_bytes, void* stream);
 /* LayerNorm statistics over the last dim: mean[m], rstd[m] (unet_attention.py:104-110, eps 1e-5). */
 int pf_ln_stats(const float* x, int rows, int c, float eps, float* mean, float* rstd, void* stream);
+/* The stem convolution (unet.py:78-80): 3x3, padding 1, x NCHW [batch][cin][h][w], w [cout][cin][3][3], out NHWC [batch][h][w][cout], fp32.
+ * cout % 4 == 0 and cout * cin * 36 bytes <= 64 KB.  cin <= 2 with cout == 64 runs the register-weight kernel, which can also emit the
+ * per-tile channel (sum, sumsq) of what it stores: stats [batch][pf_conv_in_stats_tiles][64][2] over 16x16-pixel tiles, tile ty * tilesx + tx,
+ * in-image pixels only (the layout pf_gn_finalize_tiles reads).  stats on any other shape is refused (pf_conv_in_stats_tiles returns 0). */
+int pf_conv_in(const float* x_nchw, const float* w, const float* bias, float* out_nhwc, int batch, int cin, int cout, int h, int w_,
+               float* stats, void* stream);
+int pf_conv_in_stats_tiles(int cin, int cout, int h, int w_);
+/* The head (unet.py:145-149): out = conv3x3(silu(x * sc + sh)) + bias with per-sample GroupNorm rows sc / sh [batch][cin]; x NHWC
+ * [batch][h][w][cin], w packed [9][cin][cout] (tap = ky * 3 + kx), out NCHW [batch][cout][h][w].  The zero padding is of the ACTIVATED tensor.
+ * cout in 1..4, cin % 16 == 0, batch * h * w * cin < 2^31. */
+int pf_conv_out(const float* x_nhwc, const float* sc, const float* sh, const float* w, const float* bias, float* out_nchw, int batch, int cin,
+                int cout, int h, int w_, void* stream);
+/* Time embedding with the SiLU of the ResBlocks' emb_layers folded in (unet.py:63-68,151-169):
+ * out[b] = silu(W2 . silu(W0 . [cos(t_b f) | sin(t_b f)] + b0) + b2), f_j = exp(-ln(10000) j / (channels / 2)) in fp32; w0 [d_t][channels],
+ * w2 [d_t][d_t], out [batch][d_t].  t int64 [batch], or NULL: row b is the embedding of time-step value b (the table of
+ * pf_unet_prepare_time).  channels even, channels + d_t <= 8192. */
+int pf_time_embed(const int64_t* t, const float* w0, const float* b0, const float* w2, const float* b2, float* out_silu, int batch,
+                  int channels, int d_t, void* stream);
+/* Batched mat-vec y[b][n] = W[n][:] . x[b][:] + bias[n] (bias may be NULL), W row-major [n][k], rows of x / y ldx / ldy floats apart,
+ * k <= 2048.  n_per_group > 0: the block-diagonal form, output n reads x + (n / n_per_group) * x_group_stride.  exp_flag: y = expf(...)
+ * (ungrouped only).  A row's sum is accumulated in the same order whatever its position in the batch. */
+int pf_matvec(const float* x, int ldx, const float* w, const float* bias, float* y, int ldy, int batch, int n, int k, int n_per_group,
+              int x_group_stride, int exp_flag, void* stream);
 /* LayerNorm applied and split into bf16 hi/lo planes [rows][c] | [rows][c] (the A operand of pf_conv2d with a_planes=1);
  * replaces pf_ln_stats + the LayerNorm GEMM prologue for the transformer block's q/k/v and GeGLU projections */
 int pf_ln_planes(const float* x, int rows, int c, float eps, const float* gamma, const float* beta, void* planes, void* stream);

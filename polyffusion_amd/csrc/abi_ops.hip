@@ -90,6 +90,28 @@ int pf_ln_planes(const float* x, int rows, int c, float eps, const float* gamma,
 int pf_ln_stats(const float* x, int rows, int c, float eps, float* mean, float* rstd, void* stream) {
   return launch_ln_stats(x, rows, c, eps, mean, rstd, (hipStream_t)stream);
 }
+int pf_conv_in(const float* x_nchw, const float* w, const float* bias, float* out_nhwc, int batch, int cin, int cout, int h, int w_,
+               float* stats, void* stream) {
+  PF_REQUIRE(x_nchw && w && bias && out_nhwc && batch > 0 && cin > 0 && cout > 0 && h > 0 && w_ > 0, "pf_conv_in: bad arguments");
+  return launch_conv_in(x_nchw, w, bias, out_nhwc, batch, cin, cout, h, w_, (hipStream_t)stream, stats);
+}
+int pf_conv_in_stats_tiles(int cin, int cout, int h, int w_) { return (cin > 0 && h > 0 && w_ > 0) ? launch_conv_in_stats_tiles(cin, cout, h, w_) : 0; }
+int pf_conv_out(const float* x_nhwc, const float* sc, const float* sh, const float* w, const float* bias, float* out_nchw, int batch, int cin,
+                int cout, int h, int w_, void* stream) {
+  PF_REQUIRE(x_nhwc && sc && sh && w && bias && out_nchw && batch > 0 && cin > 0 && h > 0 && w_ > 0, "pf_conv_out: bad arguments");
+  return launch_conv_out(x_nhwc, sc, sh, w, bias, out_nchw, batch, cin, cout, h, w_, (hipStream_t)stream);
+}
+int pf_time_embed(const int64_t* t, const float* w0, const float* b0, const float* w2, const float* b2, float* out_silu, int batch,
+                  int channels, int d_t, void* stream) {
+  PF_REQUIRE(w0 && b0 && w2 && b2 && out_silu && batch > 0 && channels > 0 && d_t > 0, "pf_time_embed: bad arguments");
+  return launch_time_embed(t, w0, b0, w2, b2, out_silu, batch, channels, d_t, (hipStream_t)stream);
+}
+int pf_matvec(const float* x, int ldx, const float* w, const float* bias, float* y, int ldy, int batch, int n, int k, int n_per_group,
+              int x_group_stride, int exp_flag, void* stream) {
+  PF_REQUIRE(!exp_flag || n_per_group <= 0, "pf_matvec: the exp variant has no grouped form");
+  return exp_flag ? launch_matvec_exp(x, ldx, w, bias, y, ldy, batch, n, k, (hipStream_t)stream)
+                  : launch_matvec(x, ldx, w, bias, y, ldy, batch, n, k, (hipStream_t)stream, n_per_group, x_group_stride);
+}
 int pf_conv_stats_tiles(const pf_conv_args* a) { return a ? conv_plan(*a).stats_tiles : 0; }
 size_t pf_conv_splitk_ws_bytes(const pf_conv_args* a) { return a ? conv_plan(*a).splitk_ws_bytes : 0; }
 int pf_conv_describe(const pf_conv_args* a, pf_conv_plan_info* out) {

@@ -32,11 +32,29 @@ def _weights(seed):
 
 @pytest.mark.parametrize("B,L", [(2, 1024), (16, 1024), (3, 64), (1, 256), (5, 192)])
 def test_fused_mlp_vs_torch_and_vs_the_unfused_chain(lib, B, L):
+    _check_fused_mlp(lib, B, L, rnd((B, L, C), 310 + B) * 1.4 + 0.2, torch.float32)
+
+
+@pytest.mark.parametrize("regime", ["offset_rows", "constant_rows"])
+def test_fused_mlp_layernorm_regimes(lib, regime):
+    """The LayerNorm inside the launch where its fp32 row mean matters (B, L = 1, 64): rows of mean 100 and deviation 1, and rows that are
+    exactly constant (variance 0, rstd = eps^-1/2 = 316: the output carries 316 |gamma| times the error of the mean; |v| < 1.75 keeps that
+    inside TOL_OP).  The same assertions as above, the reference evaluated in float64."""
+    B, L = 1, 64
+    if regime == "offset_rows":
+        x = rnd((B, L, C), 330) + 100.0
+    else:
+        v = torch.tensor([(0.25 + 1.5 * r / L) * (-1.0) ** r for r in range(L)], dtype=torch.float32)
+        x = v[None, :, None].repeat(B, 1, C)
+    _check_fused_mlp(lib, B, L, x, torch.float64)
+
+
+def _check_fused_mlp(lib, B, L, x, ref_dtype):
     w1, b1, w2, b2, gamma, beta, w1i, b1i = _weights(300)
-    x = rnd((B, L, C), 310 + B) * 1.4 + 0.2
-    xn = F.layer_norm(x, (C,), gamma, beta, 1e-5)
-    h = F.linear(xn, w1, b1)
-    ref = x + F.linear(h[..., :HID] * F.gelu(h[..., HID:]), w2, b2)
+    t = lambda a: a.to(ref_dtype)  # noqa: E731
+    xn = F.layer_norm(t(x), (C,), t(gamma), t(beta), 1e-5)
+    h = F.linear(xn, t(w1), t(b1))
+    ref = t(x) + F.linear(h[..., :HID] * F.gelu(h[..., HID:]), t(w2), t(b2))
 
     xd, gd, bd = dev(x), dev(gamma), dev(beta)
     p1, p2, b1d, b2d = pack3(lib, w1i), pack3(lib, w2), dev(b1i), dev(b2)
@@ -46,7 +64,7 @@ def test_fused_mlp_vs_torch_and_vs_the_unfused_chain(lib, B, L):
                                       p2.data_ptr(), b2d.data_ptr(), out.data_ptr(), None, st), "pf_mlp_geglu_fused")
     torch.cuda.synchronize()
     assert torch.isfinite(out).all()
-    assert (out.cpu() - ref).abs().max().item() < TOL_OP
+    assert (out.cpu().to(ref_dtype) - ref).abs().max().item() < TOL_OP
 
     # the chain it replaces: LayerNorm planes -> GeGLU projection (planes out) -> K = 1024 planes GEMM + residual
     lnp = torch.zeros(B * L * C, device="cuda")
