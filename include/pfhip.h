@@ -500,6 +500,67 @@ typedef struct pf_roll_stats_args {
 } pf_roll_stats_args;
 int pf_roll_stats(const pf_roll_stats_args* a, void* stream);
 
+/* ---- recognising the chords of a roll ("Chord recognition"; restates chord_extractor/ of the reference) ----
+ * The labels chord_extractor.recognize returns for the file prmat2c_to_midi_file would write from a song of `segments` consecutive images,
+ * computed on the images, with two deviations: a song always has segments * steps / 4 beats, and a song without notes is all "N".
+ *   Notes.  Onset v > 0.5 (custom_round: 0.95 < v < 1.05) on channel 0, lasting while channel 1 is > 0.5 on the following steps of the key
+ *   (as pf_prmat2c_durations), clipped at the end of its image; a NaN is silent.  A note-off closes every open note of its key, as the MIDI
+ *   reader does.  A beat is 4 steps, a bar 4 beats: position 1 + beat % 4.
+ *   Features.  chroma_q[j][pc]: the longest stretch of beat j covered by a single note of class pc = key % 12, in quarter beats (steps).
+ *   bass_q[j][pc]: eighth beats (two per step) of beat j whose lowest sounding key has class pc.
+ *   Scores.  For every window of j + 1 <= 5 beats ending at beat i that decode() reaches (it stops one beat past a downbeat) and every class
+ *   c: num = window sum of chroma_q over the template minus over its complement, bass = window sum of bass_q at the class's bass, then in
+ *   float64, in this order, (((num / 4) / size + 0.5 * (bass / 8)) - cls_const[c][0]) - cls_const[c][1]; a class of size 0 ("N") scores
+ *   consts[14].  obs = ((score + consts[j]) + (position of beat i - j == 3 ? consts[12] : 0)) + (position odd ? consts[13] : 0).  The best
+ *   class of a window is the arg-max of obs, ties to the lowest index; dp[i] = max over windows of dp[i - j - 1] + best obs, updated on
+ *   strict "<" with j ascending; the labels are read back from dp[n - 1].  The division is IEEE round-to-nearest and no other operation
+ *   rounds differently under contraction, so every score is the bit pattern numpy gives.
+ *   Tables (caller-owned, on the device, built once from the vocabulary):  cls_bits[c] = template bits 0..11 | bass class << 12 | template
+ *   size << 16;  cls_const[c] = {size * 0.1, 0.05 if the label is an inversion else 0.0} as the host computes them;  cls_rows[c] = the
+ *   condition row [36] of the label;  consts[16] = {j * 0.7 for j = 0..11, 0.15, 0.2, 0.2 (the score of "N"), 0}.
+ *   Comparison with `chord` (optional), per beat, recognised row r against condition row c: ROOT_HIT - arg-max of [0:12] equal (lowest
+ *   index on ties) and both or neither have an entry > 0.5;  CHROMA_HIT - the bit sets {k : [12 + k] > 0.5} equal;  BASS_HIT - as root on
+ *   [24:36], with bass_relative the condition's bass read as (bass + root) % 12;  FULL_HIT - all three;  CHROMA_INTER / CHROMA_UNION - sizes
+ *   of the intersection / union of the bit sets.  chord == NULL: those six are 0.
+ *   Every word of the seven outputs is written by the call: the caller does not pre-zero.  One launch, one workgroup per song, no global
+ *   atomics, nothing allocated, nothing synchronised: capturable.  Refused before any launch: null or misaligned pointers (8 bytes for the
+ *   float64 tables and path_score, 4 otherwise), songs, segments or steps <= 0, steps % 16 != 0, more than PF_CHORDREC_MAX_BEATS beats per
+ *   song (16 images of 128 steps), n_classes outside 1..PF_CHORDREC_MAX_CLASSES, max_template outside 1..12 (the caller states the largest
+ *   template size of its table; a larger entry in cls_bits is read modulo 16). */
+enum {
+  PF_CHORDREC_BEATS = 0,         /* beats of the song */
+  PF_CHORDREC_ROOT_HIT = 1,
+  PF_CHORDREC_CHROMA_HIT = 2,
+  PF_CHORDREC_BASS_HIT = 3,
+  PF_CHORDREC_FULL_HIT = 4,
+  PF_CHORDREC_CHROMA_INTER = 5,
+  PF_CHORDREC_CHROMA_UNION = 6,
+  PF_CHORDREC_SEGMENTS = 7       /* recognised segments of the song */
+};
+#define PF_CHORDREC_NCOUNT 8
+#define PF_CHORDREC_MAX_BEATS 512
+#define PF_CHORDREC_MAX_CLASSES 576
+typedef struct pf_chord_recognize_args {
+  const float* prmat2c;               /* [songs * segments][2][steps][128]: channel 0 onset, 1 sustain */
+  const float* chord;                 /* [songs][beats][36], beats = segments * steps / 4; NULL: no comparison */
+  const int32_t* cls_bits;            /* [n_classes] */
+  const double* cls_const;            /* [n_classes][2] */
+  const float* cls_rows;              /* [n_classes][36] */
+  const double* consts;               /* [16] */
+  int32_t songs, segments, steps;     /* steps % 16 == 0 (a bar is 16 steps) */
+  int32_t n_classes, max_template;
+  int32_t custom_round, bass_relative;
+  int32_t reserved;                   /* 0 */
+  int32_t* labels;                    /* [songs][beats]: index into the vocabulary */
+  int32_t* bounds;                    /* [songs][beats]: 1 on the first beat of every recognised segment, else 0 */
+  float* rows;                        /* [songs][beats][36]: cls_rows[label] */
+  int32_t* counters;                  /* [songs][PF_CHORDREC_NCOUNT] */
+  double* path_score;                 /* [songs]: dp[n - 1] */
+  int32_t* chroma_q;                  /* [songs][beats][12] */
+  int32_t* bass_q;                    /* [songs][beats][12] */
+} pf_chord_recognize_args;
+int pf_chord_recognize(const pf_chord_recognize_args* a, void* stream);
+
 /* ---- condition encoders (replace RnnEncoder.forward dl_modules/chord_enc.py:15-22, TextureEncoder.forward
  *      dl_modules/txt_enc.py:23-35 and PianoTreeEncoder.forward dl_modules/pianotree_enc.py:97-121; only the Normal's mean is produced)
  *      PF_ENC_PNOTREE: input_dim = pitch classes + 5 duration digits (135), emb_size = note embedding (128), num_channel = hidden size

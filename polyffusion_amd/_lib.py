@@ -138,6 +138,20 @@ ROLL_COUNTERS = ("N_ONSET", "N_SOUNDING", "N_ORPHAN", "CHORD_BEATS", "SOUND_ON_C
 ROLL_NCOUNT = 16
 
 
+class ChordRecognizeArgs(C.Structure):
+    """pf_chord_recognize_args (include/pfhip.h); filled by ``chordrec.recognize_rolls`` only."""
+    _fields_ = ([(n, C.c_void_p) for n in ("prmat2c", "chord", "cls_bits", "cls_const", "cls_rows", "consts")]
+                + [(n, C.c_int32) for n in ("songs", "segments", "steps", "n_classes", "max_template", "custom_round", "bass_relative", "reserved")]
+                + [(n, C.c_void_p) for n in ("labels", "bounds", "rows", "counters", "path_score", "chroma_q", "bass_q")])
+
+
+# PF_CHORDREC_*, in the enum's order
+CHORDREC_COUNTERS = ("BEATS", "ROOT_HIT", "CHROMA_HIT", "BASS_HIT", "FULL_HIT", "CHROMA_INTER", "CHROMA_UNION", "SEGMENTS")
+CHORDREC_NCOUNT = 8
+CHORDREC_MAX_BEATS = 512       # PF_CHORDREC_MAX_BEATS: beats of one song
+CHORDREC_MAX_CLASSES = 576     # PF_CHORDREC_MAX_CLASSES
+
+
 FEEDBACK = {"row": 0, "batch": 1}   # PF_FEEDBACK_ROW / PF_FEEDBACK_BATCH
 MSE_CHUNK = 2048           # PF_MSE_CHUNK: elements of a row one workgroup of pf_mse_rows reduces
 SLERP_MAX_FRAMES = 64      # PF_SLERP_MAX_FRAMES: frames one pf_slerp_rows call writes
@@ -286,6 +300,7 @@ SIGNATURES = {
     "pf_comm_destroy": (C.c_int, [C.c_void_p]),
     "pf_prmat2c_durations": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "pf_roll_stats": (C.c_int, [C.POINTER(RollStatsArgs), C.c_void_p]),
+    "pf_chord_recognize": (C.c_int, [C.POINTER(ChordRecognizeArgs), C.c_void_p]),
     "pf_encoder_create": (C.c_int, [C.c_int] * 6 + [C.POINTER(C.c_void_p)]),
     "pf_encoder_create_dist": (C.c_int, [C.c_int] * 7 + [C.POINTER(C.c_void_p)]),
     "pf_encoder_destroy": (None, [C.c_void_p]),

@@ -72,6 +72,10 @@ int pf_roll_stats(const pf_roll_stats_args* a, void* stream) {
   PF_REQUIRE(a, "pf_roll_stats: null arguments");
   return launch_roll_stats(*a, (hipStream_t)stream);
 }
+int pf_chord_recognize(const pf_chord_recognize_args* a, void* stream) {
+  PF_REQUIRE(a, "pf_chord_recognize: null arguments");
+  return launch_chord_recognize(*a, (hipStream_t)stream);
+}
 int pf_mlp_geglu_fused(const float* x, int batch, int l, const float* ln_gamma, const float* ln_beta, float ln_eps,
                        const void* w1_bf16x3, const float* b1, const void* w2_bf16x3, const float* b2,
                        float* out, void* out_planes, void* stream) {

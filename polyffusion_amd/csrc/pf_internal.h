@@ -93,6 +93,8 @@ int launch_time_embed(const int64_t* t, const float* w0, const float* b0, const 
 int launch_prmat2c_durations(const float* x, int n, int steps, int custom_round, int32_t* dur, hipStream_t stream);
 // roll statistics (include/pfhip.h, pf_roll_stats): integer counters, per-beat pitch-class counts and per-step onset counts of n images
 int launch_roll_stats(const pf_roll_stats_args& a, hipStream_t stream);
+// chord recognition (include/pfhip.h, pf_chord_recognize; chordrec.hip): labels, condition rows and comparison counters of whole songs
+int launch_chord_recognize(const pf_chord_recognize_args& a, hipStream_t stream);
 int launch_matvec(const float* x, int ldx, const float* w, const float* bias, float* y, int ldy, int batch, int n, int k,
                   hipStream_t stream, int n_per_group = 0, int x_group_stride = 0);
 // y[b][n] = expf(sum_k W[n][k] * x[b][k] + bias[n]): the same kernel with the exponential in its epilogue

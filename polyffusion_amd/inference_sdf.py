@@ -31,6 +31,7 @@ import numpy as np
 import torch
 
 from . import _lib, datasample, midi, synth
+from . import chordrec as pfchordrec
 from . import score as pfscore
 from .model_sdf import ChordEncoder, Polyffusion_SDF, TextureEncoder
 from .params import Params, find_params, load_params, preset
@@ -609,9 +610,14 @@ def make_parser() -> ArgumentParser:
     p.add_argument("--best_of", type=int, default=1, metavar="N", help="extension: generate --num_generate x N candidates (the same songs as "
                    "--num_generate of that product would give), score them and keep the best --num_generate, files named by rank; implies --score")
     p.add_argument("--rank_by", choices=list(pfscore.RANK_BY), default="chord", help="what --best_of ranks by: chord (chord_f1, default), bass "
-                   "(bass_fit), integrity (lowest first) or texture (rhythm against the texture song; chord+txt models only)")
+                   "(bass_fit), integrity (lowest first), texture (rhythm against the texture song; chord+txt models only) or extracted "
+                   "(chord_acc of --score_chords: the share of beats whose recognised chord is the conditioning chord)")
     p.add_argument("--score_bass_relative", action="store_true", help="read the bass block of a chord row as an offset from the root "
                    "(default: an absolute pitch class, as --from_midi writes it)")
+    p.add_argument("--score_chords", action="store_true", help="extension, with --score / --best_of: recognise the chords of every generated "
+                   "song on the GPU by the rule of --from_midi (polyffusion_amd.chordrec) and compare them with the chords the run conditioned "
+                   "on: chord_acc, root_acc, chroma_acc, bass_acc, chroma_iou, the counters and the recognised labels per song, and a "
+                   "\"recognized\" key in <stamp>_score.json.  With --edit / --morph: chord_acc beside the chord_f1 numbers")
     return p
 
 
@@ -625,14 +631,14 @@ def check_score_args(args, cond_type: Optional[str] = None) -> bool:
         raise SystemExit("--best_of with --edit: --edit is deterministic, every candidate would be the same song")
     scoring = bool(getattr(args, "score", False)) or best_of > 1
     if not scoring:
-        given = [f"--{k}" for k in ("score_bass_relative",) if getattr(args, k, False)] + (["--rank_by"] if args.rank_by != "chord" else [])
+        given = [f"--{k}" for k in ("score_bass_relative", "score_chords") if getattr(args, k, False)] + (["--rank_by"] if args.rank_by != "chord" else [])
         if given:
             raise SystemExit(f"{', '.join(given)}: these belong to --score / --best_of, which were not given")
         return False
     if cond_type is not None:
         if args.rank_by == "texture" and cond_type != "chord+txt":
             raise SystemExit(f"--rank_by texture compares against the texture song of a chord+txt model; this model's cond_type is {cond_type!r}")
-        if best_of > 1 and args.rank_by in ("chord", "bass") and "chord" not in cond_type.split("+"):
+        if best_of > 1 and args.rank_by in ("chord", "bass", "extracted") and "chord" not in cond_type.split("+"):
             raise SystemExit(f"--rank_by {args.rank_by} needs the chords of the run; this model's cond_type is {cond_type!r} (use --rank_by integrity)")
     return True
 
@@ -1009,6 +1015,44 @@ def score_line(c: dict) -> str:
             f"integrity {c['integrity']:.4f}  onsets {c['counters']['N_ONSET']}" + (f"  texture_fit {c['texture_fit']:.4f}" if "texture_fit" in c else ""))
 
 
+def recognizing(args) -> bool:
+    """Whether the run recognises chords: ``--score_chords``, or a ranking that needs them"""
+    return bool(getattr(args, "score_chords", False)) or (getattr(args, "best_of", 1) > 1 and getattr(args, "rank_by", "chord") == "extracted")
+
+
+def recognize_songs(gen: torch.Tensor, chd, args):
+    """``--score_chords`` on this rank's songs where they live: ``gen`` as in ``score_songs``, every song its ``gen.shape[1]`` images on one
+    time axis, against the run's chords ``chd [B, 32, 36]`` (``None``: labels only).  Returns the counters ``[n, 8]`` and the labels
+    ``[n, beats]``, both int32.  One launch, no host synchronisation."""
+    n, per, steps = gen.shape[0], gen.shape[1], gen.shape[-2]
+    beats = per * steps // 4
+    if steps % 16 != 0 or beats > _lib.CHORDREC_MAX_BEATS:
+        raise SystemExit(f"--score_chords: songs of {per} image(s) of {steps} steps: the recogniser takes whole bars of 16 steps and at most "
+                         f"{_lib.CHORDREC_MAX_BEATS} beats per song")
+    if n == 0:
+        return (torch.empty(0, _lib.CHORDREC_NCOUNT, dtype=torch.int32, device=gen.device), torch.empty(0, beats, dtype=torch.int32, device=gen.device))
+    rec = pfchordrec.recognize_rolls(gen, per, None if chd is None else chd.unsqueeze(0).expand(n, *chd.shape),
+                                     bass_relative=args.score_bass_relative)
+    return rec.counters, rec.labels
+
+
+def recognized_report(counters: torch.Tensor, labels: torch.Tensor) -> list:
+    """Per song: the five scores, the named counters and the label names (``ChordRecognition.report`` on gathered tensors)"""
+    z = counters.new_zeros(0)
+    return pfchordrec.ChordRecognition(labels, z, z, counters, z, z, z).report()
+
+
+def chords_line(r: dict) -> str:
+    runs = []
+    for name in r["labels"]:
+        if runs and runs[-1][0] == name:
+            runs[-1][1] += 1
+        else:
+            runs.append([name, 1])
+    return ("  ".join(f"{k} {r[k]:.4f}" for k in pfchordrec.SCORES) + "  " + " ".join(f"{k} {v}" for k, v in r["counters"].items())
+            + "  chords: " + " ".join(f"{name}*{n}" if n > 1 else name for name, n in runs))
+
+
 def edit_song(model, params, args, image, cond, cond_tgt, cond_mid, cond_mid_tgt, scale, seed: int, say=print, score_chords=None) -> int:
     """``--edit``: the condition song's own image through ``Experiments.edit``; writes ``<stamp>.mid`` / ``.npy`` with ``_edit<K>`` in the
     stamp and prints the largest relative residual of the last iterate over all steps (and, with ``--edit_roundtrip``, how far the repaint
@@ -1049,6 +1093,15 @@ def edit_song(model, params, args, image, cond, cond_tgt, cond_mid, cond_mid_tgt
         f1 = lambda k: repr(doc[k]["chord_f1"])
         say(f"edit score (chord_f1): source image on source chords {f1('source_on_source_chords')}, on target chords {f1('source_on_target_chords')}; "
             f"edited image on source chords {f1('edited_on_source_chords')}, on target chords {f1('edited_on_target_chords')}")
+        if recognizing(args):
+            for img_name, img in (("source", orig), ("edited", gen)):
+                for chd_name, c in zip(("source_chords", "target_chords"), score_chords):
+                    cnt, lab = recognize_songs(img.unsqueeze(0), c[:n], args)
+                    doc[f"{img_name}_on_{chd_name}"]["recognized"] = recognized_report(cnt, lab)[0]
+            acc = lambda k: repr(doc[k]["recognized"]["chord_acc"])
+            say(f"edit score (chord_acc): source image on source chords {acc('source_on_source_chords')}, on target chords "
+                f"{acc('source_on_target_chords')}; edited image on source chords {acc('edited_on_source_chords')}, on target chords "
+                f"{acc('edited_on_target_chords')}")
         with open(stamp + "_score.json", "w") as f:
             json.dump(doc, f, indent=1)
     return 0
@@ -1097,8 +1150,13 @@ def morph_songs(model, params, args, image_a, image_b, cond_a, cond_b, cond_mid_
         for name, c in zip(("chord_f1_on_a", "chord_f1_on_b"), score_chords):
             rep = pfscore.roll_stats(flat, c[:n].repeat(K, 1, 1), bass_relative=args.score_bass_relative).songs(n).report()
             doc[name] = [r["chord_f1"] for r in rep]
+        if recognizing(args):
+            for name, c in zip(("chord_acc_on_a", "chord_acc_on_b"), score_chords):
+                doc[name] = [r["chord_acc"] for r in recognized_report(*recognize_songs(gen, c[:n], args))]
+            doc["recognized"] = [r["labels"] for r in recognized_report(*recognize_songs(gen, None, args))]
         for k in range(K):
-            say(f"frame {k} (t = {rec.fractions[k]:.3f}) chord_f1: on A's chords {doc['chord_f1_on_a'][k]:.4f}, on B's chords {doc['chord_f1_on_b'][k]:.4f}")
+            say(f"frame {k} (t = {rec.fractions[k]:.3f}) chord_f1: on A's chords {doc['chord_f1_on_a'][k]:.4f}, on B's chords {doc['chord_f1_on_b'][k]:.4f}"
+                + (f"; chord_acc: on A's chords {doc['chord_acc_on_a'][k]:.4f}, on B's chords {doc['chord_acc_on_b'][k]:.4f}" if recognizing(args) else ""))
         with open(stamp + "_score.json", "w") as f:
             json.dump(doc, f, indent=1)
         say(f"scores -> {stamp}_score.json")
@@ -1378,6 +1436,8 @@ def main(argv=None):
         counters, texture = score_songs(gen, chd_score, mask, args, prmat[:B] if params.cond_type == "chord+txt" and prmat is not None else None)
         counters = pfdist.gather_rows(counters, S_all, rank, world)
         texture = None if texture is None else pfdist.gather_rows(texture, S_all, rank, world)
+        if recognizing(args):
+            rc_counters, rc_labels = (pfdist.gather_rows(v, S_all, rank, world) for v in recognize_songs(gen, chd_score, args))
     gen = pfdist.gather_rows(gen, S_all, rank, world)   # [S, ...] on every rank (131 KB per image; the only end-of-run exchange)
     if not bool(torch.isfinite(gen).all()):
         # the note threshold (> 0.5) would turn a NaN into silence: refuse instead.  The one known way to get here is an activation beyond
@@ -1394,6 +1454,10 @@ def main(argv=None):
             cands = pfscore.report_of(counters, gen.shape[1] * gen.shape[-2])
             for c, t in zip(cands, [] if texture is None else texture.tolist()):
                 c["texture_fit"] = t
+            if recognizing(args):
+                recog = recognized_report(rc_counters, rc_labels)
+                for c, r in zip(cands, recog):
+                    c.update({k: r[k] for k in pfchordrec.SCORES})
             if args.best_of > 1:
                 key, descending = pfscore.RANK_BY[args.rank_by]
                 order = pfscore.rank([c[key] for c in cands], S, descending)
@@ -1409,11 +1473,15 @@ def main(argv=None):
             say(f"song {i}: piano_roll {tuple(gen[i].shape)}  onsets>0.5: {int((gen[i][:, 0] > 0.5).sum())}  -> {stamp}.mid")
             if scoring:
                 say(f"song {i} score: {score_line(cands[order[i]])}" + (f"  (candidate {order[i]} of {S_all})" if args.best_of > 1 else ""))
+                if recognizing(args):
+                    say(f"song {i} chords: {chords_line(recog[order[i]])}")
         if scoring:
             doc = {"best_of": args.best_of, "rank_by": args.rank_by if args.best_of > 1 else None, "bass_relative": bool(args.score_bass_relative),
                    "chords": chd_score is not None, "masked": mask is not None, "steps": int(gen.shape[1] * gen.shape[-2]),
                    "songs": [dict(cands[order[i]], candidate=order[i], file=os.path.basename(stamps[i]) + ".npy") for i in range(S)],
                    "candidates": cands}
+            if recognizing(args):
+                doc["recognized"] = [dict(recog[order[i]], candidate=order[i]) for i in range(S)]
             with open(score_stamp + "_score.json", "w") as f:
                 json.dump(doc, f, indent=1)
             say(f"scores -> {score_stamp}_score.json")

@@ -15,7 +15,8 @@ path, ref:data/midi_to_data.py:109-117) writes.  The dataset song files go throu
 copies the stored bass column as it is; which convention the files of POP909 hold is a property of those files that nothing in this
 tree pins down, so ``bass_relative=True`` (``--score_bass_relative``) reads the block as an offset from the root instead.
 
-CLI: ``python -m polyffusion_amd.score --npy FILE [--cond_npz FILE] [--bass_relative]`` prints one JSON line.
+CLI: ``python -m polyffusion_amd.score --npy FILE [--cond_npz FILE] [--bass_relative] [--chords [--lab OUT]]`` prints one JSON line;
+``--chords`` adds what ``chordrec.recognize_rolls`` recognises in the roll (the reference's extractor on the device) under ``"recognized"``.
 """
 from __future__ import annotations
 
@@ -30,7 +31,8 @@ from . import _lib
 
 IDX = {n: i for i, n in enumerate(_lib.ROLL_COUNTERS)}
 SCORES = ("chord_f1", "chord_fit", "chord_cover", "bass_fit", "integrity", "onset_rate")
-RANK_BY = {"chord": ("chord_f1", True), "bass": ("bass_fit", True), "integrity": ("integrity", False), "texture": ("texture_fit", True)}
+RANK_BY = {"chord": ("chord_f1", True), "bass": ("bass_fit", True), "integrity": ("integrity", False), "texture": ("texture_fit", True),
+           "extracted": ("chord_acc", True)}      # chord_acc comes from chordrec.recognize_rolls, not from the counters above
 
 
 def _ratio(a: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
@@ -161,7 +163,12 @@ def main(argv=None) -> int:
     p.add_argument("--npy", required=True, help="[B, 2, 128, 128] piano roll (or [2B, 2, 64, 128] --autoreg halves)")
     p.add_argument("--cond_npz", help="npz with the array chord [B, 32, 36] the roll was conditioned on; without it the chord-free numbers")
     p.add_argument("--bass_relative", action="store_true", help="read the bass block of a chord row as an offset from the root")
+    p.add_argument("--chords", action="store_true", help="also recognise the chords of the roll (polyffusion_amd.chordrec: the rule of --from_midi, "
+                   "all images one song) and, with --cond_npz, compare them with its chords: a \"recognized\" key in the JSON line")
+    p.add_argument("--lab", metavar="OUT", help="with --chords: write the recognised chords as start<TAB>end<TAB>label lines (transcribe_midi's format)")
     args = p.parse_args(argv)
+    if args.lab and not args.chords:
+        raise SystemExit("--lab belongs to --chords, which was not given")
     x = torch.from_numpy(np.load(args.npy)).float()
     chord = None
     if args.cond_npz:
@@ -177,6 +184,15 @@ def main(argv=None) -> int:
     if not torch.cuda.is_available():
         raise SystemExit("polyffusion_amd.score needs an AMD GPU (no CPU fallback on this path)")
     song = roll_stats(x.cuda(), None if chord is None else chord.cuda(), bass_relative=args.bass_relative).songs(x.shape[0]).report()[0]
+    if args.chords:
+        from . import chordrec
+        try:
+            rec = chordrec.recognize_rolls(x.cuda(), x.shape[0], None if chord is None else chord.cuda(), bass_relative=args.bass_relative)
+        except ValueError as e:
+            raise SystemExit(str(e))
+        song["recognized"] = dict(rec.report()[0], path_score=float(rec.path_score[0]), lab=[[float(a), float(b), n] for a, b, n in rec.lab_rows(0)])
+        if args.lab:
+            chordrec.write_lab(args.lab, rec.lab_rows(0))
     print(json.dumps(dict(song, file=args.npy, images=int(x.shape[0]), steps=int(x.shape[-2]), chords=args.cond_npz,
                           bass_relative=bool(args.bass_relative))))
     return 0
