@@ -561,6 +561,56 @@ typedef struct pf_chord_recognize_args {
 } pf_chord_recognize_args;
 int pf_chord_recognize(const pf_chord_recognize_args* a, void* stream);
 
+/* ---- packed rolls and their nearest neighbours under transposition ("Roll matching"; not in the reference) ----
+ * pf_roll_pack: n images [n][2][steps][128] (channel 0 onset, 1 sustain) -> bits[2][n * steps][4]: plane-major, the images' rows
+ * consecutive, so a song of several images is one run of rows.  Key k of a row is bit k % 32 of word k / 32.  Plane 0 is on = r(onset),
+ * plane 1 is sounding = on | r(sustain), r exactly the rule of pf_roll_stats: v > 0.5 (custom_round: 0.95 < v < 1.05); a NaN is silent.
+ * One launch, ballots only, every output word written.  Refused: null or misaligned (4 bytes) pointers, n or steps <= 0.
+ *
+ * pf_roll_match: both sides are windows into one packed plane.  Side A, the queries: a_bits [rows_a][4] and a_starts[na], the row index
+ * of each window's first row; side B, the corpus: b_bits and b_starts[nb].  Every window is `steps` consecutive rows; windows may overlap,
+ * so a corpus with a window at every bar of every song is stored once.  The starts are trusted, as the other kernels trust their shapes:
+ * every start .. start + steps - 1 must lie inside its plane.  The row offset start * 4 is formed in 64 bits.
+ *   Shifts: k = 0 .. 2 * shifts, s_k = 0, -1, +1, -2, +2, ...  A candidate (b, k) means "the query is corpus window b transposed up by s_k
+ *   semitones".  Its shifted query is qs[t][j] = q[t][j + s] for 0 <= j + s < 128, else 0: query notes that leave the keyboard are dropped.
+ *   inter = |qs AND c|, union = |qs| + |c| - inter.  Two candidates compare as the fractions inter / union, exactly: a / b > c / d is
+ *   a * d > c * b in int64; a candidate with union == 0 counts as 0 / 1.  Per corpus window the kept candidate is the best k, ties to the
+ *   lowest k (s = 0 wins a tie).  Per query the topk best corpus windows are kept in descending order, ties to the lowest b.
+ *   Outputs: top_index / top_shift (the semitones s, not k) / top_inter / top_union [na][topk]; slots beyond nb are -1, 0, 0, 0.  With
+ *   the three table pointers non-NULL, tab_inter / tab_union / tab_shift [na][nb] hold each corpus window's kept candidate.  Every word
+ *   of every output is written: the caller does not pre-zero.
+ *   Three launches (|qs| per query and shift; the scan, a workgroup per PF_ROLL_MATCH_CHUNK corpus windows and 4 queries, which leaves its
+ *   top-k per query in the workspace; a merge of those lists in chunk order), no atomics, nothing allocated, nothing synchronised:
+ *   capturable.  Results do not depend on how queries or corpus are grouped.  Refused before any launch: null arguments, null a_bits /
+ *   a_starts / b_bits / b_starts / top_* / workspace, a_bits / b_bits / workspace not 16-byte or any other pointer not 4-byte aligned,
+ *   na, nb or steps <= 0, shifts outside 0..PF_ROLL_MATCH_MAX_SHIFTS, topk outside 1..PF_ROLL_MATCH_MAX_TOPK, reserved != 0, exactly one
+ *   or two of the three table pointers, workspace_bytes < pf_roll_match_workspace_bytes(na, nb, topk) (which is 0 for arguments the call
+ *   would refuse). */
+#define PF_ROLL_MATCH_CHUNK 256       /* corpus windows one workgroup scans; partial top-k lists are per chunk */
+#define PF_ROLL_MATCH_MAX_SHIFTS 15
+#define PF_ROLL_MATCH_MAX_TOPK 8
+typedef struct pf_roll_match_args {
+  const uint32_t* a_bits;             /* one plane of the queries' rows, [rows_a][4] */
+  const int32_t* a_starts;            /* [na] */
+  const uint32_t* b_bits;             /* one plane of the corpus' rows, [rows_b][4] */
+  const int32_t* b_starts;            /* [nb] */
+  int32_t na, nb, steps;
+  int32_t shifts, topk;
+  int32_t reserved;                   /* 0 */
+  int32_t* top_index;                 /* [na][topk] */
+  int32_t* top_shift;                 /* [na][topk] */
+  int32_t* top_inter;                 /* [na][topk] */
+  int32_t* top_union;                 /* [na][topk] */
+  int32_t* tab_inter;                 /* [na][nb] or NULL (all three or none) */
+  int32_t* tab_union;
+  int32_t* tab_shift;
+  void* workspace;
+  size_t workspace_bytes;
+} pf_roll_match_args;
+int pf_roll_pack(const float* prmat2c, int n, int steps, int custom_round, uint32_t* bits, void* stream);
+size_t pf_roll_match_workspace_bytes(int na, int nb, int topk);
+int pf_roll_match(const pf_roll_match_args* a, void* stream);
+
 /* ---- condition encoders (replace RnnEncoder.forward dl_modules/chord_enc.py:15-22, TextureEncoder.forward
  *      dl_modules/txt_enc.py:23-35 and PianoTreeEncoder.forward dl_modules/pianotree_enc.py:97-121; only the Normal's mean is produced)
  *      PF_ENC_PNOTREE: input_dim = pitch classes + 5 duration digits (135), emb_size = note embedding (128), num_channel = hidden size

@@ -152,6 +152,19 @@ CHORDREC_MAX_BEATS = 512       # PF_CHORDREC_MAX_BEATS: beats of one song
 CHORDREC_MAX_CLASSES = 576     # PF_CHORDREC_MAX_CLASSES
 
 
+class RollMatchArgs(C.Structure):
+    """pf_roll_match_args (include/pfhip.h); filled by ``rollmatch.match_windows`` only."""
+    _fields_ = ([(n, C.c_void_p) for n in ("a_bits", "a_starts", "b_bits", "b_starts")]
+                + [(n, C.c_int32) for n in ("na", "nb", "steps", "shifts", "topk", "reserved")]
+                + [(n, C.c_void_p) for n in ("top_index", "top_shift", "top_inter", "top_union", "tab_inter", "tab_union", "tab_shift", "workspace")]
+                + [("workspace_bytes", C.c_size_t)])
+
+
+ROLL_MATCH_CHUNK = 256         # PF_ROLL_MATCH_CHUNK: corpus windows one workgroup of pf_roll_match scans
+ROLL_MATCH_MAX_SHIFTS = 15     # PF_ROLL_MATCH_MAX_SHIFTS
+ROLL_MATCH_MAX_TOPK = 8        # PF_ROLL_MATCH_MAX_TOPK
+
+
 FEEDBACK = {"row": 0, "batch": 1}   # PF_FEEDBACK_ROW / PF_FEEDBACK_BATCH
 MSE_CHUNK = 2048           # PF_MSE_CHUNK: elements of a row one workgroup of pf_mse_rows reduces
 SLERP_MAX_FRAMES = 64      # PF_SLERP_MAX_FRAMES: frames one pf_slerp_rows call writes
@@ -301,6 +314,9 @@ SIGNATURES = {
     "pf_prmat2c_durations": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "pf_roll_stats": (C.c_int, [C.POINTER(RollStatsArgs), C.c_void_p]),
     "pf_chord_recognize": (C.c_int, [C.POINTER(ChordRecognizeArgs), C.c_void_p]),
+    "pf_roll_pack": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "pf_roll_match_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
+    "pf_roll_match": (C.c_int, [C.POINTER(RollMatchArgs), C.c_void_p]),
     "pf_encoder_create": (C.c_int, [C.c_int] * 6 + [C.POINTER(C.c_void_p)]),
     "pf_encoder_create_dist": (C.c_int, [C.c_int] * 7 + [C.POINTER(C.c_void_p)]),
     "pf_encoder_destroy": (None, [C.c_void_p]),

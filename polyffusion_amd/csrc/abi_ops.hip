@@ -76,6 +76,14 @@ int pf_chord_recognize(const pf_chord_recognize_args* a, void* stream) {
   PF_REQUIRE(a, "pf_chord_recognize: null arguments");
   return launch_chord_recognize(*a, (hipStream_t)stream);
 }
+int pf_roll_pack(const float* prmat2c, int n, int steps, int custom_round, uint32_t* bits, void* stream) {
+  return launch_roll_pack(prmat2c, n, steps, custom_round, bits, (hipStream_t)stream);
+}
+size_t pf_roll_match_workspace_bytes(int na, int nb, int topk) { return roll_match_workspace_bytes(na, nb, topk); }
+int pf_roll_match(const pf_roll_match_args* a, void* stream) {
+  PF_REQUIRE(a, "pf_roll_match: null arguments");
+  return launch_roll_match(*a, (hipStream_t)stream);
+}
 int pf_mlp_geglu_fused(const float* x, int batch, int l, const float* ln_gamma, const float* ln_beta, float ln_eps,
                        const void* w1_bf16x3, const float* b1, const void* w2_bf16x3, const float* b2,
                        float* out, void* out_planes, void* stream) {

@@ -95,6 +95,10 @@ int launch_prmat2c_durations(const float* x, int n, int steps, int custom_round,
 int launch_roll_stats(const pf_roll_stats_args& a, hipStream_t stream);
 // chord recognition (include/pfhip.h, pf_chord_recognize; chordrec.hip): labels, condition rows and comparison counters of whole songs
 int launch_chord_recognize(const pf_chord_recognize_args& a, hipStream_t stream);
+// packed rolls and nearest neighbours under transposition (include/pfhip.h, pf_roll_pack / pf_roll_match; rollmatch.hip)
+int launch_roll_pack(const float* x, int n, int steps, int custom_round, uint32_t* bits, hipStream_t stream);
+size_t roll_match_workspace_bytes(int na, int nb, int topk);
+int launch_roll_match(const pf_roll_match_args& a, hipStream_t stream);
 int launch_matvec(const float* x, int ldx, const float* w, const float* bias, float* y, int ldy, int batch, int n, int k,
                   hipStream_t stream, int n_per_group = 0, int x_group_stride = 0);
 // y[b][n] = expf(sum_k W[n][k] * x[b][k] + bias[n]): the same kernel with the exponential in its epilogue

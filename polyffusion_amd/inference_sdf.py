@@ -32,6 +32,7 @@ import torch
 
 from . import _lib, datasample, midi, synth
 from . import chordrec as pfchordrec
+from . import rollmatch as pfrollmatch
 from . import score as pfscore
 from .model_sdf import ChordEncoder, Polyffusion_SDF, TextureEncoder
 from .params import Params, find_params, load_params, preset
@@ -611,13 +612,28 @@ def make_parser() -> ArgumentParser:
                    "--num_generate of that product would give), score them and keep the best --num_generate, files named by rank; implies --score")
     p.add_argument("--rank_by", choices=list(pfscore.RANK_BY), default="chord", help="what --best_of ranks by: chord (chord_f1, default), bass "
                    "(bass_fit), integrity (lowest first), texture (rhythm against the texture song; chord+txt models only) or extracted "
-                   "(chord_acc of --score_chords: the share of beats whose recognised chord is the conditioning chord)")
+                   "(chord_acc of --score_chords: the share of beats whose recognised chord is the conditioning chord) or novelty (copy_score "
+                   "of --novelty_corpus, lowest first: the least copied candidates are kept)")
     p.add_argument("--score_bass_relative", action="store_true", help="read the bass block of a chord row as an offset from the root "
                    "(default: an absolute pitch class, as --from_midi writes it)")
     p.add_argument("--score_chords", action="store_true", help="extension, with --score / --best_of: recognise the chords of every generated "
                    "song on the GPU by the rule of --from_midi (polyffusion_amd.chordrec) and compare them with the chords the run conditioned "
                    "on: chord_acc, root_acc, chroma_acc, bass_acc, chroma_iou, the counters and the recognised labels per song, and a "
                    "\"recognized\" key in <stamp>_score.json.  With --edit / --morph: chord_acc beside the chord_f1 numbers")
+    # extension: nearest training segment and diversity (polyffusion_amd.rollmatch; pf_roll_pack / pf_roll_match on the images on the device)
+    p.add_argument("--novelty_corpus", metavar="FILE", help="extension, with --score / --best_of: a corpus file of python -m "
+                   "polyffusion_amd.rollmatch build; every candidate's copy_score (the best Jaccard overlap of its note cells with any corpus "
+                   "window under transposition; 1.0: a copy) and its nearest (song, bar, shift) are printed on the song's score line and "
+                   "written to <stamp>_score.json.  The mask of an inpainting run is NOT applied: the whole image is compared, so an inpainted "
+                   "song's nearest neighbour is expected to be its source.  With --edit / --morph: of the edited image / every frame")
+    p.add_argument("--novelty_shifts", type=int, default=6, metavar="S", help="with --novelty_corpus: transpositions of up to S semitones either "
+                   "way are tried (0..15, default 6)")
+    p.add_argument("--novelty_topk", type=int, default=3, metavar="K", help="with --novelty_corpus: matches kept per image (1..8, default 3; the "
+                   "score is the first)")
+    p.add_argument("--novelty_plane", choices=list(pfrollmatch.PLANES), default="onset", help="with --novelty_corpus / --diversity: compare "
+                   "onset cells (default) or sounding cells (onset | sustain)")
+    p.add_argument("--diversity", action="store_true", help="extension, with --score / --best_of: nearest_other per kept song (its best Jaccard "
+                   "overlap with any other kept song, no transposition) and the run's diversity = 1 - mean nearest_other")
     return p
 
 
@@ -630,11 +646,24 @@ def check_score_args(args, cond_type: Optional[str] = None) -> bool:
     if best_of > 1 and getattr(args, "edit", False):
         raise SystemExit("--best_of with --edit: --edit is deterministic, every candidate would be the same song")
     scoring = bool(getattr(args, "score", False)) or best_of > 1
+    dflt = make_parser().get_default
+    novelty_opts = [f"--{k}" for k in ("novelty_shifts", "novelty_topk", "novelty_plane") if getattr(args, k, dflt(k)) != dflt(k)]
     if not scoring:
-        given = [f"--{k}" for k in ("score_bass_relative", "score_chords") if getattr(args, k, False)] + (["--rank_by"] if args.rank_by != "chord" else [])
+        given = ([f"--{k}" for k in ("score_bass_relative", "score_chords", "novelty_corpus", "diversity") if getattr(args, k, False)] + novelty_opts
+                 + (["--rank_by"] if args.rank_by != "chord" else []))
         if given:
             raise SystemExit(f"{', '.join(given)}: these belong to --score / --best_of, which were not given")
         return False
+    corpus = getattr(args, "novelty_corpus", None)
+    if args.rank_by == "novelty" and best_of > 1 and not corpus:
+        raise SystemExit("--rank_by novelty ranks by copy_score, which needs --novelty_corpus FILE")
+    if not corpus and [o for o in novelty_opts if o != "--novelty_plane" or not getattr(args, "diversity", False)]:
+        raise SystemExit(f"{', '.join(novelty_opts)}: these belong to --novelty_corpus, which was not given")
+    if corpus:
+        if not 0 <= args.novelty_shifts <= _lib.ROLL_MATCH_MAX_SHIFTS:
+            raise SystemExit(f"--novelty_shifts {args.novelty_shifts}: 0..{_lib.ROLL_MATCH_MAX_SHIFTS}")
+        if not 1 <= args.novelty_topk <= _lib.ROLL_MATCH_MAX_TOPK:
+            raise SystemExit(f"--novelty_topk {args.novelty_topk}: 1..{_lib.ROLL_MATCH_MAX_TOPK}")
     if cond_type is not None:
         if args.rank_by == "texture" and cond_type != "chord+txt":
             raise SystemExit(f"--rank_by texture compares against the texture song of a chord+txt model; this model's cond_type is {cond_type!r}")
@@ -1053,6 +1082,39 @@ def chords_line(r: dict) -> str:
             + "  chords: " + " ".join(f"{name}*{n}" if n > 1 else name for name, n in runs))
 
 
+def load_novelty_corpus(args):
+    """``--novelty_corpus``: the corpus file, or ``None`` without the flag.  A corpus this run cannot be compared with is a ``SystemExit``:
+    windows of another size than the 128 steps of an image, or cells rounded by another rule than the run's (``v > 0.5``)."""
+    path = getattr(args, "novelty_corpus", None)
+    if not path:
+        return None
+    try:
+        corpus = pfrollmatch.Corpus.load(path)
+    except (OSError, ValueError, KeyError) as e:
+        raise SystemExit(f"--novelty_corpus {path}: {e}")
+    if corpus.steps != 128:
+        raise SystemExit(f"--novelty_corpus {path}: windows of {corpus.steps} steps; a generated image has 128 (rebuild the corpus)")
+    if corpus.custom_round:
+        raise SystemExit(f"--novelty_corpus {path}: built with --custom_round, this run rounds by v > 0.5 (rebuild the corpus without it)")
+    return corpus
+
+
+def novelty_songs(gen: torch.Tensor, corpus, args):
+    """``--novelty_corpus`` on this rank's songs where they live: ``gen`` as in ``score_songs``; every song's rows are cut into windows of
+    128 steps (an image each; the two halves of ``--autoreg`` together) and matched against the corpus.  Returns ``copy_score`` float64
+    ``[n]`` and ``pick`` int32 ``[n, 3]`` (window, shift, image of the song's best match).  No host synchronisation."""
+    n = gen.shape[0]
+    if n == 0:
+        return torch.empty(0, dtype=torch.float64, device=gen.device), torch.empty(0, 3, dtype=torch.int32, device=gen.device)
+    m = pfrollmatch.nearest(gen, corpus, args.novelty_shifts, args.novelty_topk, args.novelty_plane)
+    return m.song_best(gen.shape[1] * gen.shape[-2] // corpus.steps)
+
+
+def novelty_text(c: dict) -> str:
+    w = c["nearest"]
+    return f"copy_score {c['copy_score']:.4f}" + ("" if w is None else f" (nearest {w['song']} bar {w['bar']} shift {w['shift']:+d})")
+
+
 def edit_song(model, params, args, image, cond, cond_tgt, cond_mid, cond_mid_tgt, scale, seed: int, say=print, score_chords=None) -> int:
     """``--edit``: the condition song's own image through ``Experiments.edit``; writes ``<stamp>.mid`` / ``.npy`` with ``_edit<K>`` in the
     stamp and prints the largest relative residual of the last iterate over all steps (and, with ``--edit_roundtrip``, how far the repaint
@@ -1102,6 +1164,11 @@ def edit_song(model, params, args, image, cond, cond_tgt, cond_mid, cond_mid_tgt
             say(f"edit score (chord_acc): source image on source chords {acc('source_on_source_chords')}, on target chords "
                 f"{acc('source_on_target_chords')}; edited image on source chords {acc('edited_on_source_chords')}, on target chords "
                 f"{acc('edited_on_target_chords')}")
+        corpus = load_novelty_corpus(args)
+        if corpus is not None:                                   # the whole song is one candidate: source and edited image
+            for img_name, img in (("source", orig), ("edited", gen)):
+                doc[f"{img_name}_novelty"] = pfrollmatch.songs_report(*novelty_songs(img.unsqueeze(0), corpus, args), corpus)[0]
+            say(f"edit score (novelty): source image {novelty_text(doc['source_novelty'])}; edited image {novelty_text(doc['edited_novelty'])}")
         with open(stamp + "_score.json", "w") as f:
             json.dump(doc, f, indent=1)
     return 0
@@ -1154,7 +1221,16 @@ def morph_songs(model, params, args, image_a, image_b, cond_a, cond_b, cond_mid_
             for name, c in zip(("chord_acc_on_a", "chord_acc_on_b"), score_chords):
                 doc[name] = [r["chord_acc"] for r in recognized_report(*recognize_songs(gen, c[:n], args))]
             doc["recognized"] = [r["labels"] for r in recognized_report(*recognize_songs(gen, None, args))]
+        corpus = load_novelty_corpus(args)
+        if corpus is not None:                                   # every frame is a song of n images
+            doc["novelty"] = pfrollmatch.songs_report(*novelty_songs(gen, corpus, args), corpus)
+        if getattr(args, "diversity", False):
+            pw = pfrollmatch.pairwise(gen, segments=n, plane=args.novelty_plane)
+            doc["nearest_other"], doc["diversity"] = pw["nearest_other"].tolist(), pw["diversity"]
+            say(f"diversity of the {K} frames {doc['diversity']:.4f} (nearest_other per frame: " + ", ".join(f"{v:.4f}" for v in doc["nearest_other"]) + ")")
         for k in range(K):
+            if corpus is not None:
+                say(f"frame {k} novelty: {novelty_text(doc['novelty'][k])}")
             say(f"frame {k} (t = {rec.fractions[k]:.3f}) chord_f1: on A's chords {doc['chord_f1_on_a'][k]:.4f}, on B's chords {doc['chord_f1_on_b'][k]:.4f}"
                 + (f"; chord_acc: on A's chords {doc['chord_acc_on_a'][k]:.4f}, on B's chords {doc['chord_acc_on_b'][k]:.4f}" if recognizing(args) else ""))
         with open(stamp + "_score.json", "w") as f:
@@ -1427,6 +1503,7 @@ def main(argv=None):
     say(f"generating {S} song(s) x {B} segment(s) with uncond_scale = {scale} on {world} GPU(s)")
     if args.best_of > 1:
         say(f"best of {args.best_of}: {S_all} candidates, the best {S} by {pfscore.RANK_BY[args.rank_by][0]} are kept")
+    novelty_corpus = load_novelty_corpus(args) if scoring else None      # refused before the songs are generated, not after
     gen, expmt = generate_songs(model, params, args, cond, cond_mid, orig, mask, seed, rank, world, cond_concat=cond_concat, uncond_scale=scale)
     counters = texture = None
     if scoring:
@@ -1438,6 +1515,8 @@ def main(argv=None):
         texture = None if texture is None else pfdist.gather_rows(texture, S_all, rank, world)
         if recognizing(args):
             rc_counters, rc_labels = (pfdist.gather_rows(v, S_all, rank, world) for v in recognize_songs(gen, chd_score, args))
+        if novelty_corpus is not None:
+            nv_score, nv_pick = (pfdist.gather_rows(v, S_all, rank, world) for v in novelty_songs(gen, novelty_corpus, args))
     gen = pfdist.gather_rows(gen, S_all, rank, world)   # [S, ...] on every rank (131 KB per image; the only end-of-run exchange)
     if not bool(torch.isfinite(gen).all()):
         # the note threshold (> 0.5) would turn a NaN into silence: refuse instead.  The one known way to get here is an activation beyond
@@ -1458,11 +1537,17 @@ def main(argv=None):
                 recog = recognized_report(rc_counters, rc_labels)
                 for c, r in zip(cands, recog):
                     c.update({k: r[k] for k in pfchordrec.SCORES})
+            if novelty_corpus is not None:
+                for c, r in zip(cands, pfrollmatch.songs_report(nv_score, nv_pick, novelty_corpus)):
+                    c.update(r)
             if args.best_of > 1:
                 key, descending = pfscore.RANK_BY[args.rank_by]
                 order = pfscore.rank([c[key] for c in cands], S, descending)
             score_stamp = os.path.join(args.output_dir, expmt._stamp(scale, args.autoreg, extra, args.joint_blend if args.joint else None))
         gen = gen[torch.tensor(order, device=gen.device)] if order != list(range(S_all)) else gen
+        diversity = None
+        if scoring and args.diversity:                           # of the kept songs, among themselves, whole images, no transposition
+            diversity = pfrollmatch.pairwise(gen[:S], segments=gen.shape[1] * gen.shape[-2] // 128, plane=args.novelty_plane, steps=128)
         for i in range(S):
             stamp = os.path.join(args.output_dir, expmt._stamp(scale, args.autoreg, extra, args.joint_blend if args.joint else None)
                                  + (f"_{i}" if S > 1 else ""))
@@ -1472,7 +1557,9 @@ def main(argv=None):
             midi.prmat2c_to_midi_file(gen[i], stamp + ".mid", inp_mask=None if args.autoreg else mask)
             say(f"song {i}: piano_roll {tuple(gen[i].shape)}  onsets>0.5: {int((gen[i][:, 0] > 0.5).sum())}  -> {stamp}.mid")
             if scoring:
-                say(f"song {i} score: {score_line(cands[order[i]])}" + (f"  (candidate {order[i]} of {S_all})" if args.best_of > 1 else ""))
+                say(f"song {i} score: {score_line(cands[order[i]])}" + (f"  {novelty_text(cands[order[i]])}" if novelty_corpus is not None else "")
+                    + (f"  nearest_other {diversity['nearest_other'][i]:.4f}" if diversity is not None else "")
+                    + (f"  (candidate {order[i]} of {S_all})" if args.best_of > 1 else ""))
                 if recognizing(args):
                     say(f"song {i} chords: {chords_line(recog[order[i]])}")
         if scoring:
@@ -1482,6 +1569,14 @@ def main(argv=None):
                    "candidates": cands}
             if recognizing(args):
                 doc["recognized"] = [dict(recog[order[i]], candidate=order[i]) for i in range(S)]
+            if novelty_corpus is not None:
+                doc["novelty"] = {"corpus": args.novelty_corpus, "windows": len(novelty_corpus), "shifts": args.novelty_shifts,
+                                  "topk": args.novelty_topk, "plane": args.novelty_plane, "masked": False}
+            if diversity is not None:
+                for i in range(S):
+                    doc["songs"][i]["nearest_other"] = float(diversity["nearest_other"][i])
+                doc["diversity"] = diversity["diversity"]
+                say(f"diversity of the {S} kept song(s): {diversity['diversity']:.4f}")
             with open(score_stamp + "_score.json", "w") as f:
                 json.dump(doc, f, indent=1)
             say(f"scores -> {score_stamp}_score.json")

@@ -15,7 +15,8 @@ path, ref:data/midi_to_data.py:109-117) writes.  The dataset song files go throu
 copies the stored bass column as it is; which convention the files of POP909 hold is a property of those files that nothing in this
 tree pins down, so ``bass_relative=True`` (``--score_bass_relative``) reads the block as an offset from the root instead.
 
-CLI: ``python -m polyffusion_amd.score --npy FILE [--cond_npz FILE] [--bass_relative] [--chords [--lab OUT]]`` prints one JSON line;
+CLI: ``python -m polyffusion_amd.score --npy FILE [--cond_npz FILE] [--bass_relative] [--chords [--lab OUT]] [--novelty_corpus FILE
+[--novelty_shifts S --novelty_topk K]]`` prints one JSON line (``--novelty_corpus``: ``rollmatch.nearest`` against a corpus file);
 ``--chords`` adds what ``chordrec.recognize_rolls`` recognises in the roll (the reference's extractor on the device) under ``"recognized"``.
 """
 from __future__ import annotations
@@ -32,7 +33,8 @@ from . import _lib
 IDX = {n: i for i, n in enumerate(_lib.ROLL_COUNTERS)}
 SCORES = ("chord_f1", "chord_fit", "chord_cover", "bass_fit", "integrity", "onset_rate")
 RANK_BY = {"chord": ("chord_f1", True), "bass": ("bass_fit", True), "integrity": ("integrity", False), "texture": ("texture_fit", True),
-           "extracted": ("chord_acc", True)}      # chord_acc comes from chordrec.recognize_rolls, not from the counters above
+           "extracted": ("chord_acc", True),      # chord_acc comes from chordrec.recognize_rolls, not from the counters above
+           "novelty": ("copy_score", False)}      # copy_score comes from rollmatch.nearest: the least copied candidates are kept
 
 
 def _ratio(a: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
@@ -166,9 +168,18 @@ def main(argv=None) -> int:
     p.add_argument("--chords", action="store_true", help="also recognise the chords of the roll (polyffusion_amd.chordrec: the rule of --from_midi, "
                    "all images one song) and, with --cond_npz, compare them with its chords: a \"recognized\" key in the JSON line")
     p.add_argument("--lab", metavar="OUT", help="with --chords: write the recognised chords as start<TAB>end<TAB>label lines (transcribe_midi's format)")
+    p.add_argument("--novelty_corpus", metavar="FILE", help="a corpus file of python -m polyffusion_amd.rollmatch build: adds the roll's "
+                   "copy_score (best Jaccard overlap of an image's onset cells with any corpus window under transposition), where it was found "
+                   "and the matches of every image under \"novelty\"")
+    p.add_argument("--novelty_shifts", type=int, default=6, metavar="S", help="transpositions of up to S semitones either way (0..15, default 6)")
+    p.add_argument("--novelty_topk", type=int, default=3, metavar="K", help="matches kept per image (1..8, default 3)")
     args = p.parse_args(argv)
     if args.lab and not args.chords:
         raise SystemExit("--lab belongs to --chords, which was not given")
+    if not args.novelty_corpus and (args.novelty_shifts != 6 or args.novelty_topk != 3):
+        raise SystemExit("--novelty_shifts / --novelty_topk belong to --novelty_corpus, which was not given")
+    if not (0 <= args.novelty_shifts <= _lib.ROLL_MATCH_MAX_SHIFTS and 1 <= args.novelty_topk <= _lib.ROLL_MATCH_MAX_TOPK):
+        raise SystemExit(f"--novelty_shifts 0..{_lib.ROLL_MATCH_MAX_SHIFTS}, --novelty_topk 1..{_lib.ROLL_MATCH_MAX_TOPK}")
     x = torch.from_numpy(np.load(args.npy)).float()
     chord = None
     if args.cond_npz:
@@ -193,6 +204,15 @@ def main(argv=None) -> int:
         song["recognized"] = dict(rec.report()[0], path_score=float(rec.path_score[0]), lab=[[float(a), float(b), n] for a, b, n in rec.lab_rows(0)])
         if args.lab:
             chordrec.write_lab(args.lab, rec.lab_rows(0))
+    if args.novelty_corpus:
+        from . import rollmatch
+        try:
+            corpus = rollmatch.Corpus.load(args.novelty_corpus)
+            m = rollmatch.nearest(x.cuda(), corpus, args.novelty_shifts, args.novelty_topk)
+        except (OSError, ValueError, KeyError) as e:
+            raise SystemExit(f"--novelty_corpus {args.novelty_corpus}: {e}")
+        song.update(m.songs(int(m.index.shape[0]))[0])
+        song["novelty"] = dict(corpus=args.novelty_corpus, shifts=args.novelty_shifts, topk=args.novelty_topk, plane="onset", matches=m.report())
     print(json.dumps(dict(song, file=args.npy, images=int(x.shape[0]), steps=int(x.shape[-2]), chords=args.cond_npz,
                           bass_relative=bool(args.bass_relative))))
     return 0
