@@ -763,6 +763,25 @@ int pf_time_embed(const int64_t* t, const float* w0, const float* b0, const floa
  * (ungrouped only).  A row's sum is accumulated in the same order whatever its position in the batch. */
 int pf_matvec(const float* x, int ldx, const float* w, const float* bias, float* y, int ldy, int batch, int n, int k, int n_per_group,
               int x_group_stride, int exp_flag, void* stream);
+/* One GRU cell update of the encoders, in place (torch gate order r | z | n): h = (1 - z) n + z h with r = sigmoid(gi_r + gh_r),
+ * z = sigmoid(gi_z + gh_z), n = tanh(gi_n + r gh_n); gi = W_ih x + b_ih, gh = W_hh h + b_hh [rows][3 hidden], h rows ld_h floats apart.
+ * lens == NULL: row b reads gi + b * ld_gi (ld_gi >= 3 hidden; seq_len, step, reverse unused).  lens != NULL: the update over packed
+ * variable-length sequences, gi [rows][seq_len][3 hidden] (ld_gi unused): row b takes part while step < lens[b] and reads element step
+ * (forward) or lens[b] - 1 - step (reverse); any other row keeps its bits.  Null pointers, non-positive sizes, ld_h < hidden, a negative
+ * step and rows * hidden >= 2^31 are refused. */
+int pf_gru_gates(const float* gi, int ld_gi, const float* gh, float* h, int ld_h, int rows, int hidden, const int* lens, int seq_len,
+                 int step, int reverse, void* stream);
+/* One fused GRU step of the decoders for R rows: gi = Wx . x + add1 + add2, gh = Wh . h_in + b_hh, h_out = (1 - z) n + z h_in (gates as
+ * above).  x [R][ldx] (Kx columns read; ldx 0: one row for every row of the batch; Kx 0: no x part), Wx [3H][ldwx] (a column slice of
+ * a wider matrix: ldwx >= Kx), Wh [3H][H], h_in / h_out [R][H], add1 / add2 [R][ld1 / ld2] or NULL (a stride of 0 broadcasts one row).
+ * Refused before anything is enqueued: H % 4 != 0, wh or h_in not 16-byte aligned, 8 (H + Kx) floats above 64 KiB, h_out == h_in. */
+typedef struct pf_gru_step_args {
+  const float* x; int ldx, Kx; const float* wx; int ldwx;
+  const float* h_in; const float* wh; const float* b_hh;
+  const float* add1; int ld1; const float* add2; int ld2;
+  float* h_out; int R, H;
+} pf_gru_step_args;
+int pf_gru_step(const pf_gru_step_args* a, void* stream);
 /* LayerNorm applied and split into bf16 hi/lo planes [rows][c] | [rows][c] (the A operand of pf_conv2d with a_planes=1);
  * replaces pf_ln_stats + the LayerNorm GEMM prologue for the transformer block's q/k/v and GeGLU projections */
 int pf_ln_planes(const float* x, int rows, int c, float eps, const float* gamma, const float* beta, void* planes, void* stream);

@@ -102,8 +102,9 @@ def pianotree_encoder_mean(w: Tensors, grid: torch.Tensor, pitch_pad: int = 130)
     B, T, S, _ = grid.shape
     P = w["note_embedding.weight"].shape[1] - 5
     lengths = S - (grid[..., 0] == pitch_pad).sum(-1).reshape(-1)
-    onehot = F.one_hot(grid[..., 0], P + 1)[..., :P].float()
-    x = torch.cat([onehot, grid[..., 1:].float()], dim=-1)
+    dtype = w["note_embedding.weight"].dtype      # float32 as the reference runs it, float64 as an oracle
+    onehot = F.one_hot(grid[..., 0], P + 1)[..., :P].to(dtype)
+    x = torch.cat([onehot, grid[..., 1:].to(dtype)], dim=-1)
     emb = F.linear(x, w["note_embedding.weight"], w["note_embedding.bias"]).reshape(B * T, S, -1)
     g = "enc_notes_gru."
     hf = gru_direction_packed(emb, lengths, w[g + "weight_ih_l0"], w[g + "weight_hh_l0"], w[g + "bias_ih_l0"], w[g + "bias_hh_l0"], False)

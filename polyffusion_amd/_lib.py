@@ -126,6 +126,13 @@ class ChordForcedArgs(C.Structure):
                 ("root", C.c_void_p), ("chroma", C.c_void_p), ("bass", C.c_void_p), ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t)]
 
 
+class GruStepArgs(C.Structure):
+    """pf_gru_step_args (include/pfhip.h); filled by the recurrent-kernel matrix (tests/test_gpu_rnn_matrix.py) only."""
+    _fields_ = [("x", C.c_void_p), ("ldx", C.c_int), ("Kx", C.c_int), ("wx", C.c_void_p), ("ldwx", C.c_int), ("h_in", C.c_void_p),
+                ("wh", C.c_void_p), ("b_hh", C.c_void_p), ("add1", C.c_void_p), ("ld1", C.c_int), ("add2", C.c_void_p), ("ld2", C.c_int),
+                ("h_out", C.c_void_p), ("R", C.c_int), ("H", C.c_int)]
+
+
 class RollStatsArgs(C.Structure):
     """pf_roll_stats_args (include/pfhip.h); filled by ``score.roll_stats`` only."""
     _fields_ = ([(n, C.c_void_p) for n in ("prmat2c", "chord", "mask")] + [(n, C.c_int32) for n in ("n", "steps", "custom_round", "bass_relative")]
@@ -360,6 +367,8 @@ SIGNATURES = {
     "pf_conv_out": (C.c_int, [C.c_void_p] * 6 + [C.c_int] * 5 + [C.c_void_p]),
     "pf_time_embed": (C.c_int, [C.c_void_p] * 6 + [C.c_int] * 3 + [C.c_void_p]),
     "pf_matvec": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p] + [C.c_int] * 7 + [C.c_void_p]),
+    "pf_gru_gates": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p] + [C.c_int] * 3 + [C.c_void_p] + [C.c_int] * 3 + [C.c_void_p]),
+    "pf_gru_step": (C.c_int, [C.POINTER(GruStepArgs), C.c_void_p]),
     "pf_ln_planes": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "pf_mlp_geglu_fused": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p,
                                      C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),

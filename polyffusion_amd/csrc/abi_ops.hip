@@ -124,6 +124,22 @@ int pf_matvec(const float* x, int ldx, const float* w, const float* bias, float*
   return exp_flag ? launch_matvec_exp(x, ldx, w, bias, y, ldy, batch, n, k, (hipStream_t)stream)
                   : launch_matvec(x, ldx, w, bias, y, ldy, batch, n, k, (hipStream_t)stream, n_per_group, x_group_stride);
 }
+int pf_gru_gates(const float* gi, int ld_gi, const float* gh, float* h, int ld_h, int rows, int hidden, const int* lens, int seq_len,
+                 int step, int reverse, void* stream) {
+  PF_REQUIRE(gi && gh && h && rows > 0 && hidden > 0, "pf_gru_gates: bad arguments");
+  PF_REQUIRE(ld_h >= hidden, "pf_gru_gates: ld_h=%d below hidden=%d", ld_h, hidden);
+  PF_REQUIRE((int64_t)rows * hidden < ((int64_t)1 << 31), "pf_gru_gates: rows * hidden must stay below 2^31");
+  if (lens) {
+    PF_REQUIRE(seq_len > 0 && step >= 0, "pf_gru_gates: seq_len must be positive and step non-negative");
+    return launch_gru_gates_masked(gi, gh, h, ld_h, rows, hidden, seq_len, lens, step, reverse != 0, (hipStream_t)stream);
+  }
+  PF_REQUIRE(ld_gi >= 3 * hidden, "pf_gru_gates: ld_gi=%d below 3 * hidden", ld_gi);
+  return launch_gru_gates(gi, ld_gi, gh, h, ld_h, rows, hidden, (hipStream_t)stream);
+}
+int pf_gru_step(const pf_gru_step_args* a, void* stream) {
+  PF_REQUIRE(a, "pf_gru_step: null arguments");
+  return launch_gru_step_flat(*a, (hipStream_t)stream);
+}
 int pf_conv_stats_tiles(const pf_conv_args* a) { return a ? conv_plan(*a).stats_tiles : 0; }
 size_t pf_conv_splitk_ws_bytes(const pf_conv_args* a) { return a ? conv_plan(*a).splitk_ws_bytes : 0; }
 int pf_conv_describe(const pf_conv_args* a, pf_conv_plan_info* out) {

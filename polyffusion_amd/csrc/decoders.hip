@@ -474,6 +474,23 @@ int launch_gru_step(const GruStepArgs& a, hipStream_t s) {
 
 }  // namespace
 
+// pf_gru_step: the kernel alone, with everything the decode walk guarantees by construction checked here
+int pf::launch_gru_step_flat(const pf_gru_step_args& f, hipStream_t s) {
+  PF_REQUIRE(f.h_in && f.wh && f.b_hh && f.h_out && f.R > 0 && f.H > 0 && f.Kx >= 0, "pf_gru_step: bad arguments");
+  PF_REQUIRE(f.H % 4 == 0, "pf_gru_step: H=%d must be a multiple of 4", f.H);
+  PF_REQUIRE(((uintptr_t)f.wh & 15) == 0 && ((uintptr_t)f.h_in & 15) == 0, "pf_gru_step: wh and h_in must be 16-byte aligned");
+  PF_REQUIRE((size_t)RT * ((size_t)f.H + f.Kx) * sizeof(float) <= 64 * 1024, "pf_gru_step: H=%d + Kx=%d rows of 8 do not fit 64 KiB", f.H, f.Kx);
+  PF_REQUIRE(f.h_out != f.h_in, "pf_gru_step: h_out must not be h_in (other workgroups still read it)");
+  PF_REQUIRE(f.Kx == 0 || (f.x && f.wx && f.ldwx >= f.Kx && (f.ldx == 0 || f.ldx >= f.Kx)), "pf_gru_step: bad x / wx");
+  PF_REQUIRE((!f.add1 || f.ld1 == 0 || f.ld1 >= 3 * f.H) && (!f.add2 || f.ld2 == 0 || f.ld2 >= 3 * f.H), "pf_gru_step: bad add1 / add2 stride");
+  GruStepArgs a;
+  a.x = f.x; a.ldx = f.ldx; a.Kx = f.Kx; a.wx = f.wx; a.ldwx = f.ldwx;
+  a.h_in = f.h_in; a.wh = f.wh; a.b_hh = f.b_hh;
+  a.add1 = f.add1; a.ld1 = f.ld1; a.add2 = f.add2; a.ld2 = f.ld2;
+  a.h_out = f.h_out; a.R = f.R; a.H = f.H;
+  return launch_gru_step(a, s);
+}
+
 struct pf_decoder {
   int kind = 0;
   int S = 0, HD = 16;                                          // pnotree: max_simu_note, dec_dur_hid_size

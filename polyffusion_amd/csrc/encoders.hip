@@ -32,6 +32,8 @@ int pf_encoder_create_dist(int kind, int input_dim, int emb_size, int hidden_dim
                            pf_encoder** out) {
   PF_REQUIRE(out && (kind == PF_ENC_CHORD || kind == PF_ENC_TEXTURE || kind == PF_ENC_PNOTREE), "pf_encoder_create: bad kind");
   PF_REQUIRE(hidden_dim > 0 && z_dim > 0, "pf_encoder_create: bad dims");
+  // linear_mu contracts over 2 * hidden_dim, and the batched mat-vec takes K <= 2048: refused here, not after the GRU has been enqueued
+  PF_REQUIRE(hidden_dim <= 1024, "pf_encoder_create: hidden_dim=%d above 1024 (linear_mu's mat-vec takes K = 2 * hidden_dim <= 2048)", hidden_dim);
   PF_REQUIRE(!with_scale || kind != PF_ENC_PNOTREE, "pf_encoder_create_dist: the scale head exists for the chord and texture encoders only");
   std::unique_ptr<pf_encoder> e(new pf_encoder());
   e->with_scale = with_scale != 0;
@@ -53,6 +55,8 @@ int pf_encoder_create_dist(int kind, int input_dim, int emb_size, int hidden_dim
     e->fc2 = wt.linear("fc2", emb_size, 1000);
     gru_in = emb_size;
   }
+  PF_REQUIRE(gru_in > 0 && gru_in <= 2048 && emb_size <= 2048 && (kind != PF_ENC_TEXTURE || num_channel * 29 <= 2048),
+             "pf_encoder_create: a contraction longer than the mat-vec's 2048 (GRU input %d, emb_size %d, num_channel %d)", gru_in, emb_size, num_channel);
   wt.gru(kind == PF_ENC_PNOTREE ? "enc_time_gru" : "gru", gru_in, hidden_dim, 2, e->gru);
   e->mu = wt.linear("linear_mu", z_dim, 2 * hidden_dim);
   if (e->with_scale) {   // last in the table: everything before it sits where it does without the scale head

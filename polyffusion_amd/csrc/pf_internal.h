@@ -175,6 +175,8 @@ int launch_gru_gates_masked(const float* gi, const float* gh, float* h, int ld_h
                             int step, int reverse, hipStream_t s);
 int launch_txt_frontend(const float* pr, const float* w, const float* bias, float* out, int batch, int num_channel,
                         hipStream_t s);
+// decoder kernel: one fused GRU step from the flat arguments of pf_gru_step (decoders.hip)
+int launch_gru_step_flat(const pf_gru_step_args& a, hipStream_t s);
 
 }  // namespace pf
 
