@@ -142,7 +142,7 @@ class DDIMSamplerRef:
 
 
 def ddpm_update_f32(x, eps, coef, noise_p=None, noise_q=None, orig=None, mask=None):
-    """The library's DDPM / RePaint update (``ddpm_update_v`` of csrc/small_kernels.hip) in numpy float32: one rounded operation per
+    """The library's DDPM / RePaint update (``ddpm_update_v`` of csrc/sampler_steps.hip) in numpy float32: one rounded operation per
     kernel operation, in the kernel's order.  The kernel issues one opaque VALU instruction per operation (no contraction), so for
     inputs without subnormal intermediates this gives the same BITS.  ``coef``: the seven floats of ``pf_ddpm_coef`` in field order
     (c_recip, c_recipm1, c_x0, c_xt, sigma, sqrt_ab, sqrt_1mab); arrays float32; ``None`` = the term is absent."""

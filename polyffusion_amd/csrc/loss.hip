@@ -5,35 +5,14 @@
 // Both read and write 16 bytes per lane and take one Philox call per four elements when the noise is drawn (or re-drawn) in the kernel.
 // And the objective of the chord VAE (Chord_8Bar.chord_loss, models/model_chd_8bar.py:21-39):
 //   chord_ce_rows - per-sample sums of the three cross-entropies (root, chroma, bass) in float64, one workgroup per row.
-#include "noise.h"
+#include "elementwise.h"
 
 namespace pf {
 
 namespace {
 
-constexpr int kThreads = 256;
+constexpr int kThreads = kRowThreads;
 constexpr int kQChunk = 4 * kThreads;            // elements of a row one qsample workgroup owns: one 16-byte group per lane
-constexpr int kMseGroups = PF_MSE_CHUNK / 4 / kThreads;   // 16-byte groups of a chunk per lane
-static_assert(PF_MSE_CHUNK == 4 * kThreads * kMseGroups, "PF_MSE_CHUNK must be a whole number of 16-byte groups per lane");
-
-// four consecutive elements of a row starting at element e (a multiple of 4): one 16-byte access when the tensor allows it (VEC),
-// else element by element; elements at or past `n` read as 0 / are not written
-template <bool VEC>
-__device__ __forceinline__ f32x4 load4(const float* __restrict__ p, size_t e, size_t n) {
-  if (VEC) return *reinterpret_cast<const f32x4*>(p + e);
-  f32x4 v = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-  for (int j = 0; j < 4; ++j)
-    if (e + j < n) v[j] = p[e + j];
-  return v;
-}
-template <bool VEC>
-__device__ __forceinline__ void store4(float* p, size_t e, size_t n, f32x4 v) {
-  if (VEC) { *reinterpret_cast<f32x4*>(p + e) = v; return; }
-#pragma unroll
-  for (int j = 0; j < 4; ++j)
-    if (e + j < n) p[e + j] = v[j];
-}
 
 // workgroup = (row, chunk of kQChunk elements); lane = one 16-byte group.  x_t and x0 carry no __restrict__: x_t may alias x0.
 template <bool VEC, bool RNG>
@@ -62,52 +41,41 @@ __global__ __launch_bounds__(kThreads) void qsample_rows_kernel(const float* x0,
   store4<VEC>(xt + base, e, row_elems, o);
 }
 
-// workgroup = (row, chunk of PF_MSE_CHUNK elements).  Lane l owns groups l, l + 256, ... of the chunk and adds their squares in element
-// order; the lanes of a wave are combined by a butterfly (every lane ends with the same sum), the four waves in wave order.  The order is
-// fixed by (row_elems, element index) alone, so VEC and the element-by-element form give the same bits.
+// The row reduction of elementwise.h with one sum: a lane adds the squares of its groups in element order.  The order is fixed by
+// (row_elems, element index) alone, so VEC and the element-by-element form give the same bits.
 template <bool VEC, bool RNG>
 __global__ __launch_bounds__(kThreads) void mse_partial_kernel(const float* __restrict__ eps, const float* __restrict__ noise, uint64_t seed,
                                                               uint64_t draw, uint64_t off, double* __restrict__ partial, size_t row_elems,
                                                               unsigned chunks) {
-  __shared__ double wave_sum[kThreads / 64];
   const unsigned row = blockIdx.x / chunks, chunk = blockIdx.x - row * chunks;
   const size_t base = (size_t)row * row_elems;
-  double acc = 0.0;
+  double acc[1] = {0.0};
 #pragma unroll
-  for (int k = 0; k < kMseGroups; ++k) {
-    const size_t e = (size_t)chunk * PF_MSE_CHUNK + 4 * ((size_t)k * kThreads + threadIdx.x);
+  for (int k = 0; k < kRowGroups; ++k) {
+    const size_t e = row_group_elem(chunk, k);
     if (e < row_elems) {
       const f32x4 nz = RNG ? philox_normal4v((off + base + e) >> 2, draw, seed) : load4<VEC>(noise + base, e, row_elems);
       const f32x4 ev = load4<VEC>(eps + base, e, row_elems);
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
         const double d = (double)sub_rn(nz[j], ev[j]);      // the difference in float32, as the reference forms it
-        acc += d * d;                                       // exact product (48 bits), float64 sum
+        acc[0] += d * d;                                    // exact product (48 bits), float64 sum
       }
     }
   }
-#pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) acc += __shfl_xor(acc, m, 64);
-  if ((threadIdx.x & 63) == 0) wave_sum[threadIdx.x >> 6] = acc;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    double s = wave_sum[0];
-#pragma unroll
-    for (int w = 1; w < kThreads / 64; ++w) s += wave_sum[w];
-    partial[(size_t)row * chunks + chunk] = s;
-  }
+  row_reduce_store(acc, partial, row, chunks, chunk);
 }
 // one lane per row: the row's partials in index order
 __global__ void mse_finish_kernel(const double* __restrict__ partial, double* __restrict__ row_sum, int rows, unsigned chunks) {
   const int row = blockIdx.x * blockDim.x + threadIdx.x;
   if (row >= rows) return;
-  double s = 0.0;
-  for (unsigned c = 0; c < chunks; ++c) s += partial[(size_t)row * chunks + c];
-  row_sum[row] = s;
+  double s[1];
+  row_partials_sum(partial, row, chunks, s);
+  row_sum[row] = s[0];
 }
 
 // ---- chord cross-entropy.  A row has 14 * n_step items (per step: the root, 12 chroma bits, the bass); lane l owns items l, l + 256, ...
-// in index order, the lanes of a wave are combined by a butterfly and the four waves in wave order: an order fixed by n_step alone.
+// in index order, then the butterfly and the four waves in wave order of row_reduce_store: an order fixed by n_step alone.
 // -log_softmax(x)[target] = max + log(sum_j exp(x_j - max)) - x_target with x widened to float64 first.
 template <int N>
 __device__ __forceinline__ double ce_item(const float* __restrict__ x, int target, int& hit) {
@@ -135,8 +103,6 @@ __device__ __forceinline__ int argmax12(const float* __restrict__ g) {
 __global__ __launch_bounds__(kThreads) void chord_ce_rows_kernel(const float* __restrict__ root, const float* __restrict__ chroma,
                                                                 const float* __restrict__ bass, const float* __restrict__ gt, int n_step,
                                                                 double* __restrict__ ce_rows, int32_t* __restrict__ hit_rows) {
-  __shared__ double wsum[kThreads / 64][3];
-  __shared__ int whit[kThreads / 64][3];
   const int row = blockIdx.x;
   double acc[3] = {0.0, 0.0, 0.0};
   int hits[3] = {0, 0, 0};
@@ -157,28 +123,9 @@ __global__ __launch_bounds__(kThreads) void chord_ce_rows_kernel(const float* __
       hits[1] += hit;
     }
   }
-#pragma unroll
-  for (int q = 0; q < 3; ++q) {
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) {
-      acc[q] += __shfl_xor(acc[q], m, 64);
-      hits[q] += __shfl_xor(hits[q], m, 64);
-    }
-    if ((threadIdx.x & 63) == 0) { wsum[threadIdx.x >> 6][q] = acc[q]; whit[threadIdx.x >> 6][q] = hits[q]; }
-  }
-  __syncthreads();
-  if (threadIdx.x < 3) {
-    double s = wsum[0][threadIdx.x];
-    int h = whit[0][threadIdx.x];
-#pragma unroll
-    for (int w = 1; w < kThreads / 64; ++w) { s += wsum[w][threadIdx.x]; h += whit[w][threadIdx.x]; }
-    ce_rows[(size_t)row * 3 + threadIdx.x] = s;
-    if (hit_rows) hit_rows[(size_t)row * 3 + threadIdx.x] = h;
-  }
+  row_reduce_store(acc, ce_rows, row, 1, 0);                       // a row is one chunk: the sums land in ce_rows[row][3]
+  if (hit_rows) row_reduce_store(hits, hit_rows, row, 1, 0);       // (uniform over the workgroup; integers: exact in any order)
 }
-
-inline bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
-inline size_t chunks_of(size_t row_elems, size_t chunk) { return (row_elems + chunk - 1) / chunk; }
 
 }  // namespace
 
@@ -191,7 +138,7 @@ int launch_qsample_rows(const pf_qsample_rows_args& a, hipStream_t s) {
   PF_REQUIRE(a.x0 && a.t && a.sqrt_ab && a.sqrt_1mab && a.x_t && a.rows > 0 && a.row_elems > 0 && a.n_steps > 0, "qsample_rows: bad arguments");
   const size_t chunks = chunks_of(a.row_elems, kQChunk);
   PF_REQUIRE(chunks * (size_t)a.rows < (1ull << 31), "qsample_rows: %d rows of %zu elements are more workgroups than one launch holds", a.rows, a.row_elems);
-  const bool vec = a.row_elems % 4 == 0 && aligned16(a.x0) && aligned16(a.x_t) && aligned16(a.noise) && aligned16(a.noise_out);
+  const bool vec = a.row_elems % 4 == 0 && aligned16({a.x0, a.x_t, a.noise, a.noise_out});
   const dim3 grid((unsigned)(chunks * a.rows)), block(kThreads);
   const long long* t = reinterpret_cast<const long long*>(a.t);
   if (a.rng) {
@@ -219,7 +166,7 @@ int launch_mse_rows(const pf_mse_rows_args& a, hipStream_t s) {
   PF_REQUIRE(chunks * (size_t)a.rows < (1ull << 31), "mse_rows: %d rows of %zu elements are more workgroups than one launch holds", a.rows, a.row_elems);
   PF_REQUIRE(a.workspace && a.workspace_bytes >= need && ((uintptr_t)a.workspace & 7) == 0 && ((uintptr_t)a.row_sum & 7) == 0,
              "mse_rows: workspace of %zu bytes (8-byte aligned) required, got %zu", need, a.workspace_bytes);
-  const bool vec = a.row_elems % 4 == 0 && aligned16(a.eps_theta) && aligned16(a.noise);
+  const bool vec = a.row_elems % 4 == 0 && aligned16({a.eps_theta, a.noise});
   const dim3 grid((unsigned)(chunks * a.rows)), block(kThreads);
   double* partial = reinterpret_cast<double*>(a.workspace);
   if (a.rng) {

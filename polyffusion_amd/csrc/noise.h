@@ -1,4 +1,4 @@
-// noise.h - device helpers shared by the elementwise kernels of small_kernels.hip and loss.hip: the individually rounded fp32
+// noise.h - device helpers shared by the elementwise kernels of sampler_steps.hip, small_kernels.hip and loss.hip: the individually rounded fp32
 // operations and the counter-based Gaussian generator.  Every translation unit that includes this compiles the SAME bodies, which is
 // what makes "noise drawn in the kernel" bit-identical to pf_randn wherever it is drawn.
 #pragma once

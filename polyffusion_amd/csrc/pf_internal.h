@@ -105,7 +105,7 @@ int launch_matvec(const float* x, int ldx, const float* w, const float* bias, fl
 int launch_matvec_exp(const float* x, int ldx, const float* w, const float* bias, float* y, int ldy, int batch, int n, int k,
                       hipStream_t stream);
 
-// sampler elementwise kernels
+// sampler elementwise kernels (sampler_steps.hip, written against elementwise.h)
 int launch_cfg_combine(const float* eps2, float scale, float* eps, size_t n, hipStream_t s);
 int launch_cfg_combine3(const float* eps3, float s1, float s2, float* eps, size_t n, hipStream_t s);
 // overlapping windows along the time axis: canvas -> window batch, and window eps -> canvas eps with the guidance combine folded in
@@ -152,7 +152,7 @@ int launch_convT_f32(const float* x, int batch, int h, int w, int cin, const flo
 int launch_ddpm_time_embed(const int64_t* t, const float* w1, const float* b1, const float* w2, const float* b2, float* out, int batch,
                            int d_t, hipStream_t stream);
 
-// first-stage autoencoder (small_kernels.hip): GaussianDistribution.sample on computed moments; the encoder tail - GroupNorm + SiLU +
+// first-stage autoencoder (small_kernels.hip; the two samplers as bodies of elementwise.h's ew_kernel): GaussianDistribution.sample on computed moments; the encoder tail - GroupNorm + SiLU +
 // conv_out (3x3, cin -> z2) + quant_conv (1x1, z2 -> e2) + clamp + sample, x NHWC -> z / mean / log_var NCHW [B][e2 / 2][h][w], each
 // optional; the decoder front - z / scale + post_quant_conv (1x1, emb -> zc) + conv_in (3x3, zc -> cout), z NCHW -> out NHWC.
 // noise == nullptr: element i draws what launch_randn(seed, sid, off) writes at i

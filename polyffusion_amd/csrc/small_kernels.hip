@@ -2,16 +2,11 @@
 //   stem and head convolutions (NCHW <-> NHWC at the ABI edge, unet.py:78-80,145-149),
 //   timestep embedding MLP (unet.py:63-68,151-169), batched mat-vec (ResBlock emb_layers
 //   unet.py:286-289; n_cond==1 cross-attention collapse unet_attention.py:186-212),
-//   fused sampler updates (sampler_sdf.py:80-171,307-341; sampler_ddim.py:220-272,355-359),
-//   and the update of the sampler the reference does not have, DPM-Solver++(2M) (pf_dpm_step),
-//   one fixed-point iterate of exact DDIM inversion with its fused residual (pf_invert_step) and the upward step state (pf_step_advance),
-//   the frames of a path between two noises, per-row slerp as a reduce and a combine launch (pf_slerp_rows),
-//   the canvas <-> window-batch gathers of joint overlapping-window sampling (pf_window_split, pf_window_merge),
 //   note durations of a generated roll (pf_prmat2c_durations) and its integer statistics against the run's chords (pf_roll_stats),
-//   counter-based Gaussian noise, GRU gate update and the texture-encoder front end
-//   (dl_modules/chord_enc.py:15-22, txt_enc.py:23-27).
-#include "pf_internal.h"
-#include "noise.h"
+//   the first-stage autoencoder's tail and front and the two posterior samplers, the clock and matrix-pipe probes,
+//   GRU gate update and the texture-encoder front end (dl_modules/chord_enc.py:15-22, txt_enc.py:23-27).
+// (The sampler's elementwise family - guidance, windows, updates, noise, inversion, slerp - is sampler_steps.hip.)
+#include "elementwise.h"
 
 namespace pf {
 
@@ -588,793 +583,9 @@ int launch_matvec_exp(const float* x, int ldx, const float* w, const float* bias
   return launch_matvec_t<true>(x, ldx, w, bias, y, ldy, batch, n, k, stream, 0, 0);
 }
 
-// ------------------------------------------------------------------ sampler elementwise kernels
-// (mul_rn / add_rn / sub_rn, the individually rounded fp32 operations of the updates below: noise.h)
-
-static inline dim3 ew_grid(size_t n) { return dim3((unsigned)min((size_t)2048, (n + 255) / 256)); }
-
-// e_u + s * (e_c - e_u) as three rounded operations, like the reference's tensor ops (shared with window_merge_kernel below)
-__device__ __forceinline__ float cfg_combine_v(float u, float c, float s) { return add_rn(u, mul_rn(s, sub_rn(c, u))); }
-__global__ void cfg_combine_kernel(const float* __restrict__ e2, float s, float* __restrict__ e, size_t n) {
-  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x)
-    e[i] = cfg_combine_v(e2[i], e2[n + i], s);
-}
-int launch_cfg_combine(const float* eps2, float scale, float* eps, size_t n, hipStream_t s) {
-  PF_REQUIRE(eps2 && eps && n > 0, "cfg_combine: bad arguments");
-  hipLaunchKernelGGL(cfg_combine_kernel, ew_grid(n), dim3(256), 0, s, eps2, scale, eps, n);
-  PF_CHECK_HIP(hipGetLastError());
-  return PF_OK;
-}
-
-// Dual guidance (DualScale in sampler.py): e3 = [e0 | e1 | e2], the evaluations with both parts of the condition dropped, one kept, both kept.
-//   e = e0 + s1 * (e1 - e0) + s2 * (e2 - e1)   as five rounded operations in this order (e1 == e2: cfg_combine_kernel's bits on [e0 | e1])
-__device__ __forceinline__ float cfg_combine3_v(float e0, float e1, float e2, float s1, float s2) {
-  return add_rn(add_rn(e0, mul_rn(s1, sub_rn(e1, e0))), mul_rn(s2, sub_rn(e2, e1)));
-}
-__global__ void cfg_combine3_kernel(const float* __restrict__ e3, float s1, float s2, float* __restrict__ e, size_t n) {
-  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x)
-    e[i] = cfg_combine3_v(e3[i], e3[n + i], e3[2 * n + i], s1, s2);
-}
-// the same on four elements per thread, moved as 16-byte vectors (e3 and e 16-byte aligned, n % 4 == 0 - so e3 + n and e3 + 2n are aligned
-// too and group g < n / 4 ends at float 4g + 3 < n of its third: launch_cfg_combine3 decides)
-__global__ void cfg_combine3_vec_kernel(const float* __restrict__ e3, float s1, float s2, float* __restrict__ e, size_t n) {
-  const size_t ng = n >> 2;
-  for (size_t g = (size_t)blockIdx.x * blockDim.x + threadIdx.x; g < ng; g += (size_t)gridDim.x * blockDim.x) {
-    const f32x4 a = *reinterpret_cast<const f32x4*>(e3 + 4 * g), b = *reinterpret_cast<const f32x4*>(e3 + n + 4 * g),
-                c = *reinterpret_cast<const f32x4*>(e3 + 2 * n + 4 * g);
-    f32x4 o;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) o[j] = cfg_combine3_v(a[j], b[j], c[j], s1, s2);
-    *reinterpret_cast<f32x4*>(e + 4 * g) = o;
-  }
-}
-int launch_cfg_combine3(const float* eps3, float s1, float s2, float* eps, size_t n, hipStream_t s) {
-  PF_REQUIRE(eps3 && eps && n > 0, "cfg_combine3: bad arguments");
-  if ((((uintptr_t)eps3 | (uintptr_t)eps) & 15) == 0 && n % 4 == 0)
-    hipLaunchKernelGGL(cfg_combine3_vec_kernel, ew_grid(n / 4), dim3(256), 0, s, eps3, s1, s2, eps, n);
-  else
-    hipLaunchKernelGGL(cfg_combine3_kernel, ew_grid(n), dim3(256), 0, s, eps3, s1, s2, eps, n);
-  PF_CHECK_HIP(hipGetLastError());
-  return PF_OK;
-}
-
-// ---- overlapping windows along the time axis (include/pfhip.h: pf_window_split / pf_window_merge; WindowPlan in sampler.py).  A song is a
-// canvas [S][C][Hc][W], Hc = stride * (Wn - 1) + Hw; window j of song s - batch row s * Wn + j - is canvas rows [j * stride, j * stride + Hw).
-// Both kernels are gathers over their OUTPUT (split: a window element reads one canvas element; merge: a canvas element reads the <= 8
-// windows that cover its row, in ascending j): no atomics, no LDS, nothing order-dependent.  V = 4: 16-byte vectors along W (W % 4 == 0 and
-// aligned pointers, the launchers decide), V = 1: 4-byte elements; the same individually rounded operations, so the same bits.
-struct window_geom { int S, C, Hw, W, Wn, stride, Hc; };
-template <int V>
-__device__ __forceinline__ void window_ld(const float* p, float (&v)[V]) {
-  if constexpr (V == 4) {
-    const f32x4 t = *reinterpret_cast<const f32x4*>(p);
-    v[0] = t[0]; v[1] = t[1]; v[2] = t[2]; v[3] = t[3];
-  } else {
-    v[0] = *p;
-  }
-}
-template <int V>
-__device__ __forceinline__ void window_st(float* p, const float (&v)[V]) {
-  if constexpr (V == 4) {
-    const f32x4 t = {v[0], v[1], v[2], v[3]};
-    *reinterpret_cast<f32x4*>(p) = t;
-  } else {
-    *p = v[0];
-  }
-}
-template <int V>
-__global__ void window_split_kernel(const float* __restrict__ canvas, float* __restrict__ win, window_geom g) {
-  const size_t Wv = (size_t)(g.W / V), n = (size_t)g.S * g.Wn * g.C * g.Hw * Wv;
-  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
-    const size_t wv = i % Wv;
-    size_t r = i / Wv;
-    const size_t row = r % g.Hw; r /= g.Hw;
-    const size_t c = r % g.C; r /= g.C;
-    const size_t j = r % g.Wn, s = r / g.Wn;
-    float v[V];
-    window_ld<V>(canvas + ((s * g.C + c) * g.Hc + j * g.stride + row) * g.W + wv * V, v);
-    window_st<V>(win + i * V, v);
-  }
-}
-// eps = [groups][S * Wn][C][Hw][W]; per covering window e_j = the guidance combine of its groups (the device functions of pf_cfg_combine /
-// pf_cfg_combine3), then: one window - out = e_j (a select); several - num = w_0*e_0, num += w_j*e_j, den likewise from the weights, out = num / den
-template <int V>
-__global__ void window_merge_kernel(const float* __restrict__ eps, const float* __restrict__ rw, int groups, float s1, float s2, window_geom g,
-                                    float* __restrict__ out) {
-  const size_t Wv = (size_t)(g.W / V), n = (size_t)g.S * g.C * g.Hc * Wv;
-  const size_t gs = (size_t)g.S * g.Wn * g.C * g.Hw * g.W;       // elements of one group
-  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
-    const size_t wv = i % Wv;
-    size_t r = i / Wv;
-    const int y = (int)(r % g.Hc); r /= g.Hc;
-    const size_t c = r % g.C, s = r / g.C;
-    const int j0 = y < g.Hw ? 0 : (y - g.Hw) / g.stride + 1, j1 = min(g.Wn - 1, y / g.stride);    // 0 <= y - j * stride < Hw for j0 <= j <= j1
-    float num[V], den = 0.f;
-    for (int j = j0; j <= j1; ++j) {
-      const int row = y - j * g.stride;
-      const size_t src = (((s * g.Wn + j) * g.C + c) * g.Hw + row) * g.W + wv * V;
-      float e[V];
-      window_ld<V>(eps + src, e);
-      if (groups == 2) {
-        float b[V];
-        window_ld<V>(eps + gs + src, b);
-#pragma unroll
-        for (int q = 0; q < V; ++q) e[q] = cfg_combine_v(e[q], b[q], s1);
-      } else if (groups == 3) {
-        float b[V], d[V];
-        window_ld<V>(eps + gs + src, b);
-        window_ld<V>(eps + 2 * gs + src, d);
-#pragma unroll
-        for (int q = 0; q < V; ++q) e[q] = cfg_combine3_v(e[q], b[q], d[q], s1, s2);
-      }
-      if (j0 == j1) {
-#pragma unroll
-        for (int q = 0; q < V; ++q) num[q] = e[q];
-      } else {
-        const float w = rw[row];
-#pragma unroll
-        for (int q = 0; q < V; ++q) num[q] = j == j0 ? mul_rn(w, e[q]) : add_rn(num[q], mul_rn(w, e[q]));
-        den = j == j0 ? w : add_rn(den, w);
-      }
-    }
-    if (j0 != j1) {
-#pragma unroll
-      for (int q = 0; q < V; ++q) num[q] = __fdiv_rn(num[q], den);
-    }
-    window_st<V>(out + i * V, num);
-  }
-}
-static inline bool ranges_overlap(const void* a, size_t a_bytes, const void* b, size_t b_bytes) {
-  const uintptr_t pa = (uintptr_t)a, pb = (uintptr_t)b;
-  return pa < pb + b_bytes && pb < pa + a_bytes;
-}
-// the geometry both entries share; refused before any HIP call
-static int window_geom_of(const char* who, int songs, int channels, int win_h, int width, int n_windows, int stride, window_geom* g) {
-  PF_REQUIRE(songs > 0 && channels > 0 && win_h > 0 && width > 0 && n_windows > 0,
-             "%s: non-positive extent (songs %d, channels %d, win_h %d, width %d, n_windows %d)", who, songs, channels, win_h, width, n_windows);
-  PF_REQUIRE(stride >= 1, "%s: stride %d < 1", who, stride);
-  PF_REQUIRE(stride <= win_h, "%s: stride %d > win_h %d (rows between two windows would belong to none)", who, stride, win_h);
-  PF_REQUIRE((win_h + stride - 1) / stride <= 8, "%s: ceil(win_h / stride) = %d windows over one row, at most 8", who, (win_h + stride - 1) / stride);
-  const int64_t hc = (int64_t)stride * (n_windows - 1) + win_h;
-  PF_REQUIRE(hc <= INT32_MAX, "%s: canvas height %lld does not fit 32 bits", who, (long long)hc);
-  *g = window_geom{songs, channels, win_h, width, n_windows, stride, (int)hc};
-  return PF_OK;
-}
-int launch_window_split(const float* canvas, float* windows, int songs, int channels, int win_h, int width, int n_windows, int stride,
-                        hipStream_t s) {
-  window_geom g;
-  if (int rc = window_geom_of("window_split", songs, channels, win_h, width, n_windows, stride, &g)) return rc;
-  PF_REQUIRE(canvas && windows, "window_split: null pointer");
-  const size_t n = (size_t)g.S * g.Wn * g.C * g.Hw * g.W, nc = (size_t)g.S * g.C * g.Hc * g.W;
-  PF_REQUIRE(!ranges_overlap(windows, n * sizeof(float), canvas, nc * sizeof(float)), "window_split: windows aliases canvas");
-  if (g.W % 4 == 0 && (((uintptr_t)canvas | (uintptr_t)windows) & 15) == 0)
-    hipLaunchKernelGGL(window_split_kernel<4>, ew_grid(n / 4), dim3(256), 0, s, canvas, windows, g);
-  else
-    hipLaunchKernelGGL(window_split_kernel<1>, ew_grid(n), dim3(256), 0, s, canvas, windows, g);
-  PF_CHECK_HIP(hipGetLastError());
-  return PF_OK;
-}
-int launch_window_merge(const pf_window_merge_args& a, hipStream_t s) {
-  window_geom g;
-  if (int rc = window_geom_of("window_merge", a.songs, a.channels, a.win_h, a.width, a.n_windows, a.stride, &g)) return rc;
-  PF_REQUIRE(a.groups >= 1 && a.groups <= 3, "window_merge: groups %d, expected 1, 2 or 3", a.groups);
-  PF_REQUIRE(a.eps && a.row_weight && a.out, "window_merge: null pointer (eps, row_weight and out must be set)");
-  const size_t ne = (size_t)a.groups * g.S * g.Wn * g.C * g.Hw * g.W, n = (size_t)g.S * g.C * g.Hc * g.W;
-  PF_REQUIRE(!ranges_overlap(a.out, n * sizeof(float), a.eps, ne * sizeof(float)) &&
-                 !ranges_overlap(a.out, n * sizeof(float), a.row_weight, (size_t)g.Hw * sizeof(float)),
-             "window_merge: out aliases an input");
-  if (g.W % 4 == 0 && (((uintptr_t)a.eps | (uintptr_t)a.row_weight | (uintptr_t)a.out) & 15) == 0)
-    hipLaunchKernelGGL(window_merge_kernel<4>, ew_grid(n / 4), dim3(256), 0, s, a.eps, a.row_weight, a.groups, a.s1, a.s2, g, a.out);
-  else
-    hipLaunchKernelGGL(window_merge_kernel<1>, ew_grid(n), dim3(256), 0, s, a.eps, a.row_weight, a.groups, a.s1, a.s2, g, a.out);
-  PF_CHECK_HIP(hipGetLastError());
-  return PF_OK;
-}
-
-// one element of the DDPM / RePaint update on VALUES (has_*: which optional operands take part)
-__device__ __forceinline__ float ddpm_update_v(float xv, float ev, bool has_p, float np, bool has_orig, bool has_q, float nq, float ov, float m,
-                                               const pf_ddpm_coef& c) {
-  // same operation order as the reference (each product rounded, then the sum)
-  const float x0 = sub_rn(mul_rn(c.c_recip, xv), mul_rn(c.c_recipm1, ev));
-  const float mean = add_rn(mul_rn(c.c_x0, x0), mul_rn(c.c_xt, xv));
-  float xu = mean;
-  if (has_p) xu = add_rn(mean, mul_rn(c.sigma, np));
-  if (has_orig) {
-    float xk = mul_rn(c.sqrt_ab, ov);
-    if (has_q) xk = add_rn(xk, mul_rn(c.sqrt_1mab, nq));
-    xu = add_rn(mul_rn(xk, m), mul_rn(xu, sub_rn(1.0f, m)));
-  }
-  return xu;
-}
-__device__ __forceinline__ float ddpm_update(float xv, float ev, const float* np, const float* nq, const float* orig, const float* mask,
-                                             const pf_ddpm_coef& c, size_t i) {
-  return ddpm_update_v(xv, ev, np != nullptr, np ? np[i] : 0.f, orig != nullptr, nq != nullptr, nq ? nq[i] : 0.f, orig ? orig[i] : 0.f,
-                       orig ? mask[i] : 0.f, c);
-}
-// coefficients passed by value, or - table != nullptr - the row of a device table named by the device-resident step state (graph replay)
-template <class Coef>
-__device__ __forceinline__ Coef coef_of(const Coef& by_value, const Coef* table, const pf_step_state* st) { return table ? table[st->index] : by_value; }
-// noise from tensors.  x and out carry no __restrict__: x_out may alias x (the captured step updates x where it stands)
-__global__ void ddpm_step_kernel(const float* x, const float* __restrict__ eps, const float* __restrict__ np, const float* __restrict__ nq,
-                                 const float* __restrict__ orig, const float* __restrict__ mask, pf_ddpm_coef cv,
-                                 const pf_ddpm_coef* __restrict__ table, const pf_step_state* __restrict__ st, float* out, size_t n) {
-  const pf_ddpm_coef c = coef_of(cv, table, st);
-  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x)
-    out[i] = ddpm_update(x[i], eps[i], np, nq, orig, mask, c, i);
-}
-
-__global__ void axpby_kernel(const float* __restrict__ x, const float* __restrict__ y, float a, float b, float* __restrict__ out,
-                             size_t n) {
-  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x)
-    out[i] = add_rn(mul_rn(a, x[i]), mul_rn(b, y[i]));
-}
-int launch_axpby(const float* x, const float* y, float a, float b, float* out, size_t n, hipStream_t s) {
-  PF_REQUIRE(x && y && out && n > 0, "axpby: bad arguments");
-  hipLaunchKernelGGL(axpby_kernel, ew_grid(n), dim3(256), 0, s, x, y, a, b, out, n);
-  PF_CHECK_HIP(hipGetLastError());
-  return PF_OK;
-}
-
-__device__ __forceinline__ float ddim_update_v(float xv, float e, bool has_noise, float nz, bool has_orig, float ov, float onv, float m,
-                                               const pf_ddim_coef& c) {
-  const float p0 = __fdiv_rn(sub_rn(xv, mul_rn(c.s1m, e)), c.sqrt_a);   // (a correctly rounded division has nothing to be merged with)
-  float xp = add_rn(mul_rn(c.sqrt_aprev, p0), mul_rn(c.dir_coef, e));
-  if (has_noise) xp = add_rn(xp, mul_rn(c.sigma, nz));
-  if (has_orig) {
-    const float ot = add_rn(mul_rn(c.q_sqrt_a, ov), mul_rn(c.q_s1m, onv));
-    xp = add_rn(mul_rn(ot, m), mul_rn(xp, sub_rn(1.0f, m)));
-  }
-  return xp;
-}
-__device__ __forceinline__ float ddim_update(float xv, float e, const float* noise, const float* orig, const float* on, const float* mask,
-                                             const pf_ddim_coef& c, size_t i) {
-  return ddim_update_v(xv, e, noise != nullptr, noise ? noise[i] : 0.f, orig != nullptr, orig ? orig[i] : 0.f, orig ? on[i] : 0.f,
-                       orig ? mask[i] : 0.f, c);
-}
-__global__ void ddim_step_kernel(const float* x, const float* __restrict__ eps, const float* __restrict__ noise, const float* __restrict__ orig,
-                                 const float* __restrict__ on, const float* __restrict__ mask, pf_ddim_coef cv,
-                                 const pf_ddim_coef* __restrict__ table, const pf_step_state* __restrict__ st, float* out, size_t n) {
-  const pf_ddim_coef c = coef_of(cv, table, st);
-  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x)
-    out[i] = ddim_update(x[i], eps[i], noise, orig, on, mask, c, i);
-}
-// ---- device-resident step state: what changes from one reverse step to the next lives in device memory, so a captured
-// step (hipGraph) can be replayed unchanged
-__global__ void step_state_set_kernel(pf_step_state* st, long long index, unsigned long long draws) { st->index = index; st->draws = draws; }
-__global__ void step_begin_kernel(const pf_step_state* __restrict__ st, const int* __restrict__ time_steps, long long* __restrict__ t_out, int batch) {
-  const long long t = time_steps ? (long long)time_steps[st->index] : (long long)st->index;
-  for (int i = threadIdx.x; i < batch; i += blockDim.x) t_out[i] = t;
-}
-__global__ void step_end_kernel(pf_step_state* st, int draws_used) { st->index -= 1; st->draws += (unsigned long long)draws_used; }
-int launch_step_state_set(pf_step_state* st, int64_t index, uint64_t draws, hipStream_t s) {
-  PF_REQUIRE(st, "step_state_set: null state");
-  hipLaunchKernelGGL(step_state_set_kernel, dim3(1), dim3(1), 0, s, st, (long long)index, (unsigned long long)draws);
-  PF_CHECK_HIP(hipGetLastError());
-  return PF_OK;
-}
-int launch_step_begin(const pf_step_state* st, const int* time_steps, int64_t* t_out, int batch, hipStream_t s) {
-  PF_REQUIRE(st && t_out && batch > 0, "step_begin: bad arguments");
-  hipLaunchKernelGGL(step_begin_kernel, dim3(1), dim3(64), 0, s, st, time_steps, reinterpret_cast<long long*>(t_out), batch);
-  PF_CHECK_HIP(hipGetLastError());
-  return PF_OK;
-}
-int launch_step_end(pf_step_state* st, int draws_used, hipStream_t s) {
-  PF_REQUIRE(st && draws_used >= 0, "step_end: bad arguments");
-  hipLaunchKernelGGL(step_end_kernel, dim3(1), dim3(1), 0, s, st, draws_used);
-  PF_CHECK_HIP(hipGetLastError());
-  return PF_OK;
-}
-
-// ------------------------------------------------------------------ counter-based Gaussian noise (Philox4x32-10 + Box-Muller: noise.h)
-__device__ __forceinline__ void randn_body(float* __restrict__ out, size_t n, uint64_t seed, uint64_t sid, uint64_t off) {
-  const uint64_t g0 = off >> 2, g1 = (off + n + 3) >> 2;
-  for (uint64_t g = g0 + (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; g < g1; g += (uint64_t)gridDim.x * blockDim.x) {
-    float z[4];
-    philox_normal4(g, sid, seed, z);
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const uint64_t e = g * 4 + j;
-      if (e >= off && e < off + n) out[e - off] = z[j];
-    }
-  }
-}
-__global__ void randn_kernel(float* __restrict__ out, size_t n, uint64_t seed, uint64_t sid, uint64_t off) { randn_body(out, n, seed, sid, off); }
-// draw index = device-resident counter + slot (the position of this draw inside the step)
-__global__ void randn_dev_kernel(float* __restrict__ out, size_t n, uint64_t seed, const pf_step_state* __restrict__ st, int slot, uint64_t off) {
-  randn_body(out, n, seed, st->draws + (uint64_t)slot, off);
-}
-int launch_randn_dev(float* out, size_t n, uint64_t seed, const pf_step_state* st, int slot, uint64_t elem_offset, hipStream_t s) {
-  PF_REQUIRE(out && st && n > 0 && slot >= 0, "randn_dev: bad arguments");
-  hipLaunchKernelGGL(randn_dev_kernel, ew_grid(n / 4 + 1), dim3(256), 0, s, out, n, seed, st, slot, elem_offset);
-  PF_CHECK_HIP(hipGetLastError());
-  return PF_OK;
-}
-int launch_randn(float* out, size_t n, uint64_t seed, uint64_t stream_id, uint64_t elem_offset, hipStream_t s) {
-  PF_REQUIRE(out && n > 0, "randn: bad arguments");
-  hipLaunchKernelGGL(randn_kernel, ew_grid(n / 4 + 1), dim3(256), 0, s, out, n, seed, stream_id, elem_offset);
-  PF_CHECK_HIP(hipGetLastError());
-  return PF_OK;
-}
-
-// ---- the sampler updates with the noise drawn in the kernel: a thread owns the four elements of one Philox group, the draws are
-// philox_normal4 of (group, draw index, seed) - exactly what randn_kernel stores for that draw - and the update is ddpm_update /
-// ddim_update on those values: bit-identical to randn + step, without the noise tensors' round trip through HBM
-__global__ void ddpm_step_rng_kernel(const float* x, const float* __restrict__ eps, const float* __restrict__ orig, const float* __restrict__ mask,
-                                     pf_ddpm_coef cv, const pf_ddpm_coef* __restrict__ table, const pf_step_state* __restrict__ st, uint64_t seed,
-                                     uint64_t draw_q, uint64_t draw_p, uint64_t off, float* out, size_t n) {
-  const pf_ddpm_coef c = coef_of(cv, table, st);
-  if (st) { draw_q = st->draws; draw_p = st->draws + (orig ? 1u : 0u); }
-  const size_t ng = n >> 2;
-  for (size_t g = (size_t)blockIdx.x * blockDim.x + threadIdx.x; g < ng; g += (size_t)gridDim.x * blockDim.x) {
-    float zp[4], zq[4] = {0.f, 0.f, 0.f, 0.f};
-    philox_normal4((off >> 2) + g, draw_p, seed, zp);
-    if (orig) philox_normal4((off >> 2) + g, draw_q, seed, zq);
-    const f32x4 xv = *reinterpret_cast<const f32x4*>(x + 4 * g), ev = *reinterpret_cast<const f32x4*>(eps + 4 * g);
-    f32x4 ov = {0.f, 0.f, 0.f, 0.f}, mv = ov, o;
-    if (orig) { ov = *reinterpret_cast<const f32x4*>(orig + 4 * g); mv = *reinterpret_cast<const f32x4*>(mask + 4 * g); }
-#pragma unroll
-    for (int j = 0; j < 4; ++j) o[j] = ddpm_update_v(xv[j], ev[j], true, zp[j], orig != nullptr, orig != nullptr, zq[j], ov[j], mv[j], c);
-    *reinterpret_cast<f32x4*>(out + 4 * g) = o;
-  }
-}
-__global__ void ddim_step_rng_kernel(const float* x, const float* __restrict__ eps, const float* __restrict__ orig, const float* __restrict__ on,
-                                     const float* __restrict__ mask, pf_ddim_coef cv, const pf_ddim_coef* __restrict__ table,
-                                     const pf_step_state* __restrict__ st, uint64_t seed, uint64_t draw, uint64_t off, float* out, size_t n) {
-  const pf_ddim_coef c = coef_of(cv, table, st);
-  if (st) draw = st->draws;
-  const size_t ng = n >> 2;
-  for (size_t g = (size_t)blockIdx.x * blockDim.x + threadIdx.x; g < ng; g += (size_t)gridDim.x * blockDim.x) {
-    float z[4];
-    philox_normal4((off >> 2) + g, draw, seed, z);
-    const f32x4 xv = *reinterpret_cast<const f32x4*>(x + 4 * g), ev = *reinterpret_cast<const f32x4*>(eps + 4 * g);
-    f32x4 ov = {0.f, 0.f, 0.f, 0.f}, nv = ov, mv = ov, o;
-    if (orig) { ov = *reinterpret_cast<const f32x4*>(orig + 4 * g); nv = *reinterpret_cast<const f32x4*>(on + 4 * g); mv = *reinterpret_cast<const f32x4*>(mask + 4 * g); }
-#pragma unroll
-    for (int j = 0; j < 4; ++j) o[j] = ddim_update_v(xv[j], ev[j], true, z[j], orig != nullptr, ov[j], nv[j], mv[j], c);
-    *reinterpret_cast<f32x4*>(out + 4 * g) = o;
-  }
-}
-// one launcher per family: validate, then the tensor-noise or the in-kernel-noise kernel
-template <class Args>
-static int check_step_args(const Args& a, bool known_ok, bool any_noise, const char* name) {
-  PF_REQUIRE(a.x && a.eps && a.x_out && a.n > 0 && known_ok, "%s: bad arguments", name);
-  PF_REQUIRE(!(a.coef && (a.table || a.state)), "%s: coefficients both by value (coef) and from the device (table / state)", name);
-  PF_REQUIRE(a.coef || (a.table && a.state), "%s: null coefficients (set coef, or table and state)", name);
-  if (!a.rng) return PF_OK;
-  PF_REQUIRE(!any_noise, "%s_rng: the noise is drawn in the kernel, noise tensors must be NULL", name);
-  PF_REQUIRE(a.n % 4 == 0 && a.elem_offset % 4 == 0, "%s_rng: n and elem_offset must be multiples of 4 (one Philox call yields four normals)", name);
-  return PF_OK;
-}
-int launch_ddpm_step(const pf_ddpm_step_args& a, hipStream_t s) {
-  if (int rc = check_step_args(a, !a.orig || a.mask, a.noise_p || a.noise_q, "ddpm_step")) return rc;
-  const pf_ddpm_coef cv = a.coef ? *a.coef : pf_ddpm_coef{};
-  if (a.rng) {
-    PF_REQUIRE((((uintptr_t)a.x | (uintptr_t)a.eps | (uintptr_t)a.x_out | (uintptr_t)a.orig | (uintptr_t)a.mask) & 15) == 0, "ddpm_step_rng: tensors must be 16-byte aligned");
-    hipLaunchKernelGGL(ddpm_step_rng_kernel, ew_grid(a.n / 4), dim3(256), 0, s, a.x, a.eps, a.orig, a.mask, cv, a.table, a.state, a.seed, a.draw_q,
-                       a.draw_p, a.elem_offset, a.x_out, a.n);
-  } else {
-    hipLaunchKernelGGL(ddpm_step_kernel, ew_grid(a.n), dim3(256), 0, s, a.x, a.eps, a.noise_p, a.noise_q, a.orig, a.mask, cv, a.table, a.state, a.x_out, a.n);
-  }
-  PF_CHECK_HIP(hipGetLastError());
-  return PF_OK;
-}
-int launch_ddim_step(const pf_ddim_step_args& a, hipStream_t s) {
-  if (int rc = check_step_args(a, !a.orig || (a.mask && a.orig_noise), a.noise != nullptr, "ddim_step")) return rc;
-  const pf_ddim_coef cv = a.coef ? *a.coef : pf_ddim_coef{};
-  if (a.rng) {
-    PF_REQUIRE((((uintptr_t)a.x | (uintptr_t)a.eps | (uintptr_t)a.x_out | (uintptr_t)a.orig | (uintptr_t)a.orig_noise | (uintptr_t)a.mask) & 15) == 0,
-             "ddim_step_rng: tensors must be 16-byte aligned");
-    hipLaunchKernelGGL(ddim_step_rng_kernel, ew_grid(a.n / 4), dim3(256), 0, s, a.x, a.eps, a.orig, a.orig_noise, a.mask, cv, a.table, a.state, a.seed,
-                       a.draw, a.elem_offset, a.x_out, a.n);
-  } else {
-    hipLaunchKernelGGL(ddim_step_kernel, ew_grid(a.n), dim3(256), 0, s, a.x, a.eps, a.noise, a.orig, a.orig_noise, a.mask, cv, a.table, a.state, a.x_out, a.n);
-  }
-  PF_CHECK_HIP(hipGetLastError());
-  return PF_OK;
-}
-
-// ---- DPM-Solver++(2M) (include/pfhip.h): one element of the update on VALUES.  Every operation is individually rounded (noise.h), so the
-// scalar and the vector kernel give the same bits.  Roundings on the way to the result, which the tests' error budget counts:
-//   x0:           mul (s1m*e), sub, div                                  3   (what x0_out receives)
-//   first order:  those 3 + mul (c_x*x), mul (c_0*x0), add               6
-//   second order: those 6 + mul (c_1*x0_prev), add                       8
-//   known region: + mul, mul, add (the noised original), sub (1 - m), mul, mul, add (the blend)      + 7
-// `second` is uniform over the launch (c_1 != 0); x0p is a VALUE the caller loaded only when `second` holds.
-__device__ __forceinline__ float dpm_x0(float xv, float e, const pf_dpm_coef& c) { return __fdiv_rn(sub_rn(xv, mul_rn(c.s1m, e)), c.sqrt_a); }
-__device__ __forceinline__ float dpm_update_v(float xv, float x0, bool second, float x0p, bool has_orig, float ov, float onv, float m,
-                                              const pf_dpm_coef& c) {
-  float xp = add_rn(mul_rn(c.c_x, xv), mul_rn(c.c_0, x0));
-  if (second) xp = add_rn(xp, mul_rn(c.c_1, x0p));
-  if (has_orig) {
-    const float ot = add_rn(mul_rn(c.q_sqrt_a, ov), mul_rn(c.q_s1m, onv));
-    xp = add_rn(mul_rn(ot, m), mul_rn(xp, sub_rn(1.0f, m)));
-  }
-  return xp;
-}
-// x / out and x0p / x0o carry no __restrict__: x_out may alias x and x0_out may alias x0_prev (a thread reads element i of both before it
-// writes element i of either, and no other thread touches element i)
-__global__ void dpm_step_kernel(const float* x, const float* __restrict__ eps, const float* x0p, float* x0o, const float* __restrict__ orig,
-                                const float* __restrict__ on, const float* __restrict__ mask, pf_dpm_coef cv, const pf_dpm_coef* __restrict__ table,
-                                const pf_step_state* __restrict__ st, float* out, size_t n) {
-  const pf_dpm_coef c = coef_of(cv, table, st);
-  const bool second = c.c_1 != 0.f && x0p != nullptr;      // c_1 == 0: the history is not read at all (it may be uninitialised)
-  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
-    const float xv = x[i], x0 = dpm_x0(xv, eps[i], c);
-    const float o = dpm_update_v(xv, x0, second, second ? x0p[i] : 0.f, orig != nullptr, orig ? orig[i] : 0.f, orig ? on[i] : 0.f,
-                                 orig ? mask[i] : 0.f, c);
-    if (x0o) x0o[i] = x0;
-    out[i] = o;
-  }
-}
-// the same on four elements per thread, moved as 16-byte vectors (every tensor 16-byte aligned, n % 4 == 0: launch_dpm_step decides)
-__global__ void dpm_step_vec_kernel(const float* x, const float* __restrict__ eps, const float* x0p, float* x0o, const float* __restrict__ orig,
-                                    const float* __restrict__ on, const float* __restrict__ mask, pf_dpm_coef cv, const pf_dpm_coef* __restrict__ table,
-                                    const pf_step_state* __restrict__ st, float* out, size_t n) {
-  const pf_dpm_coef c = coef_of(cv, table, st);
-  const bool second = c.c_1 != 0.f && x0p != nullptr;
-  const size_t ng = n >> 2;
-  for (size_t g = (size_t)blockIdx.x * blockDim.x + threadIdx.x; g < ng; g += (size_t)gridDim.x * blockDim.x) {
-    const f32x4 xv = *reinterpret_cast<const f32x4*>(x + 4 * g), ev = *reinterpret_cast<const f32x4*>(eps + 4 * g);
-    f32x4 pv = {0.f, 0.f, 0.f, 0.f}, ov = pv, nv = pv, mv = pv, o, z;
-    if (second) pv = *reinterpret_cast<const f32x4*>(x0p + 4 * g);
-    if (orig) { ov = *reinterpret_cast<const f32x4*>(orig + 4 * g); nv = *reinterpret_cast<const f32x4*>(on + 4 * g); mv = *reinterpret_cast<const f32x4*>(mask + 4 * g); }
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      z[j] = dpm_x0(xv[j], ev[j], c);
-      o[j] = dpm_update_v(xv[j], z[j], second, pv[j], orig != nullptr, ov[j], nv[j], mv[j], c);
-    }
-    if (x0o) *reinterpret_cast<f32x4*>(x0o + 4 * g) = z;
-    *reinterpret_cast<f32x4*>(out + 4 * g) = o;
-  }
-}
-int launch_dpm_step(const pf_dpm_step_args& a, hipStream_t s) {
-  PF_REQUIRE(a.x && a.eps && a.x_out && a.n > 0, "dpm_step: bad arguments (x, eps and x_out must be set, n > 0)");
-  PF_REQUIRE((a.orig && a.orig_noise && a.mask) || (!a.orig && !a.orig_noise && !a.mask),
-             "dpm_step: the known region needs orig, orig_noise and mask - all three or none");
-  PF_REQUIRE(!(a.coef && (a.table || a.state)), "dpm_step: coefficients both by value (coef) and from the device (table / state)");
-  PF_REQUIRE(a.coef || (a.table && a.state), "dpm_step: null coefficients (set coef, or table and state)");
-  PF_REQUIRE(!a.coef || a.coef->c_1 == 0.f || a.x0_prev, "dpm_step: a second-order step (c_1 != 0) needs x0_prev");
-  const pf_dpm_coef cv = a.coef ? *a.coef : pf_dpm_coef{};
-  const uintptr_t bits = (uintptr_t)a.x | (uintptr_t)a.eps | (uintptr_t)a.x_out | (uintptr_t)a.x0_prev | (uintptr_t)a.x0_out | (uintptr_t)a.orig |
-                         (uintptr_t)a.orig_noise | (uintptr_t)a.mask;
-  if ((bits & 15) == 0 && a.n % 4 == 0)
-    hipLaunchKernelGGL(dpm_step_vec_kernel, ew_grid(a.n / 4), dim3(256), 0, s, a.x, a.eps, a.x0_prev, a.x0_out, a.orig, a.orig_noise, a.mask, cv, a.table,
-                       a.state, a.x_out, a.n);
-  else
-    hipLaunchKernelGGL(dpm_step_kernel, ew_grid(a.n), dim3(256), 0, s, a.x, a.eps, a.x0_prev, a.x0_out, a.orig, a.orig_noise, a.mask, cv, a.table,
-                       a.state, a.x_out, a.n);
-  PF_CHECK_HIP(hipGetLastError());
-  return PF_OK;
-}
-
-// ---- exact DDIM inversion (include/pfhip.h: pf_invert_step; DESIGN.md 3, "Exact DDIM inversion"): one iterate of one UPWARD step,
-//   x_out = c_y*y + c_e*eps          mul, mul, add - 3 roundings, which the tests' budget counts on |c_y*y| + |c_e*eps|
-// Every operation is individually rounded (noise.h), so the three kernels below give the same bits.  y is never written and never aliases
-// x_out (refused); eps, x_iter and out carry no __restrict__: x_out may alias x_iter (a thread reads element i before it writes element i,
-// and no other thread touches element i).
-__device__ __forceinline__ float invert_update_v(float yv, float e, const pf_invert_coef& c) { return add_rn(mul_rn(c.c_y, yv), mul_rn(c.c_e, e)); }
-__global__ void invert_step_kernel(const float* __restrict__ y, const float* eps, pf_invert_coef cv, const pf_invert_coef* __restrict__ table,
-                                   const pf_step_state* __restrict__ st, float* out, size_t n) {
-  const pf_invert_coef c = coef_of(cv, table, st);
-  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) out[i] = invert_update_v(y[i], eps[i], c);
-}
-// the same on four elements per thread, moved as 16-byte vectors (every tensor 16-byte aligned, n % 4 == 0: launch_invert_step decides)
-__global__ void invert_step_vec_kernel(const float* __restrict__ y, const float* eps, pf_invert_coef cv, const pf_invert_coef* __restrict__ table,
-                                       const pf_step_state* __restrict__ st, float* out, size_t n) {
-  const pf_invert_coef c = coef_of(cv, table, st);
-  const size_t ng = n >> 2;
-  for (size_t g = (size_t)blockIdx.x * blockDim.x + threadIdx.x; g < ng; g += (size_t)gridDim.x * blockDim.x) {
-    const f32x4 yv = *reinterpret_cast<const f32x4*>(y + 4 * g), ev = *reinterpret_cast<const f32x4*>(eps + 4 * g);
-    f32x4 o;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) o[j] = invert_update_v(yv[j], ev[j], c);
-    *reinterpret_cast<f32x4*>(out + 4 * g) = o;
-  }
-}
-// With the residual: workgroup = (row, chunk of PF_MSE_CHUNK elements), the layout of mse_partial_kernel (loss.hip).  Lane l owns the 16-byte
-// groups l, l + 256, ... of the chunk, updates them and adds (x_out - x_iter)^2 and x_out^2 in element order - the difference in float32, the
-// squares (exact in float64) and the sums in float64; the lanes of a wave are combined by a butterfly, the four waves in wave order.  The
-// order is fixed by (row_elems, element index) alone: VEC and the element-by-element form give the same bits, and a row's two sums do not
-// depend on the rows around it.  One partial pair per workgroup; invert_resid_finish_kernel adds a row's pairs in index order.
-constexpr int kInvThreads = 256;
-constexpr int kInvGroups = PF_MSE_CHUNK / 4 / kInvThreads;
-static_assert(PF_MSE_CHUNK == 4 * kInvThreads * kInvGroups, "PF_MSE_CHUNK must be a whole number of 16-byte groups per lane");
-template <bool VEC>
-__device__ __forceinline__ f32x4 inv_load4(const float* p, size_t e, size_t n) {
-  if (VEC) return *reinterpret_cast<const f32x4*>(p + e);
-  f32x4 v = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-  for (int j = 0; j < 4; ++j)
-    if (e + j < n) v[j] = p[e + j];
-  return v;
-}
-template <bool VEC>
-__global__ __launch_bounds__(kInvThreads) void invert_step_resid_kernel(const float* __restrict__ y, const float* eps, const float* xi,
-                                                                       pf_invert_coef cv, const pf_invert_coef* __restrict__ table,
-                                                                       const pf_step_state* __restrict__ st, float* out,
-                                                                       double* __restrict__ partial, size_t row_elems, unsigned chunks) {
-  __shared__ double wave_sum[kInvThreads / 64][2];
-  const pf_invert_coef c = coef_of(cv, table, st);
-  const unsigned row = blockIdx.x / chunks, chunk = blockIdx.x - row * chunks;
-  const size_t base = (size_t)row * row_elems;
-  double acc_d = 0.0, acc_x = 0.0;
-#pragma unroll
-  for (int k = 0; k < kInvGroups; ++k) {
-    const size_t e = (size_t)chunk * PF_MSE_CHUNK + 4 * ((size_t)k * kInvThreads + threadIdx.x);
-    if (e < row_elems) {
-      const f32x4 yv = inv_load4<VEC>(y + base, e, row_elems), ev = inv_load4<VEC>(eps + base, e, row_elems);
-      const f32x4 pv = xi ? inv_load4<VEC>(xi + base, e, row_elems) : yv;     // no previous iterate: the iteration starts from y
-      f32x4 o;
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        o[j] = invert_update_v(yv[j], ev[j], c);
-        if (VEC || e + j < row_elems) {
-          const double d = (double)sub_rn(o[j], pv[j]), q = (double)o[j];
-          acc_d += d * d;
-          acc_x += q * q;
-        }
-      }
-      if (VEC) {
-        *reinterpret_cast<f32x4*>(out + base + e) = o;
-      } else {
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
-          if (e + j < row_elems) out[base + e + j] = o[j];
-      }
-    }
-  }
-#pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) {
-    acc_d += __shfl_xor(acc_d, m, 64);
-    acc_x += __shfl_xor(acc_x, m, 64);
-  }
-  if ((threadIdx.x & 63) == 0) { wave_sum[threadIdx.x >> 6][0] = acc_d; wave_sum[threadIdx.x >> 6][1] = acc_x; }
-  __syncthreads();
-  if (threadIdx.x < 2) {
-    double s = wave_sum[0][threadIdx.x];
-#pragma unroll
-    for (int w = 1; w < kInvThreads / 64; ++w) s += wave_sum[w][threadIdx.x];
-    partial[((size_t)row * chunks + chunk) * 2 + threadIdx.x] = s;
-  }
-}
-// one lane per row: the row's partial pairs in index order into slot `slot` of resid [n_slots][rows][2]; with a step state the slot is
-// state->index * iters + k.  A slot outside the table is not written (memory safety only: the host refuses the ones it can see).
-__global__ void invert_resid_finish_kernel(const double* __restrict__ partial, double* __restrict__ resid, int rows, unsigned chunks,
-                                           const pf_step_state* __restrict__ st, int iters, int k, long long slot, long long n_slots) {
-  const int row = blockIdx.x * blockDim.x + threadIdx.x;
-  if (row >= rows) return;
-  if (st) slot = (long long)st->index * iters + k;
-  if (slot < 0 || slot >= n_slots) return;
-  double sd = 0.0, sx = 0.0;
-  for (unsigned c = 0; c < chunks; ++c) {
-    sd += partial[((size_t)row * chunks + c) * 2 + 0];
-    sx += partial[((size_t)row * chunks + c) * 2 + 1];
-  }
-  double* dst = resid + ((size_t)slot * rows + row) * 2;
-  dst[0] = sd;
-  dst[1] = sx;
-}
-size_t invert_step_workspace_bytes(int rows, size_t row_elems) {
-  if (rows <= 0 || row_elems == 0) return 0;
-  return (size_t)rows * ((row_elems + PF_MSE_CHUNK - 1) / PF_MSE_CHUNK) * 2 * sizeof(double);
-}
-int launch_invert_step(const pf_invert_step_args& a, hipStream_t s) {
-  PF_REQUIRE(a.y && a.eps && a.x_out && a.rows > 0 && a.row_elems > 0, "invert_step: bad arguments (y, eps and x_out must be set, rows and row_elems > 0)");
-  PF_REQUIRE(!(a.coef && (a.table || a.state)), "invert_step: coefficients both by value (coef) and from the device (table / state)");
-  PF_REQUIRE(a.coef || (a.table && a.state), "invert_step: null coefficients (set coef, or table and state)");
-  const size_t n = (size_t)a.rows * a.row_elems, bytes = n * sizeof(float);
-  PF_REQUIRE(!ranges_overlap(a.y, bytes, a.x_out, bytes), "invert_step: y aliases x_out (y is the fixed lower state of every iterate)");
-  PF_REQUIRE(!ranges_overlap(a.eps, bytes, a.x_out, bytes), "invert_step: eps aliases x_out");
-  PF_REQUIRE(!a.x_iter || a.x_iter == a.x_out || !ranges_overlap(a.x_iter, bytes, a.x_out, bytes), "invert_step: x_iter overlaps x_out without being it");
-  const pf_invert_coef cv = a.coef ? *a.coef : pf_invert_coef{};
-  const uintptr_t bits = (uintptr_t)a.y | (uintptr_t)a.eps | (uintptr_t)a.x_out | (uintptr_t)a.x_iter;
-  const bool vec = (bits & 15) == 0 && a.row_elems % 4 == 0;
-  if (!a.resid) {          // one launch, no workspace (one that is given is not touched)
-    if (vec)
-      hipLaunchKernelGGL(invert_step_vec_kernel, ew_grid(n / 4), dim3(256), 0, s, a.y, a.eps, cv, a.table, a.state, a.x_out, n);
-    else
-      hipLaunchKernelGGL(invert_step_kernel, ew_grid(n), dim3(256), 0, s, a.y, a.eps, cv, a.table, a.state, a.x_out, n);
-    PF_CHECK_HIP(hipGetLastError());
-    return PF_OK;
-  }
-  const size_t chunks = (a.row_elems + PF_MSE_CHUNK - 1) / PF_MSE_CHUNK, need = invert_step_workspace_bytes(a.rows, a.row_elems);
-  PF_REQUIRE(chunks * (size_t)a.rows < (1ull << 31), "invert_step: %d rows of %zu elements are more workgroups than one launch holds", a.rows, a.row_elems);
-  PF_REQUIRE(a.workspace, "invert_step: resid without a workspace (pf_invert_step_workspace_bytes)");
-  PF_REQUIRE(a.workspace_bytes >= need, "invert_step: workspace of %zu bytes required, got %zu", need, a.workspace_bytes);
-  PF_REQUIRE(((uintptr_t)a.workspace & 7) == 0 && ((uintptr_t)a.resid & 7) == 0, "invert_step: workspace and resid must be 8-byte aligned");
-  PF_REQUIRE(a.n_slots > 0, "invert_step: resid needs n_slots > 0, the slots the table holds");
-  if (a.state) {
-    PF_REQUIRE(a.iters >= 1 && a.k >= 0 && a.k < a.iters, "invert_step: iterate k = %d outside [0, iters = %d)", a.k, a.iters);
-  } else {
-    PF_REQUIRE(a.slot >= 0 && a.slot < a.n_slots, "invert_step: slot %lld outside [0, n_slots = %lld)", (long long)a.slot, (long long)a.n_slots);
-  }
-  const dim3 grid((unsigned)(chunks * a.rows)), block(kInvThreads);
-  double* partial = reinterpret_cast<double*>(a.workspace);
-  if (vec)
-    hipLaunchKernelGGL(invert_step_resid_kernel<true>, grid, block, 0, s, a.y, a.eps, a.x_iter, cv, a.table, a.state, a.x_out, partial, a.row_elems, (unsigned)chunks);
-  else
-    hipLaunchKernelGGL(invert_step_resid_kernel<false>, grid, block, 0, s, a.y, a.eps, a.x_iter, cv, a.table, a.state, a.x_out, partial, a.row_elems, (unsigned)chunks);
-  PF_CHECK_HIP(hipGetLastError());
-  hipLaunchKernelGGL(invert_resid_finish_kernel, dim3((unsigned)cdiv(a.rows, 64)), dim3(64), 0, s, partial, a.resid, a.rows, (unsigned)chunks, a.state, a.iters,
-                     a.k, (long long)a.slot, (long long)a.n_slots);
-  PF_CHECK_HIP(hipGetLastError());
-  return PF_OK;
-}
-// ---- a path between two noises (include/pfhip.h: pf_slerp_rows; DESIGN.md 3, "Morph"): per row, `frames` points on the great circle from
-// a to b, out[k] = w0[k]*a + w1[k]*b.  Two launches in the layout of invert_step_resid_kernel, a workgroup = (row, chunk of PF_MSE_CHUNK):
-//   reduce   the row's sum a*a, a*b, b*b - the products exact in float64, per lane in element order, the lanes of a wave by a butterfly,
-//            the four waves in wave order; one partial triple per workgroup, no atomics
-//   combine  EVERY workgroup of a row adds the row's triples in chunk order (the same three doubles in each of them), lane k < frames forms
-//            frame k's two weights in float64 and rounds each to float once; then a and b are read once and all frames written.
-// Mode lerp runs the combine launch alone with (1 - t, t).  VEC and the element-by-element form do the same operations: the same bits.
-struct slerp_fracs { double t[PF_SLERP_MAX_FRAMES]; };      // by value in the launch: the host array is copied at the call
-template <bool VEC>
-__global__ __launch_bounds__(kInvThreads) void slerp_reduce_kernel(const float* __restrict__ a, const float* __restrict__ b,
-                                                                  double* __restrict__ partial, size_t row_elems, unsigned chunks) {
-  __shared__ double wave_sum[kInvThreads / 64][3];
-  const unsigned row = blockIdx.x / chunks, chunk = blockIdx.x - row * chunks;
-  const size_t base = (size_t)row * row_elems;
-  double acc[3] = {0.0, 0.0, 0.0};
-#pragma unroll
-  for (int k = 0; k < kInvGroups; ++k) {
-    const size_t e = (size_t)chunk * PF_MSE_CHUNK + 4 * ((size_t)k * kInvThreads + threadIdx.x);
-    if (e < row_elems) {
-      const f32x4 av = inv_load4<VEC>(a + base, e, row_elems), bv = inv_load4<VEC>(b + base, e, row_elems);
-#pragma unroll
-      for (int j = 0; j < 4; ++j)
-        if (VEC || e + j < row_elems) {
-          const double p = (double)av[j], q = (double)bv[j];
-          acc[0] += p * p;
-          acc[1] += p * q;
-          acc[2] += q * q;
-        }
-    }
-  }
-#pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) {
-#pragma unroll
-    for (int c = 0; c < 3; ++c) acc[c] += __shfl_xor(acc[c], m, 64);
-  }
-  if ((threadIdx.x & 63) == 0) {
-#pragma unroll
-    for (int c = 0; c < 3; ++c) wave_sum[threadIdx.x >> 6][c] = acc[c];
-  }
-  __syncthreads();
-  if (threadIdx.x < 3) {
-    double s = wave_sum[0][threadIdx.x];
-#pragma unroll
-    for (int w = 1; w < kInvThreads / 64; ++w) s += wave_sum[w][threadIdx.x];
-    partial[((size_t)row * chunks + chunk) * 3 + threadIdx.x] = s;
-  }
-}
-// Lerp weights (1 - t, t) stand in for the slerp weights when aa == 0, bb == 0 or 1 - |c| < 2^-20: parallel rows, where the two agree to
-// O(theta^2) and sin(theta) has lost its digits, and antiparallel rows, where the great circle is not defined (the path then goes
-// through the origin).  A frame at t == 0 / t == 1 is a COPY of a / b, by a select: bit-identical, a negative zero included.
-template <bool VEC>
-__global__ __launch_bounds__(kInvThreads) void slerp_combine_kernel(const float* __restrict__ a, const float* __restrict__ b, slerp_fracs fr,
-                                                                   int frames, int mode, const double* __restrict__ partial,
-                                                                   float* __restrict__ out, double* __restrict__ stats,
-                                                                   float* __restrict__ weights, int rows, size_t row_elems, unsigned chunks) {
-  __shared__ float w_sh[PF_SLERP_MAX_FRAMES][2];
-  __shared__ int sel_sh[PF_SLERP_MAX_FRAMES];
-  const unsigned row = blockIdx.x / chunks, chunk = blockIdx.x - row * chunks;
-  if ((int)threadIdx.x < frames) {
-    const double t = fr.t[threadIdx.x];
-    double w0 = 1.0 - t, w1 = t;
-    if (mode == 0) {
-      double aa = 0.0, ab = 0.0, bb = 0.0;
-      for (unsigned c = 0; c < chunks; ++c) {
-        const double* p = partial + ((size_t)row * chunks + c) * 3;
-        aa += p[0];
-        ab += p[1];
-        bb += p[2];
-      }
-      const double c = ab / sqrt(aa * bb);
-      if (!(aa == 0.0 || bb == 0.0 || 1.0 - fabs(c) < 0x1p-20)) {
-        const double theta = acos(c), sn = sin(theta);
-        w0 = sin((1.0 - t) * theta) / sn;
-        w1 = sin(t * theta) / sn;
-      }
-      if (chunk == 0 && threadIdx.x == 0 && stats) {
-        stats[(size_t)row * 3 + 0] = aa;
-        stats[(size_t)row * 3 + 1] = ab;
-        stats[(size_t)row * 3 + 2] = bb;
-      }
-    }
-    const float f0 = (float)w0, f1 = (float)w1;
-    w_sh[threadIdx.x][0] = f0;
-    w_sh[threadIdx.x][1] = f1;
-    sel_sh[threadIdx.x] = t == 0.0 ? 1 : t == 1.0 ? 2 : 0;
-    if (chunk == 0 && weights) {
-      weights[((size_t)threadIdx.x * rows + row) * 2 + 0] = f0;
-      weights[((size_t)threadIdx.x * rows + row) * 2 + 1] = f1;
-    }
-  }
-  __syncthreads();
-  const size_t base = (size_t)row * row_elems, frame_elems = (size_t)rows * row_elems;
-#pragma unroll
-  for (int g = 0; g < kInvGroups; ++g) {
-    const size_t e = (size_t)chunk * PF_MSE_CHUNK + 4 * ((size_t)g * kInvThreads + threadIdx.x);
-    if (e < row_elems) {
-      const f32x4 av = inv_load4<VEC>(a + base, e, row_elems), bv = inv_load4<VEC>(b + base, e, row_elems);
-      for (int k = 0; k < frames; ++k) {
-        const float w0 = w_sh[k][0], w1 = w_sh[k][1];
-        const int sel = sel_sh[k];
-        f32x4 o;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          const float v = add_rn(mul_rn(w0, av[j]), mul_rn(w1, bv[j]));
-          o[j] = sel == 1 ? av[j] : sel == 2 ? bv[j] : v;
-        }
-        float* dst = out + (size_t)k * frame_elems + base + e;
-        if (VEC) {
-          *reinterpret_cast<f32x4*>(dst) = o;
-        } else {
-#pragma unroll
-          for (int j = 0; j < 4; ++j)
-            if (e + j < row_elems) dst[j] = o[j];
-        }
-      }
-    }
-  }
-}
-size_t slerp_rows_workspace_bytes(int rows, size_t row_elems) {
-  if (rows <= 0 || row_elems == 0) return 0;
-  return (size_t)rows * ((row_elems + PF_MSE_CHUNK - 1) / PF_MSE_CHUNK) * 3 * sizeof(double);
-}
-int launch_slerp_rows(const pf_slerp_args& a, hipStream_t s) {
-  PF_REQUIRE(a.a && a.b && a.out && a.t, "slerp_rows: null a, b, out or t");
-  PF_REQUIRE(a.rows > 0 && a.row_elems > 0, "slerp_rows: %d rows of %zu elements", a.rows, a.row_elems);
-  PF_REQUIRE(a.frames >= 1 && a.frames <= PF_SLERP_MAX_FRAMES, "slerp_rows: %d frames outside [1, %d]", a.frames, PF_SLERP_MAX_FRAMES);
-  PF_REQUIRE(a.mode == 0 || a.mode == 1, "slerp_rows: mode %d, expected 0 (slerp) or 1 (lerp)", a.mode);
-  slerp_fracs fr = {};
-  for (int k = 0; k < a.frames; ++k) {
-    PF_REQUIRE(a.t[k] >= 0.0 && a.t[k] <= 1.0, "slerp_rows: fraction t[%d] = %g outside [0, 1]", k, a.t[k]);     // (a NaN fails both)
-    fr.t[k] = a.t[k];
-  }
-  const size_t n = (size_t)a.rows * a.row_elems, bytes = n * sizeof(float);
-  PF_REQUIRE(!ranges_overlap(a.out, bytes * a.frames, a.a, bytes), "slerp_rows: out overlaps a");
-  PF_REQUIRE(!ranges_overlap(a.out, bytes * a.frames, a.b, bytes), "slerp_rows: out overlaps b");
-  PF_REQUIRE(((uintptr_t)a.stats & 7) == 0, "slerp_rows: stats must be 8-byte aligned");
-  const size_t chunks = (a.row_elems + PF_MSE_CHUNK - 1) / PF_MSE_CHUNK, need = slerp_rows_workspace_bytes(a.rows, a.row_elems);
-  PF_REQUIRE(chunks * (size_t)a.rows < (1ull << 31), "slerp_rows: %d rows of %zu elements are more workgroups than one launch holds", a.rows, a.row_elems);
-  if (a.mode == 0) {
-    PF_REQUIRE(a.workspace, "slerp_rows: mode slerp without a workspace (pf_slerp_rows_workspace_bytes)");
-    PF_REQUIRE(a.workspace_bytes >= need, "slerp_rows: workspace of %zu bytes required, got %zu", need, a.workspace_bytes);
-    PF_REQUIRE(((uintptr_t)a.workspace & 7) == 0, "slerp_rows: workspace must be 8-byte aligned");
-  }
-  const uintptr_t bits = (uintptr_t)a.a | (uintptr_t)a.b | (uintptr_t)a.out;
-  const bool vec = (bits & 15) == 0 && a.row_elems % 4 == 0;
-  const dim3 grid((unsigned)(chunks * a.rows)), block(kInvThreads);
-  double* partial = a.mode == 0 ? reinterpret_cast<double*>(a.workspace) : nullptr;
-  if (a.mode == 0) {
-    if (vec)
-      hipLaunchKernelGGL(slerp_reduce_kernel<true>, grid, block, 0, s, a.a, a.b, partial, a.row_elems, (unsigned)chunks);
-    else
-      hipLaunchKernelGGL(slerp_reduce_kernel<false>, grid, block, 0, s, a.a, a.b, partial, a.row_elems, (unsigned)chunks);
-    PF_CHECK_HIP(hipGetLastError());
-  }
-  if (vec)
-    hipLaunchKernelGGL(slerp_combine_kernel<true>, grid, block, 0, s, a.a, a.b, fr, a.frames, a.mode, partial, a.out, a.stats, a.weights, a.rows,
-                       a.row_elems, (unsigned)chunks);
-  else
-    hipLaunchKernelGGL(slerp_combine_kernel<false>, grid, block, 0, s, a.a, a.b, fr, a.frames, a.mode, partial, a.out, a.stats, a.weights, a.rows,
-                       a.row_elems, (unsigned)chunks);
-  PF_CHECK_HIP(hipGetLastError());
-  return PF_OK;
-}
-// the upward walk's counterpart of step_end_kernel: index += delta; draws += draws_used
-__global__ void step_advance_kernel(pf_step_state* st, long long delta, int draws_used) { st->index += delta; st->draws += (unsigned long long)draws_used; }
-int launch_step_advance(pf_step_state* st, int64_t delta, int draws_used, hipStream_t s) {
-  PF_REQUIRE(st && draws_used >= 0, "step_advance: bad arguments");
-  hipLaunchKernelGGL(step_advance_kernel, dim3(1), dim3(1), 0, s, st, (long long)delta, draws_used);
-  PF_CHECK_HIP(hipGetLastError());
-  return PF_OK;
-}
-
 // ------------------------------------------------------------------ first-stage autoencoder: posterior sample, encoder tail, decoder front
 // GaussianDistribution.sample times the latent scaling factor (autoencoder.py:316-324, latent_diffusion.py:112-120).
-// NOT inlined, contraction off: the encoder tail and gaussian_sample_kernel must give the same bits for the same moments and noise
+// NOT inlined, contraction off: the encoder tail and gaussian_sample_body must give the same bits for the same moments and noise
 // (see philox_normal4v).
 __device__ __noinline__ float gaussian_sample1(float mean, float log_var, float nz, float scale) {
 #pragma clang fp contract(off)
@@ -1389,31 +600,30 @@ __device__ __forceinline__ float noise_at(const float* __restrict__ noise, size_
   const int j = (int)(e & 3);
   return j == 0 ? v[0] : j == 1 ? v[1] : j == 2 ? v[2] : v[3];
 }
-__global__ void gaussian_sample_kernel(const float* __restrict__ mean, const float* __restrict__ log_var, const float* __restrict__ noise,
-                                       uint64_t seed, uint64_t sid, uint64_t off, float scale, float* __restrict__ z, size_t n) {
-  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x)
-    z[i] = gaussian_sample1(mean[i], log_var[i], noise_at(noise, i, seed, sid, off), scale);
-}
+struct gaussian_sample_body {
+  const float* __restrict__ mean; const float* __restrict__ log_var; const float* __restrict__ noise; uint64_t seed, sid, off; float scale;
+  float* __restrict__ z;
+  __device__ __forceinline__ void begin() {}
+  template <int V>
+  __device__ __forceinline__ void at(size_t i) const { z[i] = gaussian_sample1(mean[i], log_var[i], noise_at(noise, i, seed, sid, off), scale); }
+};
 int launch_gaussian_sample(const float* mean, const float* log_var, const float* noise, uint64_t seed, uint64_t sid, uint64_t off, float scale,
                            float* z, size_t n, hipStream_t s) {
   PF_REQUIRE(mean && log_var && z && n > 0, "gaussian_sample: bad arguments");
-  hipLaunchKernelGGL(gaussian_sample_kernel, ew_grid(n), dim3(256), 0, s, mean, log_var, noise, seed, sid, off, scale, z, n);
-  PF_CHECK_HIP(hipGetLastError());
-  return PF_OK;
+  return ew_launch_v<1>(gaussian_sample_body{mean, log_var, noise, seed, sid, off, scale, z}, n, s);
 }
 
 // Normal(mean, std).rsample() (torch.distributions: loc + eps * scale as two rounded tensor operations); noise as above
-__global__ void normal_rsample_kernel(const float* __restrict__ mean, const float* __restrict__ sd, const float* __restrict__ noise, uint64_t seed,
-                                      uint64_t sid, uint64_t off, float* __restrict__ z, size_t n) {
-  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x)
-    z[i] = add_rn(mean[i], mul_rn(noise_at(noise, i, seed, sid, off), sd[i]));
-}
+struct normal_rsample_body {
+  const float* __restrict__ mean; const float* __restrict__ sd; const float* __restrict__ noise; uint64_t seed, sid, off; float* __restrict__ z;
+  __device__ __forceinline__ void begin() {}
+  template <int V>
+  __device__ __forceinline__ void at(size_t i) const { z[i] = add_rn(mean[i], mul_rn(noise_at(noise, i, seed, sid, off), sd[i])); }
+};
 int launch_normal_rsample(const float* mean, const float* sd, const float* noise, uint64_t seed, uint64_t sid, uint64_t off, float* z, size_t n,
                           hipStream_t s) {
   PF_REQUIRE(mean && sd && z && n > 0, "normal_rsample: bad arguments");
-  hipLaunchKernelGGL(normal_rsample_kernel, ew_grid(n), dim3(256), 0, s, mean, sd, noise, seed, sid, off, z, n);
-  PF_CHECK_HIP(hipGetLastError());
-  return PF_OK;
+  return ew_launch_v<1>(normal_rsample_body{mean, sd, noise, seed, sid, off, z}, n, s);
 }
 
 // Encoder tail (autoencoder.py:198-201, 64-68, 316-324): moments = quant_conv(conv_out(swish(norm_out(x)))), mean | log_var = its halves,

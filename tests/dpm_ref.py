@@ -80,7 +80,7 @@ def update(row, x, eps, x0_prev=None, orig=None, orig_noise=None, mask=None):
 
 def budget(row, x, eps, x0_prev=None, orig=None, orig_noise=None, mask=None):
     """(bound on |x_out(float32) - x_out(float64)|, the same for x0) per element, for the kernel's individually rounded float32 operations on
-    these float32 inputs: the number of roundings on the way to the result (counted beside the kernel in csrc/small_kernels.hip: 3 for x0,
+    these float32 inputs: the number of roundings on the way to the result (counted beside the kernel in csrc/sampler_steps.hip: 3 for x0,
     6 for a first-order step, 8 for a second-order one, 7 more with the known-region blend) times 2^-24 times the sum of the magnitudes of
     the terms that are added up.  No fitted constant.
 

@@ -52,7 +52,7 @@ def update(row, y, eps):
 
 def budget(row, y, eps):
     """Bound on |x_out(float32) - x_out(float64)| per element for the kernel's individually rounded float32 operations on these float32
-    inputs.  Counted beside the kernel (csrc/small_kernels.hip): mul (c_y*y), mul (c_e*eps), add = 3 roundings, times 2^-24, times the sum
+    inputs.  Counted beside the kernel (csrc/sampler_steps.hip): mul (c_y*y), mul (c_e*eps), add = 3 roundings, times 2^-24, times the sum
     of the magnitudes of the terms that are added up, |c_y*y| + |c_e*eps|.  Nothing cancels before the sum, so no side condition; no
     fitted constant."""
     return 3 * U * (abs(float(row[0])) * _abs(y) + abs(float(row[1])) * _abs(eps))
