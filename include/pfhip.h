@@ -164,6 +164,44 @@ int pf_cfg_combine(const float* eps2, float scale, float* eps, size_t n, void* s
  * With e1 == e2 these are pf_cfg_combine's bits on [e0 ; e1] with scale s1 (finite values).  16-byte vectors when eps3 and eps are 16-byte
  * aligned and n % 4 == 0, 4-byte elements otherwise: the same bits. */
 int pf_cfg_combine3(const float* eps3, float s1, float s2, float* eps, size_t n, void* stream);
+/* Guidance rescale (not in the reference; Lin, Liu, Li & Yang 2024, "Common Diffusion Noise Schedules and Sample Steps Are Flawed", section 3.4;
+ * its companion on the host, the guidance interval, is Kynkaanniemi et al. 2024, "Applying Guidance in a Limited Interval Improves Sample and
+ * Distribution Quality" - DESIGN.md 0, row a42, and 3, "Guidance rescale and interval").  At a high scale the combined prediction has a much
+ * larger per-sample standard deviation than the conditional one; this scales it back and mixes the result with the plain combine by phi.
+ * epsg is [groups][rows][row_elems], group-major as pf_cfg_combine / pf_cfg_combine3 read it; per row r:
+ *     e_cfg[i] = pf_cfg_combine's expression (s1)        groups == 2      the same device functions, so the same individually
+ *              = pf_cfg_combine3's expression (s1, s2)   groups == 3      rounded fp32 operations as those launches
+ *     e_pos[i] = the fully conditional group: the last one
+ *     four sums over the row: e_pos, e_pos^2, e_cfg, e_cfg^2        every term widened to float64 first (squares exact); every addition in
+ *                                                                   double-double (its rounding error kept), the total rounded to float64:
+ *                                                                   within an ulp of the exact sum, i.e. within 2^-52 * sum |term|
+ *     var = sum x^2 / n - (sum x / n)^2 ;  f = sqrt(var_pos / var_cfg)                                 float64, each operation rounded
+ *     f = 1  when var_cfg is not > 0 or the root is not finite (a constant row; a quotient that is NaN, overflowed, or negative
+ *            because var_pos cancelled below zero): a stated rule, like pf_slerp_rows' lerp weights - there is no scale to restore
+ *     w = phi*f + (1 - phi)  in float64, rounded to float ONCE ;  eps[r][i] = fl(e_cfg[i] * w)         one rounded product
+ *   which is the published phi*(e_cfg*f) + (1 - phi)*e_cfg, factored: a row with f == 1 has w == 1 and comes out as e_cfg bit for bit.
+ *   Two launches without a host sync, workgroup = (row, PF_MSE_CHUNK of it), as pf_slerp_rows.  Reduce: the four sums in the lane / butterfly /
+ *   wave order of pf_invert_step's residual, one partial 4-tuple of (hi, lo) pairs per workgroup into `workspace` (pf_cfg_rescale_workspace_bytes(rows,
+ *   row_elems) bytes, 8-byte aligned: double [rows][chunks][4][2], which the call leaves behind); no atomics.  Combine: every workgroup of a row adds the row's 4-tuples in chunk order - the same four
+ *   doubles in each -, forms w, recomputes e_cfg from one more read of the groups and writes its chunk: (2*groups + 1) * n * 4 bytes move.
+ *   The chunk-0 workgroup of a row also writes stats[row] and weights[row].  A row's outputs depend on that row alone: bit-identical from
+ *   call to call and however the rows are split into calls.  epsg and eps 16-byte aligned with row_elems % 4 == 0 are moved as 16-byte
+ *   vectors, anything else element by element; the same operations, so the same bits.
+ * Refused before any launch (message prefix "cfg_rescale: "): null epsg or eps; groups outside {2, 3}; rows <= 0 or row_elems == 0; phi NaN
+ * or outside [0, 1]; eps overlapping epsg, partially too; no workspace, one too small or not 8-byte aligned; stats not 8-byte aligned; more
+ * workgroups than one launch holds (rows * chunks >= 2^31). */
+typedef struct pf_cfg_rescale_args {
+  const float* epsg;                  /* [groups][rows][row_elems] */
+  float* eps;                         /* [rows][row_elems]; may not overlap epsg */
+  double* stats;                      /* [rows][3] device doubles: var_pos, var_cfg, f; may be NULL */
+  float* weights;                     /* [rows] device floats: the w actually used; may be NULL */
+  void* workspace; size_t workspace_bytes;
+  double phi;                         /* the mix factor, in [0, 1]; 0 gives the plain combine's bits (at the cost of both launches) */
+  float s1, s2;                       /* guidance scales: s1 always, s2 with groups == 3 */
+  int32_t groups, rows; size_t row_elems;
+} pf_cfg_rescale_args;
+size_t pf_cfg_rescale_workspace_bytes(int rows, size_t row_elems);
+int pf_cfg_rescale(const pf_cfg_rescale_args* a, void* stream);
 
 /* Overlapping windows along the time axis (not in the reference; MultiDiffusion, Bar-Tal et al. 2023, on the rows of a piano roll): a song is
  * a canvas [songs][channels][canvas_h][width], canvas_h = stride * (n_windows - 1) + win_h, and the denoiser sees it as the batch of its

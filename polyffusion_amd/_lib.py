@@ -100,6 +100,13 @@ class SlerpArgs(C.Structure):
                 + [("workspace_bytes", C.c_size_t), ("mode", C.c_int32), ("frames", C.c_int32), ("rows", C.c_int32), ("row_elems", C.c_size_t)])
 
 
+class CfgRescaleArgs(C.Structure):
+    """pf_cfg_rescale_args (include/pfhip.h); filled by ``_steps.cfg_rescale`` only."""
+    _fields_ = ([(n, C.c_void_p) for n in ("epsg", "eps", "stats", "weights", "workspace")]
+                + [("workspace_bytes", C.c_size_t), ("phi", C.c_double), ("s1", C.c_float), ("s2", C.c_float), ("groups", C.c_int32),
+                   ("rows", C.c_int32), ("row_elems", C.c_size_t)])
+
+
 class WindowMergeArgs(C.Structure):
     """pf_window_merge_args (include/pfhip.h); filled by ``_steps.window_merge`` only."""
     _fields_ = ([("eps", C.c_void_p), ("row_weight", C.c_void_p), ("groups", C.c_int), ("s1", C.c_float), ("s2", C.c_float)]
@@ -291,6 +298,8 @@ SIGNATURES = {
     "pf_unet_n_launches": (C.c_int, [C.c_void_p, C.c_int, C.c_int]),
     "pf_cfg_combine": (C.c_int, [C.c_void_p, C.c_float, C.c_void_p, C.c_size_t, C.c_void_p]),
     "pf_cfg_combine3": (C.c_int, [C.c_void_p, C.c_float, C.c_float, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "pf_cfg_rescale_workspace_bytes": (C.c_size_t, [C.c_int, C.c_size_t]),
+    "pf_cfg_rescale": (C.c_int, [C.POINTER(CfgRescaleArgs), C.c_void_p]),
     "pf_window_split": (C.c_int, [C.c_void_p, C.c_void_p] + [C.c_int] * 6 + [C.c_void_p]),
     "pf_window_merge": (C.c_int, [C.POINTER(WindowMergeArgs), C.c_void_p]),
     "pf_ddpm_step": (C.c_int, [C.POINTER(DdpmStepArgs), C.c_void_p]),

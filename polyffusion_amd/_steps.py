@@ -1,6 +1,6 @@
 """The sampler's elementwise launches: noise, ``a*x + b*y`` and the three reverse-step updates (``pf_randn`` / ``pf_randn_dev``, ``pf_axpby``,
 ``pf_ddpm_step``, ``pf_ddim_step``, ``pf_dpm_step`` of include/pfhip.h), the upward iterate of exact DDIM inversion (``pf_invert_step``),
-the frames between two tensors of a morph (``pf_slerp_rows``),
+the frames between two tensors of a morph (``pf_slerp_rows``), the guidance combine rescaled per row (``pf_cfg_rescale``),
 the two launches around the denoiser of a window plan
 (``pf_window_split``, ``pf_window_merge``), and the two launches of the training objective (``pf_qsample_rows``,
 ``pf_mse_rows``) with the loss evaluation both diffusion mirrors share (``diffusion_loss_rows``).  The only place that fills
@@ -155,6 +155,46 @@ def slerp_rows(lib, a, b, fracs, *, mode: str = "slerp", out=None, want_stats: b
             workspace = slerp_workspace(lib, rows, row_elems, a.device)
         args.workspace, args.workspace_bytes = _lib.ptr(workspace), 0 if workspace is None else workspace.numel() * workspace.element_size()
     _lib.check(lib.pf_slerp_rows(C.byref(args), _lib.current_stream()), "pf_slerp_rows", lib)
+    return out, stats, weights
+
+
+def cfg_rescale_workspace(lib, rows: int, row_elems: int, device) -> torch.Tensor:
+    """The float64 workspace ``cfg_rescale`` needs for ``rows`` rows of ``row_elems`` floats."""
+    nb = int(lib.pf_cfg_rescale_workspace_bytes(int(rows), int(row_elems)))
+    return torch.empty(max(nb, 8) // 8, dtype=torch.float64, device=device)
+
+
+def cfg_rescale(lib, epsg, groups: int, scales, phi: float, *, out=None, want_stats: bool = False, workspace=None):
+    """The guidance combine of ``epsg`` ``[groups * rows, ...]`` (group-major, as the guided evaluation stacks it; ``groups`` 2 or 3, ``scales``
+    ``(s,)`` or ``(s1, s2)`` as ``guidance_plan`` returns them), every row scaled by ``w = phi * f + (1 - phi)`` with ``f`` the ratio of the
+    per-row standard deviations of the conditional group and of the combine (``pf_cfg_rescale``: a reduce and a combine launch; a row is
+    one batch entry).  Returns ``(out [rows, ...], stats, weights)``: ``stats`` float64 ``[rows, 3]`` (``var_pos``, ``var_cfg``, ``f``) and
+    ``weights`` float32 ``[rows]`` on the device, both ``None`` without ``want_stats``.  No host sync."""
+    groups = int(groups)
+    if epsg.dtype != torch.float32 or not epsg.is_contiguous():
+        raise ValueError("cfg_rescale: epsg must be contiguous float32")
+    if groups < 1 or epsg.dim() < 1 or epsg.shape[0] % groups != 0:
+        raise ValueError(f"cfg_rescale: epsg of shape {tuple(epsg.shape)} is not {groups} groups of rows")
+    rows = epsg.shape[0] // groups
+    shape = (rows,) + tuple(epsg.shape[1:])
+    row_elems = epsg.numel() // max(1, groups * rows)
+    if out is None:
+        out = torch.empty(shape, dtype=torch.float32, device=epsg.device)
+    elif out.dtype != torch.float32 or not out.is_contiguous() or out.numel() != rows * row_elems:
+        raise ValueError(f"cfg_rescale: out must be contiguous float32 of {shape}")
+    stats = weights = None
+    if want_stats:
+        stats = torch.empty(rows, 3, dtype=torch.float64, device=epsg.device)
+        weights = torch.empty(rows, dtype=torch.float32, device=epsg.device)
+    if workspace is None and rows > 0:
+        workspace = cfg_rescale_workspace(lib, rows, row_elems, epsg.device)
+    a = _lib.CfgRescaleArgs()
+    a.epsg, a.eps, a.stats, a.weights = epsg.data_ptr(), out.data_ptr(), _lib.ptr(stats), _lib.ptr(weights)
+    a.workspace, a.workspace_bytes = _lib.ptr(workspace), 0 if workspace is None else workspace.numel() * workspace.element_size()
+    a.phi = float(phi)
+    a.s1, a.s2 = (float(v) for v in (tuple(scales) + (0.0, 0.0))[:2])
+    a.groups, a.rows, a.row_elems = groups, rows, row_elems
+    _lib.check(lib.pf_cfg_rescale(C.byref(a), _lib.current_stream()), "pf_cfg_rescale", lib)
     return out, stats, weights
 
 

@@ -179,6 +179,11 @@ int pf_attention(const float* q, int ldq, const float* k, int ldk, const float* 
 
 int pf_cfg_combine(const float* eps2, float scale, float* eps, size_t n, void* stream) { return launch_cfg_combine(eps2, scale, eps, n, (hipStream_t)stream); }
 int pf_cfg_combine3(const float* eps3, float s1, float s2, float* eps, size_t n, void* stream) { return launch_cfg_combine3(eps3, s1, s2, eps, n, (hipStream_t)stream); }
+size_t pf_cfg_rescale_workspace_bytes(int rows, size_t row_elems) { return cfg_rescale_workspace_bytes(rows, row_elems); }
+int pf_cfg_rescale(const pf_cfg_rescale_args* a, void* stream) {
+  PF_REQUIRE(a, "cfg_rescale: null arguments");
+  return launch_cfg_rescale(*a, (hipStream_t)stream);
+}
 int pf_window_split(const float* canvas, float* windows, int songs, int channels, int win_h, int width, int n_windows, int stride, void* stream) {
   return launch_window_split(canvas, windows, songs, channels, win_h, width, n_windows, stride, (hipStream_t)stream);
 }

@@ -2,6 +2,7 @@
 // posterior samplers of small_kernels.hip):
 //   ew_kernel<V, Body>     a grid-stride loop over groups of V in {1, 4} floats; the body holds the operands and the arithmetic
 //   row_reduce_store<N>    workgroup = (row, chunk of PF_MSE_CHUNK elements): N per-lane sums -> one partial N-tuple, in a fixed order
+//                          (row_reduce_store_dd<N>: the same order with double-double additions, for sums held to an ulp)
 // Every operation of the bodies is individually rounded (noise.h) and the reduction order is fixed by (row_elems, element index) alone, so
 // the width of an access never changes a bit of a result.
 #pragma once
@@ -117,6 +118,61 @@ __device__ __forceinline__ void row_partials_sum(const double* __restrict__ part
   for (unsigned c = 0; c < chunks; ++c) {
 #pragma unroll
     for (int k = 0; k < N; ++k) s[k] += partial[((size_t)row * chunks + c) * N + k];
+  }
+}
+
+// ---- the same reduction, in the same order, with every addition carried out in double-double: a sum is an unevaluated pair hi + lo
+// (|lo| <= ulp(hi) / 2), an addition keeps the rounding error of hi + hi exactly (Knuth's TwoSum) and folds it into lo, so a row sum of
+// n <= 2^31 terms is good to about n * 2^-104 of sum |term| and its hi is the correctly rounded sum but for near-ties - where a plain
+// float64 sum in this order is one to several ulps off.  For callers whose tolerance is an ulp of the sum (pf_cfg_rescale).  dd_add is
+// symmetric in its operands, so both lanes of a butterfly step form the same pair.  Partials: out[((row * chunks + chunk) * N + k) * 2 + {0: hi, 1: lo}].
+struct dd { double hi, lo; };
+__device__ __forceinline__ dd dd_renorm(double s, double e) {
+#pragma clang fp contract(off)
+  const double hi = s + e;
+  return dd{hi, e - (hi - s)};
+}
+__device__ __forceinline__ dd dd_add(dd x, dd y) {
+#pragma clang fp contract(off)
+  const double s = x.hi + y.hi, bb = s - x.hi;
+  const double e = (x.hi - (s - bb)) + (y.hi - bb);      // the rounding error of s, exactly
+  return dd_renorm(s, e + (x.lo + y.lo));
+}
+__device__ __forceinline__ dd dd_add(dd x, double t) { return dd_add(x, dd{t, 0.0}); }
+
+template <int N>
+__device__ __forceinline__ void row_reduce_store_dd(dd (&acc)[N], double* __restrict__ out, unsigned row, unsigned chunks, unsigned chunk) {
+  __shared__ dd wave_sum[kRowThreads / 64][N];
+#pragma unroll
+  for (int m = 32; m >= 1; m >>= 1) {
+#pragma unroll
+    for (int k = 0; k < N; ++k) acc[k] = dd_add(acc[k], dd{__shfl_xor(acc[k].hi, m, 64), __shfl_xor(acc[k].lo, m, 64)});
+  }
+  if ((threadIdx.x & 63) == 0) {
+#pragma unroll
+    for (int k = 0; k < N; ++k) wave_sum[threadIdx.x >> 6][k] = acc[k];
+  }
+  __syncthreads();
+  if (threadIdx.x < N) {
+    dd s = wave_sum[0][threadIdx.x];
+#pragma unroll
+    for (int w = 1; w < kRowThreads / 64; ++w) s = dd_add(s, wave_sum[w][threadIdx.x]);
+    double* dst = out + (((size_t)row * chunks + chunk) * N + threadIdx.x) * 2;
+    dst[0] = s.hi;
+    dst[1] = s.lo;
+  }
+}
+// a row's pairs added in chunk order; s[k] = hi of the total
+template <int N>
+__device__ __forceinline__ void row_partials_sum_dd(const double* __restrict__ partial, unsigned row, unsigned chunks, double (&s)[N]) {
+#pragma unroll
+  for (int k = 0; k < N; ++k) {
+    dd t{0.0, 0.0};
+    for (unsigned c = 0; c < chunks; ++c) {
+      const double* src = partial + (((size_t)row * chunks + c) * N + k) * 2;
+      t = dd_add(t, dd{src[0], src[1]});
+    }
+    s[k] = t.hi;
   }
 }
 

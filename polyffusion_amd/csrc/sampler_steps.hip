@@ -1,12 +1,14 @@
 // sampler_steps.hip - the sampler's elementwise family (gfx950), written against elementwise.h:
-//   guidance combines (pf_cfg_combine, pf_cfg_combine3) and the canvas <-> window-batch gathers of joint overlapping-window sampling
+//   guidance combines (pf_cfg_combine, pf_cfg_combine3), the combine rescaled to the conditional prediction's per-row standard deviation as a
+//   reduce and a combine launch (pf_cfg_rescale), and the canvas <-> window-batch gathers of joint overlapping-window sampling
 //   (pf_window_split, pf_window_merge),
 //   fused sampler updates (sampler_sdf.py:80-171,307-341; sampler_ddim.py:220-272,355-359), and the update of the sampler the reference
 //   does not have, DPM-Solver++(2M) (pf_dpm_step), the RePaint re-noise (pf_axpby),
 //   the device-resident step state (pf_step_state_set / begin / end / advance) and counter-based Gaussian noise (pf_randn, pf_randn_dev),
 //   one fixed-point iterate of exact DDIM inversion with its fused residual (pf_invert_step),
 //   the frames of a path between two noises, per-row slerp as a reduce and a combine launch (pf_slerp_rows).
-// Every map is a body struct run by ew_kernel at one or both widths; every row sum goes through row_reduce_store / row_partials_sum.
+// Every map is a body struct run by ew_kernel at one or both widths; every row sum goes through row_reduce_store / row_partials_sum
+// or their double-double forms.
 #include "elementwise.h"
 
 namespace pf {
@@ -47,6 +49,135 @@ struct cfg_combine3_body {
 int launch_cfg_combine3(const float* eps3, float s1, float s2, float* eps, size_t n, hipStream_t s) {
   PF_REQUIRE(eps3 && eps && n > 0, "cfg_combine3: bad arguments");
   return ew_launch(aligned16({eps3, eps}) && n % 4 == 0, cfg_combine3_body{eps3, s1, s2, eps, n}, n, s);
+}
+
+// ---- guidance rescale (include/pfhip.h: pf_cfg_rescale; DESIGN.md 3, "Guidance rescale and interval"; Lin et al. 2024, section 3.4): the
+// combine above, scaled per row towards the standard deviation of the fully conditional group, out = e_cfg * w with
+// w = phi * sqrt(var_pos / var_cfg) + (1 - phi).  Two launches, a workgroup = (row, chunk of PF_MSE_CHUNK), as pf_slerp_rows:
+//   reduce   the row reduction of elementwise.h with four sums - e_pos, e_pos^2, e_cfg, e_cfg^2, every term widened to float64 first (the
+//            squares are then exact) - in its double-double form (row_reduce_store_dd: the same order, every addition keeps its rounding
+//            error), because the sums are held to an ulp: a plain float64 sum in this order was measured up to two ulps off.  One partial
+//            4-tuple of (hi, lo) pairs per workgroup, no atomics
+//   combine  EVERY workgroup of a row adds the row's 4-tuples in chunk order (the same four doubles in each of them), lane 0 forms w in
+//            float64 and rounds it to float once; then the groups are read once more, e_cfg recomputed and e_cfg * w written.
+// VEC and the element-by-element form do the same operations: the same bits.
+// the four elements at e of one row: e_pos (the last group) and e_cfg (cfg_combine_v / cfg_combine3_v of the groups); gs = one group's elements
+template <bool VEC>
+__device__ __forceinline__ void cfg_rescale_load(const float* __restrict__ epsg, int groups, size_t gs, size_t base, size_t e, size_t row_elems,
+                                                 float s1, float s2, f32x4& pos, f32x4& cfg) {
+  const f32x4 a = load4<VEC>(epsg + base, e, row_elems), b = load4<VEC>(epsg + gs + base, e, row_elems);
+  if (groups == 2) {
+    pos = b;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) cfg[j] = cfg_combine_v(a[j], b[j], s1);
+  } else {
+    pos = load4<VEC>(epsg + 2 * gs + base, e, row_elems);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) cfg[j] = cfg_combine3_v(a[j], b[j], pos[j], s1, s2);
+  }
+}
+template <bool VEC>
+__global__ __launch_bounds__(kRowThreads) void cfg_rescale_reduce_kernel(const float* __restrict__ epsg, int groups, size_t gs, float s1, float s2,
+                                                                        double* __restrict__ partial, size_t row_elems, unsigned chunks) {
+  const unsigned row = blockIdx.x / chunks, chunk = blockIdx.x - row * chunks;
+  const size_t base = (size_t)row * row_elems;
+  dd acc[4] = {};
+#pragma unroll
+  for (int k = 0; k < kRowGroups; ++k) {
+    const size_t e = row_group_elem(chunk, k);
+    if (e < row_elems) {
+      f32x4 pv, cv;
+      cfg_rescale_load<VEC>(epsg, groups, gs, base, e, row_elems, s1, s2, pv, cv);
+#pragma unroll
+      for (int j = 0; j < 4; ++j)
+        if (VEC || e + j < row_elems) {
+          const double p = (double)pv[j], c = (double)cv[j];
+          acc[0] = dd_add(acc[0], p);
+          acc[1] = dd_add(acc[1], p * p);        // (the square of a widened float is exact)
+          acc[2] = dd_add(acc[2], c);
+          acc[3] = dd_add(acc[3], c * c);
+        }
+    }
+  }
+  row_reduce_store_dd(acc, partial, row, chunks, chunk);
+}
+// var = sum x^2 / n - (sum x / n)^2 and f = sqrt(var_pos / var_cfg), in float64.  f = 1 - the row then comes out as e_cfg, bit for bit -
+// when var_cfg is not > 0 (a constant row, or NaN) or the root is not finite (a quotient that overflowed, is NaN, or is negative because
+// var_pos cancelled below zero): there is no scale to restore.
+template <bool VEC>
+__global__ __launch_bounds__(kRowThreads) void cfg_rescale_combine_kernel(const float* __restrict__ epsg, int groups, size_t gs, float s1, float s2,
+                                                                         double phi, const double* __restrict__ partial, float* __restrict__ out,
+                                                                         double* __restrict__ stats, float* __restrict__ weights,
+                                                                         size_t row_elems, unsigned chunks) {
+  __shared__ float w_sh;
+  const unsigned row = blockIdx.x / chunks, chunk = blockIdx.x - row * chunks;
+  if (threadIdx.x == 0) {
+#pragma clang fp contract(off)             // every float64 operation below individually rounded: the formula as written
+    double sum[4];                         // e_pos, e_pos^2, e_cfg, e_cfg^2
+    row_partials_sum_dd(partial, row, chunks, sum);
+    const double n = (double)row_elems, mp = sum[0] / n, mc = sum[2] / n;
+    const double var_pos = sum[1] / n - mp * mp, var_cfg = sum[3] / n - mc * mc;
+    double f = sqrt(var_pos / var_cfg);
+    if (!(var_cfg > 0.0) || !isfinite(f)) f = 1.0;
+    const float w = (float)(phi * f + (1.0 - phi));
+    w_sh = w;
+    if (chunk == 0) {
+      if (stats) {
+        stats[(size_t)row * 3 + 0] = var_pos;
+        stats[(size_t)row * 3 + 1] = var_cfg;
+        stats[(size_t)row * 3 + 2] = f;
+      }
+      if (weights) weights[row] = w;
+    }
+  }
+  __syncthreads();
+  const float w = w_sh;
+  const size_t base = (size_t)row * row_elems;
+#pragma unroll
+  for (int k = 0; k < kRowGroups; ++k) {
+    const size_t e = row_group_elem(chunk, k);
+    if (e < row_elems) {
+      f32x4 pv, cv, o;
+      cfg_rescale_load<VEC>(epsg, groups, gs, base, e, row_elems, s1, s2, pv, cv);
+#pragma unroll
+      for (int j = 0; j < 4; ++j) o[j] = mul_rn(cv[j], w);
+      store4<VEC>(out + base, e, row_elems, o);
+    }
+  }
+}
+size_t cfg_rescale_workspace_bytes(int rows, size_t row_elems) {
+  if (rows <= 0 || row_elems == 0) return 0;
+  return (size_t)rows * chunks_of(row_elems, PF_MSE_CHUNK) * 4 * 2 * sizeof(double);
+}
+int launch_cfg_rescale(const pf_cfg_rescale_args& a, hipStream_t s) {
+  PF_REQUIRE(a.epsg && a.eps, "cfg_rescale: null epsg or eps");
+  PF_REQUIRE(a.groups == 2 || a.groups == 3, "cfg_rescale: groups %d, expected 2 or 3 (one group has nothing to rescale)", a.groups);
+  PF_REQUIRE(a.rows > 0 && a.row_elems > 0, "cfg_rescale: %d rows of %zu elements", a.rows, a.row_elems);
+  PF_REQUIRE(a.phi >= 0.0 && a.phi <= 1.0, "cfg_rescale: phi %g outside [0, 1]", a.phi);       // (a NaN fails both)
+  const size_t chunks = chunks_of(a.row_elems, PF_MSE_CHUNK), need = cfg_rescale_workspace_bytes(a.rows, a.row_elems);
+  PF_REQUIRE(chunks * (size_t)a.rows < (1ull << 31), "cfg_rescale: %d rows of %zu elements are more workgroups than one launch holds", a.rows, a.row_elems);
+  const size_t gs = (size_t)a.rows * a.row_elems, bytes = gs * sizeof(float);
+  PF_REQUIRE(!ranges_overlap(a.eps, bytes, a.epsg, bytes * a.groups), "cfg_rescale: eps overlaps epsg (the combine launch reads the groups again)");
+  PF_REQUIRE(((uintptr_t)a.stats & 7) == 0, "cfg_rescale: stats must be 8-byte aligned");
+  PF_REQUIRE(a.workspace, "cfg_rescale: no workspace (pf_cfg_rescale_workspace_bytes)");
+  PF_REQUIRE(a.workspace_bytes >= need, "cfg_rescale: workspace of %zu bytes required, got %zu", need, a.workspace_bytes);
+  PF_REQUIRE(((uintptr_t)a.workspace & 7) == 0, "cfg_rescale: workspace must be 8-byte aligned");
+  const bool vec = aligned16({a.epsg, a.eps}) && a.row_elems % 4 == 0;      // then every group and every row starts 16-byte aligned too
+  const dim3 grid((unsigned)(chunks * a.rows)), block(kRowThreads);
+  double* partial = reinterpret_cast<double*>(a.workspace);
+  if (vec)
+    hipLaunchKernelGGL(cfg_rescale_reduce_kernel<true>, grid, block, 0, s, a.epsg, a.groups, gs, a.s1, a.s2, partial, a.row_elems, (unsigned)chunks);
+  else
+    hipLaunchKernelGGL(cfg_rescale_reduce_kernel<false>, grid, block, 0, s, a.epsg, a.groups, gs, a.s1, a.s2, partial, a.row_elems, (unsigned)chunks);
+  PF_CHECK_HIP(hipGetLastError());
+  if (vec)
+    hipLaunchKernelGGL(cfg_rescale_combine_kernel<true>, grid, block, 0, s, a.epsg, a.groups, gs, a.s1, a.s2, a.phi, partial, a.eps, a.stats, a.weights,
+                       a.row_elems, (unsigned)chunks);
+  else
+    hipLaunchKernelGGL(cfg_rescale_combine_kernel<false>, grid, block, 0, s, a.epsg, a.groups, gs, a.s1, a.s2, a.phi, partial, a.eps, a.stats, a.weights,
+                       a.row_elems, (unsigned)chunks);
+  PF_CHECK_HIP(hipGetLastError());
+  return PF_OK;
 }
 
 // ---- overlapping windows along the time axis (include/pfhip.h: pf_window_split / pf_window_merge; WindowPlan in sampler.py).  A song is a

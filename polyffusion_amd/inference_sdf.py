@@ -36,7 +36,8 @@ from . import rollmatch as pfrollmatch
 from . import score as pfscore
 from .model_sdf import ChordEncoder, Polyffusion_SDF, TextureEncoder
 from .params import Params, find_params, load_params, preset
-from .sampler import GUIDANCE_ORDERS, MORPH_CONDS, MORPH_EASES, DDIMSampler, DiffusionSampler, DPMSolverSampler, DualScale, SDFSampler
+from .sampler import (GUIDANCE_ORDERS, MORPH_CONDS, MORPH_EASES, DDIMSampler, DiffusionSampler, DPMSolverSampler, DualScale, SDFSampler,
+                      guidance_interval_from_fractions)
 from .unet import LatentDiffusion, UNetModel
 
 
@@ -349,6 +350,9 @@ class Experiments:
     def _stamp(self, uncond_scale, autoreg, extra="", joint=None):
         """``joint``: ``None``, or the blend of a joint run (``mean`` is written as plain ``joint``)."""
         how = ",autoreg" if autoreg else "" if not joint else ",joint" if joint == "mean" else f",joint-{joint}"
+        # the sampler's guidance settings, only when set: without them the name is what it always was
+        phi, interval = getattr(self.sampler, "guidance_rescale", 0.0), getattr(self.sampler, "guidance_interval", None)
+        how += (f",rescale={phi}" if phi else "") + (f",interval={interval[0]}-{interval[1]}" if interval is not None else "")
         return (f"{self.model_label}{extra}[scale={uncond_scale}{how}]"
                 f"_{datetime.now().strftime('%y-%m-%d_%H%M%S')}")
 
@@ -508,6 +512,12 @@ def make_parser() -> ArgumentParser:
                    "eps = eps(-,-) + Y * (eps(-,txt) - eps(-,-)) + X * (eps(chd,txt) - eps(-,txt)) ('-' = that part dropped, as cond_mode "
                    "mix2 trains it).  X == Y is --uncond_scale X; costs three denoiser evaluations per step instead of two")
     p.add_argument("--uncond_scale_txt", type=float, default=None, metavar="Y", help="extension: the texture scale Y of --uncond_scale_chd")
+    p.add_argument("--guidance_rescale", type=float, default=0.0, metavar="PHI", help="extension: guidance rescale (Lin et al. 2024, section "
+                   "3.4): the guided prediction is scaled back to the conditional prediction's per-sample standard deviation and mixed with the "
+                   "plain one by PHI in [0, 1] (0, the default: off; 0.7 is the paper's).  Per window under --joint.  No effect without guidance")
+    p.add_argument("--guidance_interval", type=float, nargs=2, default=None, metavar=("LO", "HI"), help="extension: guide only while the time "
+                   "step lies in the fractions [LO, HI] of the schedule, 0 <= LO <= HI <= 1 (Kynkaanniemi et al. 2024): t_lo = ceil(LO * (T - 1)), "
+                   "t_hi = floor(HI * (T - 1)); outside it a step evaluates the condition alone, at the plain batch.  Not with --hip_graph")
     p.add_argument("--guidance_order", choices=list(GUIDANCE_ORDERS), default="chd,txt", metavar="{chd,txt | txt,chd}", help="extension: which part the intermediate "
                    "evaluation of --uncond_scale_chd / --uncond_scale_txt keeps (the part named first); default: chd,txt")
     p.add_argument("--seed", type=int, help="use a specific seed for inference")
@@ -670,6 +680,28 @@ def check_score_args(args, cond_type: Optional[str] = None) -> bool:
         if best_of > 1 and args.rank_by in ("chord", "bass", "extracted") and "chord" not in cond_type.split("+"):
             raise SystemExit(f"--rank_by {args.rank_by} needs the chords of the run; this model's cond_type is {cond_type!r} (use --rank_by integrity)")
     return True
+
+
+def check_guidance_args(args, n_steps: Optional[int] = None):
+    """``(phi, interval)`` of ``--guidance_rescale`` / ``--guidance_interval`` as the samplers take them; every misuse is an argparse error
+    (usage + exit status 2).  ``n_steps``: the schedule's length once it is known (``None``: the flags alone, the interval is ``None``)."""
+    error = make_parser().error
+    phi, fr = getattr(args, "guidance_rescale", 0.0), getattr(args, "guidance_interval", None)
+    if not 0.0 <= phi <= 1.0:        # (a NaN fails both)
+        error(f"--guidance_rescale {phi}: PHI lies in [0, 1]")
+    if fr is None:
+        return phi, None
+    lo, hi = fr
+    if not 0.0 <= lo <= hi <= 1.0:
+        error(f"--guidance_interval {lo} {hi}: fractions of the schedule, 0 <= LO <= HI <= 1")
+    if getattr(args, "hip_graph", False):
+        error("--guidance_interval with --hip_graph: a captured step is one launch sequence, the guided and the unguided step are two")
+    if n_steps is None:
+        return phi, None
+    try:
+        return phi, guidance_interval_from_fractions(lo, hi, n_steps)
+    except ValueError as e:
+        error(f"--guidance_interval {lo} {hi}: {e}")
 
 
 def wants_dual_guidance(args, cond_type: str) -> bool:
@@ -958,21 +990,24 @@ def load_model(params, args, rank: int = 0, world: int = 1) -> Polyffusion_SDF:
 
 
 def make_sampler(model, args, seed: int, sample_offset: int = 0):
-    """(sampler, start index) as ``inference_sdf.py:735-747,215-219`` choose them."""
+    """(sampler, start index) as ``inference_sdf.py:735-747,215-219`` choose them.  Every run's sampler is made here - plain, --autoreg, --joint,
+    inpainting, --edit, --morph, --best_of, every rank of a sharded run - so --guidance_rescale / --guidance_interval reach all of them."""
+    if getattr(args, "dpm", False) and args.ddim:
+        raise SystemExit("--dpm and --ddim name two different samplers: give one of them")
+    phi, interval = check_guidance_args(args, model.ldm.n_steps)
+    guidance = dict(guidance_rescale=phi, guidance_interval=interval)
     if getattr(args, "dpm", False):
-        if args.ddim:
-            raise SystemExit("--dpm and --ddim name two different samplers: give one of them")
         sampler = DPMSolverSampler(model.ldm, args.dpm_steps, args.dpm_discretize, args.dpm_order, seed=seed, sample_offset=sample_offset,
-                                   graph=getattr(args, "hip_graph", False))
+                                   graph=getattr(args, "hip_graph", False), **guidance)
         return sampler, len(sampler.time_steps) - 1      # the grid's own length: logsnr drops repeated time steps
     if args.ddim:
         sampler = DDIMSampler(model.ldm, args.ddim_steps, args.ddim_discretize, args.ddim_eta, seed=seed, sample_offset=sample_offset,
-                              graph=getattr(args, "hip_graph", False))
+                              graph=getattr(args, "hip_graph", False), **guidance)
         t_idx = args.ddim_steps - 1    # inference_sdf.py:218 (NOT len(time_steps)-1: 'uniform' can yield one more entry)
         if t_idx >= len(sampler.time_steps):
             raise SystemExit(f"--ddim_steps {args.ddim_steps}: the discretisation has only {len(sampler.time_steps)} steps")
         return sampler, t_idx
-    return SDFSampler(model.ldm, seed=seed, sample_offset=sample_offset, graph=getattr(args, "hip_graph", False)), None
+    return SDFSampler(model.ldm, seed=seed, sample_offset=sample_offset, graph=getattr(args, "hip_graph", False), **guidance), None
 
 
 def generate_songs(model, params, args, cond, cond_mid, orig, mask, seed: int, rank: int = 0, world: int = 1, cond_concat=None,
@@ -1244,7 +1279,8 @@ def main(argv=None):
     args = make_parser().parse_args(argv)
     if args.dpm and args.ddim:
         raise SystemExit("--dpm and --ddim name two different samplers: give one of them")
-    check_edit_args(args)                                  # what the flags alone decide, before anything else
+    check_guidance_args(args)                              # what the flags alone decide, before anything else
+    check_edit_args(args)
     check_morph_args(args)
     check_score_args(args)
     if not torch.cuda.is_available():

@@ -15,6 +15,10 @@
 * ``DPMSolverSampler``  - not in the reference: DPM-Solver++(2M), the second-order multistep solver, driven like ``DDIMSampler``.
 * ``WindowPlan``        - not in the reference: a song as one canvas whose half-overlapping windows are denoised as ONE batch per step, their
   noise predictions blended where they overlap (``DiffusionSampler.windows``; ``pf_window_split`` / ``pf_window_merge``).
+* ``guidance_rescale`` / ``guidance_interval`` - not in the reference: settings of every family (``DiffusionSampler``).  Rescale (Lin et al.
+  2024, section 3.4): a guided eps scaled back towards the conditional prediction's per-sample standard deviation and mixed with the plain
+  combine by phi (``pf_cfg_rescale``).  Interval (Kynkaanniemi et al. 2024): guidance only while the time-step value lies in
+  ``[t_lo, t_hi]``, the conditional evaluation alone outside it; ``normalize_guidance_interval``, ``guidance_interval_from_fractions``.
 
 Same method names and argument meaning as the reference, so ``Experiments.predict`` drives
 them unchanged.  Differences, all host-side plumbing:
@@ -130,6 +134,35 @@ def guidance_plan(cond: torch.Tensor, uncond_scale: Scale, uncond_cond: Optional
     return torch.cat([uncond_cond, cond]), 2, (float(uncond_scale),)
 
 
+def normalize_guidance_interval(interval, n_steps: int) -> Optional[Tuple[int, int]]:
+    """``(t_lo, t_hi)`` as a pair of ints with ``0 <= t_lo <= t_hi <= n_steps - 1`` (a ``ValueError`` otherwise), time-step VALUES of a schedule
+    of ``n_steps``; the whole schedule ``(0, n_steps - 1)`` and ``None`` are ``None``: no interval, every step guided."""
+    if interval is None:
+        return None
+    try:
+        lo, hi = interval
+        lo_i, hi_i = int(lo), int(hi)
+    except (TypeError, ValueError):
+        raise ValueError(f"guidance_interval {interval!r}: expected (t_lo, t_hi) or None") from None
+    if lo_i != lo or hi_i != hi:
+        raise ValueError(f"guidance_interval {interval!r}: t_lo and t_hi are time-step values, whole numbers")
+    if not 0 <= lo_i <= hi_i <= int(n_steps) - 1:
+        raise ValueError(f"guidance_interval ({lo_i}, {hi_i}): expected 0 <= t_lo <= t_hi <= {int(n_steps) - 1}, the time-step values of the schedule")
+    return None if (lo_i, hi_i) == (0, int(n_steps) - 1) else (lo_i, hi_i)
+
+
+def guidance_interval_from_fractions(lo: float, hi: float, n_steps: int) -> Optional[Tuple[int, int]]:
+    """The interval given as fractions of the schedule, ``0 <= lo <= hi <= 1``: ``t_lo = ceil(lo * (T - 1))``, ``t_hi = floor(hi * (T - 1))``
+    (what ``--guidance_interval LO HI`` passes on), normalised as above.  Fractions so close that no time step lies between them are refused."""
+    lo, hi, T = float(lo), float(hi), int(n_steps)
+    if not 0.0 <= lo <= hi <= 1.0:       # (a NaN fails)
+        raise ValueError(f"guidance interval fractions ({lo}, {hi}): expected 0 <= LO <= HI <= 1")
+    t_lo, t_hi = math.ceil(lo * (T - 1)), math.floor(hi * (T - 1))
+    if t_lo > t_hi:
+        raise ValueError(f"guidance interval fractions ({lo}, {hi}) hold no time step of a schedule of {T}")
+    return normalize_guidance_interval((t_lo, t_hi), T)
+
+
 BLENDS = ("mean", "ramp")
 MAX_COVER = 8           # windows over one canvas row that pf_window_merge accepts: ceil(win_h / stride)
 
@@ -189,7 +222,8 @@ class DiffusionSampler:
     model: LatentDiffusion
 
     def __init__(self, model: LatentDiffusion, noise_fn: Optional[NoiseFn] = None, seed: int = 0, sample_offset: int = 0,
-                 graph: bool = False, windows: Optional[WindowPlan] = None):
+                 graph: bool = False, windows: Optional[WindowPlan] = None, guidance_rescale: float = 0.0,
+                 guidance_interval: Optional[Tuple[int, int]] = None):
         self.model = model
         # windows: x, orig, mask, orig_noise and cond_concat are song canvases [S, ., canvas_h, W], cond / uncond_cond have S * n_windows rows
         # in the plan's window order, and get_eps evaluates the denoiser on the batch of windows (pf_window_split), blending its predictions
@@ -220,6 +254,57 @@ class DiffusionSampler:
         # (the reference's `is_show_image` hook, sampler_sdf.py:338-345, as a callback).  None = no call, no cost.  Used by the
         # full-length parity runs (tools/long_parity.py) to record how two arithmetic modes drift apart along one noise tape.
         self.on_step: Optional[Callable[[int, torch.Tensor], None]] = None
+        # guidance_rescale (phi): a guided eps is scaled back towards the conditional prediction's per-sample standard deviation and mixed
+        # with the plain combine by phi (pf_cfg_rescale in place of pf_cfg_combine / pf_cfg_combine3); 0.0: today's combine, exactly.
+        # guidance_interval (t_lo, t_hi): guidance only while the time-step VALUE the denoiser is fed lies in [t_lo, t_hi]; outside it a
+        # call is get_eps(..., uncond_scale=1.0): cond alone, one evaluation at the plain batch.  None: every step is guided.
+        self.guidance_rescale = guidance_rescale
+        self.guidance_interval = guidance_interval
+        self.last_rescale = None      # (stats float64 [rows, 3] = var_pos, var_cfg, f; weights float32 [rows]) of the last rescaled call, on the device
+        self._check_guidance()
+
+    # ---- guidance rescale and guidance interval (not in the reference) ------------------------------------------------------------------
+    @property
+    def guidance_rescale(self) -> float:
+        return getattr(self, "_guidance_rescale", 0.0)
+
+    @guidance_rescale.setter
+    def guidance_rescale(self, phi):
+        phi = float(phi)
+        if not 0.0 <= phi <= 1.0:        # (a NaN fails both)
+            raise ValueError(f"guidance_rescale {phi} outside [0, 1]")
+        self._guidance_rescale = phi
+
+    @property
+    def guidance_interval(self) -> Optional[Tuple[int, int]]:
+        return getattr(self, "_guidance_interval", None)
+
+    @guidance_interval.setter
+    def guidance_interval(self, interval):
+        self._guidance_interval = normalize_guidance_interval(interval, self.model.n_steps)
+
+    def _check_guidance(self):
+        if self.graph and self.guidance_interval is not None:
+            raise ValueError(f"guidance_interval {self.guidance_interval} with graph=True: a captured step is ONE launch sequence, and the guided "
+                             "and the unguided step are two (out of scope: two captures with a hand-over between their static buffers)")
+
+    def guided_at(self, t_value) -> bool:
+        """Whether a call that feeds the denoiser time-step value ``t_value`` (for DDIM / DPM the tau entry, not the grid index) is guided."""
+        iv = self.guidance_interval
+        return iv is None or iv[0] <= int(t_value) <= iv[1]
+
+    def _guidance_at(self, t_value, uncond_scale, prep):
+        """THE place the interval is resolved, for every loop, ``p_sample``, ``invert`` and ``morph`` (all of them reach ``get_eps`` through
+        ``_eps``, which knows the time-step value on the host): ``(uncond_scale, prep)`` of this call - as given inside the interval, ``1.0``
+        and the prefix hoisted for ``cond`` alone (``prepare()``'s ``"unguided"`` entry) outside it."""
+        if self.guidance_interval is None:
+            return uncond_scale, prep
+        if t_value is None:
+            raise ValueError(f"get_eps: guidance_interval {self.guidance_interval} is set and the call does not say which time step it is "
+                             "(t_value=): it cannot tell whether it is guided")
+        if self.guided_at(t_value):
+            return uncond_scale, prep
+        return 1.0, None if prep is None else prep.get("unguided")
 
     def _step_state(self, device) -> torch.Tensor:
         key = ("state", str(device))
@@ -299,6 +384,7 @@ class DiffusionSampler:
         the update kernel), `update(bufs, e_t, table, state)`: the family's in-place update of bufs["x"].  `body_of(bufs, t_buf, state)`: a
         step of another shape than {begin, eps, update, end} (the upward step of `DDIMSampler.invert`) - it returns the closure to capture and
         `update` is not used; the static buffers of the call stay reachable as `self._last_bufs`."""
+        self._check_guidance()
         x = inputs["x"]
         dev, B, st = x.device, self._eps_rows(x), self._step_state(x.device)      # B: rows the denoiser sees (one per window under a plan)
 
@@ -317,7 +403,7 @@ class DiffusionSampler:
             return body
 
         wkey = None if self.windows is None else self.windows.key
-        key = (family, str(dev), scale_key(uncond_scale), self.seed, self._elem_offset(x.shape), ndraw, wkey) + self._shape_key(**inputs)
+        key = (family, str(dev), scale_key(uncond_scale), self.guidance_rescale, self.seed, self._elem_offset(x.shape), ndraw, wkey) + self._shape_key(**inputs)
         ent = self._graph_for(key, inputs, make_body, lambda: self._set_state(st, t_start), uncond_scale)
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         e0.record()
@@ -346,13 +432,19 @@ class DiffusionSampler:
         the model: ``cond``, ``uncond_cond`` or ``cat([uncond_cond, cond])`` by the reference's exact-float branches
         (``sampler/__init__.py:63-74``; ``guidance_plan`` decides, for ``get_eps`` too).  ``None`` entries (several context tokens) are computed inside every forward as before.
         Called explicitly by the loops of this class; pass the result as ``prep=`` with the SAME cond / guidance arguments.
-        ``out``: a previous result whose buffers are overwritten in place (captured-graph replay)."""
+        ``out``: a previous result whose buffers are overwritten in place (captured-graph replay).
+        With a ``guidance_interval`` the steps outside it evaluate ``cond`` alone: the result then carries a second prefix for that context
+        under ``"unguided"`` (the time table is shared), which ``get_eps`` picks for such a step."""
         m = self.model.eps_model
-        ctx = guidance_plan(cond, uncond_scale, uncond_cond)[0]     # (a DualScale: possibly the three groups of dual guidance)
+        ctx, groups, _ = guidance_plan(cond, uncond_scale, uncond_cond)     # (a DualScale: possibly the three groups of dual guidance)
         o = out or {}
         # one row more than the schedule has steps: the DDIM tau table is shifted by +1 (sampler_ddim.py:63-73)
-        return {"time_table": m.prepare_time(self.model.n_steps + 1, out=o.get("time_table")),
+        prep = {"time_table": m.prepare_time(self.model.n_steps + 1, out=o.get("time_table")),
                 "cross": m.prepare_cond(ctx, out=o.get("cross"))}
+        if self.guidance_interval is not None:
+            un = o.get("unguided") or {}
+            prep["unguided"] = prep if groups == 1 and ctx is cond else {"time_table": prep["time_table"], "cross": m.prepare_cond(cond, out=un.get("cross"))}
+        return prep
 
     @staticmethod
     def _prep_kw(prep):
@@ -360,22 +452,34 @@ class DiffusionSampler:
 
     # ---- eps with classifier-free guidance ----------------------------------------------------------
     def get_eps(self, x: torch.Tensor, t: torch.Tensor, c: torch.Tensor, *, uncond_scale: Scale,
-                uncond_cond: Optional[torch.Tensor], prep: Optional[dict] = None):
+                uncond_cond: Optional[torch.Tensor], prep: Optional[dict] = None, t_value: Optional[int] = None):
         """``uncond_scale``: the reference's float, or a ``DualScale`` (separate scales for the chord and texture parts of ``c``).
         With a window plan (``self.windows``): ``x`` is the canvas ``[S, C, canvas_h, W]``, ``t`` / ``c`` / ``uncond_cond`` have one row per
-        window, and the result is the canvas eps - split, the same evaluation on the windows, and ONE merge launch that also combines the groups."""
+        window, and the result is the canvas eps - split, the same evaluation on the windows, and ONE merge launch that also combines the groups.
+        ``t_value``: the time-step value of ``t`` on the host; needed (a ``ValueError`` without it) only under a ``guidance_interval``,
+        outside which the call is ``uncond_scale=1.0``.  ``guidance_rescale != 0``: a guided call combines its groups with ``pf_cfg_rescale``
+        (per batch entry; under a window plan per WINDOW, on the window batch, followed by a plain merge) and leaves the device tables
+        in ``self.last_rescale``; one group (scale 1, scale 0, no ``uncond_cond``) has nothing to rescale."""
+        uncond_scale, prep = self._guidance_at(t_value, uncond_scale, prep)
         wp = getattr(self, "windows", None)
         if wp is not None:
             return self._get_eps_windows(wp, x, t, c, uncond_scale, uncond_cond, prep)
         epsg, groups, scales = self._eps_groups(x, t, c, uncond_scale, uncond_cond, prep)
         if groups == 1:
             return epsg
+        if self.guidance_rescale != 0.0:
+            return self._rescale(epsg.contiguous(), groups, scales)
         e_t = torch.empty_like(epsg[: x.shape[0]])   # eps has out_channels; x may carry extra cond_concat channels
         if groups == 2:
             _lib.check(self._lib.pf_cfg_combine(epsg.data_ptr(), scales[0], e_t.data_ptr(), e_t.numel(), _lib.current_stream()), "pf_cfg_combine")
         else:
             _lib.check(self._lib.pf_cfg_combine3(epsg.data_ptr(), scales[0], scales[1], e_t.data_ptr(), e_t.numel(), _lib.current_stream()),
                        "pf_cfg_combine3")
+        return e_t
+
+    def _rescale(self, epsg, groups, scales):
+        e_t, stats, weights = _steps.cfg_rescale(self._lib, epsg, groups, scales, self.guidance_rescale, want_stats=True)
+        self.last_rescale = (stats, weights)
         return e_t
 
     def _eps_groups(self, x, t, c, uncond_scale, uncond_cond, prep):
@@ -417,6 +521,9 @@ class DiffusionSampler:
                              f"{c.shape[0]}" + ("" if uncond_cond is None else f", {uncond_cond.shape[0]}"))
         xw = _steps.window_split(self._lib, x, wp.n_windows, wp.stride, wp.win_h)
         epsg, groups, scales = self._eps_groups(xw, t, c, uncond_scale, uncond_cond, prep)
+        if groups > 1 and self.guidance_rescale != 0.0:
+            # the statistics are those of one WINDOW's eps, not of the canvas: the combine runs on the window batch, the merge is then plain
+            epsg, groups, scales = self._rescale(epsg.contiguous(), groups, scales), 1, ()
         return _steps.window_merge(self._lib, epsg.contiguous(), self._window_weights(wp, x.device), S, wp.n_windows, wp.stride, groups, scales)
 
     def _t_of(self, step: int, batch: int, device) -> torch.Tensor:
@@ -429,7 +536,7 @@ class DiffusionSampler:
     def _eps(self, x, c, step, uncond_scale, uncond_cond, cond_concat, prep=None):
         t = self._t_of(step, self._eps_rows(x), x.device)
         xin = x if cond_concat is None else torch.cat([x, cond_concat], dim=1)
-        return self.get_eps(xin, t, c, uncond_scale=uncond_scale, uncond_cond=uncond_cond, prep=prep)
+        return self.get_eps(xin, t, c, uncond_scale=uncond_scale, uncond_cond=uncond_cond, prep=prep, t_value=int(step))
 
     def _rng_ok(self, x, *others) -> bool:
         """The in-kernel noise path: on-device generator, whole Philox groups per tensor and per shard, and every tensor the
