@@ -202,6 +202,51 @@ typedef struct pf_cfg_rescale_args {
 } pf_cfg_rescale_args;
 size_t pf_cfg_rescale_workspace_bytes(int rows, size_t row_elems);
 int pf_cfg_rescale(const pf_cfg_rescale_args* a, void* stream);
+/* Bounding the predicted clean image (not in the reference; static clipping is clip_denoised of Ho, Jain & Abbeel 2020, dynamic thresholding
+ * is Saharia et al. 2022, "Photorealistic Text-to-Image Diffusion Models with Deep Language Understanding", section 2.3 - DESIGN.md 0, row
+ * a43, and 3, "Clipping and dynamic thresholding").  Every sampler family consumes eps, so the operation rewrites eps: per row r (a batch
+ * entry, or a song canvas under a window plan) eps becomes the eps' whose predicted x0 is the bounded one.  Per element, fp32, every
+ * operation individually rounded, no contraction:
+ *     (cx, ce, kx, k0) = table[clamp(t[r * t_stride], 0, n_table - 1)]    1/sqrt(ab), sqrt(1-ab)/sqrt(ab), 1/sqrt(1-ab), sqrt(ab)/sqrt(1-ab)
+ *     x0  = fl(fl(cx*x) - fl(ce*eps))
+ *     mode 0 (clip):     x0' = x0 < lo ? lo : x0 > hi ? hi : x0                           (a NaN x0 stays NaN)
+ *     mode 1 (dynamic):  u = fl(x0 - c), c = float((lo + hi)/2), h = (hi - lo)/2 in float64
+ *                        q = the p-quantile of |u| over the row, torch.quantile's linear rule in float64: pos = p*(row_elems - 1),
+ *                            k = floor(pos), q = a_(k) + (pos - k)*(a_(k+1) - a_(k)), a_(n) := a_(n-1); the order statistics are exact
+ *                            (a radix select over the uint32 patterns of |u|: -0 counts as +0, NaN sorts above inf), ties included
+ *                        s = min(max(q, h), s_max*h) in float64
+ *                        s == h        the row is mode 0's row, bit for bit
+ *                        q not finite  eps' = eps for the whole row (a stated rule; stats then hold s = NaN, w = 1, count 0)
+ *                        otherwise     w = float(h/s), rounded once; x0' = fl(c + fl(clamp(u, -float(s), float(s)) * w))
+ *     eps' = (x0' == x0) ? eps : fl(fl(kx*x) - fl(k0*x0'))                                untouched elements come through bit for bit
+ *   stats (optional) [rows][4] device doubles: q, s, w and the number of elements with x0' != x0 (an integer; exact); mode 0: NaN, NaN, 1, count.
+ *   Two forms with the same bits, chosen by `form` (0: resident when row_elems <= PF_X0T_RESIDENT_MAX, else streamed; 1, 2: forced):
+ *     resident  ONE launch, a workgroup of 1024 lanes per row: x and eps are read once into registers, the keys staged in LDS (4 bytes
+ *               per element, up to 128 KiB), four 8-bit histogram passes with integer LDS atomics (order-free), eps' written once.
+ *     streamed  workgroup = (row, PF_MSE_CHUNK of it): four histogram launches (one per 8-bit digit; per-chunk partials in `workspace`,
+ *               added in chunk order, no global atomics), one apply launch, and with stats one launch adding the per-chunk counts:
+ *               5 launches (6 with stats) in mode 1, 1 (2 with stats) in mode 0, whatever the data.
+ *   No host sync, no allocation, capturable.  A row's result depends on that row alone.  x (with x_row_stride % 4 == 0), eps and eps_out
+ *   16-byte aligned with row_elems % 4 == 0 are moved as 16-byte vectors, anything else element by element: the same bits.
+ *   workspace: pf_x0_threshold_workspace_bytes(rows, row_elems, form) bytes, 8-byte aligned (0 for the resident form: none needed).
+ * Refused before any launch (message prefix "x0_threshold: "): null x, eps, eps_out, t or table; rows <= 0 or row_elems == 0 (or >= 2^32);
+ * x_row_stride < row_elems; t_stride < 0 or n_table <= 0; lo >= hi or either not finite; p NaN or outside (0, 1]; s_max < 1 or NaN; an
+ * unknown mode or form; form 1 with row_elems > PF_X0T_RESIDENT_MAX; eps_out overlapping eps partially (eps_out == eps is in place), or x,
+ * table or t at all; a needed workspace that is missing, too small or not 8-byte aligned; stats not 8-byte aligned; more workgroups than
+ * one launch holds (rows * chunks >= 2^31). */
+#define PF_X0T_RESIDENT_MAX 32768
+typedef struct pf_x0_threshold_args {
+  const float* x; size_t x_row_stride;      /* the state eps was predicted from; may carry cond_concat channels behind the first row_elems */
+  const float* eps; float* eps_out;         /* [rows][row_elems]; eps_out == eps (in place) or disjoint */
+  const int64_t* t; int32_t t_stride;       /* device; row r reads t[r * t_stride] */
+  const float* table; int32_t n_table;      /* device, [n_table][4] */
+  double* stats;                            /* may be NULL */
+  void* workspace; size_t workspace_bytes;
+  double p, s_max; float lo, hi;            /* p in (0, 1]; s_max >= 1 or +inf; lo < hi */
+  int32_t mode, form, rows; size_t row_elems;
+} pf_x0_threshold_args;
+size_t pf_x0_threshold_workspace_bytes(int rows, size_t row_elems, int form);
+int pf_x0_threshold(const pf_x0_threshold_args* a, void* stream);
 
 /* Overlapping windows along the time axis (not in the reference; MultiDiffusion, Bar-Tal et al. 2023, on the rows of a piano roll): a song is
  * a canvas [songs][channels][canvas_h][width], canvas_h = stride * (n_windows - 1) + win_h, and the denoiser sees it as the batch of its

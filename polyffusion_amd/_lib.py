@@ -107,6 +107,14 @@ class CfgRescaleArgs(C.Structure):
                    ("rows", C.c_int32), ("row_elems", C.c_size_t)])
 
 
+class X0ThresholdArgs(C.Structure):
+    """pf_x0_threshold_args (include/pfhip.h); filled by ``_steps.x0_threshold`` only."""
+    _fields_ = [("x", C.c_void_p), ("x_row_stride", C.c_size_t), ("eps", C.c_void_p), ("eps_out", C.c_void_p), ("t", C.c_void_p),
+                ("t_stride", C.c_int32), ("table", C.c_void_p), ("n_table", C.c_int32), ("stats", C.c_void_p), ("workspace", C.c_void_p),
+                ("workspace_bytes", C.c_size_t), ("p", C.c_double), ("s_max", C.c_double), ("lo", C.c_float), ("hi", C.c_float),
+                ("mode", C.c_int32), ("form", C.c_int32), ("rows", C.c_int32), ("row_elems", C.c_size_t)]
+
+
 class WindowMergeArgs(C.Structure):
     """pf_window_merge_args (include/pfhip.h); filled by ``_steps.window_merge`` only."""
     _fields_ = ([("eps", C.c_void_p), ("row_weight", C.c_void_p), ("groups", C.c_int), ("s1", C.c_float), ("s2", C.c_float)]
@@ -183,6 +191,9 @@ FEEDBACK = {"row": 0, "batch": 1}   # PF_FEEDBACK_ROW / PF_FEEDBACK_BATCH
 MSE_CHUNK = 2048           # PF_MSE_CHUNK: elements of a row one workgroup of pf_mse_rows reduces
 SLERP_MAX_FRAMES = 64      # PF_SLERP_MAX_FRAMES: frames one pf_slerp_rows call writes
 SLERP_MODES = {"slerp": 0, "lerp": 1}
+X0T_RESIDENT_MAX = 32768   # PF_X0T_RESIDENT_MAX: elements of a row the resident form of pf_x0_threshold holds in LDS
+X0T_MODES = {"clip": 0, "dynamic": 1}
+X0T_FORMS = {"auto": 0, "resident": 1, "streamed": 2}
 
 
 class UNetPrepared(C.Structure):
@@ -300,6 +311,8 @@ SIGNATURES = {
     "pf_cfg_combine3": (C.c_int, [C.c_void_p, C.c_float, C.c_float, C.c_void_p, C.c_size_t, C.c_void_p]),
     "pf_cfg_rescale_workspace_bytes": (C.c_size_t, [C.c_int, C.c_size_t]),
     "pf_cfg_rescale": (C.c_int, [C.POINTER(CfgRescaleArgs), C.c_void_p]),
+    "pf_x0_threshold_workspace_bytes": (C.c_size_t, [C.c_int, C.c_size_t, C.c_int]),
+    "pf_x0_threshold": (C.c_int, [C.POINTER(X0ThresholdArgs), C.c_void_p]),
     "pf_window_split": (C.c_int, [C.c_void_p, C.c_void_p] + [C.c_int] * 6 + [C.c_void_p]),
     "pf_window_merge": (C.c_int, [C.POINTER(WindowMergeArgs), C.c_void_p]),
     "pf_ddpm_step": (C.c_int, [C.POINTER(DdpmStepArgs), C.c_void_p]),

@@ -1,6 +1,7 @@
 """The sampler's elementwise launches: noise, ``a*x + b*y`` and the three reverse-step updates (``pf_randn`` / ``pf_randn_dev``, ``pf_axpby``,
 ``pf_ddpm_step``, ``pf_ddim_step``, ``pf_dpm_step`` of include/pfhip.h), the upward iterate of exact DDIM inversion (``pf_invert_step``),
 the frames between two tensors of a morph (``pf_slerp_rows``), the guidance combine rescaled per row (``pf_cfg_rescale``),
+eps rewritten so that its predicted x0 is clipped or dynamically thresholded (``pf_x0_threshold``),
 the two launches around the denoiser of a window plan
 (``pf_window_split``, ``pf_window_merge``), and the two launches of the training objective (``pf_qsample_rows``,
 ``pf_mse_rows``) with the loss evaluation both diffusion mirrors share (``diffusion_loss_rows``).  The only place that fills
@@ -196,6 +197,73 @@ def cfg_rescale(lib, epsg, groups: int, scales, phi: float, *, out=None, want_st
     a.groups, a.rows, a.row_elems = groups, rows, row_elems
     _lib.check(lib.pf_cfg_rescale(C.byref(a), _lib.current_stream()), "pf_cfg_rescale", lib)
     return out, stats, weights
+
+
+def x0_threshold_table(alpha_bar) -> torch.Tensor:
+    """The coefficient table of ``pf_x0_threshold`` on the host, float32 ``[n_steps, 4]``: ``1/sqrt(ab)``, ``sqrt(1-ab)/sqrt(ab)``,
+    ``1/sqrt(1-ab)``, ``sqrt(ab)/sqrt(1-ab)`` of the model's float32 ``alpha_bar``, computed in float64 and rounded once."""
+    ab = alpha_bar.detach().to(device="cpu", dtype=torch.float32).double()
+    ra, rb = torch.sqrt(ab), torch.sqrt(1.0 - ab)
+    return torch.stack([1.0 / ra, rb / ra, 1.0 / rb, ra / rb], dim=1).float().contiguous()
+
+
+_X0T_WORKSPACES = {}      # str(device) -> the largest workspace x0_threshold has needed there
+
+
+def x0_threshold_workspace(lib, rows: int, row_elems: int, device, form: str = "auto"):
+    """The workspace ``x0_threshold`` needs (``None``: none - the resident form), cached per device and grown on demand.  While a stream
+    is being captured nothing is cached: a buffer allocated there belongs to the graph's pool."""
+    nb = int(lib.pf_x0_threshold_workspace_bytes(int(rows), int(row_elems), _lib.X0T_FORMS[form]))
+    if nb == 0:
+        return None
+    key = str(device)
+    ws = _X0T_WORKSPACES.get(key)
+    if ws is None or ws.numel() * 8 < nb:
+        ws = torch.empty((nb + 7) // 8, dtype=torch.int64, device=device)
+        if not (device.type == "cuda" and torch.cuda.is_current_stream_capturing()):
+            _X0T_WORKSPACES[key] = ws
+    return ws
+
+
+def x0_threshold(lib, x, eps, t, table, *, mode: str = "dynamic", p: float = 0.995, range=(0.0, 1.0), s_max: float = float("inf"),
+                 t_stride: int = 1, out=None, want_stats: bool = False, form: str = "auto", workspace=None):
+    """``eps`` ``[rows, ...]`` rewritten so that the x0 it predicts from ``x`` is clipped to ``range`` (``mode="clip"``) or dynamically
+    thresholded at the ``p``-quantile of its own magnitudes (``mode="dynamic"``; ``pf_x0_threshold``).  ``x`` ``[rows, ...]`` may have more
+    elements per row than ``eps`` (``cond_concat`` channels behind the first ones); row ``r`` reads its time-step value at
+    ``t[r * t_stride]`` (device int64) and its coefficients in ``table`` (``x0_threshold_table`` on the device).  ``out``: ``None`` (a new
+    tensor), ``eps`` itself (in place) or a disjoint tensor.  Returns ``(out, stats)``: ``stats`` float64 ``[rows, 4]`` on the device
+    (``q``, ``s``, ``w``, changed elements), ``None`` without ``want_stats``.  No host sync."""
+    if mode not in _lib.X0T_MODES:
+        raise ValueError(f"x0_threshold: mode {mode!r}, expected one of {sorted(_lib.X0T_MODES)}")
+    if form not in _lib.X0T_FORMS:
+        raise ValueError(f"x0_threshold: form {form!r}, expected one of {sorted(_lib.X0T_FORMS)}")
+    for name, v in (("x", x), ("eps", eps)):
+        if v.dtype != torch.float32 or not v.is_contiguous():
+            raise ValueError(f"x0_threshold: {name} must be contiguous float32")
+    if t.dtype != torch.int64 or not t.is_contiguous() or table.dtype != torch.float32 or not table.is_contiguous() or table.dim() != 2 or table.shape[1] != 4:
+        raise ValueError("x0_threshold: t must be contiguous int64 and table contiguous float32 [n, 4]")
+    rows = eps.shape[0] if eps.dim() else 0
+    if rows == 0 or x.dim() == 0 or x.shape[0] != rows:
+        raise ValueError(f"x0_threshold: x of shape {tuple(x.shape)} and eps of shape {tuple(eps.shape)} do not have the same rows")
+    row_elems, x_stride = eps.numel() // rows, x.numel() // rows
+    if t.numel() < (rows - 1) * int(t_stride) + 1:
+        raise ValueError(f"x0_threshold: t of {t.numel()} entries for {rows} rows at stride {t_stride}")
+    if out is None:
+        out = torch.empty_like(eps)
+    elif out.dtype != torch.float32 or not out.is_contiguous() or out.shape != eps.shape:
+        raise ValueError(f"x0_threshold: out must be contiguous float32 of {tuple(eps.shape)}")
+    stats = torch.empty(rows, 4, dtype=torch.float64, device=eps.device) if want_stats else None
+    if workspace is None:
+        workspace = x0_threshold_workspace(lib, rows, row_elems, eps.device, form)
+    a = _lib.X0ThresholdArgs()
+    a.x, a.x_row_stride, a.eps, a.eps_out = x.data_ptr(), x_stride, eps.data_ptr(), out.data_ptr()
+    a.t, a.t_stride, a.table, a.n_table = t.data_ptr(), int(t_stride), table.data_ptr(), table.shape[0]
+    a.stats, a.workspace = _lib.ptr(stats), _lib.ptr(workspace)
+    a.workspace_bytes = 0 if workspace is None else workspace.numel() * workspace.element_size()
+    a.p, a.s_max, (a.lo, a.hi) = float(p), float(s_max), (float(range[0]), float(range[1]))
+    a.mode, a.form, a.rows, a.row_elems = _lib.X0T_MODES[mode], _lib.X0T_FORMS[form], rows, row_elems
+    _lib.check(lib.pf_x0_threshold(C.byref(a), _lib.current_stream()), "pf_x0_threshold", lib)
+    return out, stats
 
 
 def window_split(lib, canvas, n_windows: int, stride: int, win_h: int) -> torch.Tensor:

@@ -184,7 +184,12 @@ int pf_cfg_rescale(const pf_cfg_rescale_args* a, void* stream) {
   PF_REQUIRE(a, "cfg_rescale: null arguments");
   return launch_cfg_rescale(*a, (hipStream_t)stream);
 }
-int pf_window_split(const float* canvas, float* windows, int songs, int channels, int win_h, int width, int n_windows, int stride, void* stream) {
+size_t pf_x0_threshold_workspace_bytes(int rows, size_t row_elems, int form) { return x0_threshold_workspace_bytes(rows, row_elems, form); }
+int pf_x0_threshold(const pf_x0_threshold_args* a, void* stream) {
+  PF_REQUIRE(a, "x0_threshold: null arguments");
+  return launch_x0_threshold(*a, (hipStream_t)stream);
+}
+int pf_window_split(const float* canvas,float* windows, int songs, int channels, int win_h, int width, int n_windows, int stride, void* stream) {
   return launch_window_split(canvas, windows, songs, channels, win_h, width, n_windows, stride, (hipStream_t)stream);
 }
 int pf_window_merge(const pf_window_merge_args* a, void* stream) {

@@ -111,6 +111,9 @@ int launch_cfg_combine3(const float* eps3, float s1, float s2, float* eps, size_
 // guidance rescale: the combine of 2 or 3 groups scaled per row towards the conditional group's standard deviation (a reduce launch + a combine launch)
 size_t cfg_rescale_workspace_bytes(int rows, size_t row_elems);
 int launch_cfg_rescale(const pf_cfg_rescale_args& a, hipStream_t s);
+// clipping / dynamic thresholding of the predicted x0, as a rewrite of eps (x0_threshold.hip): an exact per-row quantile by radix select
+size_t x0_threshold_workspace_bytes(int rows, size_t row_elems, int form);
+int launch_x0_threshold(const pf_x0_threshold_args& a, hipStream_t s);
 // overlapping windows along the time axis: canvas -> window batch, and window eps -> canvas eps with the guidance combine folded in
 int launch_window_split(const float* canvas, float* windows, int songs, int channels, int win_h, int width, int n_windows, int stride, hipStream_t s);
 int launch_window_merge(const pf_window_merge_args& a, hipStream_t s);

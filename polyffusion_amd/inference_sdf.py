@@ -21,6 +21,7 @@ checkpoint by the deterministic weight generator (no trained weights ship with t
 from __future__ import annotations
 
 import json
+import math
 import os
 import random
 from argparse import ArgumentParser
@@ -37,7 +38,7 @@ from . import score as pfscore
 from .model_sdf import ChordEncoder, Polyffusion_SDF, TextureEncoder
 from .params import Params, find_params, load_params, preset
 from .sampler import (GUIDANCE_ORDERS, MORPH_CONDS, MORPH_EASES, DDIMSampler, DiffusionSampler, DPMSolverSampler, DualScale, SDFSampler,
-                      guidance_interval_from_fractions)
+                      X0Threshold, guidance_interval_from_fractions)
 from .unet import LatentDiffusion, UNetModel
 
 
@@ -353,6 +354,8 @@ class Experiments:
         # the sampler's guidance settings, only when set: without them the name is what it always was
         phi, interval = getattr(self.sampler, "guidance_rescale", 0.0), getattr(self.sampler, "guidance_interval", None)
         how += (f",rescale={phi}" if phi else "") + (f",interval={interval[0]}-{interval[1]}" if interval is not None else "")
+        th = getattr(self.sampler, "x0_threshold", None)
+        how += "" if th is None else f",{th.label}"
         return (f"{self.model_label}{extra}[scale={uncond_scale}{how}]"
                 f"_{datetime.now().strftime('%y-%m-%d_%H%M%S')}")
 
@@ -518,6 +521,16 @@ def make_parser() -> ArgumentParser:
     p.add_argument("--guidance_interval", type=float, nargs=2, default=None, metavar=("LO", "HI"), help="extension: guide only while the time "
                    "step lies in the fractions [LO, HI] of the schedule, 0 <= LO <= HI <= 1 (Kynkaanniemi et al. 2024): t_lo = ceil(LO * (T - 1)), "
                    "t_hi = floor(HI * (T - 1)); outside it a step evaluates the condition alone, at the plain batch.  Not with --hip_graph")
+    p.add_argument("--x0_clip", action="store_true", help="extension: clip the predicted clean image to --x0_range at every step (clip_denoised "
+                   "of Ho et al. 2020), as a rewrite of the noise prediction.  Goes wherever --uncond_scale goes")
+    p.add_argument("--x0_threshold", type=float, default=None, metavar="P", help="extension: dynamic thresholding (Saharia et al. 2022, section "
+                   "2.3): at every step each sample's predicted clean image is clipped at the P-quantile (0 < P <= 1; 0.995 is the paper's) of its "
+                   "own distances from the centre of --x0_range, never below the range's half-width, and scaled back into the range.  Per song "
+                   "canvas under --joint.  Not together with --x0_clip")
+    p.add_argument("--x0_range", type=float, nargs=2, default=None, metavar=("LO", "HI"), help="extension: the data range of --x0_clip / "
+                   "--x0_threshold, LO < HI (default: 0 1, the range of prmat2c)")
+    p.add_argument("--x0_threshold_max", type=float, default=None, metavar="R", help="extension: cap the threshold of --x0_threshold at R >= 1 "
+                   "times the range's half-width (default: no cap)")
     p.add_argument("--guidance_order", choices=list(GUIDANCE_ORDERS), default="chd,txt", metavar="{chd,txt | txt,chd}", help="extension: which part the intermediate "
                    "evaluation of --uncond_scale_chd / --uncond_scale_txt keeps (the part named first); default: chd,txt")
     p.add_argument("--seed", type=int, help="use a specific seed for inference")
@@ -702,6 +715,30 @@ def check_guidance_args(args, n_steps: Optional[int] = None):
         return phi, guidance_interval_from_fractions(lo, hi, n_steps)
     except ValueError as e:
         error(f"--guidance_interval {lo} {hi}: {e}")
+
+
+def check_threshold_args(args) -> Optional[X0Threshold]:
+    """The ``X0Threshold`` of ``--x0_clip`` / ``--x0_threshold`` / ``--x0_range`` / ``--x0_threshold_max`` (``None`` without the first two);
+    every misuse is an argparse error (usage + exit status 2)."""
+    error = make_parser().error
+    clip, p = getattr(args, "x0_clip", False), getattr(args, "x0_threshold", None)
+    rng, cap = getattr(args, "x0_range", None), getattr(args, "x0_threshold_max", None)
+    if clip and p is not None:
+        error("--x0_clip and --x0_threshold name two different ways to bound the predicted image: give one of them")
+    if not clip and p is None:
+        if rng is not None or cap is not None:
+            error("--x0_range / --x0_threshold_max without --x0_clip or --x0_threshold: nothing to apply them to")
+        return None
+    if cap is not None and p is None:
+        error("--x0_threshold_max without --x0_threshold: static clipping has no threshold to cap")
+    if p is not None and not 0.0 < p <= 1.0:         # (a NaN fails both)
+        error(f"--x0_threshold {p}: P lies in (0, 1]")
+    if cap is not None and not cap >= 1.0:
+        error(f"--x0_threshold_max {cap}: R is at least 1")
+    lo, hi = (0.0, 1.0) if rng is None else rng
+    if not (math.isfinite(lo) and math.isfinite(hi) and lo < hi):
+        error(f"--x0_range {lo} {hi}: LO < HI, both finite")
+    return X0Threshold(mode="clip" if clip else "dynamic", p=0.995 if p is None else p, range=(lo, hi), s_max=float("inf") if cap is None else cap)
 
 
 def wants_dual_guidance(args, cond_type: str) -> bool:
@@ -991,11 +1028,12 @@ def load_model(params, args, rank: int = 0, world: int = 1) -> Polyffusion_SDF:
 
 def make_sampler(model, args, seed: int, sample_offset: int = 0):
     """(sampler, start index) as ``inference_sdf.py:735-747,215-219`` choose them.  Every run's sampler is made here - plain, --autoreg, --joint,
-    inpainting, --edit, --morph, --best_of, every rank of a sharded run - so --guidance_rescale / --guidance_interval reach all of them."""
+    inpainting, --edit, --morph, --best_of, every rank of a sharded run - so --guidance_rescale / --guidance_interval and
+    --x0_clip / --x0_threshold reach all of them."""
     if getattr(args, "dpm", False) and args.ddim:
         raise SystemExit("--dpm and --ddim name two different samplers: give one of them")
     phi, interval = check_guidance_args(args, model.ldm.n_steps)
-    guidance = dict(guidance_rescale=phi, guidance_interval=interval)
+    guidance = dict(guidance_rescale=phi, guidance_interval=interval, x0_threshold=check_threshold_args(args))
     if getattr(args, "dpm", False):
         sampler = DPMSolverSampler(model.ldm, args.dpm_steps, args.dpm_discretize, args.dpm_order, seed=seed, sample_offset=sample_offset,
                                    graph=getattr(args, "hip_graph", False), **guidance)
@@ -1280,6 +1318,7 @@ def main(argv=None):
     if args.dpm and args.ddim:
         raise SystemExit("--dpm and --ddim name two different samplers: give one of them")
     check_guidance_args(args)                              # what the flags alone decide, before anything else
+    check_threshold_args(args)
     check_edit_args(args)
     check_morph_args(args)
     check_score_args(args)

@@ -19,6 +19,9 @@
   2024, section 3.4): a guided eps scaled back towards the conditional prediction's per-sample standard deviation and mixed with the plain
   combine by phi (``pf_cfg_rescale``).  Interval (Kynkaanniemi et al. 2024): guidance only while the time-step value lies in
   ``[t_lo, t_hi]``, the conditional evaluation alone outside it; ``normalize_guidance_interval``, ``guidance_interval_from_fractions``.
+* ``x0_threshold`` - not in the reference: a setting of every family (``X0Threshold``).  The predicted clean image is clipped to the data
+  range (``mode="clip"``; Ho et al. 2020, ``clip_denoised``) or dynamically thresholded at a percentile of its own magnitudes
+  (``mode="dynamic"``; Saharia et al. 2022, section 2.3) inside every step, as a rewrite of eps (``pf_x0_threshold``).
 
 Same method names and argument meaning as the reference, so ``Experiments.predict`` drives
 them unchanged.  Differences, all host-side plumbing:
@@ -163,6 +166,54 @@ def guidance_interval_from_fractions(lo: float, hi: float, n_steps: int) -> Opti
     return normalize_guidance_interval((t_lo, t_hi), T)
 
 
+X0_MODES = ("clip", "dynamic")
+
+
+@dataclass(frozen=True)
+class X0Threshold:
+    """How the predicted clean image is bounded inside every reverse step (not in the reference).  ``mode="clip"``: x0 is clipped to
+    ``range`` (``clip_denoised`` of Ho et al. 2020).  ``mode="dynamic"`` (Saharia et al. 2022, section 2.3): with ``c`` / ``h`` the centre
+    / half-width of ``range``, every sample's ``x0 - c`` is clipped at ``s = min(max(q, h), s_max * h)``, ``q`` the exact ``p``-quantile
+    of its own ``|x0 - c|``, and scaled by ``h / s`` back into the range; a sample with ``q <= h`` is clipped statically.  Frozen and
+    hashable: it is part of the key of a captured step."""
+    mode: str = "dynamic"
+    p: float = 0.995
+    range: Tuple[float, float] = (0.0, 1.0)
+    s_max: float = float("inf")
+
+    def __post_init__(self):
+        if self.mode not in X0_MODES:
+            raise ValueError(f"x0_threshold mode {self.mode!r}: expected one of {X0_MODES}")
+        try:
+            lo, hi = (float(v) for v in self.range)
+        except (TypeError, ValueError):
+            raise ValueError(f"x0_threshold range {self.range!r}: expected (lo, hi)") from None
+        if not (math.isfinite(lo) and math.isfinite(hi) and lo < hi):
+            raise ValueError(f"x0_threshold range ({lo}, {hi}): expected lo < hi, both finite")
+        p, s_max = float(self.p), float(self.s_max)
+        if not 0.0 < p <= 1.0:           # (a NaN fails both)
+            raise ValueError(f"x0_threshold p {p} outside (0, 1]")
+        if not s_max >= 1.0:
+            raise ValueError(f"x0_threshold s_max {s_max} below 1")
+        object.__setattr__(self, "range", (lo, hi))
+        object.__setattr__(self, "p", p)
+        object.__setattr__(self, "s_max", s_max)
+
+    @property
+    def label(self) -> str:
+        """The setting as file names and reports spell it: ``x0clip`` / ``x0thr=P``, with the range and the cap only when not the defaults."""
+        how = "x0clip" if self.mode == "clip" else f"x0thr={self.p}"
+        how += "" if self.range == (0.0, 1.0) else f",x0range={self.range[0]}-{self.range[1]}"
+        return how + ("" if self.mode == "clip" or math.isinf(self.s_max) else f",x0max={self.s_max}")
+
+
+def normalize_x0_threshold(setting) -> Optional[X0Threshold]:
+    """``None`` or an ``X0Threshold`` (a ``ValueError`` for anything else; the dataclass validates its own fields)."""
+    if setting is None or isinstance(setting, X0Threshold):
+        return setting
+    raise ValueError(f"x0_threshold {setting!r}: expected None or an X0Threshold")
+
+
 BLENDS = ("mean", "ramp")
 MAX_COVER = 8           # windows over one canvas row that pf_window_merge accepts: ceil(win_h / stride)
 
@@ -223,7 +274,7 @@ class DiffusionSampler:
 
     def __init__(self, model: LatentDiffusion, noise_fn: Optional[NoiseFn] = None, seed: int = 0, sample_offset: int = 0,
                  graph: bool = False, windows: Optional[WindowPlan] = None, guidance_rescale: float = 0.0,
-                 guidance_interval: Optional[Tuple[int, int]] = None):
+                 guidance_interval: Optional[Tuple[int, int]] = None, x0_threshold: Optional[X0Threshold] = None):
         self.model = model
         # windows: x, orig, mask, orig_noise and cond_concat are song canvases [S, ., canvas_h, W], cond / uncond_cond have S * n_windows rows
         # in the plan's window order, and get_eps evaluates the denoiser on the batch of windows (pf_window_split), blending its predictions
@@ -261,7 +312,34 @@ class DiffusionSampler:
         self.guidance_rescale = guidance_rescale
         self.guidance_interval = guidance_interval
         self.last_rescale = None      # (stats float64 [rows, 3] = var_pos, var_cfg, f; weights float32 [rows]) of the last rescaled call, on the device
+        # x0_threshold: None, or how the predicted clean image is bounded at EVERY step (independent of the interval): get_eps ends with
+        # pf_x0_threshold on its result - after the combine, the rescale or the merge; under a window plan on the canvas.  None: today's launches.
+        self.x0_threshold = x0_threshold
+        self.last_threshold = None    # stats float64 [rows, 4] = q, s, w, changed elements of the last thresholded call, on the device
         self._check_guidance()
+
+    # ---- clipping / dynamic thresholding of the predicted x0 (not in the reference) -------------------------------------------------------
+    @property
+    def x0_threshold(self) -> Optional[X0Threshold]:
+        return getattr(self, "_x0_threshold", None)
+
+    @x0_threshold.setter
+    def x0_threshold(self, setting):
+        self._x0_threshold = normalize_x0_threshold(setting)
+
+    def _threshold(self, x, t, e_t):
+        """``e_t`` with its predicted x0 bounded as ``self.x0_threshold`` says (in place: ``e_t`` is this call's own tensor).  ``x``: what
+        eps was predicted from, ``cond_concat`` channels included (they lie behind the row's first elements); ``t``: the int64 vector the
+        denoiser was fed - under a window plan one entry per window, and a canvas reads its first window's."""
+        th = self.x0_threshold
+        if th is None:
+            return e_t
+        wp = getattr(self, "windows", None)
+        e_t = e_t.contiguous()
+        _, stats = _steps.x0_threshold(self._lib, x.contiguous(), e_t, t.contiguous(), self.model.x0_threshold_table(x.device), mode=th.mode, p=th.p,
+                                       range=th.range, s_max=th.s_max, t_stride=1 if wp is None else wp.n_windows, out=e_t, want_stats=True)
+        self.last_threshold = stats
+        return e_t
 
     # ---- guidance rescale and guidance interval (not in the reference) ------------------------------------------------------------------
     @property
@@ -403,7 +481,7 @@ class DiffusionSampler:
             return body
 
         wkey = None if self.windows is None else self.windows.key
-        key = (family, str(dev), scale_key(uncond_scale), self.guidance_rescale, self.seed, self._elem_offset(x.shape), ndraw, wkey) + self._shape_key(**inputs)
+        key = (family, str(dev), scale_key(uncond_scale), self.guidance_rescale, self.x0_threshold, self.seed, self._elem_offset(x.shape), ndraw, wkey) + self._shape_key(**inputs)
         ent = self._graph_for(key, inputs, make_body, lambda: self._set_state(st, t_start), uncond_scale)
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         e0.record()
@@ -459,7 +537,13 @@ class DiffusionSampler:
         ``t_value``: the time-step value of ``t`` on the host; needed (a ``ValueError`` without it) only under a ``guidance_interval``,
         outside which the call is ``uncond_scale=1.0``.  ``guidance_rescale != 0``: a guided call combines its groups with ``pf_cfg_rescale``
         (per batch entry; under a window plan per WINDOW, on the window batch, followed by a plain merge) and leaves the device tables
-        in ``self.last_rescale``; one group (scale 1, scale 0, no ``uncond_cond``) has nothing to rescale."""
+        in ``self.last_rescale``; one group (scale 1, scale 0, no ``uncond_cond``) has nothing to rescale.
+        ``x0_threshold``: the result - whatever produced it - then has its predicted x0 clipped or thresholded (``pf_x0_threshold``, per
+        batch entry, under a window plan per canvas), at every step, and the device ``stats`` stay in ``self.last_threshold``."""
+        e_t = self._get_eps(x, t, c, uncond_scale, uncond_cond, prep, t_value)
+        return e_t if self.x0_threshold is None else self._threshold(x, t, e_t)
+
+    def _get_eps(self, x, t, c, uncond_scale, uncond_cond, prep, t_value):
         uncond_scale, prep = self._guidance_at(t_value, uncond_scale, prep)
         wp = getattr(self, "windows", None)
         if wp is not None:

@@ -308,6 +308,14 @@ class LatentDiffusion:
             cache[key] = _steps.sqrt_tables(self.alpha_bar, device)
         return cache[key]
 
+    def x0_threshold_table(self, device) -> torch.Tensor:
+        """The coefficient table of ``pf_x0_threshold`` (``_steps.x0_threshold_table``) on ``device`` (built once per device)."""
+        key = str(device)
+        cache = self.__dict__.setdefault("_x0t_tables", {})
+        if key not in cache:
+            cache[key] = _steps.x0_threshold_table(self.alpha_bar).to(device)
+        return cache[key]
+
     def q_xt_x0(self, x0: torch.Tensor, t: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
         """``(mean, var)`` of q(x_t | x_0) (latent_diffusion.py:149-161): ``alpha_bar[t] ** 0.5 * x0`` and ``1 - alpha_bar[t]``, the
         latter shaped ``[B, 1, 1, 1]``.  An accessor kept for parity (two torch operations); ``q_sample`` / ``loss`` run the kernel."""
