@@ -434,7 +434,12 @@ int pf_axpby(const float* x, const float* noise, float a, float b, float* out, s
 
 /* Standard-normal noise, counter-based (Philox4x32-10 + Box-Muller), keyed by (seed, stream_id,
  * global element index) so results do not depend on how a batch is sharded over GPUs.
- * elem_offset = index of out[0] in the global (unsharded) tensor. */
+ * elem_offset = index of out[0] in the global (unsharded) tensor.
+ * Philox counter = (g lo, g hi, stream_id lo, stream_id hi) with g = global element index >> 2, key = (seed lo, seed hi); element 4 g + j
+ * takes normal j of (r0 cos t0, r0 sin t0, r1 cos t1, r1 sin t1), r = sqrt(-2 ln u), t = 2 pi u, from the pairs (u0, u1) and (u2, u3) of
+ * u_i = ((float)(c_i >> 8) + 0.5f) * 2^-24.  The real range of u is [2^-25, 1], not (0, 1): from c_i >> 8 = 2^23 on the sum rounds to
+ * even in float, and 2^24 - 1 gives u = 1.0 exactly.  So |out[i]| <= 5.887 (never infinite or NaN), and a pair with u0 = 1.0 - 2^-24 of
+ * all pairs - is exactly (+-)0.  The stream is part of the interface (goldens and seeds depend on it) and stays as it is. */
 int pf_randn(float* out, size_t n, uint64_t seed, uint64_t stream_id, uint64_t elem_offset, void* stream);
 
 /* Measurement aid (bench.py): writes {shader-cycle counter, constant-rate reference counter} of the moment the probe kernel runs into

@@ -22,7 +22,13 @@ __device__ __forceinline__ void philox_round(uint32_t& c0, uint32_t& c1, uint32_
   const uint32_t n2 = (uint32_t)(p0 >> 32) ^ c3 ^ k1, n3 = (uint32_t)p0;
   c0 = n0; c1 = n1; c2 = n2; c3 = n3;
 }
-// the four standard normals of group g (elements 4g .. 4g+3 of the global tensor) of draw `sid`.
+// the four standard normals of group g (elements 4g .. 4g+3 of the global tensor) of draw `sid`: counter = (g lo, g hi, sid lo, sid hi),
+// key = (seed lo, seed hi), (z0, z1) = r(u0) (cos, sin)(2 pi u1), (z2, z3) = r(u2) (cos, sin)(2 pi u3), r(u) = sqrt(-2 ln u).
+// The uniforms are NOT the open interval the form suggests: with m = c >> 8, m + 0.5f is an fp32 number only below 2^23 (u = (2 m + 1) 2^-25);
+// from 2^23 on it rounds to even, so in [0.5, 1] the uniforms lie on the grid of 2^-23 and m = 2^24 - 1 gives u = 1.0 exactly.  The real
+// range is [2^-25, 1]: u is never 0 (largest radius sqrt(50 ln 2) = 5.887, no draw is infinite or NaN), and u0 = 1.0 - 2^-24 of all pairs -
+// gives radius 0 and a pair of exact (+-)0.  Harmless, and goldens, recorded parity runs and users' seeds depend on this stream bit for bit:
+// do not "clean up" the mapping.  tests/noise_matrix.py states it exactly and tests/test_gpu_noise_matrix.py holds every site to it.
 // NOT inlined: randn_kernel and the kernels that draw their own noise must produce the same bits for the same (g, sid, seed), and the
 // generated code of logf / sincosf / the products around them depends on its surroundings when inlined (measured: two calls in one kernel
 // differ from the stand-alone kernel in the last bit of ~20 % of the draws) - one shared body is the same arithmetic by construction.

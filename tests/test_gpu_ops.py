@@ -9,6 +9,7 @@ import torch.nn.functional as F
 
 pytestmark = pytest.mark.gpu
 
+import noise_matrix as nm  # noqa: E402
 from polyffusion_amd import _lib  # noqa: E402
 
 
@@ -254,9 +255,11 @@ def test_randn_is_standard_normal_and_shard_invariant(lib):
     n = 1 << 20
     full = torch.empty(n, device="cuda")
     _lib.check(lib.pf_randn(full.data_ptr(), n, 1234, 7, 0, _lib.current_stream()))
-    a = full.cpu().double()
-    assert abs(a.mean()) < 5e-3 and abs(a.std() - 1) < 5e-3
-    assert abs((a ** 3).mean()) < 2e-2 and abs((a ** 4).mean() - 3) < 5e-2
+    # every draw against the float64 Box-Muller of an independent Philox4x32-10, within the tolerance of profiles/noise_error_model.md
+    # (tests/noise_matrix.py; tests/test_noise_matrix.py holds that oracle's own moments to a Gaussian's within sampling error)
+    a = full.cpu().numpy()
+    r = nm.ratio(a, nm.oracle(nm.Spec(seed=1234, draws=7, slot=0, off=0, n=n)))
+    assert np.isfinite(a).all() and r <= 1.0, r
     # a shard [off, off+m) of the global tensor equals the slice of the unsharded draw (any offset/length)
     for off, m in ((0, 1000), (3, 4097), (32768 * 5, 32768), (n - 5, 5)):
         part = torch.empty(m, device="cuda")
