@@ -248,6 +248,72 @@ typedef struct pf_x0_threshold_args {
 size_t pf_x0_threshold_workspace_bytes(int rows, size_t row_elems, int form);
 int pf_x0_threshold(const pf_x0_threshold_args* a, void* stream);
 
+/* Steering a population of candidates while it is sampled (not in the reference; Feynman-Kac / SMC steering of a diffusion sampler,
+ * Singhal et al. 2025; the twisted diffusion sampler of Wu et al. 2023 - DESIGN.md 0, row a44, and 3, "Steering by resampling").  Every
+ * few reverse steps the predicted clean image of every candidate is scored (pf_x0_predict, then pf_roll_stats and float64 on the device),
+ * each group of n candidates is resampled in proportion to exp(lambda * reward gain) (pf_steer_resample) and the state rows are moved to
+ * their survivors (pf_rows_gather).  None of the three has atomics, allocates or syncs with the host; all are capturable.
+ *
+ * pf_x0_predict: x0[r][i] = fl(fl(cx*x[r][i]) - fl(ce*eps[r][i])), (cx, ce) = table[clamp(t[r * t_stride], 0, n_table - 1)][0:2] - the table
+ *   and the very device function of pf_x0_threshold (csrc/x0_predict.h), fp32, every operation individually rounded.  x (with
+ *   x_row_stride % 4 == 0), eps and x0 16-byte aligned with row_elems % 4 == 0 are moved as 16-byte vectors, anything else element by
+ *   element: the same bits.  Refused before any launch (message prefix "x0_predict: "): a null pointer; rows <= 0 or row_elems == 0;
+ *   x_row_stride < row_elems; t_stride < 0 or n_table <= 0; x0 overlapping x, eps, t or table. */
+typedef struct pf_x0_predict_args {
+  const float* x; size_t x_row_stride;      /* the state eps was predicted from; may carry cond_concat channels behind the first row_elems */
+  const float* eps;                         /* [rows][row_elems] */
+  const int64_t* t; int32_t t_stride;       /* device; row r reads t[r * t_stride] */
+  const float* table; int32_t n_table;      /* device, [n_table][4] */
+  float* x0;                                /* [rows][row_elems], disjoint from every input */
+  int32_t rows; size_t row_elems;
+} pf_x0_predict_args;
+int pf_x0_predict(const pf_x0_predict_args* a, void* stream);
+/* pf_steer_resample: one workgroup per group of n particles, 1 <= n <= PF_STEER_MAX_N.  Every float64 operation below is rounded on its own,
+ * never contracted; sums are added serially in index order.  Per group G (global index g = group_offset + G), particles i = 0 .. n - 1:
+ *   1. lw_i = fl(lambda * fl(reward_i - base_i)); a particle whose reward_i or lw_i is not finite gets w_i = 0
+ *   2. m = the maximum of the finite lw_i, w_i = exp(fl(lw_i - m))                         (weights[]; the exponential claims <= 1 ulp)
+ *   3. S = sum w_i, Q = sum w_i^2 (c_i: the running sum of S after particle i), ESS = fl(fl(S*S) / Q)
+ *   4. flag 2: no particle has a finite weight - ancestors are the identity, base is unchanged (ESS is 0/0 = NaN)
+ *   5. flag 0: ESS <= fl(ess_frac * n) does not hold - ancestors are the identity, base is unchanged
+ *   6. flag 1: systematic resampling - u = c0 * 2^-32, c0 the first output word of Philox4x32-10 with counter (g lo, g hi, event lo,
+ *      event hi) and key (seed lo, seed hi ^ 0x53544552); step = fl(S / n); p_j = fl(fl(double(j) + u) * step); a_j = the first i with
+ *      c_i > p_j, clamped to n - 1; then base_j <- reward_(a_j)
+ *   stats [groups][4]: ESS, S, the flag, u (u is written whatever the flag).
+ * What follows from the rule: the key is tagged, so the steering stream is disjoint from every noise stream of the same seed and consumes no
+ * draw - an unsteered run keeps its bits.  u has 32 bits, so j + u is exact, and p_j <= (n - 2^-32) * (S/n) * (1 + 2^-53)^2 < S for
+ * n <= 256 < 2^20: the clamp never acts and, c being non-decreasing, c_(a_j) > p_j >= c_(a_j - 1) - a zero-weight particle is never chosen.
+ * Equal weights (w_i = 1, c_i = i + 1, step = 1) give the identity for every u.  ancestors are group-local.
+ * Refused before any launch (message prefix "steer_resample: "): a null pointer; groups <= 0; n outside [1, PF_STEER_MAX_N]; lambda negative
+ * or not finite; ess_frac NaN or outside (0, 1]; a misaligned pointer (8 bytes; ancestors 4); any two of the five arrays overlapping. */
+#define PF_STEER_MAX_N 256
+typedef struct pf_steer_resample_args {
+  const double* reward;                     /* [groups * n], device */
+  double* base;                             /* [groups * n], read and - on flag 1 - written */
+  double lambda, ess_frac;
+  uint64_t seed, group_offset, event;       /* group_offset: global index of the first group; event: steering events so far */
+  int32_t* ancestors;                       /* [groups * n], group-local */
+  double* weights;                          /* [groups * n] */
+  double* stats;                            /* [groups][4]: ESS, sum of weights, flag, u */
+  int32_t groups, n;
+} pf_steer_resample_args;
+int pf_steer_resample(const pf_steer_resample_args* a, void* stream);
+/* pf_rows_gather: for up to PF_GATHER_MAX_TENSORS tensors k in one launch, rows of row_elems[k] floats, `per` images per particle:
+ *   dst_k[(G*n + j)*per + s][:] = src_k[(G*n + clamp(ancestors[G*n + j], 0, n - 1))*per + s][:]
+ * The clamp is inside the kernel: a corrupt table cannot make it read outside its inputs.  dst is disjoint from src (the host ping-pongs);
+ * workgroup = (row, PF_MSE_CHUNK of the longest row); a tensor whose src and dst are 16-byte aligned with row_elems % 4 == 0 moves as
+ * 16-byte vectors, any other element by element.  Refused before any launch (message prefix "rows_gather: "): null ancestors, src or dst; n_tensors
+ * outside [1, PF_GATHER_MAX_TENSORS]; groups <= 0, n < 1 or per < 1; row_elems == 0 or >= 2^32; a misaligned pointer (4 bytes); a dst
+ * overlapping any src, another dst or ancestors; more workgroups than one launch holds (rows * chunks >= 2^31). */
+#define PF_GATHER_MAX_TENSORS 4
+typedef struct pf_rows_gather_args {
+  const float* src[PF_GATHER_MAX_TENSORS]; float* dst[PF_GATHER_MAX_TENSORS];
+  size_t row_elems[PF_GATHER_MAX_TENSORS];
+  int32_t n_tensors;
+  const int32_t* ancestors;                 /* [groups * n], group-local */
+  int32_t groups, n, per;
+} pf_rows_gather_args;
+int pf_rows_gather(const pf_rows_gather_args* a, void* stream);
+
 /* Overlapping windows along the time axis (not in the reference; MultiDiffusion, Bar-Tal et al. 2023, on the rows of a piano roll): a song is
  * a canvas [songs][channels][canvas_h][width], canvas_h = stride * (n_windows - 1) + win_h, and the denoiser sees it as the batch of its
  * n_windows windows of win_h rows.  Window j of song s is batch row s * n_windows + j (song-major) and canvas rows [j * stride, j * stride + win_h).

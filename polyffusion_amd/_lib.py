@@ -115,6 +115,29 @@ class X0ThresholdArgs(C.Structure):
                 ("mode", C.c_int32), ("form", C.c_int32), ("rows", C.c_int32), ("row_elems", C.c_size_t)]
 
 
+class X0PredictArgs(C.Structure):
+    """pf_x0_predict_args (include/pfhip.h); filled by ``_steps.x0_predict`` only."""
+    _fields_ = [("x", C.c_void_p), ("x_row_stride", C.c_size_t), ("eps", C.c_void_p), ("t", C.c_void_p), ("t_stride", C.c_int32),
+                ("table", C.c_void_p), ("n_table", C.c_int32), ("x0", C.c_void_p), ("rows", C.c_int32), ("row_elems", C.c_size_t)]
+
+
+class SteerResampleArgs(C.Structure):
+    """pf_steer_resample_args (include/pfhip.h); filled by ``_steps.steer_resample`` only."""
+    _fields_ = [("reward", C.c_void_p), ("base", C.c_void_p), ("lam", C.c_double), ("ess_frac", C.c_double), ("seed", C.c_uint64),
+                ("group_offset", C.c_uint64), ("event", C.c_uint64), ("ancestors", C.c_void_p), ("weights", C.c_void_p), ("stats", C.c_void_p),
+                ("groups", C.c_int32), ("n", C.c_int32)]
+
+
+GATHER_MAX_TENSORS = 4     # PF_GATHER_MAX_TENSORS: tensors one pf_rows_gather launch moves
+STEER_MAX_N = 256          # PF_STEER_MAX_N: particles of one group of pf_steer_resample
+
+
+class RowsGatherArgs(C.Structure):
+    """pf_rows_gather_args (include/pfhip.h); filled by ``_steps.rows_gather`` only."""
+    _fields_ = [("src", C.c_void_p * GATHER_MAX_TENSORS), ("dst", C.c_void_p * GATHER_MAX_TENSORS), ("row_elems", C.c_size_t * GATHER_MAX_TENSORS),
+                ("n_tensors", C.c_int32), ("ancestors", C.c_void_p), ("groups", C.c_int32), ("n", C.c_int32), ("per", C.c_int32)]
+
+
 class WindowMergeArgs(C.Structure):
     """pf_window_merge_args (include/pfhip.h); filled by ``_steps.window_merge`` only."""
     _fields_ = ([("eps", C.c_void_p), ("row_weight", C.c_void_p), ("groups", C.c_int), ("s1", C.c_float), ("s2", C.c_float)]
@@ -313,6 +336,9 @@ SIGNATURES = {
     "pf_cfg_rescale": (C.c_int, [C.POINTER(CfgRescaleArgs), C.c_void_p]),
     "pf_x0_threshold_workspace_bytes": (C.c_size_t, [C.c_int, C.c_size_t, C.c_int]),
     "pf_x0_threshold": (C.c_int, [C.POINTER(X0ThresholdArgs), C.c_void_p]),
+    "pf_x0_predict": (C.c_int, [C.POINTER(X0PredictArgs), C.c_void_p]),
+    "pf_steer_resample": (C.c_int, [C.POINTER(SteerResampleArgs), C.c_void_p]),
+    "pf_rows_gather": (C.c_int, [C.POINTER(RowsGatherArgs), C.c_void_p]),
     "pf_window_split": (C.c_int, [C.c_void_p, C.c_void_p] + [C.c_int] * 6 + [C.c_void_p]),
     "pf_window_merge": (C.c_int, [C.POINTER(WindowMergeArgs), C.c_void_p]),
     "pf_ddpm_step": (C.c_int, [C.POINTER(DdpmStepArgs), C.c_void_p]),

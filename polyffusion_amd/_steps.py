@@ -266,6 +266,77 @@ def x0_threshold(lib, x, eps, t, table, *, mode: str = "dynamic", p: float = 0.9
     return out, stats
 
 
+def x0_predict(lib, x, eps, t, table, *, t_stride: int = 1, out=None) -> torch.Tensor:
+    """The predicted clean image of every row of ``eps`` ``[rows, ...]`` (``pf_x0_predict``): the expression ``x0_threshold`` bounds, written
+    out.  ``x``, ``t``, ``table`` and ``t_stride`` as there; ``out``: ``None`` (a new tensor) or a tensor disjoint from the inputs.  No host sync."""
+    for name, v in (("x", x), ("eps", eps)):
+        if v.dtype != torch.float32 or not v.is_contiguous():
+            raise ValueError(f"x0_predict: {name} must be contiguous float32")
+    if t.dtype != torch.int64 or not t.is_contiguous() or table.dtype != torch.float32 or not table.is_contiguous() or table.dim() != 2 or table.shape[1] != 4:
+        raise ValueError("x0_predict: t must be contiguous int64 and table contiguous float32 [n, 4]")
+    rows = eps.shape[0] if eps.dim() else 0
+    if rows == 0 or x.dim() == 0 or x.shape[0] != rows:
+        raise ValueError(f"x0_predict: x of shape {tuple(x.shape)} and eps of shape {tuple(eps.shape)} do not have the same rows")
+    if t.numel() < (rows - 1) * int(t_stride) + 1:
+        raise ValueError(f"x0_predict: t of {t.numel()} entries for {rows} rows at stride {t_stride}")
+    if out is None:
+        out = torch.empty_like(eps)
+    elif out.dtype != torch.float32 or not out.is_contiguous() or out.shape != eps.shape:
+        raise ValueError(f"x0_predict: out must be contiguous float32 of {tuple(eps.shape)}")
+    a = _lib.X0PredictArgs()
+    a.x, a.x_row_stride, a.eps = x.data_ptr(), x.numel() // rows, eps.data_ptr()
+    a.t, a.t_stride, a.table, a.n_table = t.data_ptr(), int(t_stride), table.data_ptr(), table.shape[0]
+    a.x0, a.rows, a.row_elems = out.data_ptr(), rows, eps.numel() // rows
+    _lib.check(lib.pf_x0_predict(C.byref(a), _lib.current_stream()), "pf_x0_predict", lib)
+    return out
+
+
+def steer_resample(lib, reward, base, n: int, *, lam: float, ess: float, seed: int, group_offset: int, event: int):
+    """One resampling decision per group of ``n`` consecutive particles (``pf_steer_resample``): ``reward`` / ``base`` float64
+    ``[groups * n]`` on the device, ``base`` updated in place where a group resamples.  Returns ``(ancestors int32 [groups * n]
+    group-local, weights float64 [groups * n], stats float64 [groups, 4] = ESS, sum of weights, flag, u)``, all on the device.  No host sync."""
+    for name, v in (("reward", reward), ("base", base)):
+        if v.dtype != torch.float64 or not v.is_contiguous() or v.dim() != 1:
+            raise ValueError(f"steer_resample: {name} must be a contiguous float64 vector")
+    n = int(n)
+    if n < 1 or reward.numel() == 0 or reward.numel() % n != 0 or base.numel() != reward.numel():
+        raise ValueError(f"steer_resample: {reward.numel()} rewards and {base.numel()} base values are not whole groups of {n}")
+    groups, dev = reward.numel() // n, reward.device
+    anc = torch.empty(groups * n, dtype=torch.int32, device=dev)
+    weights = torch.empty(groups * n, dtype=torch.float64, device=dev)
+    stats = torch.empty(groups, 4, dtype=torch.float64, device=dev)
+    a = _lib.SteerResampleArgs(reward=reward.data_ptr(), base=base.data_ptr(), lam=float(lam), ess_frac=float(ess), seed=int(seed) & (2 ** 64 - 1),
+                               group_offset=int(group_offset), event=int(event), ancestors=anc.data_ptr(), weights=weights.data_ptr(),
+                               stats=stats.data_ptr(), groups=groups, n=n)
+    _lib.check(lib.pf_steer_resample(C.byref(a), _lib.current_stream()), "pf_steer_resample", lib)
+    return anc, weights, stats
+
+
+def rows_gather(lib, srcs, ancestors, n: int, per: int = 1, outs=None) -> list:
+    """Every tensor of ``srcs`` (up to four, float32 ``[groups * n * per, ...]``) with the rows of particle ``j`` of a group replaced by those
+    of particle ``ancestors[j]`` of the same group, in ONE launch (``pf_rows_gather``).  ``outs``: ``None`` (new tensors) or tensors disjoint
+    from every source.  Returns the list of results.  No host sync."""
+    srcs = list(srcs)
+    if not 1 <= len(srcs) <= _lib.GATHER_MAX_TENSORS:
+        raise ValueError(f"rows_gather: {len(srcs)} tensors, expected 1 to {_lib.GATHER_MAX_TENSORS}")
+    n, per = int(n), int(per)
+    if ancestors.dtype != torch.int32 or not ancestors.is_contiguous() or n < 1 or per < 1 or ancestors.numel() == 0 or ancestors.numel() % n != 0:
+        raise ValueError(f"rows_gather: ancestors must be contiguous int32, whole groups of {n}")
+    groups = ancestors.numel() // n
+    rows = groups * n * per
+    outs = [torch.empty_like(v) for v in srcs] if outs is None else list(outs)
+    a = _lib.RowsGatherArgs()
+    for k, (v, o) in enumerate(zip(srcs, outs)):
+        if v.dtype != torch.float32 or not v.is_contiguous() or v.dim() == 0 or v.shape[0] != rows:
+            raise ValueError(f"rows_gather: tensor {k} of shape {tuple(v.shape)} is not contiguous float32 with {rows} rows ({groups} groups of {n} x {per})")
+        if o.dtype != torch.float32 or not o.is_contiguous() or o.shape != v.shape:
+            raise ValueError(f"rows_gather: out {k} must be contiguous float32 of {tuple(v.shape)}")
+        a.src[k], a.dst[k], a.row_elems[k] = v.data_ptr(), o.data_ptr(), v.numel() // rows
+    a.n_tensors, a.ancestors, a.groups, a.n, a.per = len(srcs), ancestors.data_ptr(), groups, n, per
+    _lib.check(lib.pf_rows_gather(C.byref(a), _lib.current_stream()), "pf_rows_gather", lib)
+    return outs
+
+
 def window_split(lib, canvas, n_windows: int, stride: int, win_h: int) -> torch.Tensor:
     """Canvas ``[S, C, canvas_h, W]`` -> its windows ``[S * n_windows, C, win_h, W]``, song-major (``pf_window_split``)."""
     S, ch, _, W = canvas.shape

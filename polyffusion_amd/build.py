@@ -8,7 +8,7 @@ import sys
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
-SOURCES = ["conv_plan.hip", "conv_mfma.hip", "conv_bf16x3.hip", "conv_wino.hip", "gemm_planes_bf3.hip", "mlp_fused_bf3.hip", "attention.hip", "attention_bf3.hip", "norm_stats.hip", "small_kernels.hip", "sampler_steps.hip", "x0_threshold.hip", "chordrec.hip", "rollmatch.hip", "encoders.hip", "decoders.hip", "comm.hip", "plan.hip", "unet_blocks.hip", "unet.hip", "attention_wide.hip", "ddpm_unet.hip", "autoencoder.hip", "loss.hip", "abi_ops.hip"]
+SOURCES = ["conv_plan.hip", "conv_mfma.hip", "conv_bf16x3.hip", "conv_wino.hip", "gemm_planes_bf3.hip", "mlp_fused_bf3.hip", "attention.hip", "attention_bf3.hip", "norm_stats.hip", "small_kernels.hip", "sampler_steps.hip", "x0_threshold.hip", "steer.hip", "chordrec.hip", "rollmatch.hip", "encoders.hip", "decoders.hip", "comm.hip", "plan.hip", "unet_blocks.hip", "unet.hip", "attention_wide.hip", "ddpm_unet.hip", "autoencoder.hip", "loss.hip", "abi_ops.hip"]
 LIB = os.path.join(HERE, "libpfhip.so")
 # variants: the same sources compiled with another element type for the split-precision kernels (csrc/pf_internal.h, PF_X3_F16);
 # objects get a suffix, the library another name, the stamp its own keys.  PF_X3=f16 in the environment selects it at load (_lib.py).

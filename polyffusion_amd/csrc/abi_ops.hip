@@ -189,6 +189,18 @@ int pf_x0_threshold(const pf_x0_threshold_args* a, void* stream) {
   PF_REQUIRE(a, "x0_threshold: null arguments");
   return launch_x0_threshold(*a, (hipStream_t)stream);
 }
+int pf_x0_predict(const pf_x0_predict_args* a, void* stream) {
+  PF_REQUIRE(a, "x0_predict: null arguments");
+  return launch_x0_predict(*a, (hipStream_t)stream);
+}
+int pf_steer_resample(const pf_steer_resample_args* a, void* stream) {
+  PF_REQUIRE(a, "steer_resample: null arguments");
+  return launch_steer_resample(*a, (hipStream_t)stream);
+}
+int pf_rows_gather(const pf_rows_gather_args* a, void* stream) {
+  PF_REQUIRE(a, "rows_gather: null arguments");
+  return launch_rows_gather(*a, (hipStream_t)stream);
+}
 int pf_window_split(const float* canvas,float* windows, int songs, int channels, int win_h, int width, int n_windows, int stride, void* stream) {
   return launch_window_split(canvas, windows, songs, channels, win_h, width, n_windows, stride, (hipStream_t)stream);
 }

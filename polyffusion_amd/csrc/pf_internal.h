@@ -114,6 +114,10 @@ int launch_cfg_rescale(const pf_cfg_rescale_args& a, hipStream_t s);
 // clipping / dynamic thresholding of the predicted x0, as a rewrite of eps (x0_threshold.hip): an exact per-row quantile by radix select
 size_t x0_threshold_workspace_bytes(int rows, size_t row_elems, int form);
 int launch_x0_threshold(const pf_x0_threshold_args& a, hipStream_t s);
+// steering by resampling (steer.hip): the predicted x0 written out, the particle filter's resampling step, the move of the state rows
+int launch_x0_predict(const pf_x0_predict_args& a, hipStream_t s);
+int launch_steer_resample(const pf_steer_resample_args& a, hipStream_t s);
+int launch_rows_gather(const pf_rows_gather_args& a, hipStream_t s);
 // overlapping windows along the time axis: canvas -> window batch, and window eps -> canvas eps with the guidance combine folded in
 int launch_window_split(const float* canvas, float* windows, int songs, int channels, int win_h, int width, int n_windows, int stride, hipStream_t s);
 int launch_window_merge(const pf_window_merge_args& a, hipStream_t s);

@@ -17,6 +17,7 @@
 // row (x0t_decide), and a 16-byte and an element-wise access do the same operations: the same bits everywhere.
 #include <cmath>
 #include "elementwise.h"
+#include "x0_predict.h"
 
 namespace pf {
 
@@ -51,13 +52,11 @@ struct x0t_coef { float cx, ce, kx, k0; };
 struct x0t_row { float lo, hi, c, sf, w; int kind; };                  // how a row's x0 is bounded (x0t_decide)
 
 __device__ __forceinline__ x0t_coef x0t_coef_of(const x0t_params& a, unsigned row) {
-  int64_t tv = a.t[(size_t)row * a.t_stride];
-  tv = tv < 0 ? 0 : (tv > a.n_table - 1 ? a.n_table - 1 : tv);
-  const float* r = a.table + 4 * tv;
+  const float* r = x0_table_row(a.t, a.t_stride, a.table, a.n_table, row);
   return x0t_coef{r[0], r[1], r[2], r[3]};
 }
 __device__ __forceinline__ float x0t_centre(float lo, float hi) { return (float)(((double)lo + (double)hi) / 2.0); }
-__device__ __forceinline__ float x0t_x0(const x0t_coef& k, float x, float e) { return sub_rn(mul_rn(k.cx, x), mul_rn(k.ce, e)); }
+__device__ __forceinline__ float x0t_x0(const x0t_coef& k, float x, float e) { return x0_of(k.cx, k.ce, x, e); }   // x0_predict.h: pf_x0_predict's too
 __device__ __forceinline__ uint32_t x0t_key(const x0t_coef& k, float c, float x, float e) {
   return __float_as_uint(sub_rn(x0t_x0(k, x, e), c)) & 0x7fffffffu;
 }

@@ -159,6 +159,15 @@ def gather_rows(local: torch.Tensor, total: int, rank: int, world: int) -> torch
     return torch.cat(out, dim=0)
 
 
+def gather_objects(obj, rank: int, world: int) -> list:
+    """Every rank's (picklable) ``obj`` on every rank, in rank order - small end-of-run reports, not tensors."""
+    if world == 1 or not (dist.is_available() and dist.is_initialized()):
+        return [obj]
+    out = [None] * world
+    dist.all_gather_object(out, obj)
+    return out
+
+
 def ranks_seen():
     """(world size the process group reports, the device index every rank runs on) - bench.py prints it so a run that
     silently fell back to fewer ranks is visible in the JSON line."""

@@ -38,7 +38,7 @@ from . import score as pfscore
 from .model_sdf import ChordEncoder, Polyffusion_SDF, TextureEncoder
 from .params import Params, find_params, load_params, preset
 from .sampler import (GUIDANCE_ORDERS, MORPH_CONDS, MORPH_EASES, DDIMSampler, DiffusionSampler, DPMSolverSampler, DualScale, SDFSampler,
-                      X0Threshold, guidance_interval_from_fractions)
+                      Steering, SteeringRecord, X0Threshold, guidance_interval_from_fractions)
 from .unet import LatentDiffusion, UNetModel
 
 
@@ -356,6 +356,8 @@ class Experiments:
         how += (f",rescale={phi}" if phi else "") + (f",interval={interval[0]}-{interval[1]}" if interval is not None else "")
         th = getattr(self.sampler, "x0_threshold", None)
         how += "" if th is None else f",{th.label}"
+        st = getattr(self.sampler, "steering", None)
+        how += "" if st is None else f",{st.label}"
         return (f"{self.model_label}{extra}[scale={uncond_scale}{how}]"
                 f"_{datetime.now().strftime('%y-%m-%d_%H%M%S')}")
 
@@ -657,7 +659,76 @@ def make_parser() -> ArgumentParser:
                    "onset cells (default) or sounding cells (onset | sustain)")
     p.add_argument("--diversity", action="store_true", help="extension, with --score / --best_of: nearest_other per kept song (its best Jaccard "
                    "overlap with any other kept song, no transposition) and the run's diversity = 1 - mean nearest_other")
+    # extension: steer the candidates of --best_of while they are sampled (sampler.Steering; pf_x0_predict, pf_steer_resample, pf_rows_gather)
+    p.add_argument("--steer", action="store_true", help="extension, with --best_of N > 1: the N consecutive candidates of each kept song are one "
+                   "population of a particle filter - every --steer_every steps their predicted clean images are scored and the population is "
+                   "resampled in proportion to exp(lambda * reward gain); copies diverge again through their own noise.  The denoiser compute "
+                   "is --best_of N's, the final ranking is --best_of's; every song's candidates are sampled as a batch of their own, so the files do not depend "
+                   "on the number of GPUs.  Not with --autoreg, --dpm, --ddim at eta 0 or --hip_graph")
+    p.add_argument("--steer_by", choices=list(STEER_BY), default=None, help="the steering reward: chord (chord_f1), bass (bass_fit), integrity "
+                   "or texture (default: what --rank_by says, when it is one of these)")
+    p.add_argument("--steer_lambda", type=float, default=10.0, metavar="L", help="with --steer: weights are exp(L * reward gain); finite, >= 0 (default 10)")
+    p.add_argument("--steer_every", type=int, default=5, metavar="K", help="with --steer: every K-th reverse step is steered (default 5)")
+    p.add_argument("--steer_window", type=float, nargs=2, default=None, metavar=("LO", "HI"), help="with --steer: only steps whose time-step value "
+                   "lies in this part of the schedule are steered, fractions as --guidance_interval reads them (default: 0 1)")
+    p.add_argument("--steer_ess", type=float, default=0.5, metavar="F", help="with --steer: a population is resampled when its effective sample "
+                   "size is at most F * N; in (0, 1] (default 0.5)")
     return p
+
+
+STEER_BY = ("chord", "bass", "integrity", "texture")
+
+
+def check_steer_args(args, cond_type: Optional[str] = None) -> Optional[dict]:
+    """The settings of ``--steer`` as ``Steering`` takes them (``None`` without the flag); every misuse is a ``SystemExit`` with a message,
+    raised before any weight is loaded.  ``cond_type``: checked once it is known (``None``: the flags alone)."""
+    dflt = make_parser().get_default
+    opts = [f"--{k}" for k in ("steer_by", "steer_lambda", "steer_every", "steer_window", "steer_ess") if getattr(args, k, dflt(k)) != dflt(k)]
+    if not getattr(args, "steer", False):
+        if opts:
+            raise SystemExit(f"{', '.join(opts)}: these belong to --steer, which was not given")
+        return None
+    if getattr(args, "best_of", 1) <= 1:
+        raise SystemExit("--steer steers the N candidates of --best_of N: give --best_of N with N > 1")
+    if args.best_of > _lib.STEER_MAX_N:
+        raise SystemExit(f"--steer with --best_of {args.best_of}: at most {_lib.STEER_MAX_N} candidates per song")
+    if getattr(args, "autoreg", False):
+        raise SystemExit("--steer with --autoreg: a song is 2B-1 sampling runs one after the other, a population would have to be carried across them (use --joint)")
+    if getattr(args, "dpm", False):
+        raise SystemExit("--steer with --dpm: DPM-Solver++ is deterministic, copies of a survivor would never diverge")
+    if getattr(args, "ddim", False) and float(getattr(args, "ddim_eta", 0.0)) == 0.0:
+        raise SystemExit("--steer with --ddim at eta 0: the loop draws no noise, copies of a survivor would never diverge (give --ddim_eta > 0)")
+    if getattr(args, "hip_graph", False):
+        raise SystemExit("--steer with --hip_graph: a captured step is one launch sequence, the steered and the unsteered step are two")
+    if getattr(args, "repaint_n", 1) > 1:
+        raise SystemExit("--steer with --repaint_n > 1: a resampled state cannot be re-noised back to the step it came from")
+    by = args.steer_by if args.steer_by is not None else args.rank_by
+    if by not in STEER_BY:
+        raise SystemExit(f"--rank_by {by} is no steering reward (it needs finished songs): give --steer_by, one of {', '.join(STEER_BY)}")
+    lam, every, ess = args.steer_lambda, args.steer_every, args.steer_ess
+    lo, hi = (0.0, 1.0) if args.steer_window is None else args.steer_window
+    if not (math.isfinite(lam) and lam >= 0.0):
+        raise SystemExit(f"--steer_lambda {lam}: finite and >= 0")
+    if every < 1:
+        raise SystemExit(f"--steer_every {every}: at least 1")
+    if not 0.0 < ess <= 1.0:
+        raise SystemExit(f"--steer_ess {ess}: in (0, 1]")
+    if not 0.0 <= lo <= hi <= 1.0:
+        raise SystemExit(f"--steer_window {lo} {hi}: fractions of the schedule, 0 <= LO <= HI <= 1")
+    if cond_type is not None:
+        if by == "texture" and cond_type != "chord+txt":
+            raise SystemExit(f"--steer_by texture compares against the texture song of a chord+txt model; this model's cond_type is {cond_type!r}")
+        if by in ("chord", "bass") and "chord" not in cond_type.split("+"):
+            raise SystemExit(f"--steer_by {by} needs the chords of the run; this model's cond_type is {cond_type!r} (use --steer_by integrity)")
+    return dict(reward=by, lam=float(lam), every=int(every), window=(float(lo), float(hi)), ess=float(ess))
+
+
+def steer_shard(num_generate: int, best_of: int, rank: int, world: int):
+    """The candidates ``[lo, hi)`` of rank ``rank`` under ``--steer``: whole groups, ``shard_range(num_generate) * best_of`` - a candidate keeps
+    the global index it has in the one-rank run, and so do its group and its noise."""
+    from . import dist as pfdist
+    lo, hi = pfdist.shard_range(num_generate, rank, world)
+    return lo * best_of, hi * best_of
 
 
 def check_score_args(args, cond_type: Optional[str] = None) -> bool:
@@ -1049,7 +1120,7 @@ def make_sampler(model, args, seed: int, sample_offset: int = 0):
 
 
 def generate_songs(model, params, args, cond, cond_mid, orig, mask, seed: int, rank: int = 0, world: int = 1, cond_concat=None,
-                   uncond_scale=None):
+                   uncond_scale=None, steer: Optional[dict] = None, chd=None, txt_prmat=None):
     """This rank's share of ``args.num_generate`` (times ``args.best_of``, the candidates of ``--best_of``) independent generations of the
     same conditions.  ``uncond_scale``: the guidance scale
     (``None``: ``args.uncond_scale``; a ``DualScale`` for dual guidance) - handed to the sampler as it is.
@@ -1057,14 +1128,32 @@ def generate_songs(model, params, args, cond, cond_mid, orig, mask, seed: int, r
     The reference loops over the songs (``inference_sdf.py:774``); here they are ONE batch and the unit of multi-GPU
     sharding: rank r takes the songs ``shard_range(num_generate, r, world)``, keyed into the noise generator by their
     GLOBAL index (``sample_offset``), so the result does not depend on the number of GPUs, and the step loop has no
-    collective.  Returns (``[n_local, B, C, H, W]`` - or ``[n_local, 2B, C, H/2, W]`` with ``--autoreg`` -, the Experiments)."""
+    collective.  ``steer`` (``check_steer_args``): the ``best_of`` consecutive candidates of a kept song are one steered population
+    (``sampler.Steering``) scored against ``chd [B, 32, 36]`` - of the cells ``mask`` marks as invented - or the texture song ``txt_prmat
+    [B, H, W]``; the ranks then take whole groups (``steer_shard``) and every group is a ``paint`` call of its own, with a sampler keyed by the
+    group's global first sample: what the denoiser computes depends in its last bits on the per-launch batch (it picks its tiles by it), and
+    a launch of one group is the same launch whichever rank makes it and however many groups that rank holds - the candidates do not depend
+    on the number of GPUs, bit for bit.  The returned Experiments' sampler carries the groups' ``last_steering`` merged.  Returns (``[n_local, B, C, H, W]`` - or ``[n_local, 2B, C, H/2, W]`` with ``--autoreg`` -, the Experiments)."""
     from . import dist as pfdist
     S, B = args.num_generate * getattr(args, "best_of", 1), cond.shape[0]      # --best_of N: N candidates per song kept, all of them songs here
-    lo, hi = pfdist.shard_range(S, rank, world)
-    n_local = hi - lo
+    lo, hi = pfdist.shard_range(S, rank, world) if steer is None else steer_shard(args.num_generate, args.best_of, rank, world)
     joint = getattr(args, "joint", False)
     per_song = 1 if args.autoreg or joint else B   # images (--joint: canvases) the sampler sees per song in one paint() call
+    if steer is not None and hi - lo > args.best_of:
+        parts = [_generate_block(model, params, args, cond, cond_mid, orig, mask, seed, cond_concat, uncond_scale, g, args.best_of, per_song, joint,
+                                 steer, chd, txt_prmat) for g in range(lo, hi, args.best_of)]
+        expmt = parts[-1][1]
+        expmt.sampler.last_steering = SteeringRecord.merged([e.sampler.last_steering for _, e in parts])
+        return torch.cat([g for g, _ in parts]), expmt
+    return _generate_block(model, params, args, cond, cond_mid, orig, mask, seed, cond_concat, uncond_scale, lo, hi - lo, per_song, joint, steer, chd, txt_prmat)
+
+
+def _generate_block(model, params, args, cond, cond_mid, orig, mask, seed, cond_concat, uncond_scale, lo, n_local, per_song, joint, steer, chd, txt_prmat):
+    """``generate_songs`` for the ``n_local`` songs from global song ``lo`` on: one sampler, one batch."""
+    B = cond.shape[0]
     sampler, t_idx = make_sampler(model, args, seed, lo * per_song)
+    if steer is not None and n_local > 0:
+        sampler.steering = steering_of(steer, args, n_local, per_song, chd, mask, txt_prmat, joint)
     expmt = Experiments(params.model_name, params, sampler, t_idx=t_idx, repaint_n=args.repaint_n)
     scale = args.uncond_scale if uncond_scale is None else uncond_scale
     rep = lambda v: None if v is None else v.unsqueeze(0).expand(n_local, *v.shape).contiguous()
@@ -1082,6 +1171,18 @@ def generate_songs(model, params, args, cond, cond_mid, orig, mask, seed: int, r
         gen = expmt.predict(flat(cond), None, scale, False, flat(orig), flat(mask),
                             cond_concat=flat(cond_concat)).reshape(n_local, B, C, H, W)
     return gen, expmt
+
+
+def steering_of(steer: dict, args, n_local: int, per_song: int, chd, mask, txt_prmat, joint: bool) -> Steering:
+    """The ``Steering`` of this rank's ``n_local`` candidates: groups of ``args.best_of`` songs of ``per_song`` images (``--joint``: one
+    canvas), the reward's chords, mask and texture onsets repeated per candidate in the images' order."""
+    rep = lambda v: None if v is None else v.unsqueeze(0).expand(n_local, *v.shape).contiguous()
+    if mask is not None and joint:                               # [B, C, H, W] -> the canvas [C, B * H, W], as predict_joint stitches it
+        mask = mask.permute(1, 0, 2, 3).reshape(mask.shape[1], -1, mask.shape[3])
+    onsets = None
+    if steer["reward"] == "texture":
+        onsets = (txt_prmat > 0).sum(-1).to(torch.int32).reshape(1, -1)      # onset cells per step of the texture song, its segments joined
+    return Steering(n=args.best_of, per=per_song, chord=rep(chd), mask=rep(mask), bass_relative=bool(args.score_bass_relative), onsets=onsets, **steer)
 
 
 def autoreg_halves(v: torch.Tensor) -> torch.Tensor:
@@ -1322,6 +1423,7 @@ def main(argv=None):
     check_edit_args(args)
     check_morph_args(args)
     check_score_args(args)
+    check_steer_args(args)
     if not torch.cuda.is_available():
         raise SystemExit("inference_sdf needs an AMD GPU (no CPU fallback on this path)")
     rank, world, _ = pfdist.init_from_env()
@@ -1358,6 +1460,9 @@ def main(argv=None):
     editing = check_edit_args(args, params.cond_type, world)
     morphing = check_morph_args(args, params.cond_type, world)
     scoring = check_score_args(args, params.cond_type)
+    steer = check_steer_args(args, params.cond_type)
+    if steer is not None and (morphing or editing):
+        raise SystemExit("--steer belongs to --best_of, which --edit and --morph do not take")
     if morphing and params.get("concat_blurry", False):
         raise SystemExit("--morph does not cover the concat_blurry variant (its blurred image describes one song, a frame lies between two)")
     if editing and params.get("concat_blurry", False):
@@ -1579,20 +1684,33 @@ def main(argv=None):
     if args.best_of > 1:
         say(f"best of {args.best_of}: {S_all} candidates, the best {S} by {pfscore.RANK_BY[args.rank_by][0]} are kept")
     novelty_corpus = load_novelty_corpus(args) if scoring else None      # refused before the songs are generated, not after
-    gen, expmt = generate_songs(model, params, args, cond, cond_mid, orig, mask, seed, rank, world, cond_concat=cond_concat, uncond_scale=scale)
+    chd_steer = chd[:B] if chd is not None and not cond_is_dummy and "chord" in params.cond_type.split("+") else None
+    if steer is not None and steer["reward"] in ("chord", "bass") and chd_steer is None:
+        raise SystemExit(f"--steer_by {steer['reward']} needs the chords of the run, and this run has none")
+    gen, expmt = generate_songs(model, params, args, cond, cond_mid, orig, mask, seed, rank, world, cond_concat=cond_concat, uncond_scale=scale,
+                                steer=steer, chd=chd_steer, txt_prmat=prmat[:B] if params.cond_type == "chord+txt" and prmat is not None else None)
+    if steer is not None:
+        # the ranks hold whole groups (steer_shard): the end-of-run exchange moves groups of best_of candidates
+        gather_rows = lambda v, total, r, w: pfdist.gather_rows(v.reshape(-1, args.best_of, *v.shape[1:]), S, r, w).reshape(total, *v.shape[1:])
+        events = expmt.sampler.last_steering
+        steer_doc = dict(steer, n=args.best_of, events=None if events is None else events.report(),
+                         lineage=None if events is None else events.lineage().tolist(), groups=list(steer_shard(S, 1, rank, world)))
+        steer_docs = pfdist.gather_objects(steer_doc, rank, world)
+    else:
+        gather_rows = pfdist.gather_rows
     counters = texture = None
     if scoring:
         # scored where the songs live, against the chords the run conditioned on (a model without a chord condition, or a run on the dummy
         # condition, gets the chord-free numbers); 64 bytes of counters per song travel beside the rows
         chd_score = chd[:B] if chd is not None and not cond_is_dummy and "chord" in params.cond_type.split("+") else None
         counters, texture = score_songs(gen, chd_score, mask, args, prmat[:B] if params.cond_type == "chord+txt" and prmat is not None else None)
-        counters = pfdist.gather_rows(counters, S_all, rank, world)
-        texture = None if texture is None else pfdist.gather_rows(texture, S_all, rank, world)
+        counters = gather_rows(counters, S_all, rank, world)
+        texture = None if texture is None else gather_rows(texture, S_all, rank, world)
         if recognizing(args):
-            rc_counters, rc_labels = (pfdist.gather_rows(v, S_all, rank, world) for v in recognize_songs(gen, chd_score, args))
+            rc_counters, rc_labels = (gather_rows(v, S_all, rank, world) for v in recognize_songs(gen, chd_score, args))
         if novelty_corpus is not None:
-            nv_score, nv_pick = (pfdist.gather_rows(v, S_all, rank, world) for v in novelty_songs(gen, novelty_corpus, args))
-    gen = pfdist.gather_rows(gen, S_all, rank, world)   # [S, ...] on every rank (131 KB per image; the only end-of-run exchange)
+            nv_score, nv_pick = (gather_rows(v, S_all, rank, world) for v in novelty_songs(gen, novelty_corpus, args))
+    gen = gather_rows(gen, S_all, rank, world)   # [S, ...] on every rank (131 KB per image; the only end-of-run exchange)
     if not bool(torch.isfinite(gen).all()):
         # the note threshold (> 0.5) would turn a NaN into silence: refuse instead.  The one known way to get here is an activation beyond
         # fp16's range in the f16x3 mode on a checkpoint the probe inputs did not exercise (include/pfhip.h pf_x3_element)
@@ -1647,6 +1765,14 @@ def main(argv=None):
             if novelty_corpus is not None:
                 doc["novelty"] = {"corpus": args.novelty_corpus, "windows": len(novelty_corpus), "shifts": args.novelty_shifts,
                                   "topk": args.novelty_topk, "plane": args.novelty_plane, "masked": False}
+            if steer is not None:
+                # per rank: the events of its groups (ESS, resample flags, u per group) and the lineage of its candidates; per kept song: the
+                # start candidate it descends from
+                lin = [a for d in steer_docs if d["lineage"] is not None for a in d["lineage"]]          # [group][particle], global group order
+                doc["steer"] = {"by": steer["reward"], "lambda": steer["lam"], "every": steer["every"], "window": list(steer["window"]),
+                                "ess": steer["ess"], "n": args.best_of, "ranks": [dict(groups=d["groups"], events=d["events"]) for d in steer_docs],
+                                "lineage": [dict(candidate=order[i], descends_from=(order[i] // args.best_of) * args.best_of
+                                                 + lin[order[i] // args.best_of][order[i] % args.best_of]) for i in range(S)]}
             if diversity is not None:
                 for i in range(S):
                     doc["songs"][i]["nearest_other"] = float(diversity["nearest_other"][i])

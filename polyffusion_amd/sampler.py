@@ -22,6 +22,9 @@
 * ``x0_threshold`` - not in the reference: a setting of every family (``X0Threshold``).  The predicted clean image is clipped to the data
   range (``mode="clip"``; Ho et al. 2020, ``clip_denoised``) or dynamically thresholded at a percentile of its own magnitudes
   (``mode="dynamic"``; Saharia et al. 2022, section 2.3) inside every step, as a rewrite of eps (``pf_x0_threshold``).
+* ``steering`` - not in the reference: a setting of ``SDFSampler`` and of ``DDIMSampler`` with eta > 0 (``Steering``).  The rows of a ``paint``
+  call are groups of candidates for one song; every few steps their predicted clean images are scored and each group is resampled in
+  proportion to ``exp(lam * reward gain)`` (``pf_x0_predict``, ``pf_steer_resample``, ``pf_rows_gather``); ``SteeringRecord``.
 
 Same method names and argument meaning as the reference, so ``Experiments.predict`` drives
 them unchanged.  Differences, all host-side plumbing:
@@ -214,8 +217,130 @@ def normalize_x0_threshold(setting) -> Optional[X0Threshold]:
     raise ValueError(f"x0_threshold {setting!r}: expected None or an X0Threshold")
 
 
+# named steering rewards: the score of score.scores_of / score.texture_fit on the song-summed counters, and its sign (higher is better)
+STEER_REWARDS = {"chord": ("chord_f1", 1.0), "bass": ("bass_fit", 1.0), "integrity": ("integrity", -1.0), "texture": ("texture_fit", 1.0)}
+
+
+@dataclass
+class Steering:
+    """Steer the candidates of a song while they are sampled (Feynman-Kac / SMC steering, Singhal et al. 2025; the twisted diffusion
+    sampler of Wu et al. 2023; not in the reference).  The rows of a ``paint`` call are groups of ``n`` consecutive particles of ``per``
+    consecutive images each (a song of ``per`` segments; under a ``WindowPlan`` a particle is one canvas).  At a steered step the predicted
+    clean image of every particle is scored, each group is resampled in proportion to ``exp(lam * (reward - reward at its last
+    resampling))`` when its effective sample size is at most ``ess * n`` (``pf_steer_resample``), and ``x`` and eps move to their survivors
+    (``pf_rows_gather``); copies diverge again because every row draws its own noise.  A step is steered when it is the ``every``-th of the
+    loop, its time-step value lies in ``window`` (fractions of the schedule, as ``guidance_interval_from_fractions`` reads them) and it is
+    not the last.  The particles of a group are candidates for the SAME song: only ``x`` and eps are moved, so ``cond``, ``orig``, ``mask``
+    and ``cond_concat`` are expected equal within a group.
+
+    ``reward``: ``"chord"`` (chord_f1), ``"bass"`` (bass_fit), ``"integrity"`` (the orphan fraction, negated) or ``"texture"`` (texture_fit
+    against ``onsets``) of ``score.roll_stats`` on the predicted image - with ``chord`` (rows of 36, one per beat, in the images' order),
+    ``mask`` (shaped like the images: only cells whose mask is 0 count) and ``bass_relative`` as there, ``onsets`` int ``[particles or 1,
+    steps of a particle]`` the reference onset counts per step; or a callable ``(x0 [rows, C, H, W]) -> float64 [rows / per]`` on the device.
+    ``lam = 0`` or ``steering=None`` give today's bits."""
+    n: int
+    reward: Union[str, Callable] = "chord"
+    per: int = 1
+    lam: float = 10.0
+    every: int = 5
+    window: Tuple[float, float] = (0.0, 1.0)
+    ess: float = 0.5
+    chord: Optional[torch.Tensor] = None
+    mask: Optional[torch.Tensor] = None
+    bass_relative: bool = False
+    onsets: Optional[torch.Tensor] = None
+
+    def __post_init__(self):
+        for f in ("n", "per", "every"):
+            v = getattr(self, f)
+            if isinstance(v, bool) or int(v) != v:
+                raise ValueError(f"steering {f} {v!r}: a whole number")
+            setattr(self, f, int(v))
+        if not 1 <= self.n <= _lib.STEER_MAX_N:
+            raise ValueError(f"steering n {self.n} outside [1, {_lib.STEER_MAX_N}] particles per group")
+        if self.per < 1 or self.every < 1:
+            raise ValueError(f"steering per {self.per} and every {self.every}: both at least 1")
+        self.lam, self.ess = float(self.lam), float(self.ess)
+        if not (math.isfinite(self.lam) and self.lam >= 0.0):
+            raise ValueError(f"steering lam {self.lam}: finite and >= 0")
+        if not 0.0 < self.ess <= 1.0:        # (a NaN fails both)
+            raise ValueError(f"steering ess {self.ess} outside (0, 1]")
+        try:
+            lo, hi = (float(v) for v in self.window)
+        except (TypeError, ValueError):
+            raise ValueError(f"steering window {self.window!r}: expected (lo, hi)") from None
+        if not 0.0 <= lo <= hi <= 1.0:
+            raise ValueError(f"steering window ({lo}, {hi}): expected 0 <= lo <= hi <= 1, fractions of the schedule")
+        self.window = (lo, hi)
+        if not callable(self.reward):
+            if self.reward not in STEER_REWARDS:
+                raise ValueError(f"steering reward {self.reward!r}: expected one of {sorted(STEER_REWARDS)} or a callable")
+            if self.reward in ("chord", "bass") and self.chord is None:
+                raise ValueError(f"steering reward {self.reward!r} needs chord, the chord rows of the images")
+            if self.reward == "texture" and self.onsets is None:
+                raise ValueError("steering reward 'texture' needs onsets, the reference onset counts per step")
+
+    def window_values(self, n_steps: int) -> Tuple[int, int]:
+        """The window as time-step values of a schedule of ``n_steps``: ``(ceil(lo * (T - 1)), floor(hi * (T - 1)))`` - possibly empty."""
+        T = int(n_steps)
+        return math.ceil(self.window[0] * (T - 1)), math.floor(self.window[1] * (T - 1))
+
+    @property
+    def label(self) -> str:
+        """The setting as file names spell it: ``steer=REWARD,lam=L`` and whatever else is not the default."""
+        how = f"steer={self.reward if isinstance(self.reward, str) else 'fn'},lam={self.lam}"
+        how += "" if self.every == 5 else f",every={self.every}"
+        how += "" if self.window == (0.0, 1.0) else f",win={self.window[0]}-{self.window[1]}"
+        return how + ("" if self.ess == 0.5 else f",ess={self.ess}")
+
+
+def normalize_steering(setting) -> Optional[Steering]:
+    if setting is None or isinstance(setting, Steering):
+        return setting
+    raise ValueError(f"steering {setting!r}: expected None or a Steering")
+
+
+@dataclass
+class SteeringRecord:
+    """What the steering events of one ``paint`` call leave behind, as device tensors that nothing reads until asked: per event the loop's
+    step number and time-step value (host ints), ``rewards`` / ``weights`` float64 ``[groups * n]``, ``stats`` float64 ``[groups, 4]``
+    (ESS, sum of weights, flag - 0 kept, 1 resampled, 2 no finite weight -, u) and ``ancestors`` int32 ``[groups * n]``, group-local."""
+    n: int
+    particles: int
+    steps: list
+    t_values: list
+    rewards: list
+    weights: list
+    stats: list
+    ancestors: list
+
+    @classmethod
+    def merged(cls, records) -> "SteeringRecord":
+        """The records of several ``paint`` calls over the same steps (consecutive groups of one run) as one, their groups in the calls' order."""
+        a = records[0]
+        if any((r.n, r.steps, r.t_values) != (a.n, a.steps, a.t_values) for r in records):
+            raise ValueError("SteeringRecord.merged: the records do not describe the same events")
+        cat = lambda name: [torch.cat([getattr(r, name)[k] for r in records]) for k in range(len(a.steps))]
+        return cls(a.n, sum(r.particles for r in records), list(a.steps), list(a.t_values), cat("rewards"), cat("weights"), cat("stats"), cat("ancestors"))
+
+    def lineage(self) -> np.ndarray:
+        """int64 ``[groups, n]``: the particle of the start population every final particle descends from, group-local - the events'
+        ancestors composed (copies the tables: the one host sync).  Without an event: the identity."""
+        out = None
+        for a in self.ancestors:
+            a = a.detach().cpu().numpy().astype(np.int64).reshape(-1, self.n)
+            out = a if out is None else np.take_along_axis(out, a, axis=1)
+        return np.tile(np.arange(self.n, dtype=np.int64), (self.particles // self.n, 1)) if out is None else out
+
+    def report(self) -> dict:
+        """The events as plain Python (one host copy): step numbers, time-step values, per-group ESS and flags."""
+        st = [s.detach().cpu().numpy() for s in self.stats]
+        return {"steps": list(self.steps), "t": list(self.t_values), "ess": [s[:, 0].tolist() for s in st],
+                "resampled": [[int(f) for f in s[:, 2]] for s in st], "u": [s[:, 3].tolist() for s in st]}
+
+
 BLENDS = ("mean", "ramp")
-MAX_COVER = 8           # windows over one canvas row that pf_window_merge accepts: ceil(win_h / stride)
+MAX_COVER = 8          # windows over one canvas row that pf_window_merge accepts: ceil(win_h / stride)
 
 
 @dataclass(frozen=True)
@@ -274,7 +399,8 @@ class DiffusionSampler:
 
     def __init__(self, model: LatentDiffusion, noise_fn: Optional[NoiseFn] = None, seed: int = 0, sample_offset: int = 0,
                  graph: bool = False, windows: Optional[WindowPlan] = None, guidance_rescale: float = 0.0,
-                 guidance_interval: Optional[Tuple[int, int]] = None, x0_threshold: Optional[X0Threshold] = None):
+                 guidance_interval: Optional[Tuple[int, int]] = None, x0_threshold: Optional[X0Threshold] = None,
+                 steering: Optional[Steering] = None):
         self.model = model
         # windows: x, orig, mask, orig_noise and cond_concat are song canvases [S, ., canvas_h, W], cond / uncond_cond have S * n_windows rows
         # in the plan's window order, and get_eps evaluates the denoiser on the batch of windows (pf_window_split), blending its predictions
@@ -316,7 +442,91 @@ class DiffusionSampler:
         # pf_x0_threshold on its result - after the combine, the rescale or the merge; under a window plan on the canvas.  None: today's launches.
         self.x0_threshold = x0_threshold
         self.last_threshold = None    # stats float64 [rows, 4] = q, s, w, changed elements of the last thresholded call, on the device
+        # steering: None, or how the candidates of a song are resampled while the eager loops of paint() run (Steering).  None: today's launches.
+        self._steer_events = 0        # steering events so far: the counter word of the resampling draw, as _draws is of the noise draws
+        self.last_steering = None     # SteeringRecord of the last steered paint()
+        self.steering = steering
         self._check_guidance()
+
+    # ---- steering by resampling (not in the reference) ---------------------------------------------------------------------------------
+    @property
+    def steering(self) -> Optional[Steering]:
+        return getattr(self, "_steering", None)
+
+    @steering.setter
+    def steering(self, setting):
+        setting = normalize_steering(setting)
+        if setting is not None:
+            why = self._steer_refusal()
+            if why is not None:
+                raise ValueError(f"steering: {why}")
+        self._steering = setting
+
+    def _steer_refusal(self) -> Optional[str]:
+        """Why this sampler cannot be steered, or ``None``."""
+        if self.graph:
+            return ("graph=True: a captured step is ONE launch sequence, and the steered and the unsteered step are two (the cause that "
+                    "refuses guidance_interval; out of scope)")
+        if self.noise_fn is not None:
+            return "an injected noise_fn: copies of a survivor diverge through the per-row draws of the on-device generator"
+        return None
+
+    def _steer_begin(self, x, repaint_n: int = 1):
+        """The state of a steered ``paint`` loop, or ``None`` without steering: validates the rows, resets ``last_steering``."""
+        st = self.steering
+        if st is None:
+            return None
+        why = self._steer_refusal()
+        if why is not None:
+            raise ValueError(f"steering: {why}")
+        if int(repaint_n) > 1:
+            raise ValueError(f"steering: repaint_n {repaint_n} > 1 (a resampled state cannot be re-noised back to the step it came from)")
+        rows, block = x.shape[0], st.n * st.per
+        if rows % block != 0 or self.sample_offset % block != 0:
+            raise ValueError(f"steering: {rows} rows at sample_offset {self.sample_offset} are not whole groups of {st.n} particles of {st.per} image(s)")
+        self.last_steering = SteeringRecord(st.n, rows // st.per, [], [], [], [], [], [])
+        return {"st": st, "base": torch.zeros(rows // st.per, dtype=torch.float64, device=x.device), "window": st.window_values(self.model.n_steps),
+                "group_offset": self.sample_offset // block}
+
+    @staticmethod
+    def _steered_at(ctx, i: int, t_value: int, last: bool) -> bool:
+        """The host's decision: step ``i`` (0-based) of the loop is the ``every``-th, its time-step value lies in the window, it is not the last."""
+        lo, hi = ctx["window"]
+        return (i + 1) % ctx["st"].every == 0 and lo <= int(t_value) <= hi and not last
+
+    def _steer_reward(self, st: Steering, x0: torch.Tensor) -> torch.Tensor:
+        particles = x0.shape[0] // st.per
+        if callable(st.reward):
+            r = st.reward(x0)
+        else:
+            from . import score
+            rs = score.roll_stats(x0, st.chord, st.mask, bass_relative=st.bass_relative).songs(st.per)
+            key, sign = STEER_REWARDS[st.reward]
+            if st.reward == "texture":
+                ref = st.onsets.to(device=x0.device).reshape(-1, rs.onsets.shape[1]).expand(particles, -1)
+                r = score.texture_fit(rs, score.RollStats(rs.counters, rs.chroma, ref))
+            else:
+                r = rs.scores()[key]
+            r = r if sign > 0 else -r
+        if not isinstance(r, torch.Tensor) or r.device != x0.device or r.numel() != particles:
+            raise ValueError(f"steering: the reward must be a tensor of {particles} values (one per particle) where x0 lives")
+        return r.to(torch.float64).reshape(particles).contiguous()
+
+    def _steer_event(self, ctx, x, e_t, t, i: int, t_value: int):
+        """One steering event between ``get_eps`` and the update: ``(x, e_t)`` moved to their survivors.  ``t``: the int64 vector the
+        denoiser was fed.  Five launches beside the reward's own; no host sync."""
+        st, wp = ctx["st"], getattr(self, "windows", None)
+        x, e_t = x.contiguous(), e_t.contiguous()
+        x0 = _steps.x0_predict(self._lib, x, e_t, t.contiguous(), self.model.x0_threshold_table(x.device), t_stride=1 if wp is None else wp.n_windows)
+        reward = self._steer_reward(st, x0)
+        anc, weights, stats = _steps.steer_resample(self._lib, reward, ctx["base"], st.n, lam=st.lam, ess=st.ess, seed=self.seed,
+                                                    group_offset=ctx["group_offset"], event=self._steer_events)
+        self._steer_events += 1
+        x, e_t = _steps.rows_gather(self._lib, [x, e_t], anc, st.n, st.per)
+        rec = self.last_steering
+        for lst, v in ((rec.steps, int(i)), (rec.t_values, int(t_value)), (rec.rewards, reward), (rec.weights, weights), (rec.stats, stats), (rec.ancestors, anc)):
+            lst.append(v)
+        return x, e_t
 
     # ---- clipping / dynamic thresholding of the predicted x0 (not in the reference) -------------------------------------------------------
     @property
@@ -801,6 +1011,10 @@ class SDFSampler(DiffusionSampler):
         step = int(step)
         x = x.contiguous()
         e_t = self._eps(x, c, step, uncond_scale, uncond_cond, cond_concat, prep)
+        return self._update(x, e_t, step, repeat_noise, temperature, return_x0)
+
+    def _update(self, x, e_t, step: int, repeat_noise: bool = False, temperature: float = 1.0, return_x0: bool = False):
+        """What ``p_sample`` does with its eps: ``(x_prev, x0, e_t)``.  A steered loop calls it on the resampled ``x`` and eps."""
         coef = self._coef(step)
         x_prev = torch.empty_like(x)
         if step != 0 and not repeat_noise and temperature == 1.0 and self._rng_ok(x):
@@ -840,10 +1054,14 @@ class SDFSampler(DiffusionSampler):
         region, the forward-noised known region, the blend.  Two noise draws for step > 0 - known-region noise first, then the
         ``p_sample`` noise, the reference's order - made inside the update kernel when the on-device generator is in use.
         ``bench.py`` times exactly this method."""
-        lib, step = self._lib, int(step)
-        coef = self._coef(step)
+        step = int(step)
         x_t, orig, mask = x_t.contiguous(), orig.contiguous(), mask.contiguous()     # the update kernels read dense buffers
         e_t = self._eps(x_t, cond, step, uncond_scale, uncond_cond, cond_concat, prep)
+        return self._repaint_update(x_t, e_t, step, orig, mask)
+
+    def _repaint_update(self, x_t, e_t, step: int, orig, mask):
+        """What ``repaint_step`` does with its eps.  A steered loop calls it on the resampled ``x_t`` and eps."""
+        lib, coef = self._lib, self._coef(step)
         x = torch.empty_like(x_t)
         if step > 0 and self._rng_ok(x_t, orig, mask):
             _steps.ddpm_step(lib, x_t, e_t, x, coef=coef, orig=orig, mask=mask,
@@ -870,8 +1088,18 @@ class SDFSampler(DiffusionSampler):
             steps = steps[-1:]          # step 0 (no noise) runs eagerly below
         # everything the denoiser derives from (t, cond) alone, once for the whole loop
         prep = self.prepare(cond, uncond_scale=uncond_scale, uncond_cond=uncond_cond)
-        for step in steps:
+        steer = self._steer_begin(x, repaint_n)
+        for i, step in enumerate(steps):
             step = int(step)
+            if steer is not None:
+                # eps with everything get_eps applies, then - at a steered step - the population resampled, then the unchanged update
+                e_t = self._eps(x, cond, step, uncond_scale, uncond_cond, cond_concat, prep)
+                if self._steered_at(steer, i, step, i == len(steps) - 1):
+                    x, e_t = self._steer_event(steer, x, e_t, self._t_of(step, self._eps_rows(x), x.device), i, step)
+                x = self._update(x, e_t, step)[0] if orig is None else self._repaint_update(x, e_t, step, orig, mask)
+                if self.on_step is not None:
+                    self.on_step(step, x)
+                continue
             if orig is None:
                 x, _, _ = self.p_sample(x, cond, None, step, uncond_scale=uncond_scale, uncond_cond=uncond_cond,
                                         cond_concat=cond_concat, return_x0=False, prep=prep)
@@ -911,6 +1139,12 @@ class DDIMSampler(DiffusionSampler):
         self.ddim_sigma = (ddim_eta * ((1 - self.ddim_alpha_prev) / (1 - self.ddim_alpha)
                                        * (1 - self.ddim_alpha / self.ddim_alpha_prev)) ** 0.5)
         self.ddim_sqrt_one_minus_alpha = (1.0 - self.ddim_alpha) ** 0.5
+        self.steering = self.steering         # (checked again now that the sampler knows its eta)
+
+    def _steer_refusal(self) -> Optional[str]:
+        if getattr(self, "ddim_sigma", None) is not None and not bool((self.ddim_sigma != 0).any()):
+            return "DDIMSampler with ddim_eta == 0 draws no noise: copies of a survivor would never diverge (use eta > 0 or SDFSampler)"
+        return super()._steer_refusal()
 
     def _coef_table(self, device):
         """([S, 7] fp32 coefficient rows, [S] int32 tau table) on the device - the floats `_coef` passes by value."""
@@ -1018,9 +1252,12 @@ class DDIMSampler(DiffusionSampler):
                 return self._paint_graph(x, cond, int(t_start), orig, mask, orig_noise, uncond_scale, uncond_cond, cond_concat,
                                          noisy=bool(nonzero.all()))
         prep = self.prepare(cond, uncond_scale=uncond_scale, uncond_cond=uncond_cond)
+        steer = self._steer_begin(x, repaint_n)
         for i, step in enumerate(time_steps):
             index = len(time_steps) - i - 1
             e_t = self._eps(x, cond, int(step), uncond_scale, uncond_cond, cond_concat, prep)
+            if steer is not None and self._steered_at(steer, i, int(step), index == 0):
+                x, e_t = self._steer_event(steer, x, e_t, self._t_of(int(step), self._eps_rows(x), x.device), i, int(step))
             # x_prev and the known-region blend (fixed orig_noise, sampler_ddim.py:355-359) in one kernel
             x, _ = self._step(x, e_t, index, orig=orig, orig_noise=orig_noise, mask=mask)
             if self.on_step is not None:
@@ -1246,6 +1483,9 @@ class DPMSolverSampler(DiffusionSampler):
 
     def _morph_refusal(self) -> Optional[str]:
         return None             # no step draws noise: morph_from_noise is a path
+
+    def _steer_refusal(self) -> Optional[str]:
+        return "DPMSolverSampler is deterministic: copies of a survivor would never diverge (use SDFSampler, or DDIMSampler with eta > 0)"
 
     def coef_rows(self, t_start: Optional[int] = None) -> np.ndarray:
         """float32 ``[t_start + 1, 7]``: the coefficient rows of a loop that starts at grid index ``t_start`` (default: the whole grid)."""
