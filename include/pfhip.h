@@ -421,6 +421,49 @@ typedef struct pf_dpm_step_args {
 } pf_dpm_step_args;
 int pf_dpm_step(const pf_dpm_step_args* a, void* stream);
 
+/* The stochastic form of DPM-Solver++(2M) (SDE-DPM-Solver++(2M) of Lu et al., "DPM-Solver++", section 5 / appendix; the midpoint form other
+ * toolkits call "DPM++ 2M SDE"; DESIGN.md 3, "Stochastic DPM-Solver++(2M)"), with one more parameter eta >= 0 that the host folds into the
+ * coefficients.  In the notation above,
+ *     x0    = (x - s1m*eps) / sqrt_a
+ *     x_out = c_x*x + c_0*x0 + c_1*x0_prev + sigma_n*z          z ~ N(0, 1); the c_1 term only when c_1 != 0, the noise only when sigma_n != 0
+ *     if orig: x_out = (q_sqrt_a*orig + q_s1m*orig_noise)*mask + x_out*(1-mask)
+ *     c_x = (sigma_tgt / sigma_cur)*exp(-eta*h),  E = -alpha_tgt*expm1(-(1 + eta)*h),  c_0 = E*(1 + 1/(2r)),  c_1 = -E/(2r),
+ *     sigma_n = sigma_tgt*sqrt(-expm1(-2*eta*h))
+ * eta = 0 gives the coefficients of pf_dpm_step with sigma_n = 0; eta = 1 is the SDE solver; a first-order row has c_1 = 0 and c_0 = E.
+ * For every eta: c_x*alpha_cur + c_0 + c_1 = alpha_tgt and c_x^2*sigma_cur^2 + sigma_n^2 = sigma_tgt^2 - a step fed the true x0 maps the
+ * marginal at the current time step onto the marginal at the target.
+ *   Both conditions are uniform over the launch and are selects, not products with zero: c_1 == 0 - x0_prev is NOT READ (it may be NULL or
+ * uninitialised); sigma_n == 0 - the noise tensor is NOT READ and no Philox call is made, and the result has the bits of pf_dpm_step on
+ * the same inputs.  By value, c_1 != 0 without x0_prev and sigma_n != 0 with neither `noise` nor `rng` are refused; with a device table
+ * the host cannot see the row, and the kernel leaves the term out (memory safety only).
+ *   Noise as in pf_ddim_step: a tensor (rng == 0), or drawn INSIDE the kernel (rng == 1) - a lane owns one Philox group of four, element i
+ * of draw d is exactly what pf_randn(seed, d, elem_offset) stores at i, so the result is bit-identical to pf_randn + the tensor form.
+ * With `state` the draw index is state->draws.  rng needs n and elem_offset to be multiples of 4 and 16-byte aligned tensors; orig_noise
+ * stays a tensor.  Without rng, tensors that are all 16-byte aligned with n % 4 == 0 are moved as 16-byte vectors, anything else element
+ * by element; every operation is individually rounded, so the bits do not depend on the path.  x_out may alias x and x0_out may alias
+ * x0_prev.  No atomics, no allocation, no host sync: the launch can be captured. */
+typedef struct pf_dpm_sde_coef {
+  float s1m;                          /* sqrt(1 - ab) of the current time step */
+  float sqrt_a;                       /* sqrt(ab) of the current time step */
+  float c_x, c_0, c_1;                /* as above; c_1 == 0: first-order step */
+  float q_sqrt_a, q_s1m;              /* known-region forward noising at this index, as pf_dpm_coef */
+  float sigma_n;                      /* standard deviation of the step's fresh noise; 0: no noise term */
+} pf_dpm_sde_coef;
+typedef struct pf_dpm_sde_step_args {
+  const float *x, *eps;               /* [n] */
+  const float *x0_prev;               /* [n] the previous step's x0; read only when c_1 != 0 */
+  float* x0_out;                      /* [n] receives this step's x0; may alias x0_prev; NULL = not kept */
+  const float *orig, *orig_noise, *mask;   /* known region: all three or none */
+  const float *noise;                 /* noise tensor, read only when sigma_n != 0 (rng == 0 only) */
+  int rng;                            /* 1: the draw is made in the kernel; noise must be NULL */
+  const pf_dpm_sde_coef* coef;        /* host coefficients, copied at the call ...            */
+  const pf_dpm_sde_coef* table;       /* ... or a device table, row state->index              */
+  const pf_step_state* state;         /* device step state: required with table; with rng it also supplies the draw index */
+  uint64_t seed, draw, elem_offset;   /* rng only; draw ignored when state is set */
+  float* x_out; size_t n;             /* x_out may alias x */
+} pf_dpm_sde_step_args;
+int pf_dpm_sde_step(const pf_dpm_sde_step_args* a, void* stream);
+
 /* Exact DDIM inversion (DESIGN.md 0, row "edit by inversion", and 3, "Exact DDIM inversion"; not in the reference): one iterate of one
  * UPWARD step of the eta = 0 DDIM ODE.  The DDIM step from x at level a down to level ap is F(x) = (x - c_e*eps(x)) / c_y with
  *     c_y = sqrt(a / ap),   c_e = sqrt(1 - a) - sqrt(a * (1 - ap) / ap)

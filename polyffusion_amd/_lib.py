@@ -82,6 +82,18 @@ class DpmStepArgs(C.Structure):
                 + [("n", C.c_size_t)])
 
 
+class DpmSdeCoef(C.Structure):
+    """pf_dpm_sde_coef (include/pfhip.h): one step of the stochastic DPM-Solver++(2M) - ``DpmCoef``'s fields and ``sigma_n``, the standard
+    deviation of the step's fresh noise (``0``: no noise term)."""
+    _fields_ = DpmCoef._fields_ + [("sigma_n", C.c_float)]
+
+
+class DpmSdeStepArgs(C.Structure):
+    """pf_dpm_sde_step_args (include/pfhip.h); filled by ``_steps.dpm_sde_step`` only."""
+    _fields_ = ([(n, C.c_void_p) for n in ("x", "eps", "x0_prev", "x0_out", "orig", "orig_noise", "mask", "noise")] + _STEP_COMMON
+                + [(n, C.c_uint64) for n in ("seed", "draw", "elem_offset")] + [("x_out", C.c_void_p), ("n", C.c_size_t)])
+
+
 class InvertCoef(C.Structure):
     """pf_invert_coef (include/pfhip.h): one upward step of exact DDIM inversion, ``x = c_y*y + c_e*eps``."""
     _fields_ = [("c_y", C.c_float), ("c_e", C.c_float)]
@@ -345,6 +357,7 @@ SIGNATURES = {
     "pf_axpby": (C.c_int, [C.c_void_p, C.c_void_p, C.c_float, C.c_float, C.c_void_p, C.c_size_t, C.c_void_p]),
     "pf_ddim_step": (C.c_int, [C.POINTER(DdimStepArgs), C.c_void_p]),
     "pf_dpm_step": (C.c_int, [C.POINTER(DpmStepArgs), C.c_void_p]),
+    "pf_dpm_sde_step": (C.c_int, [C.POINTER(DpmSdeStepArgs), C.c_void_p]),
     "pf_invert_step_workspace_bytes": (C.c_size_t, [C.c_int, C.c_size_t]),
     "pf_invert_step": (C.c_int, [C.POINTER(InvertStepArgs), C.c_void_p]),
     "pf_slerp_rows_workspace_bytes": (C.c_size_t, [C.c_int, C.c_size_t]),

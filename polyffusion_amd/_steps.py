@@ -1,5 +1,5 @@
 """The sampler's elementwise launches: noise, ``a*x + b*y`` and the three reverse-step updates (``pf_randn`` / ``pf_randn_dev``, ``pf_axpby``,
-``pf_ddpm_step``, ``pf_ddim_step``, ``pf_dpm_step`` of include/pfhip.h), the upward iterate of exact DDIM inversion (``pf_invert_step``),
+``pf_ddpm_step``, ``pf_ddim_step``, ``pf_dpm_step``, ``pf_dpm_sde_step`` of include/pfhip.h), the upward iterate of exact DDIM inversion (``pf_invert_step``),
 the frames between two tensors of a morph (``pf_slerp_rows``), the guidance combine rescaled per row (``pf_cfg_rescale``),
 eps rewritten so that its predicted x0 is clipped or dynamically thresholded (``pf_x0_threshold``),
 the two launches around the denoiser of a window plan
@@ -89,6 +89,15 @@ def dpm_step(lib, x, eps, out, *, coef=None, table=None, state=None, x0_prev=Non
     second-order step (``c_1 != 0``); ``x0_out``: receives this step's (may be ``x0_prev``; ``None`` = not kept).  No noise is drawn."""
     return _launch(lib.pf_dpm_step, "pf_dpm_step", lib, _lib.DpmStepArgs(), x, eps, out, coef, table, state, None, (),
                    dict(x0_prev=x0_prev, x0_out=x0_out, orig=orig, orig_noise=orig_noise, mask=mask))
+
+
+def dpm_sde_step(lib, x, eps, out, *, coef=None, table=None, state=None, x0_prev=None, x0_out=None, noise=None, rng=None, orig=None,
+                 orig_noise=None, mask=None):
+    """One update of the stochastic DPM-Solver++(2M) into ``out`` (may be ``x``): ``dpm_step`` with ``sigma_n * z`` added before the
+    known-region blend.  ``coef``: a host ``DpmSdeCoef``, or ``table`` (rows of 8 floats) + ``state``.  ``rng``: ``None`` (z from ``noise``,
+    read only when ``sigma_n != 0``) or ``(seed, draw, elem_offset)`` (drawn in the kernel; ``draw`` comes from ``state`` when that is set)."""
+    return _launch(lib.pf_dpm_sde_step, "pf_dpm_sde_step", lib, _lib.DpmSdeStepArgs(), x, eps, out, coef, table, state, rng,
+                   ("seed", "draw", "elem_offset"), dict(x0_prev=x0_prev, x0_out=x0_out, noise=noise, orig=orig, orig_noise=orig_noise, mask=mask))
 
 
 def invert_workspace(lib, rows: int, row_elems: int, device) -> torch.Tensor:

@@ -220,6 +220,10 @@ int pf_dpm_step(const pf_dpm_step_args* a, void* stream) {
   PF_REQUIRE(a, "pf_dpm_step: null arguments");
   return launch_dpm_step(*a, (hipStream_t)stream);
 }
+int pf_dpm_sde_step(const pf_dpm_sde_step_args* a, void* stream) {
+  PF_REQUIRE(a, "pf_dpm_sde_step: null arguments");
+  return launch_dpm_sde_step(*a, (hipStream_t)stream);
+}
 size_t pf_invert_step_workspace_bytes(int rows, size_t row_elems) { return invert_step_workspace_bytes(rows, row_elems); }
 int pf_invert_step(const pf_invert_step_args* a, void* stream) {
   PF_REQUIRE(a, "pf_invert_step: null arguments");

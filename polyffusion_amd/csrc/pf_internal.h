@@ -126,6 +126,8 @@ int launch_ddpm_step(const pf_ddpm_step_args& a, hipStream_t s);
 int launch_ddim_step(const pf_ddim_step_args& a, hipStream_t s);
 // DPM-Solver++(2M): no noise, an optional history operand (x0_prev) and an optional second output (x0_out); scalar or 16-byte vector kernel
 int launch_dpm_step(const pf_dpm_step_args& a, hipStream_t s);
+// its stochastic form: the same update with sigma_n*z before the blend, the noise from a tensor or drawn in the kernel
+int launch_dpm_sde_step(const pf_dpm_sde_step_args& a, hipStream_t s);
 int launch_axpby(const float* x, const float* y, float a, float b, float* out, size_t n, hipStream_t s);
 int launch_randn(float* out, size_t n, uint64_t seed, uint64_t stream_id, uint64_t elem_offset, hipStream_t s);
 int launch_randn_dev(float* out, size_t n, uint64_t seed, const pf_step_state* st, int slot, uint64_t elem_offset, hipStream_t s);

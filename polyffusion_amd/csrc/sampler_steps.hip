@@ -3,7 +3,7 @@
 //   reduce and a combine launch (pf_cfg_rescale), and the canvas <-> window-batch gathers of joint overlapping-window sampling
 //   (pf_window_split, pf_window_merge),
 //   fused sampler updates (sampler_sdf.py:80-171,307-341; sampler_ddim.py:220-272,355-359), and the update of the sampler the reference
-//   does not have, DPM-Solver++(2M) (pf_dpm_step), the RePaint re-noise (pf_axpby),
+//   does not have, DPM-Solver++(2M) (pf_dpm_step) and its stochastic form (pf_dpm_sde_step), the RePaint re-noise (pf_axpby),
 //   the device-resident step state (pf_step_state_set / begin / end / advance) and counter-based Gaussian noise (pf_randn, pf_randn_dev),
 //   one fixed-point iterate of exact DDIM inversion with its fused residual (pf_invert_step),
 //   the frames of a path between two noises, per-row slerp as a reduce and a combine launch (pf_slerp_rows).
@@ -430,15 +430,20 @@ int launch_axpby(const float* x, const float* y, float a, float b, float* out, s
 //   known region: + mul, mul, add (the noised original), sub (1 - m), mul, mul, add (the blend)      + 7
 // `second` is uniform over the launch (c_1 != 0); x0p is a VALUE the caller loaded only when `second` holds.
 __device__ __forceinline__ float dpm_x0(float xv, float e, const pf_dpm_coef& c) { return __fdiv_rn(sub_rn(xv, mul_rn(c.s1m, e)), c.sqrt_a); }
-__device__ __forceinline__ float dpm_update_v(float xv, float x0, bool second, float x0p, bool has_orig, float ov, float onv, float m,
-                                              const pf_dpm_coef& c) {
+// (the update in its two halves, which the stochastic form below puts its noise term between)
+__device__ __forceinline__ float dpm_solve_v(float xv, float x0, bool second, float x0p, const pf_dpm_coef& c) {
   float xp = add_rn(mul_rn(c.c_x, xv), mul_rn(c.c_0, x0));
   if (second) xp = add_rn(xp, mul_rn(c.c_1, x0p));
-  if (has_orig) {
-    const float ot = add_rn(mul_rn(c.q_sqrt_a, ov), mul_rn(c.q_s1m, onv));
-    xp = add_rn(mul_rn(ot, m), mul_rn(xp, sub_rn(1.0f, m)));
-  }
   return xp;
+}
+__device__ __forceinline__ float dpm_blend_v(float xp, float ov, float onv, float m, const pf_dpm_coef& c) {
+  const float ot = add_rn(mul_rn(c.q_sqrt_a, ov), mul_rn(c.q_s1m, onv));
+  return add_rn(mul_rn(ot, m), mul_rn(xp, sub_rn(1.0f, m)));
+}
+__device__ __forceinline__ float dpm_update_v(float xv, float x0, bool second, float x0p, bool has_orig, float ov, float onv, float m,
+                                              const pf_dpm_coef& c) {
+  const float xp = dpm_solve_v(xv, x0, second, x0p, c);
+  return has_orig ? dpm_blend_v(xp, ov, onv, m, c) : xp;
 }
 // x / out and x0p / x0o carry no __restrict__: x_out may alias x and x0_out may alias x0_prev (a lane reads group g of both before it
 // writes group g of either, and no other lane touches group g)
@@ -475,6 +480,72 @@ int launch_dpm_step(const pf_dpm_step_args& a, hipStream_t s) {
   const pf_dpm_coef cv = a.coef ? *a.coef : pf_dpm_coef{};
   const bool vec = aligned16({a.x, a.eps, a.x_out, a.x0_prev, a.x0_out, a.orig, a.orig_noise, a.mask}) && a.n % 4 == 0;
   return ew_launch(vec, dpm_step_body{a.x, a.eps, a.x0_prev, a.x0_out, a.orig, a.orig_noise, a.mask, cv, a.table, a.state, a.x_out, false}, a.n, s);
+}
+
+// ---- the stochastic form, SDE-DPM-Solver++(2M) (include/pfhip.h: pf_dpm_sde_step): the update above with sigma_n*z added BEFORE the
+// known-region blend, on dpm_x0 / dpm_solve_v / dpm_blend_v - the same individually rounded operations in the same order, so a row with
+// sigma_n == 0 gives the bits of pf_dpm_step.  Roundings on the way to the result:
+//   x0:           mul (s1m*e), sub, div                                  3   (what x0_out receives)
+//   first order:  those 3 + mul (c_x*x), mul (c_0*x0), add               6
+//   second order: those 6 + mul (c_1*x0_prev), add                       8
+//   noise term:   + mul (sigma_n*z), add                                 + 2
+//   known region: + mul, mul, add (the noised original), sub (1 - m), mul, mul, add (the blend)      + 7
+// `second` (c_1 != 0) and `noisy` (sigma_n != 0) are uniform over the launch and are selects: without them the history / the noise tensor
+// is not read and no Philox call is made.  RNG as in ddim_step_body: a lane owns the four elements of one Philox group.
+template <bool RNG>
+struct dpm_sde_step_body {
+  const float* x; const float* __restrict__ eps; const float* x0p; float* x0o; const float* __restrict__ noise;
+  const float* __restrict__ orig; const float* __restrict__ on; const float* __restrict__ mask;
+  pf_dpm_sde_coef c; const pf_dpm_sde_coef* __restrict__ table; const pf_step_state* __restrict__ st;
+  uint64_t seed, draw, off; float* out;
+  pf_dpm_coef b; bool second, noisy;
+  __device__ __forceinline__ void begin() {
+    c = coef_of(c, table, st);
+    b = pf_dpm_coef{c.s1m, c.sqrt_a, c.c_x, c.c_0, c.c_1, c.q_sqrt_a, c.q_s1m};
+    second = c.c_1 != 0.f && x0p != nullptr;
+    noisy = c.sigma_n != 0.f && (RNG || noise != nullptr);
+    if (RNG && st) draw = st->draws;
+  }
+  template <int V>
+  __device__ __forceinline__ void at(size_t g) const {
+    static_assert(!RNG || V == 4, "one Philox call yields the four normals of a 16-byte group");
+    const size_t i = g * V;
+    float xv[V], ev[V], pv[V] = {}, nz[V] = {}, ov[V] = {}, nv[V] = {}, mv[V] = {}, o[V], z[V];
+    if (noisy) {
+      if constexpr (RNG) philox_normal4((off >> 2) + g, draw, seed, nz);
+      else ew_ld<V>(noise + i, nz);
+    }
+    ew_ld<V>(x + i, xv); ew_ld<V>(eps + i, ev);
+    if (second) ew_ld<V>(x0p + i, pv);
+    if (orig) { ew_ld<V>(orig + i, ov); ew_ld<V>(on + i, nv); ew_ld<V>(mask + i, mv); }
+#pragma unroll
+    for (int j = 0; j < V; ++j) {
+      z[j] = dpm_x0(xv[j], ev[j], b);
+      float xp = dpm_solve_v(xv[j], z[j], second, pv[j], b);
+      if (noisy) xp = add_rn(xp, mul_rn(c.sigma_n, nz[j]));
+      o[j] = orig ? dpm_blend_v(xp, ov[j], nv[j], mv[j], b) : xp;
+    }
+    if (x0o) ew_st<V>(x0o + i, z);
+    ew_st<V>(out + i, o);
+  }
+};
+int launch_dpm_sde_step(const pf_dpm_sde_step_args& a, hipStream_t s) {
+  PF_REQUIRE(a.x && a.eps && a.x_out && a.n > 0, "dpm_sde_step: bad arguments (x, eps and x_out must be set, n > 0)");
+  PF_REQUIRE((a.orig && a.orig_noise && a.mask) || (!a.orig && !a.orig_noise && !a.mask),
+             "dpm_sde_step: the known region needs orig, orig_noise and mask - all three or none");
+  if (int rc = check_coef_source(a, "dpm_sde_step")) return rc;
+  PF_REQUIRE(!(a.rng && a.noise), "dpm_sde_step_rng: the noise is drawn in the kernel, the noise tensor must be NULL");
+  PF_REQUIRE(!a.coef || a.coef->c_1 == 0.f || a.x0_prev, "dpm_sde_step: a second-order step (c_1 != 0) needs x0_prev");
+  PF_REQUIRE(!a.coef || a.coef->sigma_n == 0.f || a.noise || a.rng, "dpm_sde_step: a step with noise (sigma_n != 0) needs a noise tensor or rng");
+  const pf_dpm_sde_coef cv = a.coef ? *a.coef : pf_dpm_sde_coef{};
+  const bool al = aligned16({a.x, a.eps, a.x_out, a.x0_prev, a.x0_out, a.noise, a.orig, a.orig_noise, a.mask});
+  if (!a.rng)
+    return ew_launch(al && a.n % 4 == 0, dpm_sde_step_body<false>{a.x, a.eps, a.x0_prev, a.x0_out, a.noise, a.orig, a.orig_noise, a.mask, cv, a.table,
+                                                                   a.state, 0, 0, 0, a.x_out, pf_dpm_coef{}, false, false}, a.n, s);
+  PF_REQUIRE(a.n % 4 == 0 && a.elem_offset % 4 == 0, "dpm_sde_step_rng: n and elem_offset must be multiples of 4 (one Philox call yields four normals)");
+  PF_REQUIRE(al, "dpm_sde_step_rng: tensors must be 16-byte aligned");
+  return ew_launch_v<4>(dpm_sde_step_body<true>{a.x, a.eps, a.x0_prev, a.x0_out, nullptr, a.orig, a.orig_noise, a.mask, cv, a.table, a.state, a.seed,
+                                                 a.draw, a.elem_offset, a.x_out, pf_dpm_coef{}, false, false}, a.n, s);
 }
 
 // ---- device-resident step state: what changes from one reverse step to the next lives in device memory, so a captured

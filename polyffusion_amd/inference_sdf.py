@@ -37,7 +37,7 @@ from . import rollmatch as pfrollmatch
 from . import score as pfscore
 from .model_sdf import ChordEncoder, Polyffusion_SDF, TextureEncoder
 from .params import Params, find_params, load_params, preset
-from .sampler import (GUIDANCE_ORDERS, MORPH_CONDS, MORPH_EASES, DDIMSampler, DiffusionSampler, DPMSolverSampler, DualScale, SDFSampler,
+from .sampler import (DPM_STEER_REFUSAL, GUIDANCE_ORDERS, MORPH_CONDS, MORPH_EASES, DDIMSampler, DiffusionSampler, DPMSolverSampler, DualScale, SDFSampler,
                       Steering, SteeringRecord, X0Threshold, guidance_interval_from_fractions)
 from .unet import LatentDiffusion, UNetModel
 
@@ -356,6 +356,8 @@ class Experiments:
         how += (f",rescale={phi}" if phi else "") + (f",interval={interval[0]}-{interval[1]}" if interval is not None else "")
         th = getattr(self.sampler, "x0_threshold", None)
         how += "" if th is None else f",{th.label}"
+        eta = getattr(self.sampler, "eta", 0.0) if isinstance(self.sampler, DPMSolverSampler) else 0.0
+        how += f",dpm_eta={eta:g}" if eta else ""
         st = getattr(self.sampler, "steering", None)
         how += "" if st is None else f",{st.label}"
         return (f"{self.model_label}{extra}[scale={uncond_scale}{how}]"
@@ -567,6 +569,9 @@ def make_parser() -> ArgumentParser:
     p.add_argument("--dpm_order", type=int, choices=[1, 2], default=2, help="solver order, default: 2 (1 = DDIM with eta 0 on the same grid)")
     p.add_argument("--dpm_discretize", choices=["logsnr", "uniform", "quad"], default="logsnr", help="time-step grid: uniform in log-SNR "
                    "(default; what the second-order update needs to pay off) or DDIM's two grids")
+    p.add_argument("--dpm_eta", type=float, default=0.0, metavar="ETA", help="with --dpm: the stochastic form of the solver - 0 (default) is the "
+                   "deterministic sampler, 1 is SDE-DPM-Solver++(2M) (\"DPM++ 2M SDE\"), in between interpolates; every step then draws noise, "
+                   "so --steer works with it and --morph does not")
     # extension: edit the condition song itself by exact DDIM inversion (DDIMSampler.invert) - e.g. re-harmonise it
     p.add_argument("--edit", action="store_true", help="extension: edit the condition song's own image (from --from_midi, --from_dataset, "
                    "--from_song_npz or prmat2c in --cond_npz) instead of generating from noise: invert it up the eta = 0 DDIM ODE under its own "
@@ -664,7 +669,7 @@ def make_parser() -> ArgumentParser:
                    "population of a particle filter - every --steer_every steps their predicted clean images are scored and the population is "
                    "resampled in proportion to exp(lambda * reward gain); copies diverge again through their own noise.  The denoiser compute "
                    "is --best_of N's, the final ranking is --best_of's; every song's candidates are sampled as a batch of their own, so the files do not depend "
-                   "on the number of GPUs.  Not with --autoreg, --dpm, --ddim at eta 0 or --hip_graph")
+                   "on the number of GPUs.  Not with --autoreg, --dpm at --dpm_eta 0, --ddim at eta 0 or --hip_graph")
     p.add_argument("--steer_by", choices=list(STEER_BY), default=None, help="the steering reward: chord (chord_f1), bass (bass_fit), integrity "
                    "or texture (default: what --rank_by says, when it is one of these)")
     p.add_argument("--steer_lambda", type=float, default=10.0, metavar="L", help="with --steer: weights are exp(L * reward gain); finite, >= 0 (default 10)")
@@ -694,8 +699,8 @@ def check_steer_args(args, cond_type: Optional[str] = None) -> Optional[dict]:
         raise SystemExit(f"--steer with --best_of {args.best_of}: at most {_lib.STEER_MAX_N} candidates per song")
     if getattr(args, "autoreg", False):
         raise SystemExit("--steer with --autoreg: a song is 2B-1 sampling runs one after the other, a population would have to be carried across them (use --joint)")
-    if getattr(args, "dpm", False):
-        raise SystemExit("--steer with --dpm: DPM-Solver++ is deterministic, copies of a survivor would never diverge")
+    if getattr(args, "dpm", False) and float(getattr(args, "dpm_eta", 0.0)) == 0.0:
+        raise SystemExit(f"--steer with --dpm: {DPM_STEER_REFUSAL} (give --dpm_eta > 0)")
     if getattr(args, "ddim", False) and float(getattr(args, "ddim_eta", 0.0)) == 0.0:
         raise SystemExit("--steer with --ddim at eta 0: the loop draws no noise, copies of a survivor would never diverge (give --ddim_eta > 0)")
     if getattr(args, "hip_graph", False):
@@ -899,6 +904,8 @@ def check_morph_args(args, cond_type: Optional[str] = None, world: int = 1) -> b
         raise SystemExit("--morph needs --ddim (eta 0) or, between two synthetic conditions, --dpm: the frames of a loop that draws noise are not a path")
     if args.ddim and args.ddim_eta != 0.0:
         raise SystemExit(f"--morph needs --ddim_eta 0 (got {args.ddim_eta}): the frames of a loop that draws noise are not a path")
+    if dpm and float(getattr(args, "dpm_eta", 0.0)) != 0.0:
+        raise SystemExit(f"--morph needs --dpm_eta 0 (got {args.dpm_eta}): the frames of a loop that draws noise are not a path")
     if args.autoreg:
         raise SystemExit("--morph with --autoreg: the autoregressive schedule inpaints from noise; use --joint to morph songs as canvases")
     if args.inpaint_type is not None:
@@ -1097,6 +1104,16 @@ def load_model(params, args, rank: int = 0, world: int = 1) -> Polyffusion_SDF:
     return model
 
 
+def check_dpm_eta(args) -> float:
+    """``--dpm_eta`` as ``DPMSolverSampler`` takes it; a ``SystemExit`` for a value that is not finite and >= 0, or given without ``--dpm``."""
+    eta = float(getattr(args, "dpm_eta", 0.0))
+    if not (math.isfinite(eta) and eta >= 0.0):
+        raise SystemExit(f"--dpm_eta {eta}: finite and >= 0")
+    if eta != 0.0 and not getattr(args, "dpm", False):
+        raise SystemExit("--dpm_eta belongs to --dpm, which was not given")
+    return eta
+
+
 def make_sampler(model, args, seed: int, sample_offset: int = 0):
     """(sampler, start index) as ``inference_sdf.py:735-747,215-219`` choose them.  Every run's sampler is made here - plain, --autoreg, --joint,
     inpainting, --edit, --morph, --best_of, every rank of a sharded run - so --guidance_rescale / --guidance_interval and
@@ -1105,9 +1122,10 @@ def make_sampler(model, args, seed: int, sample_offset: int = 0):
         raise SystemExit("--dpm and --ddim name two different samplers: give one of them")
     phi, interval = check_guidance_args(args, model.ldm.n_steps)
     guidance = dict(guidance_rescale=phi, guidance_interval=interval, x0_threshold=check_threshold_args(args))
+    eta = check_dpm_eta(args)
     if getattr(args, "dpm", False):
         sampler = DPMSolverSampler(model.ldm, args.dpm_steps, args.dpm_discretize, args.dpm_order, seed=seed, sample_offset=sample_offset,
-                                   graph=getattr(args, "hip_graph", False), **guidance)
+                                   graph=getattr(args, "hip_graph", False), eta=eta, **guidance)
         return sampler, len(sampler.time_steps) - 1      # the grid's own length: logsnr drops repeated time steps
     if args.ddim:
         sampler = DDIMSampler(model.ldm, args.ddim_steps, args.ddim_discretize, args.ddim_eta, seed=seed, sample_offset=sample_offset,
@@ -1418,6 +1436,7 @@ def main(argv=None):
     args = make_parser().parse_args(argv)
     if args.dpm and args.ddim:
         raise SystemExit("--dpm and --ddim name two different samplers: give one of them")
+    check_dpm_eta(args)
     check_guidance_args(args)                              # what the flags alone decide, before anything else
     check_threshold_args(args)
     check_edit_args(args)
@@ -1770,7 +1789,9 @@ def main(argv=None):
                 # start candidate it descends from
                 lin = [a for d in steer_docs if d["lineage"] is not None for a in d["lineage"]]          # [group][particle], global group order
                 doc["steer"] = {"by": steer["reward"], "lambda": steer["lam"], "every": steer["every"], "window": list(steer["window"]),
-                                "ess": steer["ess"], "n": args.best_of, "ranks": [dict(groups=d["groups"], events=d["events"]) for d in steer_docs],
+                                "ess": steer["ess"], "n": args.best_of,
+                                **(dict(sampler="dpm", eta=float(args.dpm_eta)) if args.dpm else {}),      # (the stochastic 2M loop names itself)
+                                "ranks": [dict(groups=d["groups"], events=d["events"]) for d in steer_docs],
                                 "lineage": [dict(candidate=order[i], descends_from=(order[i] // args.best_of) * args.best_of
                                                  + lin[order[i] // args.best_of][order[i] % args.best_of]) for i in range(S)]}
             if diversity is not None:

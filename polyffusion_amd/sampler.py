@@ -230,7 +230,7 @@ class Steering:
     resampling))`` when its effective sample size is at most ``ess * n`` (``pf_steer_resample``), and ``x`` and eps move to their survivors
     (``pf_rows_gather``); copies diverge again because every row draws its own noise.  A step is steered when it is the ``every``-th of the
     loop, its time-step value lies in ``window`` (fractions of the schedule, as ``guidance_interval_from_fractions`` reads them) and it is
-    not the last.  The particles of a group are candidates for the SAME song: only ``x`` and eps are moved, so ``cond``, ``orig``, ``mask``
+    not the last.  The particles of a group are candidates for the SAME song: only ``x`` and eps (and a multistep solver's history) are moved, so ``cond``, ``orig``, ``mask``
     and ``cond_concat`` are expected equal within a group.
 
     ``reward``: ``"chord"`` (chord_f1), ``"bass"`` (bass_fit), ``"integrity"`` (the orphan fraction, negated) or ``"texture"`` (texture_fit
@@ -512,9 +512,11 @@ class DiffusionSampler:
             raise ValueError(f"steering: the reward must be a tensor of {particles} values (one per particle) where x0 lives")
         return r.to(torch.float64).reshape(particles).contiguous()
 
-    def _steer_event(self, ctx, x, e_t, t, i: int, t_value: int):
+    def _steer_event(self, ctx, x, e_t, t, i: int, t_value: int, extra=()):
         """One steering event between ``get_eps`` and the update: ``(x, e_t)`` moved to their survivors.  ``t``: the int64 vector the
-        denoiser was fed.  Five launches beside the reward's own; no host sync."""
+        denoiser was fed.  ``extra``: further row tensors shaped like ``x`` that belong to a particle (a multistep solver's history) - they
+        move in the same ``pf_rows_gather`` launch and follow in the result, ``(x, e_t, *extra)``.  Five launches beside the reward's own;
+        no host sync."""
         st, wp = ctx["st"], getattr(self, "windows", None)
         x, e_t = x.contiguous(), e_t.contiguous()
         x0 = _steps.x0_predict(self._lib, x, e_t, t.contiguous(), self.model.x0_threshold_table(x.device), t_stride=1 if wp is None else wp.n_windows)
@@ -522,11 +524,11 @@ class DiffusionSampler:
         anc, weights, stats = _steps.steer_resample(self._lib, reward, ctx["base"], st.n, lam=st.lam, ess=st.ess, seed=self.seed,
                                                     group_offset=ctx["group_offset"], event=self._steer_events)
         self._steer_events += 1
-        x, e_t = _steps.rows_gather(self._lib, [x, e_t], anc, st.n, st.per)
+        moved = _steps.rows_gather(self._lib, [x, e_t] + [v.contiguous() for v in extra], anc, st.n, st.per)
         rec = self.last_steering
         for lst, v in ((rec.steps, int(i)), (rec.t_values, int(t_value)), (rec.rewards, reward), (rec.weights, weights), (rec.stats, stats), (rec.ancestors, anc)):
             lst.append(v)
-        return x, e_t
+        return tuple(moved)
 
     # ---- clipping / dynamic thresholding of the predicted x0 (not in the reference) -------------------------------------------------------
     @property
@@ -1460,17 +1462,59 @@ def dpm_coef_rows(alpha_bar, time_steps, t_start: int, order: int = 2, lower_ord
     return rows
 
 
+def dpm_sde_coef_rows(alpha_bar, time_steps, t_start: int, order: int = 2, lower_order_final: bool = True, eta: float = 1.0) -> np.ndarray:
+    """float64 ``[t_start + 1, 8]``: row i = the ``pf_dpm_sde_coef`` fields (s1m, sqrt_a, c_x, c_0, c_1, q_sqrt_a, q_s1m, sigma_n) of grid
+    index i of the stochastic loop, ``dpm_coef_rows`` with
+    ``c_x = (sigma_tgt / sigma_cur) * exp(-eta*h)``, ``E = -alpha_tgt * expm1(-(1 + eta)*h)`` in place of ``-alpha_tgt * expm1(-h)``, and
+    ``sigma_n = sigma_tgt * sqrt(-expm1(-2*eta*h))``.  The rows that are first order are the same ones.  ``eta = 0``: the first seven
+    columns are ``dpm_coef_rows`` bit for bit and ``sigma_n = 0``; ``eta = 1``: SDE-DPM-Solver++(2M).  On every row
+    ``c_x*alpha_cur + c_0 + c_1 = alpha_tgt`` and ``c_x**2 * sigma_cur**2 + sigma_n**2 = sigma_tgt**2``."""
+    eta = float(eta)
+    if not (np.isfinite(eta) and eta >= 0.0):
+        raise ValueError(f"dpm_sde_coef_rows: eta {eta}, expected a finite value >= 0")
+    ab = np.asarray(alpha_bar, dtype=np.float64)
+    ts = np.asarray(time_steps)[: t_start + 1]
+    cur = ab[ts]
+    tgt = np.concatenate([ab[0:1], ab[ts[:-1]]])
+    lam = lambda a: 0.5 * np.log(a / (1.0 - a))
+    h = lam(tgt) - lam(cur)
+    rows = np.zeros((len(ts), 8), dtype=np.float64)
+    for i in range(len(ts)):
+        e = -np.sqrt(tgt[i]) * np.expm1(-((1.0 + eta) * h[i]))
+        second = (order == 2 and i < t_start and h[i] != 0.0 and h[i + 1] != 0.0
+                  and not (i == 0 and lower_order_final and len(ts) < 15))
+        k = 0.5 * h[i] / h[i + 1] if second else 0.0           # 1 / (2r), r = h_{i+1} / h_i
+        s1m, sqrt_a, s_tgt = np.sqrt(1.0 - cur[i]), np.sqrt(cur[i]), np.sqrt(1.0 - tgt[i])
+        sigma_n = s_tgt * np.sqrt(max(0.0, -np.expm1(-2.0 * eta * h[i])))
+        rows[i] = (s1m, sqrt_a, s_tgt / s1m * np.exp(-eta * h[i]), e * (1.0 + k), -e * k, sqrt_a, s1m, sigma_n)
+    return rows
+
+
+# why DPMSolverSampler at eta == 0 is not steered (the CLI says the same before it loads anything)
+DPM_STEER_REFUSAL = "DPMSolverSampler is deterministic: copies of a survivor would never diverge (use SDFSampler, or DDIMSampler with eta > 0) or eta > 0"
+
+
 class DPMSolverSampler(DiffusionSampler):
     """DPM-Solver++(2M) (Lu et al. 2022, algorithm 2; multistep, data prediction): a second-order solver of the probability-flow ODE that
     DDIM with eta = 0 solves to first order, at the same cost per step - one denoiser evaluation and ONE update kernel (``pf_dpm_step``).
     Not in the reference; it is driven like ``DDIMSampler`` (same ``paint`` / ``sample`` / ``q_sample`` / ``p_sample`` arguments, grid index
     i counts up with the time step).  The update's coefficients are computed here in float64 and rounded once (``dpm_coef_rows``); the
     previous step's data prediction lives in one buffer the kernel reads and overwrites.  Every ``paint()`` / ``sample()`` call starts a
-    fresh history: its first step is first order and never reads the buffer.  Deterministic: no step draws noise (a known region without
-    a fixed ``orig_noise`` draws a fresh one per step, as DDIM's paint does)."""
+    fresh history: its first step is first order and never reads the buffer.  With ``eta == 0`` (the default) it is deterministic: no
+    step draws noise (a known region without a fixed ``orig_noise`` draws a fresh one per step, as DDIM's paint does).
+
+    ``eta > 0``: the stochastic form (``dpm_sde_coef_rows``; ``eta = 1`` is SDE-DPM-Solver++(2M)) - every step of ``paint`` / ``sample``
+    is ONE ``pf_dpm_sde_step`` launch and consumes one draw index, on a row whose ``sigma_n`` is 0 too, so that eager and captured loops
+    count alike.  The draw is made in the kernel when ``_rng_ok`` holds, else it comes from ``randn`` as a tensor; a known region without
+    ``orig_noise`` draws its fresh noise after the step's draw, as ``DDIMSampler._step`` does.  Such a loop can be steered (copies of a
+    survivor diverge through their draws) and has no morph."""
 
     def __init__(self, model: LatentDiffusion, n_steps: int, discretize: str = "logsnr", order: int = 2, lower_order_final: bool = True,
-                 is_show_image: bool = False, **kw):
+                 is_show_image: bool = False, eta: float = 0.0, **kw):
+        eta = float(eta)
+        if not (np.isfinite(eta) and eta >= 0.0):
+            raise ValueError(f"DPM-Solver++(2M): eta {eta}, expected a finite value >= 0")
+        self.eta = eta                        # (before the base class looks at the steering setting)
         super().__init__(model, **kw)
         if int(order) not in (1, 2):
             raise ValueError(f"DPM-Solver++(2M): order {order!r}, expected 1 or 2")
@@ -1482,10 +1526,12 @@ class DPMSolverSampler(DiffusionSampler):
         self._rows = {}
 
     def _morph_refusal(self) -> Optional[str]:
+        if self.eta > 0:
+            return "DPMSolverSampler with eta > 0 draws noise in every step: the frames of such a loop are not a path (use eta 0, or DDIMSampler with eta 0)"
         return None             # no step draws noise: morph_from_noise is a path
 
     def _steer_refusal(self) -> Optional[str]:
-        return "DPMSolverSampler is deterministic: copies of a survivor would never diverge (use SDFSampler, or DDIMSampler with eta > 0)"
+        return DPM_STEER_REFUSAL if self.eta == 0 else super()._steer_refusal()
 
     def coef_rows(self, t_start: Optional[int] = None) -> np.ndarray:
         """float32 ``[t_start + 1, 7]``: the coefficient rows of a loop that starts at grid index ``t_start`` (default: the whole grid)."""
@@ -1497,12 +1543,25 @@ class DPMSolverSampler(DiffusionSampler):
     def _coef(self, index: int, t_start: int) -> _lib.DpmCoef:
         return _lib.DpmCoef(*(float(v) for v in self.coef_rows(t_start)[index]))
 
+    def sde_coef_rows(self, t_start: Optional[int] = None) -> np.ndarray:
+        """float32 ``[t_start + 1, 8]``: ``coef_rows`` for this sampler's ``eta`` (``dpm_sde_coef_rows`` rounded once)."""
+        t_start = len(self.time_steps) - 1 if t_start is None else int(t_start)
+        if ("sde", t_start) not in self._rows:
+            self._rows[("sde", t_start)] = dpm_sde_coef_rows(self._ab, self.time_steps, t_start, self.order, self.lower_order_final,
+                                                             self.eta).astype(np.float32)
+        return self._rows[("sde", t_start)]
+
+    def _sde_coef(self, index: int, t_start: int) -> _lib.DpmSdeCoef:
+        return _lib.DpmSdeCoef(*(float(v) for v in self.sde_coef_rows(t_start)[index]))
+
     def _coef_table(self, device, t_start: int):
-        """([S, 7] fp32 rows of a loop starting at ``t_start`` - rows above it are zero and never read -, [S] int32 tau table) on the device."""
+        """([S, 7] fp32 rows of a loop starting at ``t_start`` - rows above it are zero and never read -, [S] int32 tau table) on the device;
+        with ``eta > 0`` the rows are the 8 floats of ``sde_coef_rows``."""
         key = ("dpm_table", str(device), int(t_start))
         if key not in self._dev_cache:
-            rows = np.zeros((len(self.time_steps), 7), dtype=np.float32)
-            rows[: t_start + 1] = self.coef_rows(t_start)
+            src = self.sde_coef_rows(t_start) if self.eta > 0 else self.coef_rows(t_start)
+            rows = np.zeros((len(self.time_steps), src.shape[1]), dtype=np.float32)
+            rows[: t_start + 1] = src
             self._dev_cache[key] = torch.from_numpy(rows).to(device)
         tk = ("dpm_taus", str(device))
         if tk not in self._dev_cache:
@@ -1513,42 +1572,72 @@ class DPMSolverSampler(DiffusionSampler):
         """All t_start+1 steps as replays of one captured step.  The captured update reads its coefficient row from a STATIC table buffer
         (its address is part of the graph): the rows of this call's ``t_start`` are copied into it with the other inputs, so one captured
         step serves loops of every length.  The history buffer is static too; row ``t_start`` is first order and does not read it."""
-        lib = self._lib
+        lib, sde, off = self._lib, self.eta > 0, self._elem_offset(x.shape)
+        rng = sde and self._rng_ok(x)              # eta > 0: one draw per step, in the update kernel or - bufs["_noise"] - by pf_randn_dev before it
 
         def update(bf, e_t, _table, st):
             hist = bf.get("_hist")
             if hist is None:                       # first (warm-up) run of the body, before the capture
                 hist = bf["_hist"] = torch.empty_like(bf["x"])
-            xb = bf["x"]
-            _steps.dpm_step(lib, xb, e_t.contiguous(), xb, table=bf["dpm_table"], state=st, x0_prev=hist, x0_out=hist,
-                            orig=bf["orig"], orig_noise=bf["orig_noise"], mask=bf["mask"])
+            xb, known = bf["x"], dict(orig=bf["orig"], orig_noise=bf["orig_noise"], mask=bf["mask"])
+            if not sde:
+                _steps.dpm_step(lib, xb, e_t.contiguous(), xb, table=bf["dpm_table"], state=st, x0_prev=hist, x0_out=hist, **known)
+            elif rng:
+                _steps.dpm_sde_step(lib, xb, e_t.contiguous(), xb, table=bf["dpm_table"], state=st, x0_prev=hist, x0_out=hist,
+                                    rng=(self.seed, 0, off), **known)
+            else:
+                nz = _steps.randn_dev(lib, bf["_noise"][0], self.seed, st, 0, off)
+                _steps.dpm_sde_step(lib, xb, e_t.contiguous(), xb, table=bf["dpm_table"], state=st, x0_prev=hist, x0_out=hist, noise=nz, **known)
 
         table, taus = self._coef_table(x.device, t_start)
         inputs = dict(x=x, cond=cond, orig=orig, mask=mask, orig_noise=orig_noise, uncond_cond=uncond_cond, cond_concat=cond_concat,
                       dpm_table=table)
-        return self._replay_loop("dpm", inputs, table, taus, 0, 0, t_start + 1, t_start, uncond_scale, update)
+        if not sde:
+            return self._replay_loop("dpm", inputs, table, taus, 0, 0, t_start + 1, t_start, uncond_scale, update)
+        return self._replay_loop("dpm_sde", inputs, table, taus, 1, int(not rng), t_start + 1, t_start, uncond_scale, update)
 
-    def _step(self, x, e_t, index, t_start, hist, orig=None, orig_noise=None, mask=None):
+    def _step(self, x, e_t, index, t_start, hist, orig=None, orig_noise=None, mask=None, temperature=1.0, repeat_noise=False):
         """Grid index ``index`` of a loop that started at ``t_start``; ``hist``: the history buffer (read unless the row is first order,
-        then overwritten with this step's x0)."""
-        coef = self._coef(index, t_start)
+        then overwritten with this step's x0).  ``temperature`` / ``repeat_noise`` shape the noise of an ``eta > 0`` step, as in
+        ``DDIMSampler._step``; at ``eta == 0`` there is none."""
         x, e_t = x.contiguous(), e_t.contiguous()
-        if orig is not None and orig_noise is None:      # DDIM's paint: a fresh q_sample noise per step (sampler_ddim.py:355-359)
-            orig_noise = self.randn(orig.shape, x.device)
         out = torch.empty_like(x)
-        return _steps.dpm_step(self._lib, x, e_t, out, coef=coef, x0_prev=hist, x0_out=hist, orig=orig, orig_noise=orig_noise, mask=mask), coef
+        if self.eta == 0:
+            coef = self._coef(index, t_start)
+            if orig is not None and orig_noise is None:      # DDIM's paint: a fresh q_sample noise per step (sampler_ddim.py:355-359)
+                orig_noise = self.randn(orig.shape, x.device)
+            return _steps.dpm_step(self._lib, x, e_t, out, coef=coef, x0_prev=hist, x0_out=hist, orig=orig, orig_noise=orig_noise, mask=mask), coef
+        coef = self._sde_coef(index, t_start)
+        orig, orig_noise, mask = (None if v is None else v.contiguous() for v in (orig, orig_noise, mask))
+        if not repeat_noise and temperature == 1.0 and self._rng_ok(x, e_t, hist, orig, orig_noise, mask):
+            draw = self._draws                               # the step's draw happens inside the update kernel, also when sigma_n == 0
+            self._draws += 1
+            if orig is not None and orig_noise is None:      # the fresh q_sample noise comes after the step's draw
+                orig_noise = self.randn(orig.shape, x.device)
+            _steps.dpm_sde_step(self._lib, x, e_t, out, coef=coef, x0_prev=hist, x0_out=hist, rng=(self.seed, draw, self._elem_offset(x.shape)),
+                                orig=orig, orig_noise=orig_noise, mask=mask)
+            return out, coef
+        noise = self.randn((1, *x.shape[1:]) if repeat_noise else x.shape, x.device)      # one draw index per step, whatever sigma_n is
+        if repeat_noise:
+            noise = noise.expand_as(x).contiguous()
+        if temperature != 1.0:
+            noise = noise * temperature
+        if orig is not None and orig_noise is None:
+            orig_noise = self.randn(orig.shape, x.device)
+        return _steps.dpm_sde_step(self._lib, x, e_t, out, coef=coef, x0_prev=hist, x0_out=hist, noise=noise, orig=orig, orig_noise=orig_noise,
+                                   mask=mask), coef
 
     @torch.no_grad()
     def p_sample(self, x, c, t, step: int, index: int, *, repeat_noise=False, temperature=1.0, uncond_scale=1.0,
                  uncond_cond=None, cond_concat=None, prep: Optional[dict] = None, x0_prev: Optional[torch.Tensor] = None):
         """One step on its own; returns (x_prev, pred_x0, e_t) like ``DDIMSampler.p_sample``.  Without ``x0_prev`` the step is first order;
         with the ``pred_x0`` of the step at ``index + 1`` it is the second-order step of the full grid.  ``repeat_noise`` / ``temperature``
-        are accepted for the shared signature: there is no noise."""
+        shape the noise of an ``eta > 0`` step (through the tensor form, as ``DDIMSampler._step`` does); at ``eta == 0`` there is none."""
         e_t = self._eps(x, c, int(step), uncond_scale, uncond_cond, cond_concat, prep)
         full = len(self.time_steps) - 1
         second = x0_prev is not None and index < full
         hist = x0_prev.contiguous().clone() if second else torch.empty_like(e_t)     # read by a second-order row only; receives this step's x0
-        x_prev, _ = self._step(x, e_t, index, full if second else index, hist)
+        x_prev, _ = self._step(x, e_t, index, full if second else index, hist, temperature=temperature, repeat_noise=repeat_noise)
         return x_prev, hist, e_t
 
     @torch.no_grad()
@@ -1575,9 +1664,14 @@ class DPMSolverSampler(DiffusionSampler):
             return self._paint_graph(x, cond, t_start, orig, mask, orig_noise, uncond_scale, uncond_cond, cond_concat)
         prep = self.prepare(cond, uncond_scale=uncond_scale, uncond_cond=uncond_cond)
         hist = torch.empty_like(x)          # the previous step's x0; uninitialised: the first step does not read it
-        for index in range(t_start, -1, -1):
+        steer = self._steer_begin(x, repaint_n)
+        for i, index in enumerate(range(t_start, -1, -1)):
             step = int(self.time_steps[index])
             e_t = self._eps(x, cond, step, uncond_scale, uncond_cond, cond_concat, prep)
+            if steer is not None and self._steered_at(steer, i, step, index == 0):
+                # the history is a particle's own: it moves with x and e_t (not on the first step, where it is still uninitialised)
+                x, e_t, *moved = self._steer_event(steer, x, e_t, self._t_of(step, self._eps_rows(x), x.device), i, step, [] if i == 0 else [hist])
+                hist = moved[0] if moved else hist
             x, _ = self._step(x, e_t, index, t_start, hist, orig=orig, orig_noise=orig_noise, mask=mask)
             if self.on_step is not None:
                 self.on_step(step, x)
