@@ -324,9 +324,11 @@ static Tn run_st(Ctx& c, const Layer& L, const Tn& xin, int H, int W_, const flo
     int att_ns = 1;
     const size_t att_sf = planes ? attention_bf3_split_floats(B, nh, hw, &att_ns) : 0;
     float* att_scratch = att_sf ? c.talloc(att_sf) : nullptr;
-    const bool merge = att_sf && c.o.opt[PF_OPT_ATTN_WIDE] != PF_OPT_ON;   // (a second, merging launch)
+    // PF_OPT_ATTN_WIDE forced on holds where the 256-query form exists (L % 256 == 0); elsewhere the level runs the 128-query form
+    const int att_form = (c.o.opt[PF_OPT_ATTN_WIDE] == PF_OPT_ON && hw % 256 != 0) ? PF_OPT_OFF : c.o.opt[PF_OPT_ATTN_WIDE];
+    const bool merge = att_sf && att_form != PF_OPT_ON;   // (a second, merging launch)
     c.launch(PF_K_ATTN, 4.0 * B * nh * (double)hw * hw * dh, [&] {
-      return planes ? launch_attention_bf3(qkv, nullptr, C, att, B, nh, hw, c.o.opt[PF_OPT_ATTN_WIDE], c.s, att_scratch, att_sf)   // att as hi/lo planes for the to_out GEMM
+      return planes ? launch_attention_bf3(qkv, nullptr, C, att, B, nh, hw, att_form, c.s, att_scratch, att_sf)   // att as hi/lo planes for the to_out GEMM
                     : launch_attention(qkv, 3 * C, qkv + C, 3 * C, qkv + 2 * C, 3 * C, att, C, B, nh, dh, hw, hw, c.s);
     }, merge ? 2 : 1);
     last_planes = planes && (i + 1 == L.tbs.size());
